@@ -2,6 +2,15 @@
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
     python bench.py --config c3|c4|c5                    (builder-kept lines of the other single-GPU BASELINE configurations)
+    python bench.py ... --full                           (the secondary measurements listed below as well)
+    python bench.py ... --dump-outputs DIR               (what the last timed step rendered, as DIR/<name>.npy)
+
+A plain run sets up, renders one priming frame and W warm-up steps, times the K steps and prints the JSON line: `value` (rays/s),
+`ms_per_step`, the configuration, and `lattice_bytes` / `workspace_bytes` (what the priming frame left allocated).  Everything else
+the line can carry (below) is measured with ``--full`` only; without it those fields are null.  ``--dump-outputs DIR`` writes, after
+the timed steps, the frame the last of them rendered (``rgb`` [scenes, rays, 3], ``depth_ray`` and ``valid_mask`` [scenes, rays])
+and, on one GPU, the attention weights of its forward call(s) (``at_wt`` [scenes x views, rays, samples]; above 40 MB a fixed,
+seeded sample of its rows, ``at_wt_sample``), float32; the inputs depend only on the arguments.
 
 A *step* renders one full query frame of the configuration (default c2 = BASELINE's headline: "RealEstate10K pair 256x256, 64 samples" =
 65 536 rays, 64 samples per view, 2 context views) of a camera trajectory between the two context views: EVERY step has its own query
@@ -24,15 +33,18 @@ pyramid and weights replicated) and the rendered tiles [rgb, depth, valid] are e
 frame, overlapped with the next frame: strong scaling of a frame.  ``frame_per_rank`` in the JSON line is the other
 arrangement (every rank a whole frame of its own), measured right after on fewer steps.
 
-The JSON line also carries
+With ``--full`` the JSON line also carries
+  stage_ms      : HIP events around every stage of the timed steps (stage_ms_per_rank: every rank's, N > 1);
+  hbm           : the frame's HBM-side bytes (profiles/traffic.json) over the measured step time (c2, one GPU);
+  frame_per_rank: (N > 1) every rank renders whole frames of its own, fewer steps;
   roofline      : the dominant kernel (the fused per-sample kernel), timed live with HIP events on the launch stream
                   (car_profile_* of the C ABI): algorithmic fp32-equivalent FLOP per launch / mean launch time against the
                   pipes it uses; `bound` names the unit the PMC counters show busiest (profiles/);
   gather_stage  : the stand-alone epipolar gather (car_gather_bilinear, both gathers of a frame chunk) against the HBM roofline
                   with SURVEY.md §8(d)'s algorithmic bytes — warmed up, 24 timed pairs, median / min / max;
-  pair_setup_ms, lattice_bytes, workspace_bytes, eval_mode : what the restructured path costs outside the timed region — the
-                  once-per-stereo-pair projection of the pyramid onto its lattice, the memory it and the per-call workspace hold, and
-                  the frame rate when every frame brings a new pair (the eval loop, eval_realestate10k.py:142-161);
+  pair_setup_ms, eval_mode : what the restructured path costs outside the timed region — the once-per-stereo-pair projection of
+                  the pyramid onto its lattice, and the frame rate when every frame brings a new pair (the eval loop,
+                  eval_realestate10k.py:142-161);
   first_round_ab: the same steps with the first attention round over the rows of e (rounds 1-4) instead of the fused kernel's partial sums;
   rank_share    : one call of 1/G of the frame per step (a rank's share at G = 2, 4, 8 GPUs) and the scaling each projects;
   power         : socket power, shader clock and joules per frame, sampled while the timed loop's steps run a second time;
@@ -83,14 +95,20 @@ def build_model(device, P_=None, H_=None):
     return m.to(device)
 
 
+def make_scene(alpha: float, H_=None, b=1, uv=None):
+    """Input dict of one query frame (the same stereo pair(s), query pose at ``alpha``); ``uv`` replaces the whole pixel grid."""
+    from cross_attention_renderer_amd import synthetic as S
+    Hh = H if H_ is None else H_
+    if SCENE == "unposed":                                             # query = a pose of the unposed demo's rotate_interpolate path
+        return S.unposed_scene(Hh, frame=int(round(alpha * 75)), seed=5, uv=uv)
+    return S.stereo_scene(Hh, b=b, alpha=alpha, seed=5, uv=uv)
+
+
 def make_frame(alpha: float, device, H_=None, b=1):
     """Input dict + feature pyramid for one query frame (the same stereo pair(s), query pose at ``alpha``)."""
     from cross_attention_renderer_amd import synthetic as S
     Hh = H if H_ is None else H_
-    if SCENE == "unposed":                                             # query = a pose of the unposed demo's rotate_interpolate path
-        inp = S.unposed_scene(Hh, frame=int(round(alpha * 75)), seed=5)
-    else:
-        inp = S.stereo_scene(Hh, b=b, alpha=alpha, seed=5)
+    inp = make_scene(alpha, H_, b)
     z = S.feature_maps(b, V, Hh, seed=1)
     if device is not None:
         inp = {k: {kk: vv.to(device) for kk, vv in v.items()} for k, v in inp.items()}
@@ -100,21 +118,24 @@ def make_frame(alpha: float, device, H_=None, b=1):
 
 def trajectory(n_frames: int, device, band=None, cameras_on_host: bool = False, H_=None, b=1):
     """``n_frames`` input dicts of the same stereo pair(s), query pose moving from one context camera towards the other;
-    ``band`` = (start, end) restricts the rays (this rank's share of the frame)."""
-    base, _ = make_frame(0.5, None, H_, b)
+    ``band`` = (start, end) restricts the rays (this rank's share of the frame).  The frames share the context tensors and the rays;
+    the query camera of a frame does not depend on its rays, so it is built from a one-ray scene (set-up time independent of the size)."""
+    base = make_scene(0.5, H_, b)
+    uv = base["query"]["uv"] if band is None else base["query"]["uv"][:, :, band[0]:band[1]].contiguous()
+    uv = uv.to(device)
+    cam = (lambda t: t) if cameras_on_host else (lambda t: t.to(device))
+    context = {k: (cam(v) if k in ("cam2world", "intrinsics") else v.to(device)) for k, v in base["context"].items()}
+    one_ray = torch.zeros(1, 2)
     frames = []
     for i in range(n_frames):
-        inp, _ = make_frame((i + 0.5) / n_frames, None, H_, b)
-        uv = base["query"]["uv"] if band is None else base["query"]["uv"][:, :, band[0]:band[1]].contiguous()
-        cam = (lambda t: t) if cameras_on_host else (lambda t: t.to(device))
-        frames.append({"context": {k: (cam(v) if k in ("cam2world", "intrinsics") else v.to(device)) for k, v in base["context"].items()},
-                       "query": {"cam2world": cam(inp["query"]["cam2world"]), "intrinsics": cam(inp["query"]["intrinsics"]),
-                                 "uv": uv.to(device)}})
+        q = make_scene((i + 0.5) / n_frames, H_, b, uv=one_ray)["query"]
+        frames.append({"context": context, "query": {"cam2world": cam(q["cam2world"]), "intrinsics": cam(q["intrinsics"]), "uv": uv}})
     return frames
 
 
-def render_frame(model, inp, z, tile, chunk_rays):
-    """One step: the rays of ``inp`` in forward calls of ``chunk_rays`` rays, results packed as [rgb(3), depth, valid] per scene."""
+def render_frame(model, inp, z, tile, chunk_rays, outs=None):
+    """One step: the rays of ``inp`` in forward calls of ``chunk_rays`` rays, results packed as [rgb(3), depth, valid] per scene.
+    ``outs``: a list that receives every forward call's output dict."""
     uv_all = inp["query"]["uv"]
     R = uv_all.shape[2]
     for c0 in range(0, R, chunk_rays):
@@ -123,6 +144,8 @@ def render_frame(model, inp, z, tile, chunk_rays):
         tile[:, c0:c0 + chunk_rays, 0:3] = out["rgb"][:, 0]
         tile[:, c0:c0 + chunk_rays, 3:4] = out["depth_ray"]
         tile[:, c0:c0 + chunk_rays, 4:5] = out["valid_mask"]
+        if outs is not None:
+            outs.append(out)
     return tile
 
 
@@ -202,13 +225,14 @@ def gather_stage(model, inp, z, Hc: int, Pc: int, rays: int = CHUNK, warm: int =
                     "measured before the warm-up and timed steps, after one priming frame"}
 
 
-def timed_loop(model, frames, z, tile, gather, steps, chunk_rays, dist):
+def timed_loop(model, frames, z, tile, gather, steps, chunk_rays, dist, last_outs=None):
+    """``last_outs``: a list that receives the output dicts of the last step's forward call(s)."""
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        render_frame(model, frames[i % len(frames)], z, tile, chunk_rays)
+        render_frame(model, frames[i % len(frames)], z, tile, chunk_rays, last_outs if i == steps - 1 else None)
         if gather is not None:
             gather(tile.view(-1, tile.shape[-1]))
     if gather is not None:
@@ -217,6 +241,32 @@ def timed_loop(model, frames, z, tile, gather, steps, chunk_rays, dist):
     if dist is not None:
         dist.barrier()
     return time.perf_counter() - t0
+
+
+AT_WT_DUMP_BYTES = 40 << 20            # --dump-outputs: above this the attention weights are written as a seeded sample of their rows
+
+
+def step_outputs(frame, outs):
+    """What the last timed step rendered, as float32 host arrays: ``frame`` = its [scenes, rays, rgb(3) depth valid] tiles (the whole
+    frame on every rank after the all-gather), ``outs`` = its forward calls' output dicts (this rank's; None: not dumped)."""
+    arrays = {"rgb": frame[..., 0:3], "depth_ray": frame[..., 3], "valid_mask": frame[..., 4]}
+    if outs:
+        rows = torch.cat([o["at_wt"] for o in outs], dim=1)                   # [scenes x views, rays, samples], chunks in ray order
+        rows = rows.reshape(-1, rows.shape[-1])
+        keep = AT_WT_DUMP_BYTES // (4 * rows.shape[1])
+        if rows.shape[0] > keep:
+            pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            arrays["at_wt_sample"] = rows[pick.to(rows.device)]
+        else:
+            arrays["at_wt"] = rows
+    return {k: v.detach().float().cpu().contiguous() for k, v in arrays.items()}
+
+
+def write_outputs(path, arrays) -> None:
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v.numpy())
 
 
 def pair_setup(model, frame, z, reps: int = 3):
@@ -267,10 +317,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="which BASELINE configuration a step renders (c2 = the headline, what the driver runs; c3 / c4 / c5: builder-kept lines)")
-    ap.add_argument("--cpu-rays", type=int, default=4096, help="rays in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: stage times, roofline and HBM figures, the extras (see "
+                         "--no-extras) and the CPU baseline (see --cpu-rays); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them rendered to DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-rays", type=int, default=4096, help="rays in the CPU-baseline sample of --full (0 = skip)")
     ap.add_argument("--chunk-rays", type=int, default=1 << 30,
                     help="rays per scene and forward call: the whole frame (or band) by default (a 288 GB GPU does not need the reference render script's 8192-ray chunks; --chunk-rays 8192 reproduces them)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the gather-stage, pair-setup, eval-mode, rank-share, pose-route and frame-per-rank measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the gather-stage, pair-setup, eval-mode, rank-share, pose-route and frame-per-rank measurements")
     ap.add_argument("--cameras", choices=("host", "gpu", "device"), default="host",
                     help="host = camera matrices stay CPU tensors: the reference's own torch.inverse on the CPU per frame + a 768-byte upload, no "
                          "device synchronisation (default); gpu = the whole input dict on the GPU as the reference's scripts hand it over: same "
@@ -281,6 +336,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to smoke-test the multi-rank code path)")
     ap.add_argument("--device", type=int, default=None, help="device index for every rank (smoke tests of the multi-rank path on one GPU; default LOCAL_RANK)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -305,8 +362,11 @@ def main():
             sys.exit(f"bench.py: the process group reports {dist.get_world_size()} ranks, --gpus asked for {args.gpus}")
 
     import __graft_entry__ as ge
-    if rank == 0:
-        ge.build()                                   # one builder per node: concurrent hipcc runs would race on the .so
+    from cross_attention_renderer_amd import _lib
+    # one builder per node (concurrent hipcc runs would race on the .so), and only when the library is missing or was built from other
+    # sources: a tree built beforehand is used as it is, so the benchmark also runs where that tree is not writable
+    if rank == 0 and not _lib._stamp_current():
+        ge.build()
     if dist is not None:
         dist.barrier()
     from cross_attention_renderer_amd.engine import RenderEngine
@@ -337,9 +397,10 @@ def main():
     gather = TileGather(world, nb * -(-R_frame // world), 5, dev) if world > 1 else None
     if gather is not None and R != -(-R_frame // world):
         sys.exit("bench.py: the frame's rays must divide evenly over the ranks")
-    extras = world == 1 and not args.no_extras
+    extras = args.full and world == 1 and not args.no_extras
 
     gs = setup_ms = None
+    stages = []
     with torch.no_grad():
         # one priming frame (plan, lattice, workspace: untimed set-up, not one of the W warm-up steps), then the measurements that must
         # not sit between the warm-up and the timed steps (they free and allocate gigabytes: the first frame after them pays the
@@ -357,10 +418,17 @@ def main():
                 gather(tile.view(-1, 5))
         if gather is not None:
             gather.wait()
-        model._engine.profile(True)                              # stage events from here on (rank-local)
-        elapsed = timed_loop(model, frames, z, tile, gather, args.steps, args.chunk_rays, dist)
-        stages = model._engine.stage_times()
-        model._engine.profile(False)
+        if args.full:
+            model._engine.profile(True)                          # stage events from here on (rank-local)
+        last_outs = [] if args.dump_outputs and world == 1 else None
+        elapsed = timed_loop(model, frames, z, tile, gather, args.steps, args.chunk_rays, dist, last_outs)
+        if args.full:
+            stages = model._engine.stage_times()
+            model._engine.profile(False)
+        if args.dump_outputs and rank == 0:
+            # the whole frame as rank 0 receives it: rank g's (scenes, rays) band is row block g of the all-gather
+            frame = tile if gather is None else gather.out.view(world, nb, R, 5).transpose(0, 1).reshape(nb, world * R, 5)[:, :R_frame]
+            write_outputs(args.dump_outputs, step_outputs(frame, last_outs))
 
         ev_ms = ev_ms_pf = share = pose = power = ab = None
         if extras:
@@ -473,7 +541,7 @@ def main():
 
         # the other multi-GPU arrangement: every rank renders whole frames of its own (replicas), tiles all-gathered
         per_rank = None
-        if world > 1 and not args.no_extras and nb == 1:
+        if world > 1 and args.full and not args.no_extras and nb == 1:
             k2 = max(2, args.steps // 2)
             full = trajectory(k2, dev, None, args.cameras == "host", Hc, nb)
             tile2 = torch.empty(nb, R_frame, 5, device=dev)
@@ -484,12 +552,13 @@ def main():
 
     rank_stages = None
     if dist is not None:
-        mine = {}
-        for name, ms in stages:
-            mine.setdefault(name, []).append(ms)
-        mine = {k: sum(v) / len(v) for k, v in mine.items()}
-        rank_stages = [None] * world
-        dist.all_gather_object(rank_stages, mine)            # every rank's mean stage times: a short scaling curve can be read from one run
+        if args.full:
+            mine = {}
+            for name, ms in stages:
+                mine.setdefault(name, []).append(ms)
+            mine = {k: sum(v) / len(v) for k, v in mine.items()}
+            rank_stages = [None] * world
+            dist.all_gather_object(rank_stages, mine)        # every rank's mean stage times: a short scaling curve can be read from one run
         t = torch.tensor([elapsed, per_rank[1] if per_rank else 0.0], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t[0].item()
@@ -501,8 +570,9 @@ def main():
         rays_total = rays_step * args.steps
         prof = {}
         try:
-            with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-                prof = json.load(f)
+            if args.full:                                    # the static fields of the roofline and hbm blocks
+                with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                    prof = json.load(f)
         except OSError:
             pass
         by_stage = {}
@@ -573,7 +643,8 @@ def main():
                        "rays_per_step": rays_step, "rays_per_step_per_gpu": nb * R,
                        "parallelism": "one GPU" if world == 1 else f"one frame's rays banded over {world} ranks, all-gather of tiles over {'RCCL' if args.backend == 'nccl' else args.backend}"
                                                                       + (f" (all ranks on device {args.device}: a dry run of the code path, no scaling figure)" if args.device is not None else "")},
-            "stage_ms": {k: sum(v) / len(v) for k, v in by_stage.items()},
+            "full": args.full,
+            "stage_ms": {k: sum(v) / len(v) for k, v in by_stage.items()} if args.full else None,
             "stage_ms_per_rank": rank_stages,
             "roofline": roof,
             "hbm": hbm,
@@ -600,7 +671,7 @@ def main():
             "reference_flops": {"flop_per_ray": ref_flop, "equivalent_tflops": rays_total / elapsed * ref_flop / 1e12,
                                 "frac_of_fp32_mfma_peak": rays_total / elapsed * ref_flop / FP32_MFMA_PEAK / world},
             # the CPU leg runs on rank 0 of a single-GPU job only (it is a per-host figure and would stall the other ranks)
-            "cpu_baseline": cpu_baseline(args.cpu_rays, Hc, Pc) if (args.cpu_rays > 0 and world == 1) else None,
+            "cpu_baseline": cpu_baseline(args.cpu_rays, Hc, Pc) if (args.full and args.cpu_rays > 0 and world == 1) else None,
         }
         print(json.dumps(line))
     if dist is not None:

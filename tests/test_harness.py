@@ -114,8 +114,8 @@ def test_training_entry_point_runs_and_writes_reference_style_checkpoints(tmp_pa
 
 @pytest.mark.gpu
 def test_bench_prints_one_line_with_the_contract_fields():
-    """`python bench.py` (small K / W, a 256-ray CPU sample): the last stdout line is ONE JSON object with the fields the driver reads —
-    metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config —
+    """`python bench.py --full` (small K / W, a 256-ray CPU sample): the last stdout line is ONE JSON object with the fields the driver
+    reads — metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config —
     plus the `roofline` (bound in {hbm, mfma}, achieved / peak / unit / frac / traffic) and `cpu_baseline` objects, and what the
     restructured path keeps outside the timed region: `pair_setup_ms`, `lattice_bytes`, `workspace_bytes`, `eval_mode`, the gather stage with
     its spread, the rank-share projection and the cost of handing the cameras over on the GPU."""
@@ -123,7 +123,7 @@ def test_bench_prints_one_line_with_the_contract_fields():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--cpu-rays", "256"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--cpu-rays", "256"],
                          capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
@@ -159,6 +159,37 @@ def test_bench_prints_one_line_with_the_contract_fields():
     assert "available" in pw and (not pw["available"] or (pw["mean_w"] > 50 and pw["samples"] >= 5 and pw["joule_per_frame"] > 0))
     assert ("sclk_mhz_live" in r) and ("socket_w_live" in r)
     assert d["pose_route"]["download_and_sync_ms"] > 0 and d["pose_route"]["cameras_on_gpu_ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_the_last_frame(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: the contract fields, none of the secondary measurements, and the last timed
+    step's frame and attention weights as float32 arrays (at most 64 MB) that two runs with the same arguments reproduce."""
+    import json
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append((json.loads(lines[0]), {p.stem: np.load(p) for p in d.glob("*.npy")}))
+    line, arrays = runs[0]
+    assert line["metric"] == "rendered_rays_per_sec" and line["unit"] == "rays/s" and line["higher_is_better"] is True
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False and "split-f16" in line["dtype"]
+    assert abs(line["value"] - 65536 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    for k in ("stage_ms", "roofline", "hbm", "gather_stage", "eval_mode", "rank_share", "first_round_ab", "power", "pose_route", "cpu_baseline"):
+        assert line[k] is None, k
+    assert set(arrays) == {"rgb", "depth_ray", "valid_mask", "at_wt"}
+    assert arrays["rgb"].shape == (1, 65536, 3) and arrays["depth_ray"].shape == arrays["valid_mask"].shape == (1, 65536)
+    assert arrays["at_wt"].shape == (2 * 65536, 64) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert set(np.unique(arrays["valid_mask"])) <= {0.0, 1.0}
+    assert np.allclose(arrays["at_wt"].reshape(2, 65536, 64).sum(axis=(0, 2)), 1.0, atol=1e-4)     # one softmax over both views' samples
+    for k, a in arrays.items():
+        np.testing.assert_array_equal(a, runs[1][1][k], err_msg=k)
 
 
 def test_bench_refuses_a_world_size_that_is_not_the_requested_gpu_count():

@@ -8,9 +8,9 @@ mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q --maxfail=30 --timeout 900 -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc=$?"
 grep -E "passed|failed|^FAILED|^ERROR" $O/pytest.log | tail -30
 timeout 600 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; grep -E "smoke|hipcc" $O/smoke.log
-timeout 900 python bench.py > $O/bench_c2.log 2>&1; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_c2.log 2>&1; echo "bench rc=$?"
 tail -1 $O/bench_c2.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['frac_executed'], d['stage_ms'], d.get('pair_setup_ms'), d['eval_mode']['ms_per_step'], d['gather_stage']['frac'], d['rank_share'], d['power'])"
-for c in c3 c4 c5; do timeout 600 python bench.py --config $c --cpu-rays 0 > $O/bench_$c.log 2>&1; echo "bench $c rc=$?"; tail -1 $O/bench_$c.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['frac_executed'], d['stage_ms'], d.get('pair_setup_ms'), d['eval_mode']['ms_per_step'], d['gather_stage']['frac'], d['lattice_bytes'], d['workspace_bytes'])"; done
+for c in c3 c4 c5; do timeout 600 python bench.py --full --config $c --cpu-rays 0 > $O/bench_$c.log 2>&1; echo "bench $c rc=$?"; tail -1 $O/bench_$c.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['frac_executed'], d['stage_ms'], d.get('pair_setup_ms'), d['eval_mode']['ms_per_step'], d['gather_stage']['frac'], d['lattice_bytes'], d['workspace_bytes'])"; done
 timeout 900 bash tools/profile_bench.sh r6final2 > $O/profile.log 2>&1; echo "profile rc=$?"; tail -5 $O/profile.log
 timeout 600 python tools/bench_variants.py > $O/variants.log 2>&1; echo "variants rc=$?"; grep -v amdgpu.ids $O/variants.log
 timeout 300 python tools/train_step_probe.py > $O/train.log 2>&1; echo "train rc=$?"; tail -3 $O/train.log

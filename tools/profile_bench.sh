@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $ROOT/bench.py --steps 1 --warmup 1 --cpu-rays 0"
+BENCH="python $ROOT/bench.py --full --steps 1 --warmup 1 --cpu-rays 0"
 PMC_EXTRA=${PMC_EXTRA:---no-extras}     # the PMC passes count bytes per frame: no gather-stage / per-rank extras
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- $BENCH ${TRACE_EXTRA:-} > $OUT/trace.log 2>&1
 echo "trace rc=$?"

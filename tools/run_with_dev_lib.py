@@ -1,6 +1,6 @@
 """Runs a script of this repository (bench.py, a tools/ script) with the DEVELOPMENT build of the library (tools/build_dev.py: CAR_DEV_FLAGS,
 e.g. -DCAR_WG_ORDER=2) in place of the product's: the package's loader is handed the development library before anything else asks for it.
-Development tool only — the product never does this.    python tools/run_with_dev_lib.py bench.py --no-extras --cpu-rays 0"""
+Development tool only — the product never does this.    python tools/run_with_dev_lib.py bench.py --full --no-extras --cpu-rays 0"""
 import ctypes
 import os
 import runpy
