@@ -21,6 +21,8 @@
 // e leaves as whole 128-byte lines (turned through the wave's LDS tile).  profiles/round3_fused_experiments.md has the measurements.
 // The geometric query g (16 floats per sample) is written out for the second attention round (car_round2.hip recomputes the
 // 16 -> 128 half of query_repeat_embed from it instead of reading a 128-wide row back).
+// F16 = true (car_render_forward_f16, the opt-in render precision): every layer takes ONE product per term from the compact blob of
+// car_plan_f16_build, B operands rounded to nearest (car_fused_mma.h); geometry, gather, scaling and every output's layout are the same.
 #include "car_common.h"
 #include "car_geom.h"
 #include <type_traits>
@@ -111,15 +113,17 @@ __device__ __forceinline__ constexpr int chunk_tiles(int g) {
     return 2 * kTD;
 }
 // the chunk after g inside the two source passes (g + 1 in [1, 36]): selects only, no branch tree in the hot loop
+template <bool F16 = false>
 __device__ __forceinline__ NextChunk next_chunk_w2(const float* __restrict__ blob, float* lds, int gn) {
+    constexpr int kTF = tile_floats<F16>(), kKB = kTF / 256;
     const bool w2 = gn < kG_K1b;
     const int step = gn >= kG_W2b ? gn - kG_W2b : gn;
     NextChunk n;
-    n.src = blob + (long)(w2 ? kOffW2 + step * kTE : chunk_tile_offset(kG_K1b)) * kTile;
-    n.dst = lds + kLdsW + (gn & 1) * kChunkTiles * kTile;
-    n.nkb = w2 ? 2 * kTE : 2 * chunk_tiles(kG_K1b);
+    n.src = blob + (long)(w2 ? kOffW2 + step * kTE : chunk_tile_offset(kG_K1b)) * kTF;
+    n.dst = lds + kLdsW + (gn & 1) * kChunkTiles * kTF;
+    n.nkb = w2 ? kKB * kTE : kKB * chunk_tiles(kG_K1b);
 #ifdef CAR_BOUNDS
-    n.lim = blob + (long)kBlobTiles * kTile;
+    n.lim = blob + (long)kBlobTiles * kTF;
 #endif
     return n;
 }
@@ -136,8 +140,11 @@ __device__ __forceinline__ NextChunk next_chunk_w2(const float* __restrict__ blo
 // 50-53: the chunk loop without slot fences, vector / LDS instructions interleaved under the MFMAs by sched_group_barrier (results stay right)
 // ROWS: one source pass over explicit rows, e_0 = W2 relu(h) + b2 written [row][kE], nothing else (the three-view exchange's two layers,
 // models.py:345-475 through engine._encode_three_views); the chunk loop is the product kernel's own
-template <int ABL, bool ROWS = false>
+// F16: the opt-in precision (one product per term, compact blob); only with ABL 0 and ROWS false
+template <int ABL, bool ROWS = false, bool F16 = false>
 __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
+    static_assert(!F16 || (ABL == 0 && !ROWS), "the fp16 instance is the one-call route's partial-sum kernel only");
+    constexpr int kTF = tile_floats<F16>(), kP = chunk_pieces<F16>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // scalar: everything derived from it stays out of the vector ALU
@@ -193,7 +200,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
     }
     for (int k = tid; k < kBiasFloats; k += kThreads) lds[kLdsBias + k] = a.bias[k];
     int g = 0;
-    stream_issue_all<ABL>(a.blob, lds, 0, lane, wave);
+    stream_issue_all<ABL, F16>(a.blob, lds, 0, lane, wave);
 
     // ---- geometry: the 192 samples of the group are spread over the 192 lanes of waves 0-2 (one sample per lane, both source views),
     //      instead of every wave repeating its 16 samples in four lane groups: a third of the issue time on the critical path ----
@@ -374,7 +381,8 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         const float4 x0 = *reinterpret_cast<const float4*>(stage + s * kStageLd + 8 * q4);
         const float4 x1 = *reinterpret_cast<const float4*>(stage + s * kStageLd + 8 * q4 + 4);
         const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-        split8_scaled(x, bhi, blo);
+        if constexpr (F16) cvt8_scaled(x, bhi);
+        else split8_scaled(x, bhi, blo);
     };
 
     // first chunk of source 0: nothing to hide it under
@@ -416,12 +424,12 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             const int nc = (c + 1 < kKS) ? c + 1 : 0;
             const int n2sv = (c + 2 < kKS) ? sv : 1;
             const int n2c = (c + 2 < kKS) ? c + 2 : c + 2 - kKS;
-            const float* wl = lds + kLdsW + (g & 1) * kChunkTiles * kTile + 4 * lane;
-            const NextChunk nx = next_chunk_w2(a.blob, lds, g + 1);
+            const float* wl = lds + kLdsW + (g & 1) * kChunkTiles * kTF + 4 * lane;
+            const NextChunk nx = next_chunk_w2<F16>(a.blob, lds, g + 1);
             // 9 slots of (4 ds_read_b128 + 6 MFMAs of 16 cycles); between them one piece of the gather / DMA issue: slots 0-2 carry the
             // DMA pieces, slot 0 the affine start values, slots 3 and 6 one row group each — blend, store the h rows, re-issue.
             auto piece = [&](int qs) {
-                if (qs < kPieces) { const long long t0 = tick(); stream_issue_piece<ABL>(nx, qs, lane, wave); t_piece += tick() - t0; }
+                if (qs < kP) { const long long t0 = tick(); stream_issue_piece<ABL>(nx, qs, lane, wave); t_piece += tick() - t0; }
                 if constexpr (ABL == 43) {                             // the eight tap loads spread over slots 3-8, one or two per slot
                     if (qs == 0) { affine_row(nsv, nc, 0); affine_row(nsv, nc, 1); }
                     else if (qs == 3) { blend_row(bufA, nsv, 0); finish_row(0); issue_tap(bufA, n2sv, n2c, 0, 0); }
@@ -505,8 +513,8 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             } else {
 #pragma unroll
             for (int qs = 0; qs < kTE / 2; ++qs) {
-                const float* w0 = wl + (2 * qs * 2) * 256;
-                { const long long t0 = tick(); if constexpr (ABL != 5) mfma_pair<ABL>(acc[2 * qs], acc[2 * qs + 1], w0, w0 + 512, bhi, blo); t_mfma += tick() - t0; }
+                const float* w0 = wl + 2 * qs * kTF;
+                { const long long t0 = tick(); if constexpr (ABL != 5) mfma_pair<ABL, F16>(acc[2 * qs], acc[2 * qs + 1], w0, w0 + kTF, bhi, blo); t_mfma += tick() - t0; }
                 piece(qs);
                 if constexpr (ABL < 50 || ABL > 53) __builtin_amdgcn_sched_barrier(0);
             }
@@ -601,7 +609,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             *reinterpret_cast<float4*>(a.e + i_row[it] * (2 * kE) + kE + 32 * m + 4 * qd) = v;
         }
     };
-    chained_layer<kTE, false, ABL, kG_K1b, 2>(k1, acc, p, a.blob, lds, lane, wave, store_tiles);
+    chained_layer<kTE, false, ABL, kG_K1b, F16, 2>(k1, acc, p, a.blob, lds, lane, wave, store_tiles);
     mark(7);
     {
         constexpr bool kStream = !(ABL == 3 || ABL == 12 || ABL == 5);
@@ -638,28 +646,28 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
 #pragma unroll
         for (int c = 0; c < kChK1; ++c) {
             const int g = kG_K1a + c;
-            const float* wl = lds + kLdsW + (g & 1) * kChunkTiles * kTile + 4 * lane;
-            const NextChunk nx = next_chunk(a.blob, lds, g + 1);
+            const float* wl = lds + kLdsW + (g & 1) * kChunkTiles * kTF + 4 * lane;
+            const NextChunk nx = next_chunk<F16>(a.blob, lds, g + 1);
 #pragma unroll
             for (int kl = 0; kl < 2; ++kl) {
                 const int m = 2 * c + kl;
                 if (m < kSteps) {
                     // vector memory operations issued after e_0(m)'s two: e_0(m + 1)'s, and for the second K step of a chunk the
-                    // chunk's three weight pieces in between
+                    // chunk's kP weight pieces in between
                     if (kl == 0) { if (m + 1 < kSteps) wait_vm(std::integral_constant<int, 2>()); else wait_vm(std::integral_constant<int, 0>()); }
-                    else { if (m + 1 < kSteps) wait_vm(std::integral_constant<int, 5>()); else wait_vm(std::integral_constant<int, 3>()); }
+                    else { if (m + 1 < kSteps) wait_vm(std::integral_constant<int, kP + 2>()); else wait_vm(std::integral_constant<int, kP>()); }
                     const float* eb = ebuf[m & 1] + s * 32;
                     const int rot = (s >> 1) & 7;
                     const float4 x0 = *reinterpret_cast<const float4*>(eb + 4 * (q4 ^ rot));
                     const float4 x1 = *reinterpret_cast<const float4*>(eb + 4 * ((4 + q4) ^ rot));
                     const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
                     half8 bhi, blo;
-                    split8(x, p, bhi, blo);
+                    operand8<F16>(x, p, bhi, blo);
 #pragma unroll
                     for (int q = 0; q < kTD / 2; ++q) {
-                        const float* w0 = wl + ((kl * kTD + 2 * q) * 2) * 256;
-                        mfma_pair<ABL>(k1[2 * q], k1[2 * q + 1], w0, w0 + 512, bhi, blo);
-                        if (kl == 0 && q < kPieces) stream_issue_piece<ABL>(nx, q, lane, wave);
+                        const float* w0 = wl + (kl * kTD + 2 * q) * kTF;
+                        mfma_pair<ABL, F16>(k1[2 * q], k1[2 * q + 1], w0, w0 + kTF, bhi, blo);
+                        if (kl == 0 && q < kP) stream_issue_piece<ABL>(nx, q, lane, wave);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (m + 2 < kSteps) issue_e0(m + 2);              // into the buffer just read
@@ -689,18 +697,18 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         m = fmaxf(m, __shfl_xor(m, 16, 64));
         m = fmaxf(m, __shfl_xor(m, 32, 64));                           // >= 1: the bias column
         pow2_scale(m, p, pinv);
-        split8(gx8, p, ghi, glo);
+        operand8<F16>(gx8, p, ghi, glo);
     }
     f32x4 t1[kTD], mt[kTD];
 #pragma unroll
     for (int t = 0; t < kTD; ++t) t1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    stream_issue_all<ABL>(a.blob, lds, kG_Q1 + 1, lane, wave);
-    small_layer(t1, ghi, glo, lds + kLdsW + (kG_Q1 & 1) * kChunkTiles * kTile + 4 * lane);          // q1
+    stream_issue_all<ABL, F16>(a.blob, lds, kG_Q1 + 1, lane, wave);
+    small_layer<F16>(t1, ghi, glo, lds + kLdsW + (kG_Q1 & 1) * kChunkTiles * kTF + 4 * lane);          // q1
     stream_sync<ABL>();
     scale_acc<kTD>(t1, lsc[kLayerQ1] * pinv);
     pow2_scale(fmaxf(sample_max<kTD, true>(t1), 1e-30f), p, pinv);
     init_bias<kTD>(mt, lds + kLdsBias + kBiasV, q4, p / lsc[kLayerM]);
-    chained_layer<kTD, true, ABL, kG_M>(mt, t1, p, a.blob, lds, lane, wave);
+    chained_layer<kTD, true, ABL, kG_M, F16>(mt, t1, p, a.blob, lds, lane, wave);
     scale_acc<kTD>(mt, lsc[kLayerM] * pinv);                           // M x + v
     float dot = 0.0f;
 #pragma unroll
@@ -798,7 +806,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
 
 int launch_fused(int abl, int blk0, int nblk, const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h, int lat_w, int lat_pad,
                  const float* gmeta, const float* wpt, const float* blob, const float* bias, int b, int V, int R, int P, int H, int W, int no_sample, float* e,
-                 float* g, float* logit, float* pt, float* pixel_val, float* part, void* stream) {
+                 float* g, float* logit, float* pt, float* pixel_val, float* part, void* stream, bool f16 = false) {
     CAR_REQUIRE(poses && rays && steps && lattice && gmeta && wpt && blob && bias, "car_fused_samples: null input");
     CAR_REQUIRE(e && g && logit && pt && pixel_val, "car_fused_samples: null output");
     CAR_REQUIRE(V == 2, "car_fused_samples: built for V = 2 (got %d)", V);
@@ -823,7 +831,7 @@ int launch_fused(int abl, int blk0, int nblk, const float* poses, const float* r
 #endif
     long groups = (long)b * V * car_div_up(R, kTileRays) * car_div_up(P, kTileSteps);
     if (nblk > 0) groups = (groups - blk0 < nblk) ? groups - blk0 : nblk;     // development build: a slice of the sample groups
-    void (*kern)(const FusedArgs) = fused_kernel<0>;
+    void (*kern)(const FusedArgs) = f16 ? fused_kernel<0, false, true> : fused_kernel<0>;
 #if defined(CAR_ABLATION) && !defined(CAR_ABLATION_NONE)       // CAR_ABLATION_NONE: the development build's entries without the timing variants
     switch (abl) {
         case 1: kern = fused_kernel<1>; break;   case 2: kern = fused_kernel<2>; break;   case 3: kern = fused_kernel<3>; break;
@@ -872,6 +880,17 @@ extern "C" int car_fused_samples_parts(const float* poses, const float* rays, co
     CAR_REQUIRE(part, "car_fused_samples_parts: null output");
     return launch_fused(0, 0, 0, poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob, bias, b, V, R, P, H, W, no_sample, e, g, logit, pt,
                         pixel_val, part, stream);
+}
+
+// The opt-in fp16 precision of the same launch (car_render_forward_f16): blob is the compact one of car_plan_f16_build (hi-only tiles),
+// bias / wpt its table; part may be NULL (the rows-first route).  Same outputs, same layouts.
+extern "C" size_t car_fused_blob16_floats(void) { return (size_t)kBlobTiles * tile_floats<true>(); }
+extern "C" int car_fused_samples_f16(const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h, int lat_w,
+                                     int lat_pad, const float* gmeta, const float* wpt, const float* blob16, const float* bias, int b, int V, int R,
+                                     int P, int H, int W, int no_sample, float* e, float* g, float* logit, float* pt, float* pixel_val,
+                                     float* part, void* stream) {
+    return launch_fused(0, 0, 0, poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob16, bias, b, V, R, P, H, W, no_sample, e, g, logit,
+                        pt, pixel_val, part, stream, true);
 }
 
 #ifdef CAR_ABLATION

@@ -9,6 +9,7 @@ constexpr int kKS = kC / 32;       // 18 K steps (= weight chunks) of the 576 ->
 constexpr int kTE = kE / 16;       // 18 output tiles of 16 channels
 constexpr int kTD = kD / 16;       // 8 output tiles
 constexpr int kTile = 512;         // packed floats per (K step, tile): [hi|lo][64 lanes][8 halves] = 2 KB
+constexpr int kTileHi = 256;       // the same in the compact blob of the fp16 precision (car_plan_f16_build): [64 lanes][8 halves] = 1 KB
 
 // ---- packed-weight blob: offsets in tiles, layer by layer, [K step][tile] inside a layer ---------------------------
 // The first round's logit <key, qry> / 16 with key = Wk2 relu(k1) + bk2 and qry = Wq2 relu(q1) + bq2 (models.py:491, 529, 533) is a

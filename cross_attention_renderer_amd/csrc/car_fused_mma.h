@@ -11,6 +11,11 @@
 // chained layers (the whole input vector sits in registers), per launch for the first layer (bounded by the maxima of the
 // projected maps) — so that the largest value lands in [2^13, 2^14): no overflow, and everything within 2^-17 of the largest
 // value keeps its full 22 bits.
+//
+// F16 (the opt-in render precision, car_render_forward_f16): ONE product per term.  The weights come from the compact blob of
+// car_plan_f16_build (hi-only tiles of 1 KB, each value rounded to nearest after the same 2^shift), the B operands are rounded to
+// nearest by one v_cvt_pk_f16_f32 per pair after the same powers of two; accumulation stays fp32.  Chunks are half the bytes, so
+// the stream needs ceil(18 / kWaves) pieces per chunk and its two LDS buffers are half as far apart.
 #pragma once
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -22,7 +27,11 @@ typedef __attribute__((address_space(3))) void lds_void;
 constexpr int kStageLd = 36;       // row stride of the wave-private h tile (floats)
 
 // ---- dynamic LDS carve-up (floats) --------------------------------------------------------------------------------
-constexpr int kLdsW = 0;                                        // [2][18][512]           weight chunks          72 KB
+constexpr int kLdsW = 0;                                        // [2][18][512]           weight chunks          72 KB (F16: [2][18][256] in front of it)
+
+// floats per (K step, tile) of a blob and LDS-DMA pieces per chunk, per precision
+template <bool F16> __host__ __device__ __forceinline__ constexpr int tile_floats() { return F16 ? kTileHi : kTile; }
+template <bool F16> __host__ __device__ __forceinline__ constexpr int chunk_pieces() { return F16 ? (kChunkTiles + kWaves - 1) / kWaves : kPieces; }
 
 __device__ __forceinline__ constexpr int chunk_tile_offset(int g);      // defined by the including kernel file
 __device__ __forceinline__ constexpr int chunk_tiles(int g);
@@ -34,14 +43,16 @@ struct NextChunk {
     const float* lim = nullptr;        // one past the packed array the chunk lies in (nullptr: unknown to this kernel)
 #endif
 };
+template <bool F16 = false>
 __device__ __forceinline__ NextChunk next_chunk(const float* __restrict__ blob, float* lds, int g) {
+    constexpr int kTF = tile_floats<F16>();
     const int ge = g < kNumChunks ? g : kNumChunks - 1;            // past the end: re-copy the last chunk onto itself
     NextChunk n;
-    n.src = blob + (long)chunk_tile_offset(ge) * kTile;
-    n.dst = lds + kLdsW + (ge & 1) * kChunkTiles * kTile;
-    n.nkb = 2 * chunk_tiles(ge);
+    n.src = blob + (long)chunk_tile_offset(ge) * kTF;
+    n.dst = lds + kLdsW + (ge & 1) * kChunkTiles * kTF;
+    n.nkb = (kTF / 256) * chunk_tiles(ge);
 #ifdef CAR_BOUNDS
-    n.lim = blob + (long)kBlobTiles * kTile;
+    n.lim = blob + (long)kBlobTiles * kTF;
 #endif
     return n;
 }
@@ -82,12 +93,12 @@ __device__ __forceinline__ void stream_issue_piece(const NextChunk& n, int p, in
     else CAR_DMA_PIECE("");
 #undef CAR_DMA_PIECE
 }
-template <int ABL = 0>
+template <int ABL = 0, bool F16 = false>
 __device__ __forceinline__ void stream_issue_all(const float* __restrict__ blob, float* lds, int g, int lane, int wave) {
     if (g >= kNumChunks) return;
-    const NextChunk n = next_chunk(blob, lds, g);
+    const NextChunk n = next_chunk<F16>(blob, lds, g);
 #pragma unroll
-    for (int p = 0; p < kPieces; ++p) stream_issue_piece<ABL>(n, p, lane, wave);
+    for (int p = 0; p < chunk_pieces<F16>(); ++p) stream_issue_piece<ABL>(n, p, lane, wave);
 }
 // end of a chunk: the DMA of the next chunk has landed and every wave is done reading the current one.  KEEP = number of
 // vector loads this wave issued AFTER its last DMA piece and wants to leave in flight across the barrier (loads return in
@@ -104,6 +115,32 @@ __device__ __forceinline__ void stream_sync() {
 
 #include "car_split.h"
 
+// F16: x * p (or x, already scaled) rounded to nearest fp16, one v_cvt_pk_f16_f32 per pair
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void cvt8_scaled(const float (&x)[8], half8& h) {
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        const half2v v = __builtin_convertvector(f32x2{x[e], x[e + 1]}, half2v);
+        h[e] = v[0]; h[e + 1] = v[1];
+    }
+}
+__device__ __forceinline__ void cvt8(const float (&x)[8], float p, half8& h) {
+    float y[8];
+    const f32x2 p2 = {p, p};
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        const f32x2 v = f32x2{x[e], x[e + 1]} * p2;
+        y[e] = v[0]; y[e + 1] = v[1];
+    }
+    cvt8_scaled(y, h);
+}
+// B operand of one K step in the precision of the instance: split into (hi, lo), or rounded once into hi
+template <bool F16>
+__device__ __forceinline__ void operand8(const float (&x)[8], float p, half8& hi, half8& lo) {
+    if constexpr (F16) cvt8(x, p, hi);
+    else split8(x, p, hi, lo);
+}
+
 // largest magnitude of a sample's values: the sample's row is spread over NT x 4 registers of the four lanes (s, q = 0..3)
 template <int NT, bool RELU>
 __device__ __forceinline__ float sample_max(const f32x4 (&v)[NT]) {
@@ -116,9 +153,17 @@ __device__ __forceinline__ float sample_max(const f32x4 (&v)[NT]) {
     return fmaxf(m, __shfl_xor(m, 32, 64));
 }
 
-// two output tiles x three split products, interleaved so consecutive MFMAs never share an accumulator
-template <int ABL = 0>
+// two output tiles x three split products, interleaved so consecutive MFMAs never share an accumulator.  F16: one product each, from
+// the compact tiles (w0, w1 one KB apart), blo unused
+template <int ABL = 0, bool F16 = false>
 __device__ __forceinline__ void mfma_pair(f32x4& c0, f32x4& c1, const float* w0, const float* w1, const half8& bhi, const half8& blo) {
+    if constexpr (F16) {
+        const half8 a0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0));
+        const half8 a1 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1));
+        c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bhi, c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bhi, c1, 0, 0, 0);
+        return;
+    }
     half8 ah0, ah1, al0, al1;
     if constexpr (ABL == 12 || ABL == 13) { ah0 = bhi; ah1 = blo; al0 = blo; al1 = bhi; }        // development build: no A-operand reads from LDS
     else {
@@ -163,16 +208,16 @@ __device__ __forceinline__ void store_rows(const f32x4 (&acc)[NT], float* row, i
 struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 // G0: index of the layer's first weight chunk.  The chunk order is static, so every chunk's place in the blob, its size and its LDS
 // buffer are constants here (resolving them at run time cost a chain of ~20 scalar branches per chunk).
-template <int NSRC, bool RELU, int ABL, int G0, int HOOK_OPS = 0, class Hook = NoHook>
+template <int NSRC, bool RELU, int ABL, int G0, bool F16 = false, int HOOK_OPS = 0, class Hook = NoHook>
 __device__ __forceinline__ void chained_layer(f32x4 (&acc)[kTD], const f32x4 (&src)[NSRC], float p, const float* __restrict__ blob,
                                               float* lds, int lane, int wave, Hook after = Hook()) {
-    constexpr int kSteps = NSRC / 2;
+    constexpr int kSteps = NSRC / 2, kTF = tile_floats<F16>(), kP = chunk_pieces<F16>();
 #pragma unroll
     for (int m0 = 0; m0 < kSteps; m0 += 2) {
         const int nks = m0 + 1 < kSteps ? 2 : 1;
         const int g = G0 + m0 / 2;
-        const float* wl = lds + kLdsW + (g & 1) * kChunkTiles * kTile + 4 * lane;
-        const NextChunk nx = next_chunk(blob, lds, g + 1);
+        const float* wl = lds + kLdsW + (g & 1) * kChunkTiles * kTF + 4 * lane;
+        const NextChunk nx = next_chunk<F16>(blob, lds, g + 1);
 #pragma unroll
         for (int kl = 0; kl < 2; ++kl) {
             if (kl < nks) {
@@ -184,18 +229,18 @@ __device__ __forceinline__ void chained_layer(f32x4 (&acc)[kTD], const f32x4 (&s
                     if (RELU) x[e] = fmaxf(x[e], 0.f);
                 }
                 half8 bhi, blo;
-                split8(x, p, bhi, blo);
+                operand8<F16>(x, p, bhi, blo);
 #pragma unroll
                 for (int q = 0; q < kTD / 2; ++q) {
-                    const float* w0 = wl + ((kl * kTD + 2 * q) * 2) * 256;
-                    mfma_pair<ABL>(acc[2 * q], acc[2 * q + 1], w0, w0 + 512, bhi, blo);
+                    const float* w0 = wl + (kl * kTD + 2 * q) * kTF;
+                    mfma_pair<ABL, F16>(acc[2 * q], acc[2 * q + 1], w0, w0 + kTF, bhi, blo);
                     // every DMA piece of the successor goes out in the first K step's four slots, ahead of the hook's memory
                     // operations: the chunk's closing "at most HOOK_OPS outstanding" must cover all of them
                     if (kl == 0) {
-                        if (q < 3) { if (q < kPieces) stream_issue_piece<ABL>(nx, q, lane, wave); }
+                        if (q < 3) { if (q < kP) stream_issue_piece<ABL>(nx, q, lane, wave); }
                         else {
 #pragma unroll
-                            for (int p_ = 3; p_ < kPieces; ++p_) stream_issue_piece<ABL>(nx, p_, lane, wave);
+                            for (int p_ = 3; p_ < kP; ++p_) stream_issue_piece<ABL>(nx, p_, lane, wave);
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -208,11 +253,13 @@ __device__ __forceinline__ void chained_layer(f32x4 (&acc)[kTD], const f32x4 (&s
 }
 
 // a K = 16 (+ folded bias) layer with 128 outputs: one K step, B operand (ghi, glo) prepared by the caller
+template <bool F16 = false>
 __device__ __forceinline__ void small_layer(f32x4 (&acc)[kTD], const half8& ghi, const half8& glo, const float* wl) {
+    constexpr int kTF = tile_floats<F16>();
 #pragma unroll
     for (int q = 0; q < kTD / 2; ++q) {
-        const float* w0 = wl + (2 * q * 2) * 256;
-        mfma_pair(acc[2 * q], acc[2 * q + 1], w0, w0 + 512, ghi, glo);
+        const float* w0 = wl + 2 * q * kTF;
+        mfma_pair<0, F16>(acc[2 * q], acc[2 * q + 1], w0, w0 + kTF, ghi, glo);
     }
 }
 

@@ -13,6 +13,11 @@
 
 extern "C" size_t car_fused_blob_floats(void);
 extern "C" size_t car_fused_bias_floats(void);
+extern "C" size_t car_fused_blob16_floats(void);
+extern "C" int car_fused_samples_f16(const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h, int lat_w,
+                                     int lat_pad, const float* gmeta, const float* wpt, const float* blob16, const float* bias, int b, int V, int R,
+                                     int P, int H, int W, int no_sample, float* e, float* g, float* logit, float* pt, float* pixel_val,
+                                     float* part, void* stream);
 extern "C" int car_fused_tile_steps(void);
 extern "C" size_t car_round2_packed_floats(void);
 extern "C" size_t car_round2_bias_floats(void);
@@ -91,6 +96,26 @@ __global__ void pack16_kernel(const float* __restrict__ W, int ldw, const float*
         _Float16* o = out + tile * 1024 + lane * 8 + e;
         o[0] = hi;
         o[512] = lo;
+    }
+}
+// The compact tiles of the fp16 precision (car_plan_f16_build): the same values and order as pack16_kernel's hi halves (rounded to
+// nearest after the layer's power of two), without the lo halves: per (K step, tile) [lane][8 halves], 1 KB.
+__global__ void pack16_hi_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ bias, int N, int K, int n_tiles,
+                                 int ksteps, int mode, int base, const float* __restrict__ p_slot, _Float16* __restrict__ out) {
+    const long total = (long)ksteps * n_tiles * 512;
+    const float p = p_slot[0];
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
+        const long tile = idx >> 9;
+        const int t = (int)(tile % n_tiles), ks = (int)(tile / n_tiles);
+        const int n = 16 * t + (lane & 15), q = lane >> 4;
+        const int k = mode == 0 ? 32 * ks + 8 * q + e : base + 16 * (2 * ks + e / 4) + 4 * q + e % 4;
+        float w = 0.0f;
+        if (n < N) {
+            if (k < K) w = W[(long)n * ldw + k] * p;
+            else if (k == K && bias) w = bias[n] * p;
+        }
+        out[idx] = (_Float16)w;
     }
 }
 // <Wa r + ba, Wb x + bb> = r^T (M x + v) + u^T x + c for two 128-wide layers that are only ever dotted with each other (the first round's
@@ -605,7 +630,12 @@ extern "C" int car_workspace_find(const car_dims* dims, const char* name, size_t
 
 // Packs the six layers of the fused per-sample kernel (csrc/car_fused.hip) into its operand order: fp16 hi/lo tiles, every layer
 // times its own power of two (chosen from its largest weight; 1/p goes into the bias table).  Asynchronous, device side only.
+// hi_only: the compact blob of the fp16 precision (pack16_hi_kernel), same bias table and point table.
+static int fused_pack(const car_weights* w, float* blob_f, float* bias, float* wpt, void* stream, bool hi_only);
 extern "C" int car_fused_pack(const car_weights* w, float* blob_f, float* bias, float* wpt, void* stream) {
+    return fused_pack(w, blob_f, bias, wpt, stream, false);
+}
+static int fused_pack(const car_weights* w, float* blob_f, float* bias, float* wpt, void* stream, bool hi_only) {
     CAR_REQUIRE(w && blob_f && bias && wpt, "car_fused_pack: null pointer");
     CAR_REQUIRE(w->query_encode_latent_w && w->query_encode_latent_b && w->query_encode_latent_2_w && w->query_encode_latent_2_b &&
                 w->key_map_w && w->key_map_b && w->key_map_2_w && w->key_map_2_b && w->query_embed_w && w->query_embed_b &&
@@ -620,6 +650,10 @@ extern "C" int car_fused_pack(const car_weights* w, float* blob_f, float* bias, 
         hipLaunchKernelGGL(layer_scale_kernel, dim3(1), dim3(1024), 0, st, W, ldw, N, K, b, pscale + layer, fdown + layer);
     };
     auto pack16 = [&](const float* W, int ldw, const float* b, int N, int K, int n_tiles, int ksteps, int mode, int kbase, int layer, int tile_off) {
+        if (hi_only)
+            hipLaunchKernelGGL(pack16_hi_kernel, dim3(256), dim3(256), 0, st, W, ldw, b, N, K, n_tiles, ksteps, mode, kbase, pscale + layer,
+                               blob + (size_t)tile_off * kTileHi * 2);
+        else
         hipLaunchKernelGGL(pack16_kernel, dim3(256), dim3(256), 0, st, W, ldw, b, N, K, n_tiles, ksteps, mode, kbase, pscale + layer,
                            blob + (size_t)tile_off * kTile16 * 2);
     };
@@ -815,6 +849,32 @@ extern "C" int car_plan_build(const car_dims* dims, const car_weights* w, void* 
     return CAR_OK;
 }
 
+// ---- the fp16 precision's plan (car_plan_f16_*): the fused kernel's compact blob, its bias table and point table ----------
+struct Plan16 { size_t blob, fbias, wpt, total; };                 // offsets in floats
+Plan16 plan16_layout() {
+    Plan16 p;
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t at = o; o += up64(n); return at; };
+    p.blob = take(car_fused_blob16_floats());
+    p.fbias = take(car_fused_bias_floats());
+    p.wpt = take((size_t)kC * 4);
+    p.total = o;
+    return p;
+}
+extern "C" size_t car_plan_f16_bytes(const car_dims* dims) {
+    if (check_dims(dims, "car_plan_f16_bytes") != CAR_OK) return 0;
+    return plan16_layout().total * sizeof(float);
+}
+extern "C" int car_plan_f16_build(const car_dims* dims, const car_weights* w, void* plan16, void* stream) {
+    CAR_TRY(check_dims(dims, "car_plan_f16_build"));
+    CAR_REQUIRE(w && plan16, "car_plan_f16_build: null pointer");
+    CAR_REQUIRE(car_fused_blob16_floats() == (size_t)kBlobTiles * kTileHi && car_fused_bias_floats() == (size_t)(kBiasFloats + kBiasScratch),
+                "car_plan_f16_build: the fused kernel was built with another weight layout");
+    const Plan16 p = plan16_layout();
+    float* base = static_cast<float*>(plan16);
+    return fused_pack(w, base + p.blob, base + p.fbias, base + p.wpt, stream, true);
+}
+
 extern "C" int car_project_maps(const car_dims* dims, const void* plan, const float* const* maps, float* gmaps, void* stream) {
     CAR_TRY(check_dims(dims, "car_project_maps"));
     CAR_REQUIRE(plan && maps && gmaps, "car_project_maps: null pointer");
@@ -879,8 +939,9 @@ extern "C" int car_merge_lattice_max(const float* const* levels, const int* leve
 
 // the launches of one forward call in two phases: CAR_PHASE_SAMPLES = rays + the fused per-sample kernel (compute / power bound),
 // CAR_PHASE_RAYS = the attention rounds and the per-ray chains (HBM bound), which only read what the first phase left in the workspace
+// plan16 (car_plan_f16_build) non-null: the fused kernel's fp16 instance; every other launch is the fp32 route's own
 static int render_phases(const car_dims* dims, const void* plan, const car_inputs* in, const car_outputs* out,
-                         void* workspace, size_t workspace_bytes, int phases, void* stream) {
+                         void* workspace, size_t workspace_bytes, int phases, void* stream, const void* plan16 = nullptr) {
     CAR_TRY(check_dims(dims, "car_render_forward"));
     CAR_REQUIRE(plan && in && out && workspace, "car_render_forward: null pointer");
     CAR_REQUIRE(in->poses && in->uv && in->lattice && in->gmeta && out->rgb, "car_render_forward: poses, uv, lattice, gmeta and rgb are required");
@@ -913,7 +974,13 @@ static int render_phases(const car_dims* dims, const void* plan, const car_input
     {   // a6-a13 + round-1 logits: the fused per-sample kernel
         Stage stage("fused_samples", st);
         const Lattice L = lattice_of(d);
-        if (rows_first)
+        if (plan16) {
+            const Plan16 q = plan16_layout();
+            const float* p16 = static_cast<const float*>(plan16);
+            CAR_TRY(car_fused_samples_f16(in->poses, ws + w.rays, steps, in->lattice, L.h, L.w, L.pad, in->gmeta, p16 + q.wpt, p16 + q.blob,
+                                          p16 + q.fbias, b, V, R, P, d.H, d.W, d.no_sample != 0, ws + w.e, ws + w.g, ws + w.logit, ws + w.pt, pixel_val,
+                                          rows_first ? nullptr : ws + w.part, stream));
+        } else if (rows_first)
             CAR_TRY(car_fused_samples(in->poses, ws + w.rays, steps, in->lattice, L.h, L.w, L.pad, in->gmeta, pl + p.wpt, pl + p.blob,
                                       pl + p.fbias, b, V, R, P, d.H, d.W, d.no_sample != 0, ws + w.e, ws + w.g, ws + w.logit, ws + w.pt, pixel_val, stream));
         else
@@ -986,4 +1053,15 @@ extern "C" int car_render_forward_phase(const car_dims* dims, const void* plan, 
     CAR_REQUIRE(which == CAR_PHASE_SAMPLES || which == CAR_PHASE_RAYS || which == (CAR_PHASE_SAMPLES | CAR_PHASE_RAYS),
                 "car_render_forward_phase: phases = %d (CAR_PHASE_SAMPLES, CAR_PHASE_RAYS or both, optionally | CAR_PHASE_ROWS_FIRST_ROUND)", phases);
     return render_phases(dims, plan, in, out, workspace, workspace_bytes, phases, stream);
+}
+
+// The opt-in fp16 precision of the same forward: the fused per-sample kernel takes one product per term from plan16 (car_plan_f16_build);
+// plan still supplies the sample positions, the round-2 packing and the per-ray chains.  Phases and flags as car_render_forward_phase.
+extern "C" int car_render_forward_f16(const car_dims* dims, const void* plan, const void* plan16, const car_inputs* in, const car_outputs* out,
+                                      void* workspace, size_t workspace_bytes, int phases, void* stream) {
+    CAR_REQUIRE(plan16, "car_render_forward_f16: null plan16");
+    const int which = phases & ~CAR_PHASE_ROWS_FIRST_ROUND;
+    CAR_REQUIRE(which == CAR_PHASE_SAMPLES || which == CAR_PHASE_RAYS || which == (CAR_PHASE_SAMPLES | CAR_PHASE_RAYS),
+                "car_render_forward_f16: phases = %d (CAR_PHASE_SAMPLES, CAR_PHASE_RAYS or both, optionally | CAR_PHASE_ROWS_FIRST_ROUND)", phases);
+    return render_phases(dims, plan, in, out, workspace, workspace_bytes, phases, stream, plan16);
 }

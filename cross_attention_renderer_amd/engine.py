@@ -129,11 +129,40 @@ class RenderEngine:
         self._plan_key = None
         self._plan: Optional[Tensor] = None
         self._plan_keep: List[Tensor] = []
+        self._plan_w = None            # the car_weights struct of the current plan (its tensors: _plan_keep)
+        self._plan16_key = None        # fp16 precision: car_plan_f16_build's plan, cached under the fp32 plan's key
+        self._plan16: Optional[Tensor] = None
+        self.last_precision = None     # "fp32" / "fp16": the arithmetic of the last forward's fused per-sample kernel
         self._pair_key = None
         self._xlat = None              # merged lattice of the three-view exchange (car_merge_lattice), cached like the projected maps
         self._xlat_key = None
         self._pair: Optional[Tensor] = None
         self._work: Optional[Tensor] = None
+
+    @property
+    def render_precision(self) -> str:
+        """-> the module's ``render_precision`` ("fp32", the default, or the opt-in "fp16": DESIGN.md 4.11)."""
+        p = getattr(self.m, "render_precision", "fp32")
+        if p not in ("fp32", "fp16"):
+            raise ValueError(f"render_precision must be 'fp32' or 'fp16' (got {p!r})")
+        return p
+
+    def _one_call_refusal(self, b: int, R: int, z: List[Tensor]) -> Optional[str]:
+        """Why this forward cannot take the one-call route (None: it can).  The fp16 precision exists on that route only."""
+        m = self.m
+        if not (self.fuse_samples and self.project_maps):
+            return "the engine's fuse_samples / project_maps switches select the stage route"
+        if m.n_view != 2:
+            return f"n_view = {m.n_view} (the one-call route renders two context views)"
+        if m.no_latent_concat:
+            return "no_latent_concat (the one-call route concatenates the two views' latents)"
+        if len(z) != 3 or sum(t.shape[1] for t in z) != 576 or m.hidden_dim != 128 or m.phi.n_blocks != 3 or m.phi.d_hidden != 128:
+            return "widths other than midas_vit's (three pyramid levels of 576 channels in all, hidden width 128, three decoder blocks)"
+        if not self._common_lattice(z):
+            return "a pyramid whose levels have no common lattice (each must be an integer factor coarser than the widest, same in both directions)"
+        if not self._lattice_fits(b, R, z):
+            return "a lattice beyond 2 GiB per view and padding mode (finest level wider than ~470 pixels)"
+        return None
 
     @property
     def pose_route(self) -> str:
@@ -465,9 +494,24 @@ class RenderEngine:
             _lib.check(-1, "car_plan_bytes")
         plan = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
         _lib.check(lib.car_plan_build(ctypes.byref(d), ctypes.byref(w), _ptr(plan), _stream()), "car_plan_build")
-        self._plan, self._plan_key, self._plan_keep = plan, key, keep
+        self._plan, self._plan_key, self._plan_keep, self._plan_w = plan, key, keep, w
         self._pair_key = None
         return plan
+
+    def _plan16_for(self, d, device) -> Tensor:
+        """car_plan_f16_build: the fused kernel's compact fp16 layers, built from the same weights as the current fp32 plan and cached
+        under its key (so a change of the parameters rebuilds both).  Call after _plan_for."""
+        if self._plan16 is not None and self._plan16_key == self._plan_key:
+            return self._plan16
+        lib = self.lib
+        nbytes = lib.car_plan_f16_bytes(ctypes.byref(d))
+        if nbytes == 0:
+            _lib.check(-1, "car_plan_f16_bytes")
+        self._plan16 = None
+        plan16 = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+        _lib.check(lib.car_plan_f16_build(ctypes.byref(d), ctypes.byref(self._plan_w), _ptr(plan16), _stream()), "car_plan_f16_build")
+        self._plan16, self._plan16_key = plan16, self._plan_key
+        return plan16
 
     def _pair_for(self, plan: Tensor, z: List[Tensor], device, s0: int, s1: int, R: int):
         """car_project_maps for scenes [s0, s1): the first point-MLP layer applied per texel of the pyramid and every level summed on the
@@ -519,6 +563,8 @@ class RenderEngine:
         n = b * V
         d_all = self._dims(b, R, z)
         plan = self._plan_for(d_all, dev)
+        f16 = self.render_precision == "fp16"
+        plan16 = self._plan16_for(d_all, dev) if f16 else None
         lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _lib.check(lib.car_lattice_shape(ctypes.byref(d_all), ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad)), "car_lattice_shape")
         lattice_scene = V * 2 * lh.value * lw.value * 576                                        # floats per scene
@@ -611,7 +657,10 @@ class RenderEngine:
                     ci.gmeta = gmeta_ptr
                     ci.steps = steps.data_ptr()
                     co = _lib.CarOutputs(*[tgt[k].data_ptr() for k in order])
-                    if phases == 3:
+                    if f16:
+                        _lib.check(lib.car_render_forward_f16(ctypes.byref(d), _ptr(plan), _ptr(plan16), ctypes.byref(ci), ctypes.byref(co),
+                                                              _ptr(work), work.numel() * 4, phases, st), "car_render_forward_f16")
+                    elif phases == 3:
                         _lib.check(lib.car_render_forward(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co),
                                                           _ptr(work), work.numel() * 4, st), "car_render_forward")
                     else:
@@ -624,6 +673,7 @@ class RenderEngine:
                     calls += 1
                     d_last = d
         self.last_calls = calls
+        self.last_precision = "fp16" if f16 else "fp32"
         res = {
             "rgb": out["rgb"], "valid_mask": out["valid_mask"], "depth_ray": out["depth_ray"], "at_wt": out["at_wt"],
             "at_wts": [out["at_wt"]], "at_wt_max": out["at_wt_max"].long(), "coords": out["coords"], "uv": inp["query"]["uv"],
@@ -743,11 +793,18 @@ class RenderEngine:
         steps = self._linspace(0.1, 10.0, P, dev) if m.no_sample else self._linspace(0.0, 1.0, P, dev)
 
         concat2 = (V == 2 and not m.no_latent_concat)
+        if self.render_precision == "fp16":
+            why = self._one_call_refusal(b, R, z)
+            if why is not None:
+                raise ValueError(f"render_precision='fp16' exists on the one-call route only, and this forward cannot take it: {why}. "
+                                 "Set render_precision='fp32' for this configuration.")
+            return self._render_one_call(inp, z, poses, uv, steps, b, V, R, P, H, W, debug)
         if (self.fuse_samples and self.project_maps and concat2 and len(z) == 3
                 and sum(t.shape[1] for t in z) == 576 and m.hidden_dim == 128 and m.phi.n_blocks == 3 and m.phi.d_hidden == 128
                 and self._common_lattice(z) and self._lattice_fits(b, R, z)):
             return self._render_one_call(inp, z, poses, uv, steps, b, V, R, P, H, W, debug)
 
+        self.last_precision = "fp32"
         pk = self._weights(dev)
         maps = self._channel_last(z)
         C = sum(t.shape[3] for t in maps)

@@ -140,6 +140,20 @@ class CrossAttentionRenderer(nn.Module):
         # where forward's 4x4 pose algebra runs (engine._poses): "host" = the reference's torch.inverse on the CPU wherever the camera
         # tensors live (strict parity, the default); "device" = car_pose_setup on the GPU when the cameras are there (opt-in)
         self.pose_route = "host"
+        # arithmetic of the inference forward's fused per-sample kernel: "fp32" (the default, 1e-4 parity with the reference) or the opt-in
+        # "fp16" (one fp16 product per term; preview frames and trajectory videos — DESIGN.md 4.11).  "fp16" exists on the one-call route
+        # only (two views, midas_vit widths, a common lattice): any other forward raises instead of falling back; training refuses it
+        self.render_precision = "fp32"
+
+    @property
+    def render_precision(self) -> str:
+        return self._render_precision
+
+    @render_precision.setter
+    def render_precision(self, value: str) -> None:
+        if value not in ("fp32", "fp16"):
+            raise ValueError(f"render_precision must be 'fp32' or 'fp16' (got {value!r})")
+        self._render_precision = value
 
     # ------------------------------------------------------------------------------------------
     def get_z(self, input, val=False) -> List[Tensor]:

@@ -461,6 +461,9 @@ def render_train(module, inp, z: Optional[List[Tensor]] = None) -> Dict[str, Ten
     ``rgb`` and ``depth_ray`` carry gradients to the renderer's parameters and to ``z`` (``z=None``: ``get_z`` runs under autograd, so
     the encoder trains too)."""
     m = module
+    if getattr(m, "render_precision", "fp32") != "fp32":
+        raise ValueError(f"render_train: render_precision={m.render_precision!r} is an inference setting; training runs in fp32 "
+                         "(set render_precision='fp32')")
     if m.n_view not in (1, 2, 3):
         raise NotImplementedError("render_train covers one, two or three context views (the reference's n_view)")
     dev = inp["query"]["uv"].device

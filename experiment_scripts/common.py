@@ -50,6 +50,15 @@ def parser(description: str) -> argparse.ArgumentParser:
     return p
 
 
+def add_precision(p):
+    """--precision of the inference scripts (render / eval): the arithmetic of the fused per-sample kernel (model.render_precision)."""
+    p.add_argument("--precision", choices=("fp32", "fp16"), default="fp32",
+                   help="fp32 = 1e-4 parity with the reference (default); fp16 = the opt-in reduced precision of the two-view one-call route "
+                        "(one fp16 product per term in the fused per-sample kernel, ~25 %% faster frames, errors far below an 8-bit frame's "
+                        "step; DESIGN.md 4.11).  Configurations off that route refuse fp16 instead of falling back")
+    return p
+
+
 def build_model(opt, device, with_encoder=None):
     """The renderer; with a checkpoint (or --with_encoder) the multi-view DPT encoder is built too, so that ``get_z`` runs on the
     context images.  Loading follows the reference (strict unless --reconstruct, eval_realestate10k.py:110-118) and FAILS on keys that
@@ -78,6 +87,7 @@ def build_model(opt, device, with_encoder=None):
                     p_.add_(0.02 * torch.randn(p_.shape, generator=g))
     model.H = model.W = opt.img_sidelength
     model.pose_route = "device" if getattr(opt, "cameras", "host") == "device" else "host"
+    model.render_precision = getattr(opt, "precision", "fp32")
     return model.to(device)
 
 

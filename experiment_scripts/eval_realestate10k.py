@@ -78,8 +78,9 @@ def evaluate(rank, opt, default_data=DEFAULT_DATA):
             print(f"item {k}: elapsed {elapsed:.3f} s, {what} {psnrs[-1]:.2f} dB, valid {tile[0, :, 4].mean().item():.3f}")
     if rank == 0 and psnrs:
         print("mean psnr", sum(min(p, 200.0) for p in psnrs) / len(psnrs))
+        print("render precision", model.render_precision)
 
 
 if __name__ == "__main__":
-    opt = common.parser(__doc__).parse_args()
+    opt = common.add_precision(common.parser(__doc__)).parse_args()
     common.spawn(evaluate, opt)

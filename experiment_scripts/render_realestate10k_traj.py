@@ -79,5 +79,5 @@ def render(rank, opt):
 
 
 if __name__ == "__main__":
-    opt = common.parser(__doc__).parse_args()
+    opt = common.add_precision(common.parser(__doc__)).parse_args()
     common.spawn(render, opt)

@@ -70,7 +70,7 @@ def render(rank, opt):
 
 
 if __name__ == "__main__":
-    p = common.parser(__doc__)
+    p = common.add_precision(common.parser(__doc__))
     p.add_argument("--im1", type=str, default=None)
     p.add_argument("--im2", type=str, default=None)
     p.add_argument("--pose", type=str, default=None, help=".npz with R (3,3), t (3,) of the second camera relative to the first")

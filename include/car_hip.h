@@ -451,6 +451,21 @@ int car_render_forward(const car_dims* dims, const void* plan, const car_inputs*
 #define CAR_PHASE_ROWS_FIRST_ROUND 4
 int car_render_forward_phase(const car_dims* dims, const void* plan, const car_inputs* in, const car_outputs* out,
                              void* workspace, size_t workspace_bytes, int phases, void* stream);
+/* Opt-in fp16 render precision of the same forward.  Off unless a host asks for it; the entries above are unchanged.
+ *   car_plan_f16_bytes / car_plan_f16_build   once per set of weights, next to the fp32 plan: the fused per-sample kernel's layers as
+ *                                       compact fp16 tiles (one half per weight, rounded to nearest after the layer's power of two) with
+ *                                       their bias / scale table (car_plan_f16_build reads the same car_weights as car_plan_build)
+ *   car_render_forward_f16              car_render_forward_phase with the fused kernel's fp16 instance: one v_mfma_f32_16x16x32_f16
+ *                                       product per term instead of three, B operands rounded to nearest fp16 after the same powers of
+ *                                       two, fp32 accumulation.  `plan` (car_plan_build) still supplies the sample positions, the second
+ *                                       round and the per-ray chains, which run as in fp32.  Same phases and flags, same workspace.
+ * Results: coords, pixel_val and valid_mask are bit-identical to the fp32 route (geometry is untouched); e, the logits and everything
+ * computed from them differ by fp16 rounding (tests/test_render_fp16.py: rgb PSNR >= 60 dB, |rgb| <= 1e-2, |depth_ray| <= 5e-3,
+ * |at_wt| <= 1e-4 on the fixtures).  Not for training. */
+size_t car_plan_f16_bytes(const car_dims* dims);
+int car_plan_f16_build(const car_dims* dims, const car_weights* weights, void* plan16, void* stream);
+int car_render_forward_f16(const car_dims* dims, const void* plan, const void* plan16, const car_inputs* in, const car_outputs* out,
+                           void* workspace, size_t workspace_bytes, int phases, void* stream);
 /* Where a named intermediate lives inside the workspace after car_render_forward (tests, debugging, profiling): one of
  * "rays" "e" "g" "logit" "logit2" "pt" "at_wt2" "ebar" "z1" "uh" "part".  Returns 0 and the float offset / count. */
 int car_workspace_find(const car_dims* dims, const char* name, size_t* offset_floats, size_t* n_floats);
