@@ -11,8 +11,9 @@ Two routes:
     ``car_render_forward`` per batch of rays (csrc/car_render.hip: weight packing and the launch sequence are C++).  This
     module only sizes the calls: rays (and, if need be, scenes) are chunked so that the per-call workspace fits the free device
     memory (rays and scenes are independent, so this changes nothing);
-  * the other constructor variants (n_view 1 / 3, no_latent_concat, other widths) are sequenced here stage by stage —
-    also the A/B partner of the first route in the tests.
+  * the other constructor variants (n_view 1 / 3, no_latent_concat, other widths) are sequenced here stage by stage
+    (``RenderEngine._staged``) — also the A/B partner of the first route in the tests.  The training forward (training.render_train)
+    is the same method with a save dict: the literal stage forms, every activation its backward reads kept.
 
 Stage map:
   a3 poses.pack_poses (host, torch.inverse like the reference)          a11-a13, a15, a17  car_linear (fp32 MFMA)
@@ -67,6 +68,15 @@ class PackedLinear:
             tiles = torch.empty(lib.car_linear_x3_packed_floats(self.K, self.N), device=device, dtype=torch.float32)
             _lib.check(lib.car_linear_x3_pack(_ptr(w), self.K, self.K, self.N, _ptr(tiles), _stream()), "car_linear_x3_pack")
             self.x3 = (tiles, bdev)
+
+
+def _mode(m) -> str:
+    """How the staged forward makes the per-sample features e: "concat2" (two views, point MLP over own ‖ other features), "concat3"
+    (the three-view exchange), "single" (one view, update_val_merge over features ‖ point channels), "plain" (no_latent_concat: the
+    gathered features themselves)."""
+    if m.no_latent_concat:
+        return "plain"
+    return {1: "single", 2: "concat2", 3: "concat3"}[m.n_view]
 
 
 class RenderEngine:
@@ -253,9 +263,10 @@ class RenderEngine:
         forward that later receives these very tensors waits for the side stream's event and finds its lattice ready.  Needs a plan (one
         forward with the current weights) and room for a second lattice; returns False — and does nothing — otherwise, or when ``z`` is the
         pyramid already in place.  Same kernels, same arguments, same results as the projection inside forward."""
-        m = self.m
-        if (self._plan is None or not self.fuse_samples or not self.project_maps or m.n_view != 2 or len(z) != 3 or z[0].device.type != "cuda"
-                or sum(t.shape[1] for t in z) != 576 or not self._common_lattice(z)):
+        if self._plan is None or not z or z[0].device.type != "cuda":
+            return False
+        b = z[0].shape[0] // self.m.n_view
+        if self._one_call_refusal(b, 48, z) is not None:
             return False
         key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in z)
         if key == self._maps_key and self._pair is not None:
@@ -265,13 +276,11 @@ class RenderEngine:
         if key in self._pf and all(a is b_ for a, b_ in zip(self._pf[key]["src"], z)):
             return True
         dev = z[0].device
-        V = m.n_view
-        b = z[0].shape[0] // V
         d = self._dims(b, 48, z)
         if d.P != self._plan_key[1] or tuple(d.level_c[:3]) != self._plan_key[2]:
             return False
         need = 4 * self.lib.car_gmaps_floats(ctypes.byref(d))
-        if need == 0 or not self._lattice_fits(b, 48, z) or need > self._free_budget(dev) // 3:
+        if need == 0 or need > self._free_budget(dev) // 3:
             return False                                             # another lattice must leave the workspace its room
         with torch.cuda.device(dev):
             if self._pf_stream is None:
@@ -556,8 +565,28 @@ class RenderEngine:
     def _workspace_budget(self, device) -> int:
         return int(self.max_workspace_bytes) if self.max_workspace_bytes is not None else self._free_budget(device)
 
-    def _render_one_call(self, inp, z, poses, uv, steps, b, V, R, P, H, W, debug) -> Dict[str, Tensor]:
+    def _rays_in(self, inp, b: int, R: int):
+        """a3: the pose records, the query pixels [b, R, 2] and the P sample steps of a forward."""
+        m = self.m
+        dev = inp["query"]["uv"].device
+        poses = self._poses(inp, m.H, b * m.n_view, dev)
+        uv = inp["query"]["uv"].detach().reshape(b, R, 2).float().contiguous()
+        steps = self._linspace(0.1, 10.0, m.npoints, dev) if m.no_sample else self._linspace(0.0, 1.0, m.npoints, dev)
+        return poses, uv, steps
+
+    @staticmethod
+    def _outputs(inp, z: List[Tensor], t: Dict[str, Tensor], debug: bool) -> Dict[str, Tensor]:
+        """The forward's output dict (models.py:570-621) from the seven tensors both routes write (``t``, keyed by output name)."""
+        return {"rgb": t["rgb"], "valid_mask": t["valid_mask"], "depth_ray": t["depth_ray"], "at_wt": t["at_wt"], "at_wts": [t["at_wt"]],
+                "at_wt_max": t["at_wt_max"].long(), "coords": t["coords"], "uv": inp["query"]["uv"],
+                # the reference returns pixel_val on the CPU (models.py:570), forcing a device sync on every call; here it stays on the
+                # device unless debug is set
+                "pixel_val": t["pixel_val"].cpu() if debug else t["pixel_val"], "z": z}
+
+    def _render_one_call(self, inp, z, b: int, R: int, debug: bool) -> Dict[str, Tensor]:
         m, lib = self.m, self.lib
+        V, P = m.n_view, m.npoints
+        poses, uv, steps = self._rays_in(inp, b, R)
         dev = uv.device
         f32 = dict(device=dev, dtype=torch.float32)
         n = b * V
@@ -674,13 +703,7 @@ class RenderEngine:
                     d_last = d
         self.last_calls = calls
         self.last_precision = "fp16" if f16 else "fp32"
-        res = {
-            "rgb": out["rgb"], "valid_mask": out["valid_mask"], "depth_ray": out["depth_ray"], "at_wt": out["at_wt"],
-            "at_wts": [out["at_wt"]], "at_wt_max": out["at_wt_max"].long(), "coords": out["coords"], "uv": inp["query"]["uv"],
-            # the reference returns pixel_val on the CPU (models.py:570), forcing a device sync on every call; here it stays on the
-            # device unless debug is set
-            "pixel_val": out["pixel_val"].cpu() if debug else out["pixel_val"], "z": z,
-        }
+        res = self._outputs(inp, z, out, debug)
         if debug:
             if calls != 1:
                 raise RuntimeError("debug=True needs the forward to fit one car_render_forward call (intermediates live in its workspace)")
@@ -773,48 +796,51 @@ class RenderEngine:
             return self._render(inp, z, debug)
 
     def _render(self, inp, z: List[Tensor], debug: bool) -> Dict[str, Tensor]:
-        m, lib = self.m, self.lib
-        ctx, qry = inp["context"], inp["query"]
-        uv_in = qry["uv"]
-        dev = uv_in.device
-        b, V = ctx["rgb"].shape[:2]
-        n_qry, R = uv_in.shape[1:3]
+        m = self.m
+        b, V = inp["context"]["rgb"].shape[:2]
+        n_qry, R = inp["query"]["uv"].shape[1:3]
         if n_qry != 1:
             raise ValueError("forward supports one query view per scene (reference models.py:213, 619)")
         if V != m.n_view:
             raise ValueError(f"input has {V} context views, module was built with n_view={m.n_view}")
+        why = self._one_call_refusal(b, R, z)
+        if why is None:
+            return self._render_one_call(inp, z, b, R, debug)
+        if self.render_precision == "fp16":
+            raise ValueError(f"render_precision='fp16' exists on the one-call route only, and this forward cannot take it: {why}. "
+                             "Set render_precision='fp32' for this configuration.")
+        self.last_precision = "fp32"
+        return self._staged(inp, z, debug)
+
+    def _staged(self, inp, z: List[Tensor], debug: bool = False, save: Optional[dict] = None) -> Dict[str, Tensor]:
+        """The stage-by-stage forward of every configuration the one-call route does not take.
+
+        ``save=None``: inference, with the fused stage kernels the engine's switches select and buffers reused where nothing is kept.
+        ``save`` a dict: the training forward (training.render_train) — the literal forms (gather -> GEMM, five key / query launches, the
+        unfused second round, a copy of the decoder's state per block), every activation its backward reads stored into ``save``."""
+        m, lib = self.m, self.lib
+        keep = save is not None
+        dev = inp["query"]["uv"].device
+        b, V = inp["context"]["rgb"].shape[:2]
+        R = inp["query"]["uv"].shape[2]
         P, H, W = m.npoints, m.H, m.W
-        n, S = b * V, b * V * R * P
+        n, S, bR = b * V, b * V * R * P, b * R
         st = _stream()
         f32 = dict(device=dev, dtype=torch.float32)
         # a3: pose algebra on the host, exactly the reference's torch calls
-        poses = self._poses(inp, H, n, dev)
-        uv = uv_in.detach().reshape(b, R, 2).float().contiguous()
-        steps = self._linspace(0.1, 10.0, P, dev) if m.no_sample else self._linspace(0.0, 1.0, P, dev)
-
-        concat2 = (V == 2 and not m.no_latent_concat)
-        if self.render_precision == "fp16":
-            why = self._one_call_refusal(b, R, z)
-            if why is not None:
-                raise ValueError(f"render_precision='fp16' exists on the one-call route only, and this forward cannot take it: {why}. "
-                                 "Set render_precision='fp32' for this configuration.")
-            return self._render_one_call(inp, z, poses, uv, steps, b, V, R, P, H, W, debug)
-        if (self.fuse_samples and self.project_maps and concat2 and len(z) == 3
-                and sum(t.shape[1] for t in z) == 576 and m.hidden_dim == 128 and m.phi.n_blocks == 3 and m.phi.d_hidden == 128
-                and self._common_lattice(z) and self._lattice_fits(b, R, z)):
-            return self._render_one_call(inp, z, poses, uv, steps, b, V, R, P, H, W, debug)
-
-        self.last_precision = "fp32"
+        poses, uv, steps = self._rays_in(inp, b, R)
         pk = self._weights(dev)
         maps = self._channel_last(z)
         C = sum(t.shape[3] for t in maps)
-        Dl = m.latent_dim
+        mode = _mode(m)
+        Dl, hid = m.latent_dim, m.phi.d_hidden
+        Ce = V * (C // 2) if mode in ("concat2", "concat3") else C
 
-        # a4-a6: rays
+        # a4-a6: rays (constant with respect to every parameter, like the rest of the geometry)
         rays = torch.empty(n, R, 12, **f32)
         coords9 = torch.empty(n, R, 9, **f32)
         ld_phi = _round_up(9 * V, 4)
-        phi_x = torch.zeros(b * R, ld_phi, **f32)
+        phi_x = torch.zeros(bR, ld_phi, **f32)
         _lib.check(lib.car_ray_setup(_ptr(poses), _ptr(uv), b, V, R, H, W, P, int(m.no_sample), _ptr(steps),
                                      _ptr(rays), _ptr(coords9), _ptr(phi_x), ld_phi, st), "car_ray_setup")
 
@@ -822,40 +848,31 @@ class RenderEngine:
         pixel_val = torch.empty(n, R, P, 2, **f32)
         pt = torch.empty(n, R, P, 3, **f32)
         g = torch.empty(S, 16, **f32)
-        single = (V == 1 and not m.no_latent_concat)
-        concat3 = (V == 3 and not m.no_latent_concat)
-        kmajor = False
-        grid_in = torch.empty(n, R, P, V, 2, **f32) if concat2 else None
-        pt_in = torch.empty(n, R, P, V, 3, **f32) if concat3 else None
-        x1 = None
-        proj = concat2 and self.project_maps
-        if proj:
-            ld1 = 4                                   # only the 3 point channels: [S*V, 4]
+        proj = mode == "concat2" and self.project_maps and not keep     # the first point-MLP layer per texel (car_gather_encode)
+        grid_in = torch.empty(n, R, P, V, 2, **f32) if mode == "concat2" else None
+        pt_in = torch.empty(n, R, P, V, 3, **f32) if mode == "concat3" else None
+        x1, ld1, col = None, 0, 0
+        if proj or mode == "concat3":
+            ld1 = 4                                   # only the 3 point channels: [S*V, 4]; the three-view route assembles its rows below
             x1 = torch.zeros(S * V, ld1, **f32)
-        elif concat3:
-            ld1 = 4                                   # point channels only; the 579-wide rows are assembled below
-            x1 = torch.zeros(S * V, ld1, **f32)
-        elif concat2:
-            ld1 = _round_up(C + 3, 32)
+        elif mode in ("concat2", "single"):
+            col = C                                   # features in [0, C), point channels in [C, C + 3) (two views) or [C, C + 6) (one)
+            ld1 = _round_up(C + (3 if mode == "concat2" else 6), 32)
             x1 = torch.empty(S * V, ld1, **f32)
-        elif single:
-            ld1 = _round_up(C + 6, 32)
-            x1 = torch.empty(S, ld1, **f32)
+            if keep:
+                x1[:, C + (3 if mode == "concat2" else 6):].zero_()     # the row padding: the backward reads whole rows
         _lib.check(lib.car_sample_setup(_ptr(poses), _ptr(rays), _ptr(steps), b, V, R, P, H, W, int(m.no_sample),
-                                        _ptr(pixel_val), _ptr(pt), _ptr(g), _ptr(grid_in), _ptr(x1),
-                                        ld1 if x1 is not None else 0, 0 if (proj or concat3) else C, _ptr(pt_in), st),
+                                        _ptr(pixel_val), _ptr(pt), _ptr(g), _ptr(grid_in), _ptr(x1), ld1, col, _ptr(pt_in), st),
                    "car_sample_setup")
 
         # a7, a9-a11: per-sample features e
+        h1 = grid_other = cross = None
+        kmajor = False
         if proj:
             gmaps, wpt = self._projected_maps(maps, dev)
             h1 = torch.empty(S * V, C, **f32)
             self.gather_encode(gmaps, wpt, pixel_val, grid_in, x1, V, R * P, h1, C)
-            e = torch.empty(S, V * (C // 2), **f32)
-            self.linear(h1, C, pk["query_encode_latent_2"], e, C // 2, S * V)
-            del h1
-            Ce = V * (C // 2)
-        elif concat2:
+        elif mode == "concat2":
             self.gather(maps, pixel_val, R * P, 0, PLACE_OWN, V, x1, ld1, 0, run=P)
             gi = grid_in.view(b, V, R, P, V, 2)
             # pixel_val_stack (models.py:316): map (b, s) is sampled where the *other* line's points land in view s
@@ -863,31 +880,33 @@ class RenderEngine:
             self.gather(maps, grid_other, R * P, 1, PLACE_OTHER2, V, x1, ld1, 0, run=P)
             h1 = torch.empty(S * V, C, **f32)
             self.linear(x1, ld1, pk["query_encode_latent"], h1, C, S * V, RELU_OUT)
-            e = torch.empty(S, V * (C // 2), **f32)
+        if mode == "concat2":
+            e = torch.empty(S, Ce, **f32)
             self.linear(h1, C, pk["query_encode_latent_2"], e, C // 2, S * V)
-            del h1
-            Ce = V * (C // 2)
-        elif concat3:
-            e = self._encode_three_views(maps, poses, pixel_val, x1, pt_in, b, R, P, H, W, C, pk)
-            Ce = 3 * (C // 2)
-            kmajor = self.project_maps                              # the inference path of _encode_three_views leaves e component-major
-        elif single:
+        elif mode == "concat3":
+            k3 = {} if keep else None
+            e = self._encode_three_views(maps, poses, pixel_val, x1, pt_in, b, R, P, H, W, C, pk, keep=k3)
+            kmajor = self.project_maps and not keep                   # the inference path of _encode_three_views leaves e component-major
+            if keep:
+                x1, h1, ld1, cross = k3["x3"], k3["h1"], k3["ld"], k3["cross"]
+        elif mode == "single":
             self.gather(maps, pixel_val, R * P, 0, PLACE_PLAIN, V, x1, ld1, 0, run=P)
-            e = torch.empty(S, C, **f32)
-            self.linear(x1, ld1, pk["update_val_merge"], e, C, S)
-            Ce = C
-        else:
-            e = torch.empty(S, C, **f32)
-            self.gather(maps, pixel_val, R * P, 0, PLACE_PLAIN, V, e, C, 0, run=P)
-            Ce = C
-        del x1
+            e = torch.empty(S, Ce, **f32)
+            self.linear(x1, ld1, pk["update_val_merge"], e, Ce, S)
+        else:                                                          # no_latent_concat: the gathered features are e
+            e = torch.empty(S, Ce, **f32)
+            self.gather(maps, pixel_val, R * P, 0, PLACE_PLAIN, V, e, Ce, 0, run=P)
+        if keep:
+            save.update(x1=x1, h1=h1, grid_other=grid_other, cross=cross, maps=maps, ld1=ld1, ld_phi=ld_phi, Ce=Ce)
+        x1 = h1 = None
 
         # a12: keys;  a13: geometric query.  The value projection (latent_value, no nonlinearity before the weighted sum)
         # commutes with the attention average: sum_s w_s (Wv e_s + bv) = Wv (sum_s w_s e_s) + bv because the softmax
         # weights of a ray sum to 1, so it is applied once per ray after the reduction instead of once per sample.
         kmap = pk["key_map.kmajor" if kmajor else "key_map"]
         q = torch.empty(S, 128, **f32)
-        if (self.fuse_kq and self.linear_x3 and not self.linear_flags and kmap.x3 is not None and kmap.N == 128 and m.hidden_dim == 128
+        key = logit1 = None
+        if (not keep and self.fuse_kq and self.linear_x3 and not self.linear_flags and kmap.x3 is not None and kmap.N == 128 and m.hidden_dim == 128
                 and Ce % 4 == 0 and e.data_ptr() % 16 == 0 and S >= self.linear_x3_min_rows):
             # key_map -> relu -> key_map_2, query_embed -> relu -> query_embed_2 and the first round's logits in one kernel: the 128-wide
             # k1 / key / q1 rows are never written (csrc/car_linear16.hip, KQ instance)
@@ -895,18 +914,109 @@ class RenderEngine:
             tail, tail_bias = self._kq_weights(dev)
             logit1 = torch.empty(S, **f32)
             rc = lib.car_key_query_logits(_ptr(e), Ce, _ptr(tiles), _ptr(bias_k1), Ce, _ptr(g), _ptr(tail), _ptr(tail_bias), S, _ptr(q), _ptr(logit1), st)
-            if not self._lds_refused(rc, "car_key_query_logits"):
-                return self._finish(inp, z, b, V, R, P, Ce, Dl, e, None, q, g, pt, pixel_val, poses, rays, coords9, phi_x, ld_phi, debug, kmajor,
-                                    logit1=logit1)
-            self.fuse_kq = False                                   # LDS reservation refused: the five separate launches below
-        k1 = torch.empty(S, 128, **f32)
-        self.linear(e, Ce, kmap, k1, 128, S, RELU_OUT)
-        key = torch.empty(S, 128, **f32)
-        self.linear(k1, 128, pk["key_map_2"], key, 128, S)
-        self.linear(g, 16, pk["query_embed"], k1, 128, S, RELU_OUT)
-        self.linear(k1, 128, pk["query_embed_2"], q, 128, S)
+            if self._lds_refused(rc, "car_key_query_logits"):
+                self.fuse_kq, logit1 = False, None                     # LDS reservation refused: the five separate launches below
+        if logit1 is None:
+            k1 = torch.empty(S, 128, **f32)
+            self.linear(e, Ce, kmap, k1, 128, S, RELU_OUT)
+            key = torch.empty(S, 128, **f32)
+            self.linear(k1, 128, pk["key_map_2"], key, 128, S)
+            q1 = torch.empty(S, 128, **f32) if keep else k1             # inference: the query's hidden layer in k1's buffer
+            self.linear(g, 16, pk["query_embed"], q1, 128, S, RELU_OUT)
+            self.linear(q1, 128, pk["query_embed_2"], q, 128, S)
+            if keep:
+                save.update(k1=k1, key=key, q1=q1)
 
-        return self._finish(inp, z, b, V, R, P, Ce, Dl, e, key, q, g, pt, pixel_val, poses, rays, coords9, phi_x, ld_phi, debug, kmajor)
+        # a14 + a16: attention round 1, depth read-out
+        at_wt = torch.empty(n, R, P, **f32)
+        depth = torch.empty(b, R, 1, **f32)
+        amax = torch.empty(n, R, 1, dtype=torch.int32, device=dev)
+        ebar1 = torch.empty(bR, Ce, **f32)
+        lg, qr = (logit1, None) if logit1 is not None else (key, q)    # the logits of car_key_query_logits, or keys and queries
+        _lib.check(lib.car_attend(_ptr(lg), _ptr(qr), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt), _ptr(ebar1),
+                                  Ce, 1, _ptr(pt), _ptr(poses), _ptr(depth), _ptr(amax), st), "car_attend")
+        lv = pk["latent_value.kmajor" if kmajor else "latent_value"]
+        zrep = torch.empty(bR, V * Dl, **f32)
+        at_wt2 = None
+        if m.repeat_attention:
+            z1 = torch.empty(bR, Dl, **f32)
+            self.linear(ebar1, Ce, lv, z1, Dl, bR)
+            # a15: second round; the z_embed half of query_repeat_embed is per ray, the local_coords half per sample
+            hb = torch.empty(bR, 128, **f32)
+            self.linear(z1, Dl, pk["encode_latent"], hb, 128, bR)
+            uh = torch.empty(bR, 128, **f32)
+            self.linear(hb, 128, pk["query_repeat_embed.h"], uh, 128, bR)
+            at_wt2 = torch.empty(n, R, P, **f32)
+            ebar2 = torch.empty(bR, Ce, **f32) if keep else ebar1      # inference: round 2's average in round 1's buffer
+            if self.fuse_round2 and not keep:
+                # ug = Wr1[:,128:] g + br1, q2 = Wr2 relu(ug + uh) + b and <q2, qry>/16 in one kernel: neither is written
+                r2w, r2b = self._round2_weights(dev)
+                logit2 = torch.empty(S, **f32)
+                _lib.check(lib.car_round2_logits(_ptr(g), _ptr(uh), _ptr(q), _ptr(r2w), _ptr(r2b),
+                                                 b, V, R, P, _ptr(logit2), st), "car_round2_logits")
+                _lib.check(lib.car_attend(_ptr(logit2), None, 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
+                                          _ptr(ebar2), Ce, 1, None, None, None, None, st), "car_attend")
+            else:
+                k1r = torch.empty(S, 128, **f32)
+                self.linear(g, 16, pk["query_repeat_embed.g"], k1r, 128, S)
+                _lib.check(lib.car_add_ray_bias_relu(_ptr(k1r), _ptr(uh), b, V, R, P, 128, st), "car_add_ray_bias_relu")
+                key2 = torch.empty(S, 128, **f32) if keep or key is None else key   # inference: round 2's keys in round 1's buffer
+                self.linear(k1r, 128, pk["query_repeat_embed_2"], key2, 128, S)
+                _lib.check(lib.car_attend(_ptr(key2), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
+                                          _ptr(ebar2), Ce, 1, None, None, None, None, st), "car_attend")
+                if keep:
+                    save.update(k1r=k1r, key2=key2)
+            # z = (Wv ebar2 + bv) + V * z1   (models.py:561-565: "+ z_local" per view, then the view sum)
+            if keep:
+                _lib.check(lib.car_add(_ptr(zrep), V * Dl, _ptr(z1), Dl, float(V), None, 0, 0.0, bR, Dl, st), "car_add")
+                save.update(z1=z1, hb=hb, at_wt2=at_wt2, ebar2=ebar2)
+            else:
+                zrep.view(bR, V, Dl)[:, 0] = z1 * float(V)
+            self.linear(ebar2, Ce, lv, zrep, V * Dl, bR, ACCUM)
+        else:
+            self.linear(ebar1, Ce, lv, zrep, V * Dl, bR)
+        # the per-view replication of models.py:541, 565, 605-606
+        if keep:
+            for v in range(1, V):
+                _lib.check(lib.car_add(_ptr(zrep[:, v * Dl:]), V * Dl, _ptr(zrep), V * Dl, 1.0, None, 0, 0.0, bR, Dl, st), "car_add")
+        elif V > 1:
+            zv = zrep.view(bR, V, Dl)
+            zv[:, 1:] = zv[:, :1]
+
+        # a17: light-field decoder
+        x = torch.empty(bR, hid, **f32)
+        net = None if keep else torch.empty(bR, hid, **f32)
+        self.linear(phi_x, ld_phi, pk["phi.lin_in"], x, hid, bR)
+        xas, nets = [], []
+        for i in range(m.phi.n_blocks):
+            if keep:                                                   # the backward reads every block's input and hidden activation
+                x, net = x.clone(), torch.empty(bR, hid, **f32)
+                xas.append(x)
+                nets.append(net)
+            self.linear(zrep, V * Dl, pk[f"phi.lin_z.{i}"], x, hid, bR, ACCUM)
+            self.linear(x, hid, pk[f"phi.blocks.{i}.fc_0"], net, hid, bR, RELU_IN)
+            if keep:
+                x = x.clone()
+            self.linear(net, hid, pk[f"phi.blocks.{i}.fc_1"], x, hid, bR, RELU_IN | ACCUM)
+        out3 = torch.empty(bR, 4, **f32)
+        self.linear(x, hid, pk["phi.lin_out"], out3, 4, bR, RELU_IN)
+
+        # a18: valid mask, white background
+        rgb = torch.empty(b, 1, R, 3, **f32)
+        valid = torch.empty(b, R, 1, **f32)
+        _lib.check(lib.car_finalize(_ptr(rays), _ptr(out3), 4, b, V, R, _ptr(rgb), _ptr(valid), st), "car_finalize")
+        if keep:
+            save.update(e=e, q=q, at_wt=at_wt, ebar1=ebar1, g=g, pt=pt, poses=poses, rays=rays, phi_x=phi_x, pixel_val=pixel_val,
+                        zrep=zrep, xas=xas, nets=nets, x3=x, valid=valid)
+        out = self._outputs(inp, z, dict(rgb=rgb, valid_mask=valid, depth_ray=depth, at_wt=at_wt, at_wt_max=amax, coords=coords9,
+                                         pixel_val=pixel_val), debug)
+        if debug:
+            out["stages"] = {"rays": rays, "pt": pt.view(n, R, P, 3),
+                             "local_coords": g.view(n, R, P, 16),
+                             # the reference's channel order e[s, 3 ch + k] (models.py:446) when e was kept component-major
+                             "interp_val": (e.view(S, 3, Ce // 3).permute(0, 2, 1).reshape(n, R, P, Ce) if kmajor else e.view(n, R, P, Ce)),
+                             "z_final": zrep[:, :Dl].reshape(b, R, Dl), "at_wt2": at_wt2, "poses": poses}
+        return out
 
     def _exchange_lattice(self, gmaps, ptrs, hs, ws, n_maps, C, dev):
         """The projected levels of the three-view exchange summed on their common lattice (car_merge_lattice), cached with the projected
@@ -1026,104 +1136,3 @@ class RenderEngine:
             keep.update(x3=x3, h1=h1, ld=ld)
         # channel index = ch*3 + k (torch.cat on dim 2 then flatten(1, 2), models.py:446)
         return enc.view(S, 3, C // 2).permute(0, 2, 1).contiguous().view(S, 3 * (C // 2))
-
-    def _finish(self, inp, z, b, V, R, P, Ce, Dl, e, key, q, g, pt, pixel_val, poses, rays, coords9, phi_x, ld_phi, debug, kmajor=False, logit1=None):
-        """Attention rounds, decoder and output dict of the staged route; ``g`` is the geometric
-        query local_coords [S,16]."""
-        m, lib = self.m, self.lib
-        dev = e.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        st = _stream()
-        pk = self._packed
-        lv = pk["latent_value.kmajor" if kmajor else "latent_value"]
-        n, S = b * V, b * V * R * P
-        n_qry = 1
-        qry = inp["query"]
-        # a14 + a16: attention round 1, depth read-out
-        at_wt = torch.empty(n, R, P, **f32)
-        depth = torch.empty(b, R, **f32)
-        amax = torch.empty(n, R, dtype=torch.int32, device=dev)
-        rep = m.repeat_attention
-        ebar = torch.empty(b * R, Ce, **f32)
-        if logit1 is not None:                             # the logits came out of car_key_query_logits
-            _lib.check(lib.car_attend(_ptr(logit1), None, 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt), _ptr(ebar),
-                                      Ce, 1, _ptr(pt), _ptr(poses), _ptr(depth), _ptr(amax), st), "car_attend")
-        else:
-            _lib.check(lib.car_attend(_ptr(key), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt), _ptr(ebar),
-                                      Ce, 1, _ptr(pt), _ptr(poses), _ptr(depth), _ptr(amax), st), "car_attend")
-        zrep = torch.empty(b * R, V * Dl, **f32)
-        at_wt2 = None
-        if rep:
-            z1 = torch.empty(b * R, Dl, **f32)
-            self.linear(ebar, Ce, lv, z1, Dl, b * R)
-            # a15: second round; the z_embed half of query_repeat_embed is per ray, the local_coords half per sample
-            hb = torch.empty(b * R, 128, **f32)
-            self.linear(z1, Dl, pk["encode_latent"], hb, 128, b * R)
-            uh = torch.empty(b * R, 128, **f32)
-            self.linear(hb, 128, pk["query_repeat_embed.h"], uh, 128, b * R)
-            at_wt2 = torch.empty(n, R, P, **f32)
-            if self.fuse_round2:
-                # ug = Wr1[:,128:] g + br1, q2 = Wr2 relu(ug + uh) + b and <q2, qry>/16 in one kernel: neither is written
-                r2w, r2b = self._round2_weights(dev)
-                logit2 = torch.empty(S, **f32)
-                _lib.check(lib.car_round2_logits(_ptr(g), _ptr(uh), _ptr(q), _ptr(r2w), _ptr(r2b),
-                                                 b, V, R, P, _ptr(logit2), st), "car_round2_logits")
-                _lib.check(lib.car_attend(_ptr(logit2), None, 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
-                                          _ptr(ebar), Ce, 1, None, None, None, None, st), "car_attend")
-            else:
-                k1 = torch.empty(S, 128, **f32)
-                if key is None:
-                    key = torch.empty(S, 128, **f32)
-                self.linear(g, 16, pk["query_repeat_embed.g"], k1, 128, S)
-                _lib.check(lib.car_add_ray_bias_relu(_ptr(k1), _ptr(uh), b, V, R, P, 128, st), "car_add_ray_bias_relu")
-                self.linear(k1, 128, pk["query_repeat_embed_2"], key, 128, S)
-                _lib.check(lib.car_attend(_ptr(key), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
-                                          _ptr(ebar), Ce, 1, None, None, None, None, st), "car_attend")
-            # z = (Wv ebar2 + bv) + V * z1   (models.py:561-565: "+ z_local" per view, then the view sum)
-            zv = zrep.view(b * R, V, Dl)
-            zv[:, 0] = z1 * float(V)
-            self.linear(ebar, Ce, lv, zrep, V * Dl, b * R, ACCUM)
-        else:
-            self.linear(ebar, Ce, lv, zrep, V * Dl, b * R)
-        if V > 1:                                         # the per-view replication of models.py:541, 565, 605-606
-            zv = zrep.view(b * R, V, Dl)
-            zv[:, 1:] = zv[:, :1]
-
-        # a17: light-field decoder
-        hid = m.phi.d_hidden
-        x = torch.empty(b * R, hid, **f32)
-        net = torch.empty(b * R, hid, **f32)
-        self.linear(phi_x, ld_phi, pk["phi.lin_in"], x, hid, b * R)
-        for i in range(m.phi.n_blocks):
-            self.linear(zrep, V * Dl, pk[f"phi.lin_z.{i}"], x, hid, b * R, ACCUM)
-            self.linear(x, hid, pk[f"phi.blocks.{i}.fc_0"], net, hid, b * R, RELU_IN)
-            self.linear(net, hid, pk[f"phi.blocks.{i}.fc_1"], x, hid, b * R, RELU_IN | ACCUM)
-        out3 = torch.empty(b * R, 4, **f32)
-        self.linear(x, hid, pk["phi.lin_out"], out3, 4, b * R, RELU_IN)
-
-        # a18: valid mask, white background, output dict
-        rgb = torch.empty(b, R, 3, **f32)
-        valid = torch.empty(b, R, **f32)
-        _lib.check(lib.car_finalize(_ptr(rays), _ptr(out3), 4, b, V, R, _ptr(rgb), _ptr(valid), st), "car_finalize")
-
-        out = {
-            "rgb": rgb.view(b, n_qry, R, 3),
-            "valid_mask": valid[..., None],
-            "depth_ray": depth[..., None],
-            "at_wt": at_wt,
-            "at_wts": [at_wt],
-            "at_wt_max": amax.long()[..., None],
-            "coords": coords9,
-            "uv": qry["uv"],
-            # the reference returns pixel_val on the CPU (models.py:570), forcing a device sync on every call; here it
-            # stays on the device unless debug is set
-            "pixel_val": pixel_val.view(n, R, P, 2).cpu() if debug else pixel_val.view(n, R, P, 2),
-            "z": z,
-        }
-        if debug:
-            out["stages"] = {"rays": rays, "pt": pt.view(n, R, P, 3),
-                             "local_coords": g.view(n, R, P, 16),
-                             # the reference's channel order e[s, 3 ch + k] (models.py:446) when e was kept component-major
-                             "interp_val": (e.view(S, 3, Ce // 3).permute(0, 2, 1).reshape(n, R, P, Ce) if kmajor else e.view(n, R, P, Ce)),
-                             "z_final": zrep[:, :Dl].reshape(b, R, Dl), "at_wt2": at_wt2, "poses": poses}
-        return out

@@ -6,9 +6,9 @@ hundred random rays per scene, a loss on ``rgb`` (and optionally ``depth_ray``, 
 ``average_gradients`` (training.py:21-28) when several GPUs train replicas.  Here ``render_train`` is that forward as a
 ``torch.autograd.Function`` whose forward AND backward are HIP kernels of ``libcar_hip.so``:
 
-  forward   the stage entries of ``engine.py`` (geometry, literal gather -> 579-wide GEMM, attention rounds, decoder), none fused away,
-            because the backward needs what the fused inference kernels never write: the gathered rows, the first layer's
-            activations, keys, queries;
+  forward   the engine's staged forward (``RenderEngine._staged``) with a save dict: its literal stage forms (gather -> 579-wide GEMM,
+            five key / query launches, the unfused second round), none fused away, because the backward needs what the fused
+            inference kernels never write: the gathered rows, the first layer's activations, keys, queries;
   backward  ``car_linear`` with transposed weights (data gradients), ``car_linear_wgrad`` (weight / bias gradients),
             ``car_attend_backward``, ``car_gather_bilinear_backward`` (scatter-add into the pyramid), and the element-wise pieces
             (csrc/car_backward.hip).
@@ -30,7 +30,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .engine import ACCUM, PLACE_OTHER2, PLACE_OWN, PLACE_PLAIN, RELU_IN, RELU_OUT, PackedLinear, RenderEngine, _ptr, _round_up, _stream
+from .engine import ACCUM, PLACE_OTHER2, PLACE_OWN, PLACE_PLAIN, RELU_IN, PackedLinear, RenderEngine, _mode, _ptr, _round_up, _stream
 
 Tensor = torch.Tensor
 WGRAD_FP32 = 16            # CAR_WGRAD_FP32 (include/car_hip.h)
@@ -107,14 +107,6 @@ class _Ops:
 
 
 # parameters the path reads, in the order their gradients are returned
-def _mode(m) -> str:
-    """How the per-sample features e are made: "concat2" (two views, point MLP over own ‖ other features), "single" (one view,
-    update_val_merge over features ‖ point channels), "plain" (no_latent_concat: the gathered features themselves)."""
-    if m.no_latent_concat:
-        return "plain"
-    return {1: "single", 2: "concat2", 3: "concat3"}[m.n_view]
-
-
 def _param_names(m) -> List[str]:
     names = {"concat2": ["query_encode_latent", "query_encode_latent_2"], "concat3": ["query_encode_latent", "query_encode_latent_2"],
              "single": ["update_val_merge"], "plain": []}[_mode(m)]
@@ -132,141 +124,19 @@ class _RenderTrain(torch.autograd.Function):
     def forward(ctx, module, inp, n_levels, *tensors):
         z = list(tensors[:n_levels])
         eng: RenderEngine = module._engine
-        m, lib = module, eng.lib
-        dev = inp["query"]["uv"].device
-        st = _stream()
-        f32 = dict(device=dev, dtype=torch.float32)
+        m = module
+        saved: dict = {}
+        out = eng._staged(inp, z, save=saved)
         b, V = inp["context"]["rgb"].shape[:2]
         R = inp["query"]["uv"].shape[2]
-        P, H, W = m.npoints, m.H, m.W
-        n, S = b * V, b * V * R * P
-        pk = eng._weights(dev)
-        maps = eng._channel_last(z)
+        maps = saved.pop("maps")
         C = sum(t.shape[3] for t in maps)
-        mode = _mode(m)
-        Dl, Ce, hid = m.latent_dim, (V * (C // 2) if mode in ("concat2", "concat3") else C), m.phi.d_hidden
-        poses = eng._poses(inp, H, n, dev)
-        uv = inp["query"]["uv"].detach().reshape(b, R, 2).float().contiguous()
-        nos = int(m.no_sample)
-        steps = eng._linspace(0.1, 10.0, P, dev) if nos else eng._linspace(0.0, 1.0, P, dev)
-
-        # geometry (constant with respect to every parameter)
-        rays = torch.empty(n, R, 12, **f32)
-        coords9 = torch.empty(n, R, 9, **f32)
-        ld_phi = _round_up(9 * V, 4)
-        phi_x = torch.zeros(b * R, ld_phi, **f32)
-        _check(lib.car_ray_setup(_ptr(poses), _ptr(uv), b, V, R, H, W, P, nos, _ptr(steps), _ptr(rays), _ptr(coords9), _ptr(phi_x), ld_phi, st),
-               "car_ray_setup")
-        pixel_val = torch.empty(n, R, P, 2, **f32)
-        pt = torch.empty(n, R, P, 3, **f32)
-        g = torch.empty(S, 16, **f32)
-        grid_in = grid_other = h1 = x1 = None
-        ld1 = 0
-        if mode == "concat2":
-            grid_in = torch.empty(n, R, P, V, 2, **f32)
-            ld1 = _round_up(C + 3, 32)
-            x1 = torch.empty(S * V, ld1, **f32)                   # columns [0, C + 3) are written below; only the row padding is zeroed
-            x1[:, C + 3:].zero_()
-            _check(lib.car_sample_setup(_ptr(poses), _ptr(rays), _ptr(steps), b, V, R, P, H, W, nos, _ptr(pixel_val), _ptr(pt), _ptr(g), _ptr(grid_in),
-                                        _ptr(x1), ld1, C, None, st), "car_sample_setup")
-            # a7 / a10: the two gathers, literal
-            eng.gather(maps, pixel_val, R * P, 0, PLACE_OWN, V, x1, ld1, 0, run=P)
-            gi = grid_in.view(b, V, R, P, V, 2)
-            grid_other = torch.stack([gi[:, 1, :, :, 0], gi[:, 0, :, :, 1]], dim=1).contiguous()
-            eng.gather(maps, grid_other, R * P, 1, PLACE_OTHER2, V, x1, ld1, 0, run=P)
-            # a11
-            h1 = torch.empty(S * V, C, **f32)
-            eng.linear(x1, ld1, pk["query_encode_latent"], h1, C, S * V, RELU_OUT)
-            e = torch.empty(S, Ce, **f32)
-            eng.linear(h1, C, pk["query_encode_latent_2"], e, C // 2, S * V)
-        elif mode == "concat3":                                  # models.py:345-475: the three-view exchange, sequenced by the engine
-            xpe = torch.zeros(S * V, 4, **f32)                    # tanh(pt in frame s / 5) per (sample, frame)
-            pt_in = torch.empty(n, R, P, V, 3, **f32)
-            _check(lib.car_sample_setup(_ptr(poses), _ptr(rays), _ptr(steps), b, V, R, P, H, W, nos, _ptr(pixel_val), _ptr(pt), _ptr(g), None,
-                                        _ptr(xpe), 4, 0, _ptr(pt_in), st), "car_sample_setup")
-            keep3: dict = {}
-            e = eng._encode_three_views(maps, poses, pixel_val, xpe, pt_in, b, R, P, H, W, C, pk, keep=keep3)
-            x1, h1, ld1 = keep3["x3"], keep3["h1"], keep3["ld"]
-        elif mode == "single":                                   # models.py:478-485: features ‖ tanh(pt/5) ‖ tanh(pt/100) -> update_val_merge
-            ld1 = _round_up(C + 6, 32)
-            x1 = torch.zeros(S, ld1, **f32)
-            _check(lib.car_sample_setup(_ptr(poses), _ptr(rays), _ptr(steps), b, V, R, P, H, W, nos, _ptr(pixel_val), _ptr(pt), _ptr(g), None,
-                                        _ptr(x1), ld1, C, None, st), "car_sample_setup")
-            eng.gather(maps, pixel_val, R * P, 0, PLACE_PLAIN, V, x1, ld1, 0, run=P)
-            e = torch.empty(S, Ce, **f32)
-            eng.linear(x1, ld1, pk["update_val_merge"], e, Ce, S)
-        else:                                                    # no_latent_concat: the gathered features are e
-            _check(lib.car_sample_setup(_ptr(poses), _ptr(rays), _ptr(steps), b, V, R, P, H, W, nos, _ptr(pixel_val), _ptr(pt), _ptr(g), None,
-                                        None, 0, 0, None, st), "car_sample_setup")
-            e = torch.empty(S, Ce, **f32)
-            eng.gather(maps, pixel_val, R * P, 0, PLACE_PLAIN, V, e, Ce, 0, run=P)
-        # a12, a13
-        k1 = torch.empty(S, 128, **f32)
-        eng.linear(e, Ce, pk["key_map"], k1, 128, S, RELU_OUT)
-        key = torch.empty(S, 128, **f32)
-        eng.linear(k1, 128, pk["key_map_2"], key, 128, S)
-        q1 = torch.empty(S, 128, **f32)
-        eng.linear(g, 16, pk["query_embed"], q1, 128, S, RELU_OUT)
-        q = torch.empty(S, 128, **f32)
-        eng.linear(q1, 128, pk["query_embed_2"], q, 128, S)
-        # a14, a16
-        at_wt = torch.empty(n, R, P, **f32)
-        depth = torch.empty(b, R, **f32)
-        amax = torch.empty(n, R, dtype=torch.int32, device=dev)
-        ebar1 = torch.empty(b * R, Ce, **f32)
-        _check(lib.car_attend(_ptr(key), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt), _ptr(ebar1), Ce, 1, _ptr(pt), _ptr(poses),
-                              _ptr(depth), _ptr(amax), st), "car_attend")
-        zrep = torch.empty(b * R, V * Dl, **f32)
-        saved = dict(x1=x1, h1=h1, e=e, k1=k1, key=key, q1=q1, q=q, at_wt=at_wt, ebar1=ebar1, g=g, pt=pt, poses=poses, rays=rays, phi_x=phi_x,
-                     pixel_val=pixel_val, grid_other=grid_other, cross=(keep3["cross"] if mode == "concat3" else None))
         ops = getattr(eng, "_train_ops", None)              # kept on the engine: its transposed-weight cache (keyed on data_ptr / _version)
         if ops is None or ops.eng is not eng:               # then survives from step to step and re-packs only what the optimizer changed
             ops = eng._train_ops = _Ops(eng)
-        if m.repeat_attention:
-            z1 = torch.empty(b * R, Dl, **f32)
-            eng.linear(ebar1, Ce, pk["latent_value"], z1, Dl, b * R)
-            hb = torch.empty(b * R, 128, **f32)
-            eng.linear(z1, Dl, pk["encode_latent"], hb, 128, b * R)
-            uh = torch.empty(b * R, 128, **f32)
-            eng.linear(hb, 128, pk["query_repeat_embed.h"], uh, 128, b * R)
-            k1r = torch.empty(S, 128, **f32)
-            eng.linear(g, 16, pk["query_repeat_embed.g"], k1r, 128, S)
-            _check(lib.car_add_ray_bias_relu(_ptr(k1r), _ptr(uh), b, V, R, P, 128, st), "car_add_ray_bias_relu")
-            key2 = torch.empty(S, 128, **f32)
-            eng.linear(k1r, 128, pk["query_repeat_embed_2"], key2, 128, S)
-            at_wt2 = torch.empty(n, R, P, **f32)
-            ebar2 = torch.empty(b * R, Ce, **f32)
-            _check(lib.car_attend(_ptr(key2), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2), _ptr(ebar2), Ce, 1, None, None, None,
-                                  None, st), "car_attend")
-            ops.add(zrep, V * Dl, z1, Dl, float(V), None, 0, 0.0, b * R, Dl)                     # z = V z1 + latent_value(ebar2)
-            eng.linear(ebar2, Ce, pk["latent_value"], zrep, V * Dl, b * R, ACCUM)
-            saved.update(z1=z1, hb=hb, k1r=k1r, key2=key2, at_wt2=at_wt2, ebar2=ebar2)
-        else:
-            eng.linear(ebar1, Ce, pk["latent_value"], zrep, V * Dl, b * R)
-        for v in range(1, V):                                                                    # per-view replication (models.py:541, 565)
-            ops.add(zrep[:, v * Dl:], V * Dl, zrep, V * Dl, 1.0, None, 0, 0.0, b * R, Dl)
-        # a17
-        x = torch.empty(b * R, hid, **f32)
-        eng.linear(phi_x, ld_phi, pk["phi.lin_in"], x, hid, b * R)
-        xas, nets = [], []
-        for i in range(m.phi.n_blocks):
-            xa = x.clone()
-            eng.linear(zrep, V * Dl, pk[f"phi.lin_z.{i}"], xa, hid, b * R, ACCUM)
-            net = torch.empty(b * R, hid, **f32)
-            eng.linear(xa, hid, pk[f"phi.blocks.{i}.fc_0"], net, hid, b * R, RELU_IN)
-            x = xa.clone()
-            eng.linear(net, hid, pk[f"phi.blocks.{i}.fc_1"], x, hid, b * R, RELU_IN | ACCUM)
-            xas.append(xa)
-            nets.append(net)
-        out3 = torch.empty(b * R, 4, **f32)
-        eng.linear(x, hid, pk["phi.lin_out"], out3, 4, b * R, RELU_IN)
-        rgb = torch.empty(b, R, 3, **f32)
-        valid = torch.empty(b, R, **f32)
-        _check(lib.car_finalize(_ptr(rays), _ptr(out3), 4, b, V, R, _ptr(rgb), _ptr(valid), st), "car_finalize")
-        saved.update(zrep=zrep, xas=xas, nets=nets, x3=x, valid=valid)
         ctx.saved, ctx.ops, ctx.module, ctx.n_levels = saved, ops, module, n_levels
-        ctx.dims = (b, V, R, P, C, Dl, Ce, hid, ld1, ld_phi)
-        ctx.mode = mode
+        ctx.dims = (b, V, R, m.npoints, C, m.latent_dim, saved.pop("Ce"), m.phi.d_hidden, saved.pop("ld1"), saved.pop("ld_phi"))
+        ctx.mode = _mode(m)
         ctx.maps = maps
         ctx.params = {nme: t for nme, t in zip(_param_names(m), tensors[n_levels:])}
         # the activations live as plain attributes (most are views into buffers autograd does not need to track), so autograd's own
@@ -277,7 +147,7 @@ class _RenderTrain(torch.autograd.Function):
         # a level that lies channel-last in memory gets its gradient back as a view of the channel-last scatter buffer (same strides as the
         # level: no NHWC -> NCHW copy, as the forward took it without the NCHW -> NHWC one)
         ctx.z_channel_last = [t.dtype == torch.float32 and t.permute(0, 2, 3, 1).is_contiguous() for t in z]
-        outs = (rgb.view(b, 1, R, 3), depth[..., None], valid[..., None], at_wt, amax.long()[..., None], coords9, pixel_val)
+        outs = tuple(out[k] for k in ("rgb", "depth_ray", "valid_mask", "at_wt", "at_wt_max", "coords", "pixel_val"))
         ctx.mark_non_differentiable(*outs[2:])
         return outs
 
