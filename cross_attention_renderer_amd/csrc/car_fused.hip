@@ -34,11 +34,8 @@ constexpr int kWaves = 12, kRows = 16, kGroup = kWaves * kRows;      // 192 samp
 // first step, rows 8-15: the second), so the 8 rows of a tap instruction are one step of neighbouring rays.  24 x 8 touches 22 % fewer
 // lattice nodes per workgroup than 48 x 4 (751 vs 964 over the four (view, source) maps of the bench frame; 12 x 16: 804, 96 x 2:
 // 1374 — profiles/round3_fused_experiments.md section 15), i.e. more of a workgroup's tap lines come from its own L1.
-#ifndef CAR_TILE_STEPS
-#define CAR_TILE_STEPS 8
-#endif
 constexpr int kWaveRays = 8, kWaveSteps = kRows / kWaveRays;          // a wave's 16 rows
-constexpr int kTileSteps = CAR_TILE_STEPS, kStepWaves = kTileSteps / kWaveSteps, kRayWaves = kWaves / kStepWaves, kTileRays = kRayWaves * kWaveRays;
+constexpr int kTileSteps = 8, kStepWaves = kTileSteps / kWaveSteps, kRayWaves = kWaves / kStepWaves, kTileRays = kRayWaves * kWaveRays;
 static_assert(kStepWaves * kRayWaves == kWaves && kTileSteps % kWaveSteps == 0, "tile shape");
 // row s of wave w: ray (w / kStepWaves) * 8 + (s & 7), step (w % kStepWaves) * 2 + (s >> 3) of the tile
 __device__ __forceinline__ int tile_ray(int w, int s) { return (w / kStepWaves) * kWaveRays + (s & (kWaveRays - 1)); }
@@ -79,7 +76,6 @@ struct FusedArgs {
     int b, V, R, P, H, W;
     int no_sample;             // samples at the depths `steps` on the query ray (models.py:221-222) instead of along the epipolar segment
     long S;
-    int blk0;                  // first sample group of this launch (0 except in the development build's partial launches)
     float* e;
     float* g;
     float* logit;
@@ -128,22 +124,14 @@ __device__ __forceinline__ NextChunk next_chunk_w2(const float* __restrict__ blo
     return n;
 }
 
-// ABL > 0: timing-only ablations (wrong results), instantiated only in the -DCAR_ABLATION development build (tools/):
-// 1 no tap loads, 2 no gather work, 3 = 2 + no weight DMA / barriers, 5 no e-path MFMAs, weight DMA or barriers in the two source
-// passes (the gather + the key / query layers); 11 the full kernel without the barrier of the weight stream (racy);
-// 12 = 3 + no A-operand reads from LDS (matrix pipe + VALU only); 13 the full kernel without the A-operand reads;
-// 4: the full kernel with shader-clock stamps at its phase boundaries (written over pixel_val);
-// 20: the full kernel with shader-clock sums per piece of the chunk loop (where a wave waits inside a chunk)
-// 21: the full kernel, writing each sample's north-west lattice node per source (-1: no fetch) over pixel_val (tap statistics)
-// 22: every tap inside a 1 MB window of its lattice (L2 hits); 28: inside 32 nodes (L1 hits); 23: no weight DMA (barriers kept); 24 = 22 + 23;
-// 30-33: the weight DMA with cache-policy bits nt / sc1 / sc0 sc1 / sc0; 40-43: waves leaving the barrier apart, taps spread over the slots;
-// 50-53: the chunk loop without slot fences, vector / LDS instructions interleaved under the MFMAs by sched_group_barrier (results stay right)
-// ROWS: one source pass over explicit rows, e_0 = W2 relu(h) + b2 written [row][kE], nothing else (the three-view exchange's two layers,
-// models.py:345-475 through engine._encode_three_views); the chunk loop is the product kernel's own
-// F16: the opt-in precision (one product per term, compact blob); only with ABL 0 and ROWS false
-template <int ABL, bool ROWS = false, bool F16 = false>
+// Three instances (car_fused_samples*, car_fused_rows):
+// ROWS = false, F16 = false: the whole per-sample chain in split-fp16 arithmetic (car_fused_samples, car_fused_samples_parts).
+// ROWS = true: one source pass over explicit rows, e_0 = W2 relu(h) + b2 written [row][kE], nothing else (the three-view exchange's two
+// layers, models.py:345-475 through engine._encode_three_views); the chunk loop is the same.
+// F16 = true: the opt-in precision (one product per term, compact blob; car_fused_samples_f16), with ROWS false only.
+template <bool ROWS = false, bool F16 = false>
 __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
-    static_assert(!F16 || (ABL == 0 && !ROWS), "the fp16 instance is the one-call route's partial-sum kernel only");
+    static_assert(!F16 || !ROWS, "the fp16 instance is the one-call route's partial-sum kernel only");
     constexpr int kTF = tile_floats<F16>(), kP = chunk_pieces<F16>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -154,7 +142,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
     {   // workgroup b runs on XCD b % 8 (observed, speed only): give every XCD a contiguous band of sample groups so that the
         // lattice rows its workgroups share stay in one L2
         const int q8 = nblk / 8, r8 = nblk % 8, xcd = blk % 8, idx = blk / 8;
-        blk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx + a.blk0;
+        blk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
     }
     // the tile's sample of (wave, row lane & 15): tile_ray / tile_step above; the 8 rows a tap instruction gathers are one step of
     // neighbouring rays (shared lattice rows)
@@ -165,27 +153,12 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
     // (a tile's 8 step groups on consecutive workgroups) this one fetches 4.5 % fewer bytes on the memory side and runs the launch 2.4 %
     // faster; putting a tile's 2 x 8 workgroups side by side fetches 5 % MORE.  A pure permutation of the work: results are unchanged.
     const int nsets = ROWS ? a.b * a.ncomp : a.b * a.V;
-#if !defined(CAR_WG_ORDER) || CAR_WG_ORDER == 2
     const int pg = blk / (nsets * bundles), nset = (blk / bundles) % nsets, bun = blk % bundles;
-#elif CAR_WG_ORDER == 0                                                // development build: rounds 2-5, (sample set, ray tile, step group)
-    const int pg = blk % pgs, bun = (blk / pgs) % bundles, nset = blk / (pgs * bundles);
-#else                                                                  // development build: (ray tile, sample set, step group)
-    const int pg = blk % pgs, nset = (blk / pgs) % nsets, bun = blk / (pgs * nsets);
-#endif
     const int nn = ROWS ? nset / a.ncomp : nset, comp = ROWS ? nset % a.ncomp : 0;
     const int ray_i = bun * kTileRays + tile_ray(wave, s), pp = pg * kTileSteps + tile_step(wave, s);
     const bool live = ray_i < a.R && pp < a.P;
     const long i = ((long)nn * a.R + (ray_i < a.R ? ray_i : a.R - 1)) * a.P + (pp < a.P ? pp : a.P - 1);
 
-    // ABL 4 (development build): the full kernel, plus shader-clock stamps of wave 0 at the phase boundaries, written over pixel_val
-    long long stamp[12];
-#ifdef CAR_STAMP_ALL
-    constexpr bool kStamp = true;
-#else
-    constexpr bool kStamp = (ABL == 4);
-#endif
-    auto mark = [&](int k) { if constexpr (kStamp) stamp[k] = (long long)__builtin_amdgcn_s_memtime(); };
-    mark(0);
     // Scale of the first layer's output h (split-fp16 arithmetic, car_fused_mma.h): h is bounded by the largest lattice value plus the
     // point / bias term (the tap weights are non-negative and sum to at most one, |tanh| <= 1): one power of two hp per launch.
     // Everything that is added up into h — tap weights, point terms, the bias — is multiplied by hp ONCE, where it is made (exact:
@@ -200,7 +173,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
     }
     for (int k = tid; k < kBiasFloats; k += kThreads) lds[kLdsBias + k] = a.bias[k];
     int g = 0;
-    stream_issue_all<ABL, F16>(a.blob, lds, 0, lane, wave);
+    stream_issue_all<F16>(a.blob, lds, 0, lane, wave);
 
     // ---- geometry: the 192 samples of the group are spread over the 192 lanes of waves 0-2 (one sample per lane, both source views),
     //      instead of every wave repeating its 16 samples in four lane groups: a third of the issue time on the critical path ----
@@ -266,11 +239,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             // loads of its lanes return zeros without touching memory — an instruction whose lanes are all out of range costs the
             // texture path nothing (profiles/round3_fused_experiments.md) — and weight zero makes the contribution exactly +-0
             const bool dead = mode == 1 && (flags & 4);
-            if constexpr (ABL == 21) { if (g_live) reinterpret_cast<int*>(a.pixel_val)[2 * gi + sv] = dead ? -1 : node; }      // tools/bench_fused.py 21: tap statistics
-            unsigned tap_off = (unsigned)node * (unsigned)(kC * 4);
-            if constexpr (ABL == 22 || ABL == 24) tap_off = (unsigned)(node % 448) * (unsigned)(kC * 4);       // timing probe: every tap inside a 1 MB window (L2 hits)
-            if constexpr (ABL == 28) tap_off = (unsigned)(gs & 7) * (unsigned)(kC * 4);                        // timing probe: 32 nodes in all (L1 hits)
-            reinterpret_cast<unsigned*>(lds + kLdsTapB)[sg * 2 + sv] = dead ? kDeadTap : tap_off;
+            reinterpret_cast<unsigned*>(lds + kLdsTapB)[sg * 2 + sv] = dead ? kDeadTap : (unsigned)node * (unsigned)(kC * 4);
             *reinterpret_cast<float4*>(lds + kLdsTapW + (sg * 2 + sv) * 4) =
                 dead ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(w[0] * hp, w[1] * hp, w[2] * hp, w[3] * hp);
             const float px = sv == 0 ? smp.pt_in[0][0] : smp.pt_in[1][0], py = sv == 0 ? smp.pt_in[0][1] : smp.pt_in[1][1],
@@ -278,7 +247,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             *reinterpret_cast<float4*>(lds + kLdsPe + (sg * 2 + sv) * 4) = make_float4(tanhf(px / 5.0f) * hp, tanhf(py / 5.0f) * hp, tanhf(pz / 5.0f) * hp, 0.0f);
         }
         if (g_live) {
-            if constexpr (!kStamp && ABL != 20 && ABL != 21) { a.pixel_val[2 * gi] = smp.grid[0]; a.pixel_val[2 * gi + 1] = smp.grid[1]; }
+            a.pixel_val[2 * gi] = smp.grid[0]; a.pixel_val[2 * gi + 1] = smp.grid[1];
             a.pt[3 * gi + 0] = smp.pt[0]; a.pt[3 * gi + 1] = smp.pt[1]; a.pt[3 * gi + 2] = smp.pt[2];
         }
         float* gl = lds + kLdsG + sg * 16;
@@ -290,7 +259,6 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         }
     }
     __syncthreads();                                                   // tables and tap records visible
-    mark(1);
 
     // ---- gather machinery: lane owns rows rr = (lane>>3) + 8*it (it = 0, 1) and channel quad qd = lane & 7 of a chunk.
     //      A batch = the 4 tap loads of one row group `it`; two batches (bufA: it 0, bufB: it 1) are in flight, each issued right
@@ -300,7 +268,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
     float4 hacc[2];
     f32x4 bufA[4], bufB[4];
     const unsigned qd16 = 16u * qd;
-    const unsigned row_step = (ABL == 22 || ABL == 24 || ABL == 28) ? 16u * (kC * 4) : (unsigned)a.lw * (kC * 4);
+    const unsigned row_step = (unsigned)a.lw * (kC * 4);
 
     // Buffer loads, range-checked against ONE (view, padding mode) lattice: the workgroup's samples all lie on the epipolar lines of
     // context view nn % V, so source view sv reads the border-padded lattice of that view when sv is the view itself and the
@@ -316,7 +284,6 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.lattice + lat0), 0, (int)a.map_bytes, 0x00027000),
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.lattice + lat1), 0, (int)a.map_bytes, 0x00027000)};
     auto issue_row = [&](f32x4 (&tap)[4], int sv, int c, int it) {
-        if constexpr (ABL == 1 || ABL == 2 || ABL == 3 || ABL == 12) return;
         const int chunk_off = 128 * c;                                 // the chunk's 32 channels: scalar offset, not range-checked
         const unsigned tbv = reinterpret_cast<const unsigned*>(lds + kLdsTapB)[(wave * kRows + r0 + 8 * it) * 2 + sv];
         const unsigned o00 = tbv + qd16, o10 = o00 + row_step;          // east taps: the instruction's immediate offset (one node = 2304 B)
@@ -329,14 +296,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         tap[2] = ld(o10);
         tap[3] = ld(o10 + (unsigned)(kC * 4));
     };
-    auto issue_tap = [&](f32x4 (&tap)[4], int sv, int c, int it, int t) {          // development build (ABL 43): one tap of a batch
-        const int chunk_off = 128 * c;
-        const unsigned tbv = reinterpret_cast<const unsigned*>(lds + kLdsTapB)[(wave * kRows + r0 + 8 * it) * 2 + sv];
-        const unsigned o = tbv + qd16 + ((t & 2) ? row_step : 0u) + ((t & 1) ? (unsigned)(kC * 4) : 0u);
-        tap[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc[sv], (int)o, chunk_off, 0));
-    };
     auto blend_row = [&](const f32x4 (&tap)[4], int sv, int it) {
-        if constexpr (ABL == 2 || ABL == 3 || ABL == 12) return;
         const float4 w = *reinterpret_cast<const float4*>(lds + kLdsTapW + ((wave * kRows + r0 + 8 * it) * 2 + sv) * 4);
         const float ww[4] = {w.x, w.y, w.z, w.w};
         f32x2 lo2 = {hacc[it].x, hacc[it].y}, hi2 = {hacc[it].z, hacc[it].w};          // v_pk_fma_f32: two FMAs per instruction
@@ -350,7 +310,6 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         hacc[it] = make_float4(lo2[0], lo2[1], hi2[0], hi2[1]);
     };
     auto affine_row = [&](int sv, int c, int it) {
-        if constexpr (ABL == 2 || ABL == 3 || ABL == 12) return;
         const int rr = r0 + 8 * it;
         const float4 pe = *reinterpret_cast<const float4*>(lds + kLdsPe + ((wave * kRows + rr) * 2 + sv) * 4);
         const float4* wp = reinterpret_cast<const float4*>(lds + kLdsWpt + 16 * (8 * c + qd));
@@ -363,7 +322,6 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
                                fmaf(wx.z, pe.x, fmaf(wy.z, pe.y, fmaf(wz.z, pe.z, wb.z))), fmaf(wx.w, pe.x, fmaf(wy.w, pe.y, fmaf(wz.w, pe.z, wb.w))));
     };
     auto finish_row = [&](int it) {
-        if constexpr (ABL == 2 || ABL == 3 || ABL == 12) return;
         const float4 o = hacc[it];
         *reinterpret_cast<float4*>(stage + (r0 + 8 * it) * kStageLd + 4 * qd) =
             make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
@@ -394,21 +352,9 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         finish_row(it);
     }
     stream_sync();                                                     // weight chunk 0 landed
-    mark(2);
-    // development build, variants 63-65: ONE tap buffer — a row group's taps are issued four slots (not a whole chunk) before they are blended:
-    // row group 0 in slot 0, blended in slot 4, where row group 1 is issued, blended in slot 8; nothing in flight over the barrier.  The 16
-    // registers this frees hold the NEXT slot's A operands (64, 65): a true double buffer instead of 4 reads + wait in front of every 6 MFMAs
-    constexpr bool kOneTapBuf = (ABL == 63 || ABL == 64 || ABL == 65);
-    constexpr bool kTapsLive = (ABL == 0 || ABL >= 4) && !kOneTapBuf;
-    if constexpr (!kOneTapBuf) {
-        issue_row(bufA, 0, 1, 0);                                      // pipeline prologue: chunk (0, 1), both row groups
-        issue_row(bufB, 0, 1, 1);
-    }
+    issue_row(bufA, 0, 1, 0);                                          // pipeline prologue: chunk (0, 1), both row groups
+    issue_row(bufB, 0, 1, 1);
 
-    // ABL 20 (development build): shader-clock time the wave spends, per piece of the chunk loop, summed over the source passes and
-    // written over pixel_val (tools/bench_fused.py 20); in every other variant tick() is 0 and all of this folds away
-    long long t_blend = 0, t_dma = 0, t_bar = 0, t_chunks = 0, t_issue = 0, t_piece = 0, t_aff = 0, t_mfma = 0;
-    auto tick = [&]() -> long long { if constexpr (ABL == 20) return (long long)__builtin_amdgcn_s_memtime(); else return 0; };
     f32x4 acc[kTE];
     float m0 = 0.0f;                                                   // largest |e_0| of this lane's sample
     half8 bhi, blo;
@@ -429,127 +375,24 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             // 9 slots of (4 ds_read_b128 + 6 MFMAs of 16 cycles); between them one piece of the gather / DMA issue: slots 0-2 carry the
             // DMA pieces, slot 0 the affine start values, slots 3 and 6 one row group each — blend, store the h rows, re-issue.
             auto piece = [&](int qs) {
-                if (qs < kP) { const long long t0 = tick(); stream_issue_piece<ABL>(nx, qs, lane, wave); t_piece += tick() - t0; }
-                if constexpr (ABL == 43) {                             // the eight tap loads spread over slots 3-8, one or two per slot
-                    if (qs == 0) { affine_row(nsv, nc, 0); affine_row(nsv, nc, 1); }
-                    else if (qs == 3) { blend_row(bufA, nsv, 0); finish_row(0); issue_tap(bufA, n2sv, n2c, 0, 0); }
-                    else if (qs == 4) issue_tap(bufA, n2sv, n2c, 0, 1);
-                    else if (qs == 5) issue_tap(bufA, n2sv, n2c, 0, 2);
-                    else if (qs == 6) { issue_tap(bufA, n2sv, n2c, 0, 3); blend_row(bufB, nsv, 1); finish_row(1); issue_tap(bufB, n2sv, n2c, 1, 0); }
-                    else if (qs == 7) issue_tap(bufB, n2sv, n2c, 1, 1);
-                    else if (qs == 8) { issue_tap(bufB, n2sv, n2c, 1, 2); issue_tap(bufB, n2sv, n2c, 1, 3); }
-                    return;
-                }
-                if (qs == 0) { const long long t0 = tick(); affine_row(nsv, nc, 0); affine_row(nsv, nc, 1); t_aff += tick() - t0; }
-                else if (qs == 3) { const long long t0 = tick(); blend_row(bufA, nsv, 0); const long long t1 = tick(); finish_row(0); issue_row(bufA, n2sv, n2c, 0); t_blend += t1 - t0; t_issue += tick() - t1; }
-                else if (qs == 6) { const long long t0 = tick(); blend_row(bufB, nsv, 1); const long long t1 = tick(); finish_row(1); issue_row(bufB, n2sv, n2c, 1); t_blend += t1 - t0; t_issue += tick() - t1; }
+                if (qs < kP) stream_issue_piece(nx, qs, lane, wave);
+                if (qs == 0) { affine_row(nsv, nc, 0); affine_row(nsv, nc, 1); }
+                else if (qs == 3) { blend_row(bufA, nsv, 0); finish_row(0); issue_row(bufA, n2sv, n2c, 0); }
+                else if (qs == 6) { blend_row(bufB, nsv, 1); finish_row(1); issue_row(bufB, n2sv, n2c, 1); }
             };
-            if constexpr (kOneTapBuf) {
-                auto load_a = [&](int qs, half8 (&a)[4]) {
-                    const float* w0 = wl + (2 * qs * 2) * 256;
-                    a[0] = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0));
-                    a[1] = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 512));
-                    a[2] = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 256));
-                    a[3] = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 768));
-                };
-                auto mma = [&](f32x4& c0, f32x4& c1, const half8 (&a)[4]) {
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], bhi, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], bhi, c1, 0, 0, 0);
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], blo, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], blo, c1, 0, 0, 0);
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[2], bhi, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[3], bhi, c1, 0, 0, 0);
-                };
-                auto piece1 = [&](int qs) {
-                    if (qs < kPieces) stream_issue_piece<ABL>(nx, qs, lane, wave);
-                    if (qs == 0) { affine_row(nsv, nc, 0); affine_row(nsv, nc, 1); issue_row(bufA, nsv, nc, 0); }
-                    else if (qs == 4) { blend_row(bufA, nsv, 0); finish_row(0); issue_row(bufA, nsv, nc, 1); }
-                    else if (qs == 8) { blend_row(bufA, nsv, 1); finish_row(1); }
-                };
-                half8 a0[4], a1[4];
-                if constexpr (ABL != 63) load_a(0, a0);
-#pragma unroll
-                for (int qs = 0; qs < kTE / 2; ++qs) {
-                    if constexpr (ABL == 63) { load_a(qs, a0); mma(acc[2 * qs], acc[2 * qs + 1], a0); piece1(qs); }
-                    else {
-                        if (qs + 1 < kTE / 2) { if (qs & 1) load_a(qs + 1, a0); else load_a(qs + 1, a1); }
-                        if constexpr (ABL == 65) piece1(qs);               // 65: the piece under the LDS round trip, then the MFMAs
-                        if (qs & 1) mma(acc[2 * qs], acc[2 * qs + 1], a1); else mma(acc[2 * qs], acc[2 * qs + 1], a0);
-                        if constexpr (ABL == 64) piece1(qs);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else if constexpr (ABL == 60 || ABL == 61 || ABL == 62) {
-                // development build: the A operands of slot qs + 1 are read right after slot qs's MFMAs have issued — into the registers those
-                // MFMAs have just read — so that their LDS round trip runs under the slot's gather / DMA piece instead of in front of the next
-                // MFMAs (no extra registers: the read-ahead of round 3 needed 16 and spilled).  61: the piece comes BEFORE the MFMAs instead
-                // (reads issued, piece, MFMAs).  62: both (reads for the next slot after the MFMAs, and the piece first).
-                auto load_a = [&](int qs, half8& ah0, half8& ah1, half8& al0, half8& al1) {
-                    const float* w0 = wl + (2 * qs * 2) * 256;
-                    ah0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0));
-                    ah1 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 512));
-                    al0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 256));
-                    al1 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 768));
-                };
-                auto mma = [&](f32x4& c0, f32x4& c1, const half8& ah0, const half8& ah1, const half8& al0, const half8& al1) {
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bhi, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bhi, c1, 0, 0, 0);
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, blo, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, blo, c1, 0, 0, 0);
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, bhi, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, bhi, c1, 0, 0, 0);
-                };
-                half8 ah0, ah1, al0, al1;
-                if constexpr (ABL != 61) load_a(0, ah0, ah1, al0, al1);
-#pragma unroll
-                for (int qs = 0; qs < kTE / 2; ++qs) {
-                    if constexpr (ABL == 61) { load_a(qs, ah0, ah1, al0, al1); piece(qs); }
-                    if constexpr (ABL == 62) piece(qs);
-                    mma(acc[2 * qs], acc[2 * qs + 1], ah0, ah1, al0, al1);
-                    if constexpr (ABL != 61) { if (qs + 1 < kTE / 2) load_a(qs + 1, ah0, ah1, al0, al1); }
-                    if constexpr (ABL == 60) piece(qs);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
 #pragma unroll
             for (int qs = 0; qs < kTE / 2; ++qs) {
                 const float* w0 = wl + 2 * qs * kTF;
-                { const long long t0 = tick(); if constexpr (ABL != 5) mfma_pair<ABL, F16>(acc[2 * qs], acc[2 * qs + 1], w0, w0 + kTF, bhi, blo); t_mfma += tick() - t0; }
+                mfma_pair<F16>(acc[2 * qs], acc[2 * qs + 1], w0, w0 + kTF, bhi, blo);
                 piece(qs);
-                if constexpr (ABL < 50 || ABL > 53) __builtin_amdgcn_sched_barrier(0);
-            }
-            }
-            // development build, variants 50-53: no slot fences — the scheduler is asked to put the chunk's vector / LDS instructions UNDER
-            // the MFMAs instead (two vector instructions per 16-clock MFMA are free: profiles/round4_fused_experiments.md section 5)
-            if constexpr (ABL >= 50 && ABL <= 53) {
-#pragma unroll
-                for (int k = 0; k < 54; ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                              // one MFMA
-                    if constexpr (ABL == 50 || ABL == 52) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // one LDS read
-                    __builtin_amdgcn_sched_group_barrier(0x002, ABL == 51 || ABL == 53 ? 1 : 2, 0);  // one / two vector instructions
-                    if constexpr (ABL == 51 || ABL == 53) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    if constexpr (ABL >= 52) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);       // a vector-memory read where one is due
-                }
+                __builtin_amdgcn_sched_barrier(0);
             }
             read_b(bhi, blo);                                          // next chunk's B operand (own LDS tile, in-order LDS)
             // the 8 tap loads issued in slots 3 and 6 stay in flight over the barrier (they are younger than every DMA piece)
-            if constexpr (ABL == 20) {
-                const long long t0 = tick();
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                const long long t1 = tick();
-                __syncthreads();
-                t_dma += t1 - t0; t_bar += tick() - t1; t_chunks += 1;
-            } else
-            stream_sync<ABL, kTapsLive ? 8 : 0>();
-            if constexpr (ABL == 40 || ABL == 41 || ABL == 42) {       // development build: the three waves of a SIMD (w, w + 4, w + 8) leave the barrier apart
-                constexpr int kS = ABL == 40 ? 4 : ABL == 41 ? 8 : 2;
-                if (wave >= 4) __builtin_amdgcn_s_sleep(kS);
-                if (wave >= 8) __builtin_amdgcn_s_sleep(kS);
-            }
+            stream_sync<8>();
             ++g;
         }
         scale_acc<kTE>(acc, e_down);
-        mark(3 + sv);
         if (sv == 0) {
             m0 = sample_max<kTE, false>(acc);
             // e_0 out, as whole lines: the wave's h tile is free between the B-operand read that closed the pass and the next chunk's
@@ -609,10 +452,8 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             *reinterpret_cast<float4*>(a.e + i_row[it] * (2 * kE) + kE + 32 * m + 4 * qd) = v;
         }
     };
-    chained_layer<kTE, false, ABL, kG_K1b, F16, 2>(k1, acc, p, a.blob, lds, lane, wave, store_tiles);
-    mark(7);
+    chained_layer<kTE, false, kG_K1b, F16, 2>(k1, acc, p, a.blob, lds, lane, wave, store_tiles);
     {
-        constexpr bool kStream = !(ABL == 3 || ABL == 12 || ABL == 5);
         // lane (r0, qd) fetches 16 bytes of row rr = r0 + 8 it of the wave's tile; a row's eight 16-byte segments are stored rotated
         // by f(rr) = (rr >> 1) & 7 (the lane asks for segment qd ^ f(rr)), so that the B-operand reads below — 16 rows per pass,
         // 128 bytes apart — spread over the banks
@@ -621,7 +462,6 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         for (int it = 0; it < 2; ++it) esrc[it] = a.e + i_row[it] * (2 * kE) + 4 * (qd ^ (((r0 + 8 * it) >> 1) & 7));
         float* const ebuf[2] = {stage, lds + kLdsE0 + wave * 512};
         auto issue_e0 = [&](int m) {                                   // K step m (channels 32 m .. 32 m + 31) -> buffer m & 1
-            if constexpr (!kStream) return;
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_void*)(ebuf[m & 1] + it * 256));
@@ -633,7 +473,6 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             }
         };
         auto wait_vm = [&](auto n) {                                   // at most n of this wave's vector memory operations outstanding
-            if constexpr (!kStream) return;
             constexpr int N = decltype(n)::value;
             if constexpr (N >= 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
             else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -666,8 +505,8 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
 #pragma unroll
                     for (int q = 0; q < kTD / 2; ++q) {
                         const float* w0 = wl + (kl * kTD + 2 * q) * kTF;
-                        mfma_pair<ABL, F16>(k1[2 * q], k1[2 * q + 1], w0, w0 + kTF, bhi, blo);
-                        if (kl == 0 && q < kP) stream_issue_piece<ABL>(nx, q, lane, wave);
+                        mfma_pair<F16>(k1[2 * q], k1[2 * q + 1], w0, w0 + kTF, bhi, blo);
+                        if (kl == 0 && q < kP) stream_issue_piece(nx, q, lane, wave);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (m + 2 < kSteps) issue_e0(m + 2);              // into the buffer just read
@@ -677,12 +516,10 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             if (2 * c + 2 < kSteps && 2 * c + 3 < kSteps) wait_vm(std::integral_constant<int, 4>());
             else if (2 * c + 2 < kSteps) wait_vm(std::integral_constant<int, 2>());
             else wait_vm(std::integral_constant<int, 0>());
-            if constexpr (kStream && ABL != 11) __syncthreads();
+            __syncthreads();
         }
     }
-    mark(8);
     scale_acc<kTD>(k1, lsc[kLayerK1] * pinv);                          // k1 = key_map([e_0 ; e_1]); r = relu(k1) is used straight from these registers
-    mark(5);
     // ---- logit = <key, qry> / 16 as the bilinear form r^T (M x + v) + u^T x + c of r = relu(k1) and x = relu(Wq1 g + bq1)
     //      (car_fused_layout.h): one 128 x 128 layer instead of key_map_2 and query_embed_2 ------------------------------------------
     half8 ghi, glo;                                                    // B operand of the layer fed by g (k = 16: folded bias)
@@ -702,13 +539,13 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
     f32x4 t1[kTD], mt[kTD];
 #pragma unroll
     for (int t = 0; t < kTD; ++t) t1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    stream_issue_all<ABL, F16>(a.blob, lds, kG_Q1 + 1, lane, wave);
+    stream_issue_all<F16>(a.blob, lds, kG_Q1 + 1, lane, wave);
     small_layer<F16>(t1, ghi, glo, lds + kLdsW + (kG_Q1 & 1) * kChunkTiles * kTF + 4 * lane);          // q1
-    stream_sync<ABL>();
+    stream_sync();
     scale_acc<kTD>(t1, lsc[kLayerQ1] * pinv);
     pow2_scale(fmaxf(sample_max<kTD, true>(t1), 1e-30f), p, pinv);
     init_bias<kTD>(mt, lds + kLdsBias + kBiasV, q4, p / lsc[kLayerM]);
-    chained_layer<kTD, true, ABL, kG_M, F16>(mt, t1, p, a.blob, lds, lane, wave);
+    chained_layer<kTD, true, kG_M, F16>(mt, t1, p, a.blob, lds, lane, wave);
     scale_acc<kTD>(mt, lsc[kLayerM] * pinv);                           // M x + v
     float dot = 0.0f;
 #pragma unroll
@@ -766,7 +603,6 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             }
         }
     }
-    mark(6);
     if (a.part) {
 #pragma unroll
         for (int rw = 0; rw < kRaysPerWave; ++rw) {
@@ -789,22 +625,10 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
             }
         }
     }
-    if constexpr (ABL == 20) {
-        if (lane == 0) {
-            long long* out = reinterpret_cast<long long*>(a.pixel_val) + ((long)blk * kWaves + wave) * 8;
-            out[0] = t_blend; out[1] = t_dma; out[2] = t_bar; out[3] = t_chunks; out[4] = t_issue; out[5] = t_piece; out[6] = t_aff; out[7] = t_mfma;
-        }
-    }
-    if constexpr (kStamp) {
-        if (tid == 0) {
-            long long* out = reinterpret_cast<long long*>(a.pixel_val) + (long)blk * 16;
-            for (int k = 0; k < 10; ++k) out[k] = stamp[k];
-        }
-    }
 }
 
 
-int launch_fused(int abl, int blk0, int nblk, const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h, int lat_w, int lat_pad,
+int launch_fused(const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h, int lat_w, int lat_pad,
                  const float* gmeta, const float* wpt, const float* blob, const float* bias, int b, int V, int R, int P, int H, int W, int no_sample, float* e,
                  float* g, float* logit, float* pt, float* pixel_val, float* part, void* stream, bool f16 = false) {
     CAR_REQUIRE(poses && rays && steps && lattice && gmeta && wpt && blob && bias, "car_fused_samples: null input");
@@ -824,32 +648,12 @@ int launch_fused(int abl, int blk0, int nblk, const float* poses, const float* r
     a.b = b; a.V = V; a.R = R; a.P = P; a.H = H; a.W = W;
     a.no_sample = no_sample != 0;
     a.S = (long)b * V * R * P;
-    a.blk0 = blk0;
     a.e = e; a.g = g; a.logit = logit; a.pt = pt; a.pixel_val = pixel_val; a.part = part;
 #ifdef CAR_BOUNDS
     a.lattice_floats = (long)b * V * 2 * lat_h * lat_w * kC;
 #endif
-    long groups = (long)b * V * car_div_up(R, kTileRays) * car_div_up(P, kTileSteps);
-    if (nblk > 0) groups = (groups - blk0 < nblk) ? groups - blk0 : nblk;     // development build: a slice of the sample groups
-    void (*kern)(const FusedArgs) = f16 ? fused_kernel<0, false, true> : fused_kernel<0>;
-#if defined(CAR_ABLATION) && !defined(CAR_ABLATION_NONE)       // CAR_ABLATION_NONE: the development build's entries without the timing variants
-    switch (abl) {
-        case 1: kern = fused_kernel<1>; break;   case 2: kern = fused_kernel<2>; break;   case 3: kern = fused_kernel<3>; break;
-        case 4: kern = fused_kernel<4>; break;   case 5: kern = fused_kernel<5>; break;   case 11: kern = fused_kernel<11>; break;
-        case 12: kern = fused_kernel<12>; break;   case 13: kern = fused_kernel<13>; break;   case 20: kern = fused_kernel<20>; break;
-        case 21: kern = fused_kernel<21>; break;   case 22: kern = fused_kernel<22>; break;   case 23: kern = fused_kernel<23>; break;
-        case 24: kern = fused_kernel<24>; break;   case 28: kern = fused_kernel<28>; break;   case 30: kern = fused_kernel<30>; break;
-        case 31: kern = fused_kernel<31>; break;   case 32: kern = fused_kernel<32>; break;   case 33: kern = fused_kernel<33>; break;
-        case 40: kern = fused_kernel<40>; break;   case 41: kern = fused_kernel<41>; break;   case 42: kern = fused_kernel<42>; break;
-        case 43: kern = fused_kernel<43>; break;   case 50: kern = fused_kernel<50>; break;   case 51: kern = fused_kernel<51>; break;
-        case 52: kern = fused_kernel<52>; break;   case 53: kern = fused_kernel<53>; break;   case 60: kern = fused_kernel<60>; break;
-        case 61: kern = fused_kernel<61>; break;   case 62: kern = fused_kernel<62>; break;   case 63: kern = fused_kernel<63>; break;
-        case 64: kern = fused_kernel<64>; break;   case 65: kern = fused_kernel<65>; break;
-        default: break;
-    }
-#else
-    (void)abl;
-#endif
+    const long groups = (long)b * V * car_div_up(R, kTileRays) * car_div_up(P, kTileSteps);
+    void (*kern)(const FusedArgs) = f16 ? fused_kernel<false, true> : fused_kernel<>;
     hipError_t e1 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     if (e1 != hipSuccess) { car_set_error("car_fused_samples: cannot reserve %zu bytes of LDS: %s", kLdsBytes, hipGetErrorString(e1)); return CAR_E_LAUNCH; }
     (void)hipGetLastError();
@@ -866,7 +670,7 @@ extern "C" size_t car_fused_bias_floats(void) { return (size_t)(kBiasFloats + kB
 extern "C" int car_fused_samples(const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h, int lat_w,
                                  int lat_pad, const float* gmeta, const float* wpt, const float* blob, const float* bias, int b, int V, int R, int P,
                                  int H, int W, int no_sample, float* e, float* g, float* logit, float* pt, float* pixel_val, void* stream) {
-    return launch_fused(0, 0, 0, poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob, bias, b, V, R, P, H, W, no_sample, e, g, logit, pt,
+    return launch_fused(poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob, bias, b, V, R, P, H, W, no_sample, e, g, logit, pt,
                         pixel_val, nullptr, stream);
 }
 
@@ -878,7 +682,7 @@ extern "C" int car_fused_samples_parts(const float* poses, const float* rays, co
                                        int P, int H, int W, int no_sample, float* e, float* g, float* logit, float* pt, float* pixel_val,
                                        float* part, void* stream) {
     CAR_REQUIRE(part, "car_fused_samples_parts: null output");
-    return launch_fused(0, 0, 0, poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob, bias, b, V, R, P, H, W, no_sample, e, g, logit, pt,
+    return launch_fused(poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob, bias, b, V, R, P, H, W, no_sample, e, g, logit, pt,
                         pixel_val, part, stream);
 }
 
@@ -889,33 +693,9 @@ extern "C" int car_fused_samples_f16(const float* poses, const float* rays, cons
                                      int lat_pad, const float* gmeta, const float* wpt, const float* blob16, const float* bias, int b, int V, int R,
                                      int P, int H, int W, int no_sample, float* e, float* g, float* logit, float* pt, float* pixel_val,
                                      float* part, void* stream) {
-    return launch_fused(0, 0, 0, poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob16, bias, b, V, R, P, H, W, no_sample, e, g, logit,
+    return launch_fused(poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob16, bias, b, V, R, P, H, W, no_sample, e, g, logit,
                         pt, pixel_val, part, stream, true);
 }
-
-#ifdef CAR_ABLATION
-// development build only (tools/build_dev.py): timing-only variants of the kernel, results are wrong by construction
-extern "C" int car_fused_samples_ablate(int abl, const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h,
-                                        int lat_w, int lat_pad, const float* gmeta, const float* wpt, const float* blob, const float* bias, int b,
-                                        int V, int R, int P, int H, int W, int no_sample, float* e, float* g, float* logit, float* pt,
-                                        float* pixel_val, void* stream) {
-    return launch_fused(abl, 0, 0, poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob, bias, b, V, R, P, H, W, no_sample, e, g, logit, pt,
-                        pixel_val, nullptr, stream);
-}
-// the same launch cut into slices of `nblk` sample groups (one kernel launch each): every slice starts its workgroups in phase
-extern "C" int car_fused_samples_sliced(int nblk, const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h,
-                                        int lat_w, int lat_pad, const float* gmeta, const float* wpt, const float* blob, const float* bias, int b,
-                                        int V, int R, int P, int H, int W, int no_sample, float* e, float* g, float* logit, float* pt,
-                                        float* pixel_val, void* stream) {
-    const long groups = (long)b * V * car_div_up(R, kTileRays) * car_div_up(P, kTileSteps);
-    for (long b0 = 0; b0 < groups; b0 += nblk) {
-        const int rc = launch_fused(0, (int)b0, nblk, poses, rays, steps, lattice, lat_h, lat_w, lat_pad, gmeta, wpt, blob, bias, b, V, R, P, H, W, no_sample, e, g,
-                                    logit, pt, pixel_val, nullptr, stream);
-        if (rc != CAR_OK) return rc;
-    }
-    return CAR_OK;
-}
-#endif
 
 // The three-view exchange's two layers for explicit rows (models.py:345-475 through engine._encode_three_views): the ROWS instance of the fused
 // per-sample kernel — its source pass, one per (sample set, component), nothing behind it.  rows = n_sets * R * P * ncomp, row = sample * ncomp +
@@ -939,7 +719,7 @@ extern "C" int car_fused_rows(const float* lattice, int lat_h, int lat_w, int la
     a.e = e;
     a.row_src = row_src; a.row_grid = row_grid; a.row_pe = row_pe; a.ncomp = ncomp;
     const long groups = (long)n_sets * ncomp * car_div_up(R, kTileRays) * car_div_up(P, kTileSteps);
-    void (*kern)(const FusedArgs) = fused_kernel<0, true>;
+    void (*kern)(const FusedArgs) = fused_kernel<true>;
     hipError_t e1 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     if (e1 != hipSuccess) { car_set_error("car_fused_rows: cannot reserve %zu bytes of LDS: %s", kLdsBytes, hipGetErrorString(e1)); return CAR_E_LAUNCH; }
     (void)hipGetLastError();

@@ -58,9 +58,7 @@ __device__ __forceinline__ NextChunk next_chunk(const float* __restrict__ blob, 
 }
 // piece p of the next chunk: wave w copies KB number kWaves p + w (wrapped into the chunk: re-copying identical bytes is harmless).
 // LDS-DMA in inline asm, see car_linear.hip.  Must only run after the barrier that retired the buffer's previous chunk.
-template <int ABL = 0>
 __device__ __forceinline__ void stream_issue_piece(const NextChunk& n, int p, int lane, int wave) {
-    if constexpr (ABL == 3 || ABL == 12 || ABL == 5 || ABL == 23 || ABL == 24) return;      // 23 / 24: no weight DMA, barriers kept
     int kb = kWaves * p + wave;
     kb = kb < n.nkb ? kb : kb - n.nkb;
     kb = kb < n.nkb ? kb : kb - n.nkb;
@@ -84,33 +82,26 @@ __device__ __forceinline__ void stream_issue_piece(const NextChunk& n, int p, in
 #endif
     const unsigned voff = 16u * (unsigned)lane;
     unsigned keep;
-#define CAR_DMA_PIECE(POLICY) asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3" POLICY "\n\ts_mov_b32 m0, %0" \
-                                           : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(gsrc) : "memory")
-    if constexpr (ABL == 30) CAR_DMA_PIECE(" nt");                    // development build: cache-policy probes of the weight stream
-    else if constexpr (ABL == 31) CAR_DMA_PIECE(" sc1");
-    else if constexpr (ABL == 32) CAR_DMA_PIECE(" sc0 sc1");
-    else if constexpr (ABL == 33) CAR_DMA_PIECE(" sc0");
-    else CAR_DMA_PIECE("");
-#undef CAR_DMA_PIECE
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(gsrc) : "memory");
 }
-template <int ABL = 0, bool F16 = false>
+template <bool F16 = false>
 __device__ __forceinline__ void stream_issue_all(const float* __restrict__ blob, float* lds, int g, int lane, int wave) {
     if (g >= kNumChunks) return;
     const NextChunk n = next_chunk<F16>(blob, lds, g);
 #pragma unroll
-    for (int p = 0; p < chunk_pieces<F16>(); ++p) stream_issue_piece<ABL>(n, p, lane, wave);
+    for (int p = 0; p < chunk_pieces<F16>(); ++p) stream_issue_piece(n, p, lane, wave);
 }
 // end of a chunk: the DMA of the next chunk has landed and every wave is done reading the current one.  KEEP = number of
 // vector loads this wave issued AFTER its last DMA piece and wants to leave in flight across the barrier (loads return in
 // order, so "at most KEEP outstanding" still means every DMA piece has landed).
-template <int ABL = 0, int KEEP = 0>
+template <int KEEP = 0>
 __device__ __forceinline__ void stream_sync() {
-    if constexpr (ABL == 3 || ABL == 12 || ABL == 5) return;
     if constexpr (KEEP == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else if constexpr (KEEP == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if constexpr (KEEP == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (ABL != 11) __syncthreads();                          // 11 (development build): the weight stream without its barrier
+    __syncthreads();
 }
 
 #include "car_split.h"
@@ -155,7 +146,7 @@ __device__ __forceinline__ float sample_max(const f32x4 (&v)[NT]) {
 
 // two output tiles x three split products, interleaved so consecutive MFMAs never share an accumulator.  F16: one product each, from
 // the compact tiles (w0, w1 one KB apart), blo unused
-template <int ABL = 0, bool F16 = false>
+template <bool F16 = false>
 __device__ __forceinline__ void mfma_pair(f32x4& c0, f32x4& c1, const float* w0, const float* w1, const half8& bhi, const half8& blo) {
     if constexpr (F16) {
         const half8 a0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0));
@@ -164,14 +155,10 @@ __device__ __forceinline__ void mfma_pair(f32x4& c0, f32x4& c1, const float* w0,
         c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bhi, c1, 0, 0, 0);
         return;
     }
-    half8 ah0, ah1, al0, al1;
-    if constexpr (ABL == 12 || ABL == 13) { ah0 = bhi; ah1 = blo; al0 = blo; al1 = bhi; }        // development build: no A-operand reads from LDS
-    else {
-        ah0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0));
-        ah1 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1));
-        al0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 256));
-        al1 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1 + 256));
-    }
+    const half8 ah0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0));
+    const half8 ah1 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1));
+    const half8 al0 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w0 + 256));
+    const half8 al1 = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1 + 256));
     c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bhi, c0, 0, 0, 0);
     c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bhi, c1, 0, 0, 0);
     c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, blo, c0, 0, 0, 0);
@@ -208,7 +195,7 @@ __device__ __forceinline__ void store_rows(const f32x4 (&acc)[NT], float* row, i
 struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 // G0: index of the layer's first weight chunk.  The chunk order is static, so every chunk's place in the blob, its size and its LDS
 // buffer are constants here (resolving them at run time cost a chain of ~20 scalar branches per chunk).
-template <int NSRC, bool RELU, int ABL, int G0, bool F16 = false, int HOOK_OPS = 0, class Hook = NoHook>
+template <int NSRC, bool RELU, int G0, bool F16 = false, int HOOK_OPS = 0, class Hook = NoHook>
 __device__ __forceinline__ void chained_layer(f32x4 (&acc)[kTD], const f32x4 (&src)[NSRC], float p, const float* __restrict__ blob,
                                               float* lds, int lane, int wave, Hook after = Hook()) {
     constexpr int kSteps = NSRC / 2, kTF = tile_floats<F16>(), kP = chunk_pieces<F16>();
@@ -233,14 +220,14 @@ __device__ __forceinline__ void chained_layer(f32x4 (&acc)[kTD], const f32x4 (&s
 #pragma unroll
                 for (int q = 0; q < kTD / 2; ++q) {
                     const float* w0 = wl + (kl * kTD + 2 * q) * kTF;
-                    mfma_pair<ABL, F16>(acc[2 * q], acc[2 * q + 1], w0, w0 + kTF, bhi, blo);
+                    mfma_pair<F16>(acc[2 * q], acc[2 * q + 1], w0, w0 + kTF, bhi, blo);
                     // every DMA piece of the successor goes out in the first K step's four slots, ahead of the hook's memory
                     // operations: the chunk's closing "at most HOOK_OPS outstanding" must cover all of them
                     if (kl == 0) {
-                        if (q < 3) { if (q < kP) stream_issue_piece<ABL>(nx, q, lane, wave); }
+                        if (q < 3) { if (q < kP) stream_issue_piece(nx, q, lane, wave); }
                         else {
 #pragma unroll
-                            for (int p_ = 3; p_ < kP; ++p_) stream_issue_piece<ABL>(nx, p_, lane, wave);
+                            for (int p_ = 3; p_ < kP; ++p_) stream_issue_piece(nx, p_, lane, wave);
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -248,7 +235,7 @@ __device__ __forceinline__ void chained_layer(f32x4 (&acc)[kTD], const f32x4 (&s
                 after(m);
             }
         }
-        if (nks == 2) stream_sync<ABL, 2 * HOOK_OPS>(); else stream_sync<ABL, HOOK_OPS>();
+        if (nks == 2) stream_sync<2 * HOOK_OPS>(); else stream_sync<HOOK_OPS>();
     }
 }
 
@@ -259,7 +246,7 @@ __device__ __forceinline__ void small_layer(f32x4 (&acc)[kTD], const half8& ghi,
 #pragma unroll
     for (int q = 0; q < kTD / 2; ++q) {
         const float* w0 = wl + 2 * q * kTF;
-        mfma_pair<0, F16>(acc[2 * q], acc[2 * q + 1], w0, w0 + kTF, ghi, glo);
+        mfma_pair<F16>(acc[2 * q], acc[2 * q + 1], w0, w0 + kTF, ghi, glo);
     }
 }
 

@@ -18,9 +18,6 @@ struct GatherLevels {
     int n_levels;
 };
 
-constexpr int kGatherWave = 7;      // launch_gather: the wave-task kernel (falls back to (32, 3) for channel counts it does not cover)
-constexpr int kGatherCfg = kGatherWave;    // the product's configuration (tools/bench_gather.py: wave-tasks 55-65 % of the HBM peak, (32 rows, 3 items) 52-54 %, (16, 3) 49-50 %)
-
 // A workgroup handles kGRows sampled points at a time: the bilinear tap indices / weights are computed once per (point,
 // level) into LDS, then every thread moves float4s: 4 tap reads (L1 / L2 resident maps), one 16-byte store, kItems items
 // (4 kItems tap loads) in flight per thread.  The stage is bound by the texture path (five bytes through it per byte written).
@@ -200,10 +197,44 @@ __global__ void __launch_bounds__(256) gather_wave_kernel(GatherLevels L, WaveLe
     }
 }
 
-}  // namespace
+// The wave-task kernel, or the per-float4 kernel with (32 rows, 3 items) for channel counts the wave tasks do not cover.  Measured on the
+// bench frame (tools/bench_gather.py, at 206ca6d): wave tasks 55-65 % of the HBM peak, (32 rows, 3 items) 52-54 %, (16, 3) 49-50 %.
+int launch_gather(const GatherLevels& L, int n_maps, const float* grid, long pts, int run, int mode, int place, int V, float* out, int ld_out,
+                  int col_out, void* stream) {
+    WaveLevels WL;
+    bool ok = true;
+    int tasks = 0;
+    for (int l = 0; l < L.n_levels; ++l) {
+        const int quads = L.c[l] / 4;
+        ok = ok && quads > 0 && (quads & (quads - 1)) == 0 && (quads <= 64 || quads % 64 == 0);
+        WL.lpr[l] = quads < 64 ? quads : 64;
+        WL.rpt[l] = 64 / WL.lpr[l];
+        ok = ok && WL.rpt[l] <= kWRows;                                // a 4-channel level (64 rows per task > the group's 32) takes the per-float4 kernel
+        const int segs = quads / WL.lpr[l];
+        WL.lpr_shift[l] = WL.seg_shift[l] = 0;
+        while ((1 << WL.lpr_shift[l]) < WL.lpr[l]) ++WL.lpr_shift[l];
+        while ((1 << WL.seg_shift[l]) < segs) ++WL.seg_shift[l];
+        WL.tasks[l] = tasks;
+        tasks += (kWRows / WL.rpt[l]) * segs;
+    }
+    for (int l = L.n_levels; l <= CAR_MAX_LEVELS; ++l) WL.tasks[l] = tasks;
+    for (int l = L.n_levels; l < CAR_MAX_LEVELS; ++l) { WL.lpr[l] = WL.rpt[l] = 1; WL.lpr_shift[l] = WL.seg_shift[l] = 0; }
+    auto blocks = [&](int rows) {                                      // work groups of `rows` rows, at most 65536 (the kernels loop)
+        const long groups = run > 1 ? (long)n_maps * ((pts / run + rows - 1) / rows) * run : ((long)n_maps * pts + rows - 1) / rows;
+        return dim3((unsigned)(groups < 65536 ? groups : 65536));
+    };
+    (void)hipGetLastError();
+    if (ok)
+        hipLaunchKernelGGL(gather_wave_kernel, blocks(kWRows), dim3(256), 0, (hipStream_t)stream, L, WL, n_maps, grid, pts, run, mode, place, V,
+                           out, ld_out, col_out);
+    else                                                               // odd channel counts: the per-float4 kernel
+        hipLaunchKernelGGL((gather_kernel<32, 3>), blocks(32), dim3(256), 0, (hipStream_t)stream, L, n_maps, grid, pts, run, mode, place, V,
+                           out, ld_out, col_out);
+    CAR_CHECK_LAUNCH("car_gather_bilinear");
+    return CAR_OK;
+}
 
-int launch_gather(int cfg, const GatherLevels& L, int n_maps, const float* grid, long pts, int run, int mode, int place, int V, float* out,
-                  int ld_out, int col_out, void* stream);
+}  // namespace
 
 extern "C" int car_gather_bilinear(const float* const* maps, const int* level_c, const int* level_h,
                                    const int* level_w, int n_levels, int n_maps, const float* grid, long pts, int run, int mode,
@@ -229,78 +260,5 @@ extern "C" int car_gather_bilinear(const float* const* maps, const int* level_c,
                 "car_gather_bilinear: output window [%d,%d) must be float4-aligned inside a row of %d", col_out, col_out + 4 * q, ld_out);
     CAR_REQUIRE((long)n_maps * level_h[0] * level_w[0] < 2147483647L, "car_gather_bilinear: map too large for 32-bit texel indices");
     if (run < 1 || pts % run != 0) run = 1;
-    return launch_gather(kGatherCfg, L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-}
-
-#ifdef CAR_ABLATION
-// development build only: the same kernel with another (rows per group, items in flight) pair — tools/bench_gather.py
-extern "C" int car_gather_bilinear_cfg(int cfg, const float* const* maps, const int* level_c, const int* level_h, const int* level_w, int n_levels,
-                                       int n_maps, const float* grid, long pts, int run, int mode, int place, int V, float* out, int ld_out,
-                                       int col_out, void* stream) {
-    GatherLevels L;
-    L.n_levels = n_levels;
-    int q = 0;
-    for (int l = 0; l < n_levels; ++l) { L.map[l] = maps[l]; L.c[l] = level_c[l]; L.h[l] = level_h[l]; L.w[l] = level_w[l]; L.q0[l] = q; q += level_c[l] / 4; }
-    L.q0[n_levels] = q;
-    for (int l = n_levels; l < CAR_MAX_LEVELS; ++l) { L.map[l] = nullptr; L.c[l] = L.h[l] = L.w[l] = 0; if (l > n_levels) L.q0[l] = q; }
-    if (run < 1 || pts % run != 0) run = 1;
-    return launch_gather(cfg, L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-}
-#endif
-
-namespace {
-template <int ROWS, int ITEMS>
-int launch_cfg(const GatherLevels& L, int n_maps, const float* grid, long pts, int run, int mode, int place, int V, float* out, int ld_out,
-               int col_out, void* stream) {
-    const long groups = run > 1 ? (long)n_maps * ((pts / run + ROWS - 1) / ROWS) * run : ((long)n_maps * pts + ROWS - 1) / ROWS;
-    const unsigned blocks = (unsigned)(groups < 65536 ? groups : 65536);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((gather_kernel<ROWS, ITEMS>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, L, n_maps, grid, pts, run, mode,
-                       place, V, out, ld_out, col_out);
-    CAR_CHECK_LAUNCH("car_gather_bilinear");
-    return CAR_OK;
-}
-}  // namespace
-
-int launch_gather(int cfg, const GatherLevels& L, int n_maps, const float* grid, long pts, int run, int mode, int place, int V, float* out,
-                  int ld_out, int col_out, void* stream) {
-    if (cfg == kGatherWave) {
-        WaveLevels WL;
-        bool ok = true;
-        int tasks = 0;
-        for (int l = 0; l < L.n_levels; ++l) {
-            const int quads = L.c[l] / 4;
-            ok = ok && quads > 0 && (quads & (quads - 1)) == 0 && (quads <= 64 || quads % 64 == 0);
-            WL.lpr[l] = quads < 64 ? quads : 64;
-            WL.rpt[l] = 64 / WL.lpr[l];
-            ok = ok && WL.rpt[l] <= kWRows;                            // a 4-channel level (64 rows per task > the group's 32) takes the per-float4 kernel
-            const int segs = quads / WL.lpr[l];
-            WL.lpr_shift[l] = WL.seg_shift[l] = 0;
-            while ((1 << WL.lpr_shift[l]) < WL.lpr[l]) ++WL.lpr_shift[l];
-            while ((1 << WL.seg_shift[l]) < segs) ++WL.seg_shift[l];
-            WL.tasks[l] = tasks;
-            tasks += (kWRows / WL.rpt[l]) * segs;
-        }
-        for (int l = L.n_levels; l <= CAR_MAX_LEVELS; ++l) WL.tasks[l] = tasks;
-        for (int l = L.n_levels; l < CAR_MAX_LEVELS; ++l) { WL.lpr[l] = WL.rpt[l] = 1; WL.lpr_shift[l] = WL.seg_shift[l] = 0; }
-        if (ok) {
-            const long groups = run > 1 ? (long)n_maps * ((pts / run + kWRows - 1) / kWRows) * run : ((long)n_maps * pts + kWRows - 1) / kWRows;
-            const unsigned blocks = (unsigned)(groups < 65536 ? groups : 65536);
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(gather_wave_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L, WL, n_maps, grid, pts, run, mode, place, V,
-                               out, ld_out, col_out);
-            CAR_CHECK_LAUNCH("car_gather_bilinear");
-            return CAR_OK;
-        }
-        cfg = 1;                                                       // odd channel counts: the per-float4 kernel
-    }
-    switch (cfg) {
-        case 1: return launch_cfg<32, 3>(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-        case 2: return launch_cfg<64, 3>(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-        case 3: return launch_cfg<16, 4>(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-        case 4: return launch_cfg<32, 4>(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-        case 5: return launch_cfg<64, 4>(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-        case 6: return launch_cfg<64, 6>(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-        default: return launch_cfg<16, 3>(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
-    }
+    return launch_gather(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
 }

@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(kThreads) linear16_kernel(const LinArgs a) {
         stream_sync();                                                 // chunk 0 landed, the table is visible
         f32x4 key[kTD];
         init_bias<kTD>(key, lb, q4, p2 / lsc[0]);
-        chained_layer<kTD, true, 0, kG_K2>(key, acc, p2, a.tail, lds, lane, wave);
+        chained_layer<kTD, true, kG_K2>(key, acc, p2, a.tail, lds, lane, wave);
         scale_acc<kTD>(key, lsc[0] * p2inv);
         half8 ghi, glo;                                                // B operand of the layer fed by g (k = 16: folded bias)
         {
@@ -256,7 +256,7 @@ __global__ void __launch_bounds__(kThreads) linear16_kernel(const LinArgs a) {
         scale_acc<kTD>(t1, lsc[1] * p2inv);
         pow2_scale(fmaxf(sample_max<kTD, true>(t1), 1e-30f), p2, p2inv);
         init_bias<kTD>(qv, lb + kD, q4, p2 / lsc[2]);
-        chained_layer<kTD, true, 0, kG_Q2>(qv, t1, p2, a.tail, lds, lane, wave);
+        chained_layer<kTD, true, kG_Q2>(qv, t1, p2, a.tail, lds, lane, wave);
         scale_acc<kTD>(qv, lsc[2] * p2inv);
         float dot = 0.0f;
 #pragma unroll

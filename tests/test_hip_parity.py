@@ -129,7 +129,7 @@ def test_split_fp16_linear_matches_torch(M, K, N, flags):
 
 
 @pytest.mark.parametrize("M,K,N,flags", [(4100, 288, 576, 0), (1000, 128, 128, 4), (333, 576, 64, 0), (777, 64, 32, 2)])
-def test_split_fp16_linear_with_the_relu_mask_in_its_store(M, K, N, flags):
+def test_split_fp16_linear_with_the_relu_mask_applied_as_it_writes(M, K, N, flags):
     """car_linear_x3_masked = car_linear_x3 followed by car_relu_mask, bit for bit (the backward's data gradient of a layer behind a ReLU),
     for every tile count of the kernel, with ACCUM and RELU_OUT, a strided activation, and -0.0 / NaN activations (not > 0: zeroed)."""
     from cross_attention_renderer_amd.engine import PackedLinear

@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes over the fused per-sample kernel alone (tools/bench_fused.py): SQ wave-state counters, TA/TCP and LDS activity.
-# usage: tools/pmc_fused.sh [ablation variants...]   (default: 0)
+# usage: tools/pmc_fused.sh [bench_fused.py variants...]   (default: 0, car_fused_samples)
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/pmc_fused
