@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +130,8 @@ SIGNATURES = {
     "car_scale_rows": (c_int, [_P, c_int, _P, c_int, _P, c_long, c_float, c_long, c_int, c_int, _P]),
     "car_add": (c_int, [_P, c_int, _P, c_int, c_float, _P, c_int, c_float, c_long, c_int, _P]),
     "car_reduce_samples": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_ssim_scratch_doubles": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "car_ssim": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

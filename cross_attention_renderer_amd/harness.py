@@ -74,6 +74,43 @@ def psnr(img: torch.Tensor, ref: torch.Tensor) -> float:
     return float("inf") if mse == 0 else -10.0 * math.log10(mse)
 
 
+def ssim(img: torch.Tensor, ref: torch.Tensor, data_range: float = 2.0) -> torch.Tensor:
+    """SSIM of the reference's eval script (eval_realestate10k.py:192-194: scikit-image 0.18.3 ``structural_similarity(x, y,
+    win_size=11, multichannel=True, gaussian_weights=True)``) on the device: ``car_ssim`` (csrc/car_metrics.hip).
+
+    ``img`` and ``ref`` are (H, W, C) or (B, H, W, C) tensors on a ROCm device, C in 1..4, H and W >= 11; they are taken as
+    contiguous float32.  Returns a float64 device tensor of shape () or (B,), each pair's mean over channels of the mean SSIM
+    over the pixels at least 5 from every edge.  The launch goes on the current stream and nothing waits for it: ``.item()``
+    synchronises.
+
+    ``data_range`` defaults to 2.0, not 1.0, on purpose: the reference passes none, and scikit-image 0.18.3 then takes the range
+    of its float dtype, -1..1, so the paper's SSIM figures use C1 = 0.02**2 and C2 = 0.06**2 even for images in [0, 1].  Pass 1.0
+    for the usual convention for [0, 1] images.
+
+    Raises ValueError for CPU tensors (there is no CPU fallback), mismatched shapes and the shapes / ranges car_ssim refuses."""
+    import ctypes
+    from . import _lib
+    if not (torch.is_tensor(img) and torch.is_tensor(ref)):
+        raise ValueError("ssim: img and ref must be tensors")
+    if img.device.type != "cuda" or ref.device != img.device:
+        raise ValueError(f"ssim: needs both images on one ROCm device (got {img.device} and {ref.device}); there is no CPU fallback")
+    if img.shape != ref.shape or img.dim() not in (3, 4):
+        raise ValueError(f"ssim: need two (H, W, C) or (B, H, W, C) images of one shape, got {tuple(img.shape)} and {tuple(ref.shape)}")
+    x, y = (t.to(torch.float32).contiguous() for t in (img, ref))
+    B, H, W, C = x.shape if x.dim() == 4 else (1, *x.shape)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        n = lib.car_ssim_scratch_doubles(B, H, W, C)
+        out = torch.empty(B, dtype=torch.float64, device=x.device)
+        scratch = torch.empty(max(n, 1), dtype=torch.float64, device=x.device)      # car_ssim refuses the shape when n == 0
+        code = lib.car_ssim(x.data_ptr(), y.data_ptr(), B, H, W, C, ctypes.c_double(data_range), out.data_ptr(), scratch.data_ptr(),
+                            n, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if code == -1:
+        raise ValueError(lib.car_last_error().decode())
+    _lib.check(code, "car_ssim")
+    return out[0] if img.dim() == 3 else out
+
+
 def write_png(path: str, rgb: torch.Tensor) -> None:
     """(H, W, 3) float image in [-1, 1] -> 8-bit PNG (imageio is not available in this image)."""
     img = ((rgb.clamp(-1, 1) + 1) * 127.5).round().to(torch.uint8).cpu().numpy()

@@ -5,11 +5,13 @@
     python experiment_scripts/eval_realestate10k.py --experiment_name demo --views 2 --synthetic [--gpus N]
 
 Per item (eval_realestate10k.py:131-199): ``z = model.get_z(model_input)`` on the context images, the query view rendered in 9 ray
-chunks (18 for three views), PSNR of the rendered against the ground-truth query frame.  Items come from
-``dataio.RealEstate10kVis`` (the reference's reader, pinned in tests/test_dataio.py).  LPIPS / SSIM need lpips / skimage, which are
-not installed here.  With --gpus N the rays of every item are banded over N processes instead of N replicas evaluating everything.
+chunks (18 for three views), MSE, PSNR and SSIM of the rendered against the ground-truth query frame.  Items come from
+``dataio.RealEstate10kVis`` (the reference's reader, pinned in tests/test_dataio.py).  SSIM is the reference's scikit-image call
+(eval_realestate10k.py:192-194) computed on the device by ``harness.ssim``, with its default data_range of 2.
+LPIPS is not available: it needs the lpips package and VGG16 weights, neither of which can be installed offline.  With --gpus N
+the rays of every item are banded over N processes instead of N replicas evaluating everything.
 --synthetic: a seeded pair and feature pyramid (no dataset, no encoder); the target is then the un-chunked render of the same frame,
-so the figure checks chunk / shard invariance (inf or > 100 dB), not image quality — and is labelled so."""
+so the figures check chunk / shard invariance (inf or > 100 dB, SSIM 1), not image quality — and is labelled so."""
 import os
 import sys
 import time
@@ -29,7 +31,7 @@ def evaluate(rank, opt, default_data=DEFAULT_DATA):
     real = not opt.synthetic and (opt.data_root or os.path.isdir(default_data[0]))
     model = common.build_model(opt, dev, with_encoder=True if real else None)
     n_chunks = 9 if opt.views < 3 else 18                    # eval_realestate10k.py:144-149
-    psnrs = []
+    psnrs, mses, ssims = [], [], []
     if real:
         ds = dataio.RealEstate10kVis(opt.data_root or default_data[0], opt.pose_root or default_data[1], num_ctxt_views=opt.views,
                                      num_query_views=1, augment=False)
@@ -74,11 +76,16 @@ def evaluate(rank, opt, default_data=DEFAULT_DATA):
             target, what = harness.render_frame(model, inp, z, chunk_rays=16384)[0, :, :3], "psnr vs un-chunked render"
         rgb, target = composite(tile[0, :, :3]), composite(target)
         psnrs.append(harness.psnr(rgb, target))
+        mses.append(torch.mean((rgb - target) ** 2).item())                                  # img2mse (eval_realestate10k.py:183)
+        ssims.append(harness.ssim(rgb.reshape(H, H, 3), target.reshape(H, H, 3)).item())     # eval_realestate10k.py:192-195
         if rank == 0:
             print(f"item {k}: elapsed {elapsed:.3f} s, {what} {psnrs[-1]:.2f} dB, valid {tile[0, :, 4].mean().item():.3f}")
+            print(f"item {k} ssim {ssims[-1]:.6f}, mse {mses[-1]:.3e}")
     if rank == 0 and psnrs:
         print("mean psnr", sum(min(p, 200.0) for p in psnrs) / len(psnrs))
         print("render precision", model.render_precision)
+        print("mean mse", sum(mses) / len(mses))
+        print("mean ssim", sum(ssims) / len(ssims))
 
 
 if __name__ == "__main__":

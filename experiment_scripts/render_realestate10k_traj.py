@@ -71,7 +71,9 @@ def render(rank, opt):
                            os.path.join(out_dir, f"frame_{i:04d}.pt"))
                 gt = frame["query"].get("rgb")
                 if gt is not None and tuple(gt.shape[2:4]) == (H, H):
-                    print(f"{scene} frame {i}: PSNR {harness.psnr((rgb.clamp(-1, 1) + 1) / 2, (gt[0, 0].clamp(-1, 1) + 1) / 2):.2f} dB")
+                    img, ref = (rgb.clamp(-1, 1) + 1) / 2, (gt[0, 0].clamp(-1, 1) + 1) / 2
+                    print(f"{scene} frame {i}: PSNR {harness.psnr(img, ref):.2f} dB")
+                    print(f"{scene} frame {i}: SSIM {harness.ssim(img, ref.to(img.device)).item():.4f}")
     torch.cuda.synchronize()
     if rank == 0:
         dt = time.time() - t0

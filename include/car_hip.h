@@ -479,6 +479,18 @@ int car_profile_count(void);                                   /* stages recorde
 int car_profile_read(int i, const char** name, float* ms);     /* stage i; CAR_E_ARG when out of range                            */
 void car_profile_reset(void);
 
+/* ---- evaluation metric: SSIM (eval_realestate10k.py:192-194, scikit-image 0.18.3
+ *      structural_similarity(x, y, win_size=11, multichannel=True, gaussian_weights=True)).
+ * x, y [B,H,W,C] fp32 channel-last, C in 1..4, H and W >= 11; mssim [B] fp64 receives each pair's mean SSIM.  Per channel: fp64
+ * moments through the 11-tap Gaussian (sigma 1.5, truncate 3.5), sample covariances (121/120), C1 = (0.01 data_range)^2,
+ * C2 = (0.03 data_range)^2, the mean of S over the pixels >= 5 from every edge; then the mean over the channels.
+ * data_range: the reference passes none, and skimage 0.18.3 then takes 2.0 for float images (its dtype range -1..1), not 1.0.
+ * scratch: car_ssim_scratch_doubles(B, H, W, C) doubles, caller-owned (0 for a shape car_ssim refuses).  Sums in a fixed order:
+ * bitwise reproducible, and a pair gives the same bits alone as inside a batch. */
+size_t car_ssim_scratch_doubles(int B, int H, int W, int C);
+int car_ssim(const float* x, const float* y, int B, int H, int W, int C, double data_range, double* mssim, double* scratch,
+             size_t scratch_doubles, void* stream);
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
