@@ -22,6 +22,7 @@ Stage map:
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Dict, List, Optional
 
@@ -79,18 +80,48 @@ def _mode(m) -> str:
     return {1: "single", 2: "concat2", 3: "concat3"}[m.n_view]
 
 
+class _Cached:
+    """One object built on the device from source tensors and plain values, rebuilt when any of them changes.  The key is each source's
+    data pointer, _version, shape, strides, dtype and device, plus the plain values.  The sources are held beside the value as storage
+    aliases (``t.detach()``: ``p.data = new`` swaps a Parameter's storage under the same object), so no address in the key can be handed
+    to another tensor — with a _version that may match — while the entry lives."""
+
+    def __init__(self):
+        self.key = self.src = self.value = None
+
+    @staticmethod
+    def key_of(src, extra=()) -> tuple:
+        return tuple((t.data_ptr(), t._version, t.shape, t.stride(), t.dtype, t.device) for t in src) + tuple(extra)
+
+    def holds(self, src, extra=()) -> bool:
+        return self.value is not None and self.key == self.key_of(src, extra)
+
+    def get(self, src, extra, build):
+        key = self.key_of(src, extra)
+        if self.value is None or key != self.key:
+            self.drop()                # the old value goes before the builder allocates the new one (a lattice is 2.9 GB at c2)
+            value = build()
+            self.key, self.src, self.value = key, [t.detach() for t in src], value
+        return self.value
+
+    def put(self, src, extra, value) -> None:
+        self.key, self.src, self.value = self.key_of(src, extra), [t.detach() for t in src], value
+
+    def drop(self) -> None:
+        self.key = self.src = self.value = None
+
+
 class RenderEngine:
-    """Per-module state of the HIP path: packed weights (re-packed when the parameters change) and the
-    channel-last copies of the last feature pyramid."""
+    """Per-module state of the HIP path: what it builds on the device once and reuses while its sources hold (_Cached) — packed layers,
+    the channel-last pyramid and its lattice, pose records — and the switches of its routes."""
 
     def __init__(self, module):
         self.m = module
         self.lib = _lib.load()
-        self._packed: Dict[str, PackedLinear] = {}
-        self._packed_key = None
-        self._maps_key = None
-        self._maps: List[Tensor] = []
-        self._maps_src = None          # the z tensors the channel-last copies were made from (kept alive, see _channel_last)
+        # _weights, _channel_last, _projected_maps, _poses, _plan_for, _plan16_for, _pair_for, _exchange_lattice; _packed_layers by packer
+        self._packed, self._pyramid, self._gmaps, self._pose = _Cached(), _Cached(), _Cached(), _Cached()
+        self._plan, self._plan16, self._pairs, self._xlat = _Cached(), _Cached(), _Cached(), _Cached()
+        self._layer_packs: Dict[str, _Cached] = collections.defaultdict(_Cached)
         self._steps: Dict[tuple, Tensor] = {}
         self.linear_flags = 0          # tests may set NO_GLDS for A/B
         self.linear_x3 = True          # stage entries: wide layers on the split-fp16 path (car_linear_x3); False = all on the fp32 pipe
@@ -112,42 +143,43 @@ class RenderEngine:
         self.first_round_parts = True
         self.wgrad_fp32 = False        # training: True keeps the wide layers' weight gradients on the fp32 matrix pipe (CAR_WGRAD_FP32) instead of bf16 x 3
         self.fuse_kq = True            # staged route: key / query chains and the first round's logits in one kernel (car_key_query_logits); False = five launches (A/B)
-        self._kq = None
-        self._kq_key = None
         # three-view exchange, first + second layer: "rows" = the fused per-sample kernel's source pass over the rows (car_fused_rows, default);
         # True = the gather-fed linear kernel (car_lattice_encode_linear); False = two launches (A/B partners)
         self.fuse_exchange = "rows"
-        self._xpack = None
-        self._xpack_key = None
         # sizing of the one-call route (tests shrink them to force several calls)
         self.max_workspace_bytes: Optional[int] = None     # None: 85 % of the free device memory
         self.max_level_bytes: Optional[int] = None         # tests: lattice bytes of one call (forces scene groups); None = no limit
         self.max_pair_bytes: Optional[int] = None          # tests: bytes of one lattice buffer (forces lattice groups, each projected on its own)
         self.last_pair_groups = 1      # number of lattice buffers (car_project_maps calls' scene groups) of the last forward
         self.last_calls = 0            # number of car_render_forward calls the last forward was split into
-        self._round2_key = None
-        self._round2 = None
         self._pf = None                # prefetch(): announced stereo pairs (key -> channel-last pyramid + lattice), projected on a side stream
         self._pf_stream = None
         self.prefetch_side_stream = True   # False (A/B): prefetch() projects on the launch stream itself
-        self._pose_key = None
-        self._pose_dev = None
-        self._pose_src = None
-        self._gmaps_key = None
-        self._gmaps: List[Tensor] = []
-        self._wpt: Optional[Tensor] = None
-        self._plan_key = None
-        self._plan: Optional[Tensor] = None
-        self._plan_keep: List[Tensor] = []
-        self._plan_w = None            # the car_weights struct of the current plan (its tensors: _plan_keep)
-        self._plan16_key = None        # fp16 precision: car_plan_f16_build's plan, cached under the fp32 plan's key
-        self._plan16: Optional[Tensor] = None
         self.last_precision = None     # "fp32" / "fp16": the arithmetic of the last forward's fused per-sample kernel
-        self._pair_key = None
-        self._xlat = None              # merged lattice of the three-view exchange (car_merge_lattice), cached like the projected maps
-        self._xlat_key = None
-        self._pair: Optional[Tensor] = None
         self._work: Optional[Tensor] = None
+
+    @property
+    def _maps(self) -> Optional[List[Tensor]]:
+        """The cached channel-last pyramid of _channel_last (None: none)."""
+        return self._pyramid.value
+
+    @property
+    def _pair(self) -> Optional[Tensor]:
+        """The cached lattice buffer of _pair_for (None: none)."""
+        return self._pairs.value
+
+    @property
+    def _plan_w(self):
+        """struct CarWeights of the cached plan (the tensors its pointers lead to ride on it as ``keep``): what car_plan_f16_build reads."""
+        return self._plan.value[1]
+
+    @property
+    def _pair_key(self):
+        return self._pairs.key
+
+    @_pair_key.setter
+    def _pair_key(self, key) -> None:
+        self._pairs.key = key          # None: the next _pair_for re-projects (bench.py times the pair set-up this way)
 
     @property
     def render_precision(self) -> str:
@@ -187,62 +219,39 @@ class RenderEngine:
     # ------------------------------------------------------------------ weights
     def _weights(self, device) -> Dict[str, PackedLinear]:
         m = self.m
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in m.parameters())
-        if key == self._packed_key:
-            return self._packed
-        sd = {k: v for k, v in m.named_parameters()}
-        pk: Dict[str, PackedLinear] = {}
+        sd = dict(m.named_parameters())
+        names = [] if m.no_latent_concat else ["query_encode_latent", "query_encode_latent_2"] if m.n_view > 1 else ["update_val_merge"]
+        names += ["latent_value", "key_map", "key_map_2", "query_embed", "query_embed_2", "encode_latent", "query_repeat_embed_2", "phi.lin_in",
+                  "phi.lin_out"] + [f"phi.{n}" for i in range(m.phi.n_blocks) for n in (f"lin_z.{i}", f"blocks.{i}.fc_0", f"blocks.{i}.fc_1")]
 
-        def add(name, w=None, b=None, use_bias=True):
-            W = sd[name + ".weight"] if w is None else w
-            B = (sd[name + ".bias"] if b is None else b) if use_bias else None
-            pk[name] = PackedLinear(W, B, device, name)
-
-        if m.n_view > 1 and not m.no_latent_concat:
-            add("query_encode_latent")
-            add("query_encode_latent_2")
-        elif not m.no_latent_concat:
-            add("update_val_merge")
-        for n in ("latent_value", "key_map", "key_map_2", "query_embed", "query_embed_2", "encode_latent",
-                  "query_repeat_embed_2", "phi.lin_in", "phi.lin_out"):
-            add(n)
-        if m.n_view == 3 and not m.no_latent_concat:
-            # inference keeps e in component-major order [S, 3, C/2] (what query_encode_latent_2 writes) instead of the reference's channel-
-            # major interleave e[s, 3 ch + k] (models.py:446): the layers that read e get their input columns permuted once instead
-            for n in ("latent_value", "key_map"):
-                w = sd[n + ".weight"].reshape(sd[n + ".weight"].shape[0], -1)
-                pk[n + ".kmajor"] = PackedLinear(w.view(w.shape[0], -1, 3).permute(0, 2, 1).reshape(w.shape[0], -1), sd[n + ".bias"], device, n + ".kmajor")
-        wr = sd["query_repeat_embed.weight"].reshape(128, -1)
-        pk["query_repeat_embed.h"] = PackedLinear(wr[:, :128], None, device, "query_repeat_embed.h")           # z_embed half, per ray
-        pk["query_repeat_embed.g"] = PackedLinear(wr[:, 128:], sd["query_repeat_embed.bias"], device, "query_repeat_embed.g")  # local_coords half
-        for i in range(m.phi.n_blocks):
-            add(f"phi.lin_z.{i}")
-            add(f"phi.blocks.{i}.fc_0")
-            add(f"phi.blocks.{i}.fc_1")
-        self._packed, self._packed_key = pk, key
-        return pk
+        def build():
+            pk = {n: PackedLinear(sd[n + ".weight"], sd[n + ".bias"], device, n) for n in names}
+            if m.n_view == 3 and not m.no_latent_concat:
+                # inference keeps e in component-major order [S, 3, C/2] (what query_encode_latent_2 writes) instead of the reference's channel-
+                # major interleave e[s, 3 ch + k] (models.py:446): the layers that read e get their input columns permuted once instead
+                for n in ("latent_value", "key_map"):
+                    w = sd[n + ".weight"].reshape(sd[n + ".weight"].shape[0], -1)
+                    pk[n + ".kmajor"] = PackedLinear(w.view(w.shape[0], -1, 3).permute(0, 2, 1).reshape(w.shape[0], -1), sd[n + ".bias"], device, n + ".kmajor")
+            wr = sd["query_repeat_embed.weight"].reshape(128, -1)
+            pk["query_repeat_embed.h"] = PackedLinear(wr[:, :128], None, device, "query_repeat_embed.h")           # z_embed half, per ray
+            pk["query_repeat_embed.g"] = PackedLinear(wr[:, 128:], sd["query_repeat_embed.bias"], device, "query_repeat_embed.g")  # local_coords half
+            return pk
+        return self._packed.get([sd[n + k] for n in names + ["query_repeat_embed"] for k in (".weight", ".bias")], (str(device),), build)
 
     # ------------------------------------------------------------------ feature maps
     def _channel_last(self, z: List[Tensor]) -> List[Tensor]:
-        """Channel-last copies of the pyramid, cached on the identity/version of the z tensors.  The tensors themselves are kept
-        next to the key: a freed z would hand its address (and _version 0) to the next scene's pyramid of the same shape, and
-        the stale maps would be rendered."""
-        key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in z)
-        if key != self._maps_key or self._maps_src is None or any(a is not b_ for a, b_ in zip(self._maps_src, z)):
-            pf = self._pf.get(key) if self._pf else None
-            if pf is not None and all(a is b_ for a, b_ in zip(pf["src"], z)):
-                # this pyramid was announced by prefetch(): its channel-last copies and its lattice are (being) made on the side stream.
-                # The launch stream waits for them here — at the latest possible point — and takes them over
-                del self._pf[key]
-                torch.cuda.current_stream().wait_event(pf["done"])
-                self._maps, self._maps_key, self._maps_src = pf["maps"], key, list(z)
-                self._pair = None
-                self._pair, self._pair_key = pf["pair"], (key, pf["plan_key"], 0, pf["b"])
-                return self._maps
-            self._maps = [self._as_channel_last(t) for t in z]
-            self._maps_key = key
-            self._maps_src = list(z)
-        return self._maps
+        """Channel-last copies of the pyramid, cached on the z tensors."""
+        def build():
+            pf = self._pf.pop(_Cached.key_of(z), None) if self._pf else None
+            if pf is None:
+                return [self._as_channel_last(t) for t in z]
+            # this pyramid was announced by prefetch(): its channel-last copies and its lattice are (being) made on the side stream. The
+            # launch stream waits for them here — at the latest possible point — and takes them over, the lattice with the plan it was
+            # projected with (a plan rebuilt since then no longer matches it: _pair_for re-projects)
+            torch.cuda.current_stream().wait_event(pf["done"])
+            self._pairs.put([pf["plan"], *z], (0, pf["b"]), pf["pair"])
+            return pf["maps"]
+        return self._pyramid.get(z, (), build)
 
     @staticmethod
     def _as_channel_last(t: Tensor) -> Tensor:
@@ -263,22 +272,23 @@ class RenderEngine:
         forward that later receives these very tensors waits for the side stream's event and finds its lattice ready.  Needs a plan (one
         forward with the current weights) and room for a second lattice; returns False — and does nothing — otherwise, or when ``z`` is the
         pyramid already in place.  Same kernels, same arguments, same results as the projection inside forward."""
-        if self._plan is None or not z or z[0].device.type != "cuda":
+        if self._plan.value is None or not z or z[0].device.type != "cuda":
             return False
         b = z[0].shape[0] // self.m.n_view
         if self._one_call_refusal(b, 48, z) is not None:
             return False
-        key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in z)
-        if key == self._maps_key and self._pair is not None:
+        if self._pyramid.holds(z) and self._pair is not None:
             return False
         if self._pf is None:
             self._pf = {}
-        if key in self._pf and all(a is b_ for a, b_ in zip(self._pf[key]["src"], z)):
+        key = _Cached.key_of(z)
+        if key in self._pf:
             return True
         dev = z[0].device
         d = self._dims(b, 48, z)
-        if d.P != self._plan_key[1] or tuple(d.level_c[:3]) != self._plan_key[2]:
-            return False
+        if not self._plan.holds(*self._plan_sources(d, dev)):
+            return False                                             # the plan in place was built for other dims or weights
+        plan, _ = self._plan.value
         need = 4 * self.lib.car_gmaps_floats(ctypes.byref(d))
         if need == 0 or need > self._free_budget(dev) // 3:
             return False                                             # another lattice must leave the workspace its room
@@ -302,11 +312,12 @@ class RenderEngine:
                 for dst, t in zip(maps, z):
                     dst.copy_(t.detach().permute(0, 2, 3, 1))
                 ptrs = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in maps])
-                _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(self._plan), ptrs, _ptr(pair), ctypes.c_void_p(side.cuda_stream)),
+                _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), ptrs, _ptr(pair), ctypes.c_void_p(side.cuda_stream)),
                            "car_project_maps")
                 done = torch.cuda.Event()
                 done.record(side)
-            self._pf[key] = {"key": key, "src": list(z), "maps": maps, "pair": pair, "done": done, "plan_key": self._plan_key, "b": b}
+            # the entry holds everything the side stream reads (z, the plan) and writes until the launch stream has waited for ``done``
+            self._pf[key] = {"src": list(z), "maps": maps, "pair": pair, "done": done, "plan": plan, "b": b}
         return True
 
     def drop_prefetched(self) -> None:
@@ -321,22 +332,20 @@ class RenderEngine:
         table (W1[:, C:C+3], b1).  Recomputed only when the pyramid or the layer's parameters change."""
         m = self.m
         w1, b1 = m.query_encode_latent.weight, m.query_encode_latent.bias
-        key = (self._maps_key, w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, str(device))
-        if key == self._gmaps_key:
-            return self._gmaps, self._wpt
-        C = w1.shape[0]
-        w = w1.detach().reshape(C, -1).to(device=device, dtype=torch.float32)
-        gm, off = [], 0
-        for t in maps:
-            n, Hl, Wl, Cl = t.shape
-            layer = PackedLinear(w[:, off:off + Cl].contiguous(), None, device, "project_maps")
-            g = torch.empty(n, Hl, Wl, C, device=device, dtype=torch.float32)
-            self.linear(t, Cl, layer, g, C, n * Hl * Wl)
-            gm.append(g)
-            off += Cl
-        wpt = torch.cat([w[:, off:off + 3], b1.detach().to(device=device, dtype=torch.float32)[:, None]], dim=1).contiguous()
-        self._gmaps, self._wpt, self._gmaps_key = gm, wpt, key
-        return gm, wpt
+
+        def build():
+            C = w1.shape[0]
+            w = w1.detach().reshape(C, -1).to(device=device, dtype=torch.float32)
+            gm, off = [], 0
+            for t in maps:
+                n, Hl, Wl, Cl = t.shape
+                layer = PackedLinear(w[:, off:off + Cl].contiguous(), None, device, "project_maps")
+                g = torch.empty(n, Hl, Wl, C, device=device, dtype=torch.float32)
+                self.linear(t, Cl, layer, g, C, n * Hl * Wl)
+                gm.append(g)
+                off += Cl
+            return gm, torch.cat([w[:, off:off + 3], b1.detach().to(device=device, dtype=torch.float32)[:, None]], dim=1).contiguous()
+        return self._gmaps.get([*maps, w1, b1], (str(device),), build)
 
     def gather_encode(self, gmaps: List[Tensor], wpt: Tensor, pixel_val: Tensor, grid_in: Tensor, ptenc: Tensor,
                       V: int, pts: int, out: Tensor, ld_out: int):
@@ -377,8 +386,8 @@ class RenderEngine:
             _lib.check(self.lib.car_pose_setup(_ptr(c2w), _ptr(c2w_q), _ptr(Kc), _ptr(Kq), b, V, H, _ptr(poses), _stream()),
                        "car_pose_setup")
             return poses
-        key = tuple((t.data_ptr(), t._version, tuple(t.shape), str(t.device)) for t in ts) + (H, str(dev))
-        if key != self._pose_key:
+
+        def build():
             src = inp
             if any(t.is_cuda for t in ts):
                 import time
@@ -386,10 +395,8 @@ class RenderEngine:
                 src = self._cameras_to_host(ts)
                 self.last_pose_sync_ms = (time.perf_counter() - t0) * 1e3
             # pinned staging: the 768-byte upload is queued behind the previous frame's kernels instead of waiting for them
-            self._pose_dev = pack_poses(src, H).pin_memory().to(dev, non_blocking=True)
-            self._pose_key = key
-            self._pose_src = ts                      # keep the tensors alive so data_ptr cannot be recycled
-        return self._pose_dev
+            return pack_poses(src, H).pin_memory().to(dev, non_blocking=True)
+        return self._pose.get(ts, (H, str(dev)), build)
 
     @staticmethod
     def _cameras_to_host(ts):
@@ -415,50 +422,32 @@ class RenderEngine:
             self._steps[k] = torch.linspace(a, b_, P).to(device)      # CPU linspace, like the reference's values
         return self._steps[k]
 
-    def _round2_weights(self, device):
-        """query_repeat_embed[:, 128:] and query_repeat_embed_2 packed for csrc/car_round2.hip (device-side packer of the C ABI)."""
-        m = self.m
-        ps = (m.query_repeat_embed.weight, m.query_repeat_embed.bias, m.query_repeat_embed_2.weight, m.query_repeat_embed_2.bias)
-        key = tuple((t.data_ptr(), t._version) for t in ps) + (str(device),)
-        if key != self._round2_key:
-            lib = self.lib
+    def _packed_layers(self, packer: str, layers, sizes, device) -> List[Tensor]:
+        """The weights ([N, K] rows) and biases of ``layers`` through ``packer``, a device-side packer of the C ABI, into zeroed buffers of
+        ``sizes`` floats, re-packed when one of them changes."""
+        ps = [getattr(self.m.get_submodule(n), k) for n in layers for k in ("weight", "bias")]
+
+        def build():
             f = [t.detach().to(device=device, dtype=torch.float32).reshape(t.shape[0], -1).contiguous() for t in ps]
-            w = torch.empty(lib.car_round2_packed_floats(), device=device, dtype=torch.float32)
-            bz = torch.empty(lib.car_round2_bias_floats(), device=device, dtype=torch.float32)
-            _lib.check(lib.car_round2_pack(_ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(f[3]), _ptr(w), _ptr(bz), _stream()), "car_round2_pack")
-            self._round2, self._round2_key = (w, bz), key
-        return self._round2
+            out = [torch.zeros(n, device=device, dtype=torch.float32) for n in sizes]
+            _lib.check(getattr(self.lib, packer)(*[_ptr(t) for t in f + out], _stream()), packer)
+            return out
+        return self._layer_packs[packer].get(ps, (str(device),), build)
+
+    def _round2_weights(self, device):
+        """query_repeat_embed[:, 128:] and query_repeat_embed_2 packed for csrc/car_round2.hip."""
+        return self._packed_layers("car_round2_pack", ("query_repeat_embed", "query_repeat_embed_2"),
+                                   (self.lib.car_round2_packed_floats(), self.lib.car_round2_bias_floats()), device)
 
     def _exchange_pack(self, device):
-        """query_encode_latent (its point columns and bias) and query_encode_latent_2 packed for car_fused_rows (car_fused_pack_rows)."""
-        m = self.m
-        ps = (m.query_encode_latent.weight, m.query_encode_latent.bias, m.query_encode_latent_2.weight, m.query_encode_latent_2.bias)
-        key = tuple((t.data_ptr(), t._version) for t in ps) + (str(device),)
-        if key != self._xpack_key:
-            lib = self.lib
-            f = [t.detach().to(device=device, dtype=torch.float32).reshape(t.shape[0], -1).contiguous() if t.dim() > 1
-                 else t.detach().to(device=device, dtype=torch.float32).contiguous() for t in ps]
-            blob = torch.zeros(lib.car_fused_blob_floats(), device=device, dtype=torch.float32)
-            bias = torch.empty(lib.car_fused_bias_floats(), device=device, dtype=torch.float32)
-            wpt = torch.empty(576 * 4, device=device, dtype=torch.float32)
-            _lib.check(lib.car_fused_pack_rows(*[_ptr(t) for t in f], _ptr(blob), _ptr(bias), _ptr(wpt), _stream()), "car_fused_pack_rows")
-            self._xpack, self._xpack_key = (blob, bias, wpt), key
-        return self._xpack
+        """query_encode_latent (its point columns and bias) and query_encode_latent_2 packed for car_fused_rows."""
+        return self._packed_layers("car_fused_pack_rows", ("query_encode_latent", "query_encode_latent_2"),
+                                   (self.lib.car_fused_blob_floats(), self.lib.car_fused_bias_floats(), 576 * 4), device)
 
     def _kq_weights(self, device):
-        """key_map_2, query_embed and query_embed_2 packed for the key / query chain kernel (car_kq_pack)."""
-        m = self.m
-        ps = (m.key_map_2.weight, m.key_map_2.bias, m.query_embed.weight, m.query_embed.bias, m.query_embed_2.weight, m.query_embed_2.bias)
-        key = tuple((t.data_ptr(), t._version) for t in ps) + (str(device),)
-        if key != self._kq_key:
-            lib = self.lib
-            f = [t.detach().to(device=device, dtype=torch.float32).reshape(t.shape[0], -1).contiguous() if t.dim() > 1
-                 else t.detach().to(device=device, dtype=torch.float32).contiguous() for t in ps]
-            tail = torch.empty(lib.car_kq_tail_floats(), device=device, dtype=torch.float32)
-            bias = torch.empty(lib.car_kq_bias_floats(), device=device, dtype=torch.float32)
-            _lib.check(lib.car_kq_pack(*[_ptr(t) for t in f], _ptr(tail), _ptr(bias), _stream()), "car_kq_pack")
-            self._kq, self._kq_key = (tail, bias), key
-        return self._kq
+        """key_map_2, query_embed and query_embed_2 packed for the key / query chain kernel (car_key_query_logits)."""
+        return self._packed_layers("car_kq_pack", ("key_map_2", "query_embed", "query_embed_2"),
+                                   (self.lib.car_kq_tail_floats(), self.lib.car_kq_bias_floats()), device)
 
     # ------------------------------------------------------------------ the one-call route (default configuration)
     def _dims(self, b: int, R: int, z: List[Tensor]) -> "_lib.CarDims":
@@ -472,16 +461,10 @@ class RenderEngine:
         d.no_sample = int(m.no_sample)
         return d
 
-    def _plan_for(self, d, device) -> Tensor:
-        """car_plan_build: every layer packed for the kernels, once per set of parameter values."""
-        m, lib = self.m, self.lib
-        names = list(_lib.WEIGHT_FIELDS[0]) + [f"phi.lin_z.{i}" for i in range(3)] + [f"phi.blocks.{i}.fc_0" for i in range(3)] \
-            + [f"phi.blocks.{i}.fc_1" for i in range(3)]
-        sd = dict(m.named_parameters())
-        key = (str(device), d.P, tuple(d.level_c[:d.n_levels])) + tuple(
-            (sd[n + k].data_ptr(), sd[n + k]._version) for n in names for k in (".weight", ".bias"))
-        if key == self._plan_key:
-            return self._plan
+    def _car_weights(self, device):
+        """struct CarWeights: every layer the plans pack, weights as fp32 [N, K] rows and biases on the device.  The tensors its pointers
+        lead to ride on it (``keep``), so they live as long as the struct."""
+        sd = dict(self.m.named_parameters())
         keep: List[Tensor] = []
 
         def dev(name):
@@ -498,46 +481,53 @@ class RenderEngine:
             w.phi_lin_z_w[i], w.phi_lin_z_b[i] = dev(f"phi.lin_z.{i}.weight"), dev(f"phi.lin_z.{i}.bias")
             w.phi_fc_0_w[i], w.phi_fc_0_b[i] = dev(f"phi.blocks.{i}.fc_0.weight"), dev(f"phi.blocks.{i}.fc_0.bias")
             w.phi_fc_1_w[i], w.phi_fc_1_b[i] = dev(f"phi.blocks.{i}.fc_1.weight"), dev(f"phi.blocks.{i}.fc_1.bias")
-        nbytes = lib.car_plan_bytes(ctypes.byref(d))
+        w.keep = keep
+        return w
+
+    def _plan_sources(self, d, device):
+        """What a plan is built from: the parameters of every layer it packs, and the device and dims it packs them for."""
+        sd = dict(self.m.named_parameters())
+        names = list(_lib.WEIGHT_FIELDS[0]) + [f"phi.{n}" for i in range(3) for n in (f"lin_z.{i}", f"blocks.{i}.fc_0", f"blocks.{i}.fc_1")]
+        return [sd[n + k] for n in names for k in (".weight", ".bias")], (str(device), d.P, tuple(d.level_c[:d.n_levels]))
+
+    def _build_plan(self, what: str, d, device, w) -> Tensor:
+        """car_<what>_build of the layers ``w`` (struct CarWeights) into a buffer of car_<what>_bytes: "plan" (every layer packed for the
+        kernels) or "plan_f16" (the fused kernel's compact fp16 layers)."""
+        nbytes = getattr(self.lib, f"car_{what}_bytes")(ctypes.byref(d))
         if nbytes == 0:
-            _lib.check(-1, "car_plan_bytes")
+            _lib.check(-1, f"car_{what}_bytes")
         plan = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
-        _lib.check(lib.car_plan_build(ctypes.byref(d), ctypes.byref(w), _ptr(plan), _stream()), "car_plan_build")
-        self._plan, self._plan_key, self._plan_keep, self._plan_w = plan, key, keep, w
-        self._pair_key = None
+        _lib.check(getattr(self.lib, f"car_{what}_build")(ctypes.byref(d), ctypes.byref(w), _ptr(plan), _stream()), f"car_{what}_build")
         return plan
 
+    def _plan_for(self, d, device) -> Tensor:
+        """car_plan_build: every layer packed for the kernels, once per set of parameter values.  Cached with the CarWeights it was built
+        from (_plan_w)."""
+        def build():
+            w = self._car_weights(device)
+            return self._build_plan("plan", d, device, w), w
+        return self._plan.get(*self._plan_sources(d, device), build)[0]
+
     def _plan16_for(self, d, device) -> Tensor:
-        """car_plan_f16_build: the fused kernel's compact fp16 layers, built from the same weights as the current fp32 plan and cached
-        under its key (so a change of the parameters rebuilds both).  Call after _plan_for."""
-        if self._plan16 is not None and self._plan16_key == self._plan_key:
-            return self._plan16
-        lib = self.lib
-        nbytes = lib.car_plan_f16_bytes(ctypes.byref(d))
-        if nbytes == 0:
-            _lib.check(-1, "car_plan_f16_bytes")
-        self._plan16 = None
-        plan16 = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
-        _lib.check(lib.car_plan_f16_build(ctypes.byref(d), ctypes.byref(self._plan_w), _ptr(plan16), _stream()), "car_plan_f16_build")
-        self._plan16, self._plan16_key = plan16, self._plan_key
-        return plan16
+        """car_plan_f16_build: the fused kernel's compact fp16 layers, built from the same weights as the fp32 plan and cached on it (a change
+        of the parameters rebuilds both).  Call after _plan_for."""
+        plan, w = self._plan.value
+        return self._plan16.get([plan], (), lambda: self._build_plan("plan_f16", d, device, w))
 
     def _pair_for(self, plan: Tensor, z: List[Tensor], device, s0: int, s1: int, R: int):
         """car_project_maps for scenes [s0, s1): the first point-MLP layer applied per texel of the pyramid and every level summed on the
-        common lattice, once per stereo pair (and weights).  Returns (buffer, its car_dims).  One buffer is cached: the whole batch
+        common lattice, once per stereo pair (and plan).  Returns (buffer, its car_dims).  One buffer is cached: the whole batch
         normally; when the lattices of all scenes do not fit the device memory (_render_one_call) the last group's."""
         maps = self._channel_last(z)
         V = self.m.n_view
         d = self._dims(s1 - s0, R, z)
-        key = (self._maps_key, self._plan_key, s0, s1)
-        if key != self._pair_key or self._pair is None:
-            lib = self.lib
-            self._pair = None                                # release the previous pair's maps before allocating
-            pair = torch.empty(lib.car_gmaps_floats(ctypes.byref(d)), device=device, dtype=torch.float32)
+
+        def build():
+            pair = torch.empty(self.lib.car_gmaps_floats(ctypes.byref(d)), device=device, dtype=torch.float32)
             ptrs = (ctypes.c_void_p * len(maps))(*[t[s0 * V:s1 * V].data_ptr() for t in maps])
-            _lib.check(lib.car_project_maps(ctypes.byref(d), _ptr(plan), ptrs, _ptr(pair), _stream()), "car_project_maps")
-            self._pair, self._pair_key = pair, key
-        return self._pair, d
+            _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), ptrs, _ptr(pair), _stream()), "car_project_maps")
+            return pair
+        return self._pairs.get([plan, *z], (s0, s1), build), d
 
     @staticmethod
     def _common_lattice(z: List[Tensor]) -> bool:
@@ -610,14 +600,12 @@ class RenderEngine:
         # half of the usable device memory for the workspace; then the scenes are rendered in groups, each with its own
         # car_project_maps (re-done on every forward: the one cached buffer holds the last group — a fallback, not a fast path).
         self._channel_last(z)
-        whole_cached = self._pair is not None and self._pair_key == (self._maps_key, self._plan_key, 0, b)
         pg = b
-        if not whole_cached:
+        if not self._pairs.holds([plan, *z], (0, b)):
             # what is live while a group renders: ONE lattice buffer (the previous group's is dropped before the next is allocated, below)
             # and the workspace.  The cached buffer and workspace of an earlier forward count as available because both are released
             # before this forward allocates (a stale workspace sized for another split would otherwise sit beside the new pair)
-            self._pair = None
-            self._pair_key = None
+            self._pairs.drop()
             if pair_bytes(b) > (self._free_budget(dev)) // 2:
                 self._work = None                                      # grouped fallback: start from everything this engine can free
             usable = self._free_budget(dev)
@@ -1019,26 +1007,24 @@ class RenderEngine:
         return out
 
     def _exchange_lattice(self, gmaps, ptrs, hs, ws, n_maps, C, dev):
-        """The projected levels of the three-view exchange summed on their common lattice (car_merge_lattice), cached with the projected
-        maps; None when the levels have no common lattice, the channel count is not the lattice kernels' 576, or it would not fit."""
+        """The projected levels of the three-view exchange summed on their common lattice (car_merge_lattice), cached on those levels;
+        None when the levels have no common lattice, the channel count is not the lattice kernels' 576, or it would not fit."""
         if C != 576:
             return None
-        key = self._gmaps_key                                      # identifies the projected levels' CONTENT (pyramid + layer versions)
-        if self._xlat is not None and self._xlat_key == key:
-            return self._xlat
-        L = len(gmaps)
-        lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        if self.lib.car_merge_lattice(ptrs, hs, ws, L, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad), _stream()) != 0:
-            return None
-        floats = n_maps * 2 * lh.value * lw.value * C
-        if n_maps * 2 * lh.value * lw.value >= 2 ** 31 - 1 or floats * 4 > self._free_budget(dev) // 2:
-            return None
-        self._xlat = None                                           # the previous lattice goes before the next one is allocated
-        lattice = torch.empty(floats, device=dev, dtype=torch.float32)
-        gmax = torch.empty(1, device=dev, dtype=torch.float32)     # largest |lattice value|: taken in the merge's own pass
-        _lib.check(self.lib.car_merge_lattice_max(ptrs, hs, ws, L, n_maps, _ptr(lattice), _ptr(gmax), _stream()), "car_merge_lattice_max")
-        self._xlat, self._xlat_key = (lattice, lh.value, lw.value, lpad.value, gmax), key
-        return self._xlat
+
+        def build():
+            L = len(gmaps)
+            lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+            if self.lib.car_merge_lattice(ptrs, hs, ws, L, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad), _stream()) != 0:
+                return None
+            floats = n_maps * 2 * lh.value * lw.value * C
+            if n_maps * 2 * lh.value * lw.value >= 2 ** 31 - 1 or floats * 4 > self._free_budget(dev) // 2:
+                return None
+            lattice = torch.empty(floats, device=dev, dtype=torch.float32)
+            gmax = torch.empty(1, device=dev, dtype=torch.float32)     # largest |lattice value|: taken in the merge's own pass
+            _lib.check(self.lib.car_merge_lattice_max(ptrs, hs, ws, L, n_maps, _ptr(lattice), _ptr(gmax), _stream()), "car_merge_lattice_max")
+            return lattice, lh.value, lw.value, lpad.value, gmax
+        return self._xlat.get(gmaps, (), build)
 
     def _encode_three_views(self, maps, poses, pixel_val, ptenc, pt_in, b, R, P, H, W, C, pk, keep=None):
         """Cross-view exchange for three context views (models.py:345-475), restated literally: for the samples of context c

@@ -24,13 +24,14 @@ attention round, any channel widths.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Dict, List, Optional
 
 import torch
 
 from . import _lib
-from .engine import ACCUM, PLACE_OTHER2, PLACE_OWN, PLACE_PLAIN, RELU_IN, PackedLinear, RenderEngine, _mode, _ptr, _round_up, _stream
+from .engine import ACCUM, PLACE_OTHER2, PLACE_OWN, PLACE_PLAIN, RELU_IN, PackedLinear, RenderEngine, _Cached, _mode, _ptr, _round_up, _stream
 
 Tensor = torch.Tensor
 WGRAD_FP32 = 16            # CAR_WGRAD_FP32 (include/car_hip.h)
@@ -45,15 +46,11 @@ class _Ops:
 
     def __init__(self, eng: RenderEngine):
         self.eng, self.lib = eng, eng.lib
-        self._t: Dict[tuple, PackedLinear] = {}
+        self._t: Dict[str, _Cached] = collections.defaultdict(_Cached)
 
     def transposed(self, name: str, w: Tensor) -> PackedLinear:
         """W [N, K] -> the layer x -> x W (weight W^T [K, N], no bias): car_linear then computes dX = dY W."""
-        key = (name, w.data_ptr(), w._version, str(w.device), tuple(w.shape))
-        if key not in self._t:
-            self._t = {k: v for k, v in self._t.items() if k[0] != name}
-            self._t[key] = PackedLinear(w.detach().reshape(w.shape[0], -1).t().contiguous(), None, w.device, name + "^T")
-        return self._t[key]
+        return self._t[name].get([w], (), lambda: PackedLinear(w.detach().reshape(w.shape[0], -1).t().contiguous(), None, w.device, name + "^T"))
 
     def wgrad(self, dy: Tensor, ldy: int, x: Tensor, ldx: int, M: int, N: int, K: int, dw: Tensor, lddw: int, db: Optional[Tensor], relu_x=False):
         # engine.wgrad_fp32 = True keeps the wide layers' weight gradients on the fp32 matrix pipe (CAR_WGRAD_FP32): the reference's fp32
@@ -131,7 +128,7 @@ class _RenderTrain(torch.autograd.Function):
         R = inp["query"]["uv"].shape[2]
         maps = saved.pop("maps")
         C = sum(t.shape[3] for t in maps)
-        ops = getattr(eng, "_train_ops", None)              # kept on the engine: its transposed-weight cache (keyed on data_ptr / _version)
+        ops = getattr(eng, "_train_ops", None)              # kept on the engine: its transposed-weight cache (engine._Cached per layer)
         if ops is None or ops.eng is not eng:               # then survives from step to step and re-packs only what the optimizer changed
             ops = eng._train_ops = _Ops(eng)
         ctx.saved, ctx.ops, ctx.module, ctx.n_levels = saved, ops, module, n_levels

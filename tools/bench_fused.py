@@ -40,9 +40,10 @@ def main():
     chunk = {"context": inp["context"], "query": dict(inp["query"], uv=uv)}
     with torch.no_grad():
         model(chunk, z=z)                              # plan, projected maps, workspace (and the rays of this chunk inside it)
-    if eng._pose_dev is None:                          # cameras on the GPU: the engine made the records with car_pose_setup
+    poses = eng._pose.value
+    if poses is None:                                  # cameras on the GPU: the engine made the records with car_pose_setup
         from cross_attention_renderer_amd.poses import pack_poses
-        eng._pose_dev = pack_poses({k: {kk: vv.cpu() for kk, vv in v.items()} for k, v in chunk.items()}, bench.H).to(dev)
+        poses = pack_poses({k: {kk: vv.cpu() for kk, vv in v.items()} for k, v in chunk.items()}, bench.H).to(dev)
     torch.cuda.synchronize()
     d = eng._dims(1, R, z)
     off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
@@ -114,7 +115,7 @@ def main():
         if v not in NAMES:
             raise SystemExit(f"unknown variant {v}: one of {NAMES}")
         p16 = v == 2
-        args = (eng._pose_dev.data_ptr(), ws("rays"), steps.data_ptr(), eng._pair.data_ptr(), lh.value, lw.value, lpad.value, gmeta,
+        args = (poses.data_ptr(), ws("rays"), steps.data_ptr(), eng._pair.data_ptr(), lh.value, lw.value, lpad.value, gmeta,
                 plan16.data_ptr() + 4 * o_wpt16 if p16 else wpt.data_ptr(), plan16.data_ptr() if p16 else blob.data_ptr(),
                 plan16.data_ptr() + 4 * o_bias16 if p16 else bias.data_ptr(), 1, 2, Rk, bench.P, bench.H, bench.H, 0,
                 ws("e"), ws("g"), ws("logit"), ws("pt"), pixel_val.data_ptr())
