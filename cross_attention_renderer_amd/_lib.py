@@ -132,6 +132,16 @@ SIGNATURES = {
     "car_reduce_samples": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "car_ssim_scratch_doubles": (c_size_t, [c_int, c_int, c_int, c_int]),
     "car_ssim": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
+    "car_lpips_packed_floats": (c_size_t, []),
+    "car_lpips_pack": (c_int, [_P, _P, _P, _P, _P]),
+    "car_lpips_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_lpips": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "car_conv3x3_packed_floats": (c_size_t, [c_int, c_int]),
+    "car_conv3x3_pack": (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    "car_conv3x3": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "car_maxpool2x2": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_lpips_head_scratch_doubles": (c_size_t, [c_int, c_int, c_int]),
+    "car_lpips_head": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,0 +1,569 @@
+// car_lpips.hip — LPIPS v0.1, net = 'vgg' (include/car_hip.h: car_conv3x3, car_maxpool2x2, car_lpips_head, car_lpips).
+//
+// The metric is a fixed network: a per-channel scaling of the [-1, 1] image, the 13 3x3 convolutions of VGG16's `features` (ReLU behind
+// each, 2x2 max-pool in front of blocks 2-5), and at the five taps relu1_2 .. relu5_3 the channel-normalised squared difference of the two
+// images' features, weighted by a 1x1 layer, averaged over the tap's pixels and summed over the taps.  Weights come from the caller.
+//
+// conv3x3_kernel is car_linear16.hip's layer machinery (car_fused_mma.h: split-fp16 operands, three v_mfma_f32_16x16x32_f16 products per
+// term, fp32 accumulation, weight chunks streamed L2 -> LDS by LDS-DMA) run as an implicit GEMM over 9 K in ONE sweep: a row of the A
+// operand is an output pixel, K step c reads 32 channels of tap c / (K / 32) — the pixel's own address plus one of nine offsets — and a tap
+// outside the image contributes zeros.  The row's power of two follows the largest magnitude seen so far along the 9 K values exactly as
+// in car_linear16.hip.  A row's result depends on its own nine pixels and the weights only, never on its neighbours in the launch: an
+// image gives the same bits wherever it sits in the batch, which is what makes LPIPS of two identical images exactly 0.
+// The first layer (K = 3) is a plain fp32 vector kernel with the scaling layer folded in: the weights carry 1 / scale at pack time and
+// the shift is subtracted from a pixel as it is loaded, so a padded tap stays the exact zero of the scaled image's padding.
+// The max-pool is a kernel of its own (profiles/lpips.md).  The head runs in fp64 with every sum in a fixed order.
+#include "car_common.h"
+#include <math.h>
+#include <stdint.h>
+
+namespace {
+
+constexpr int kWaves = 12, kRows = 16, kGroupRows = kWaves * kRows;
+constexpr int kThreads = 64 * kWaves;
+constexpr int kPieces = 3;                         // LDS-DMA pieces of the widest chunk here (16 tiles = 32 KB over 12 waves)
+constexpr int pieces_of(int nt) { return (2 * nt + kWaves - 1) / kWaves; }
+
+#include "car_fused_mma.h"
+
+// this kernel addresses its weight chunks itself (chunk_desc below); the fused kernel's chunk table that car_fused_mma.h asks for is unused
+__device__ __forceinline__ constexpr int chunk_tile_offset(int) { return 0; }
+__device__ __forceinline__ constexpr int chunk_tiles(int) { return 0; }
+
+// ---- the network ---------------------------------------------------------------------------------------------------------------------
+constexpr int kLayers = 13, kTaps = 5;
+constexpr int kWidth[kLayers] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+constexpr int kTapWidth[kTaps] = {64, 128, 256, 512, 512};
+constexpr int kLinFloats = 64 + 128 + 256 + 512 + 512;
+constexpr bool layer_ends_block(int l) { return l == 1 || l == 3 || l == 6 || l == 9 || l == 12; }
+constexpr bool pool_in_front(int l) { return l == 2 || l == 4 || l == 7 || l == 10; }
+constexpr int kFirstFloats = 27 * 64 + 64;         // first layer: [tap * 3 + channel][64] weights / scale, then the bias
+#define CAR_LPIPS_SHIFT {-0.030f, -0.088f, -0.188f}       // the scaling layer: (v - shift) / scale per channel
+#define CAR_LPIPS_SCALE {0.458, 0.448, 0.450}
+constexpr long kMaxPixels = 1L << 27;              // 2 B H W: keeps every row count, grid and per-image offset far inside 32 bits
+
+// ---- 3x3 convolution, K >= 64 ------------------------------------------------------------------------------------------------------
+struct ConvArgs {
+    const float* X;                        // [n, H, W, K]
+    const float* Wp; int tiles_total;      // [K step][tiles_total][512]: k = tap * K + channel
+    const float* bias;                     // N floats
+    const float* down;                     // 2^-shift of the packed layer
+    float* Y;                              // [n, H, W, N]
+    int H, W, K, N, lgk, chunks;           // lgk = log2(K / 32)
+    long M;                                // n H W output pixels
+};
+
+template <int NT>
+__global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];      // [2][NT][512]
+    static_assert(kWaves * pieces_of(NT) <= 3 * 2 * NT, "stream_issue_piece wraps a piece index into the chunk with two subtractions");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int s = lane & 15, q4 = lane >> 4;
+    // the column groups of a block of pixels read the same pixels: one XCD, consecutive slots (car_linear16.hip)
+    const int groups = a.tiles_total / NT;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const long rblock = (long)(slot / groups) * 8 + xcd;
+    if (rblock * kGroupRows >= a.M) return;                            // the grid is padded to whole rounds of eight row blocks
+    const long row = rblock * kGroupRows + wave * kRows + s;
+    const long lrow = row < a.M ? row : a.M - 1;
+    const int tile0 = (slot % groups) * NT;
+    const int K = a.K;
+    // the pixel, and which of its nine taps lie inside its image
+    const int pix = (int)(lrow % ((long)a.H * a.W)), py = pix / a.W, px = pix % a.W;
+    unsigned inside = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+        if ((unsigned)(py + t / 3 - 1) < (unsigned)a.H && (unsigned)(px + t % 3 - 1) < (unsigned)a.W) inside |= 1u << t;
+    const float* xpix = a.X + lrow * K + 8 * q4;
+
+    auto chunk_desc = [&](int c) {
+        const int ce = c < a.chunks ? c : a.chunks - 1;
+        NextChunk n;
+        n.src = a.Wp + ((long)ce * a.tiles_total + tile0) * kTile;
+        n.dst = lds + (ce & 1) * NT * kTile;
+        n.nkb = 2 * NT;
+#ifdef CAR_BOUNDS
+        n.lim = a.Wp + (long)a.chunks * a.tiles_total * kTile;
+#endif
+        return n;
+    };
+    {
+        const NextChunk n0 = chunk_desc(0);
+#pragma unroll
+        for (int p = 0; p < pieces_of(NT); ++p) stream_issue_piece(n0, p, lane, wave);
+    }
+    // this lane's eight values of K step c: tap t = c >> lgk, channels 32 (c & (K / 32 - 1)) + 8 q4 .. + 7 of pixel (py + t / 3 - 1,
+    // px + t % 3 - 1).  issue_x only issues the loads — from the pixel itself when the tap is outside, a valid address whose values are
+    // dropped; finish_x turns them into values when they are consumed (car_linear16.hip)
+    auto tap_of = [&](int c) { return c >> a.lgk; };
+    auto issue_x = [&](int c, float4 (&raw)[2]) {
+        const int t = tap_of(c), kc = c & ((1 << a.lgk) - 1);
+        const int off = ((t / 3 - 1) * a.W + (t % 3 - 1)) * K;
+        const float* src = xpix + (((inside >> t) & 1u) ? off : 0) + 32 * kc;
+        CAR_BOUNDS_TRAP(src >= a.X && src + 8 <= a.X + a.M * K);
+        raw[0] = *reinterpret_cast<const float4*>(src);
+        raw[1] = *reinterpret_cast<const float4*>(src + 4);
+    };
+    auto finish_x = [&](int c, const float4 (&raw)[2], float (&x)[8]) {
+        const bool in = ((inside >> tap_of(c)) & 1u) != 0;
+        const float e[8] = {raw[0].x, raw[0].y, raw[0].z, raw[0].w, raw[1].x, raw[1].y, raw[1].z, raw[1].w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = in ? e[i] : 0.0f;
+    };
+    auto row_max = [&](const float (&x)[8]) {
+        float m = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x[e]));
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        return fmaxf(m, __shfl_xor(m, 32, 64));
+    };
+    const float dW = a.down[0];
+    float xc[8];
+    {
+        float4 raw[2];
+        issue_x(0, raw);
+        finish_x(0, raw, xc);
+    }
+    float mrun = fmaxf(row_max(xc), 1e-30f), p, pinv;
+    pow2_scale(mrun, p, pinv);
+
+    f32x4 acc[NT];
+    init_bias<NT>(acc, a.bias + 16 * tile0, q4, p / dW);
+    half8 bhi, blo;
+    split8(xc, p, bhi, blo);
+    stream_sync();                                                     // weight chunk 0 landed
+
+#pragma unroll 1
+    for (int c = 0; c < a.chunks; ++c) {
+        const float* wl = lds + (c & 1) * NT * kTile + 4 * lane;
+        const NextChunk nx = chunk_desc(c + 1);
+        const int cn = c + 1 < a.chunks ? c + 1 : c;
+        float4 rawn[2];
+        issue_x(cn, rawn);                                             // next K step's values: in flight under this step's MFMAs
+#pragma unroll
+        for (int qs = 0; qs < NT / 2; ++qs) {
+            const float* w0 = wl + (2 * qs * 2) * 256;
+            mfma_pair(acc[2 * qs], acc[2 * qs + 1], w0, w0 + 512, bhi, blo);
+            // nothing follows the last chunk: re-copying it onto itself would write the buffer this iteration's MFMAs are reading
+            if (qs < pieces_of(NT) && c + 1 < a.chunks) stream_issue_piece(nx, qs, lane, wave);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // the next K step may outgrow the row's power of two: move the row (accumulators and scale) to the smaller one, exactly
+        float xn[8];
+        finish_x(cn, rawn, xn);
+        const float mn = row_max(xn);
+        if (__builtin_amdgcn_ballot_w64(mn > mrun) != 0) {
+            float pn, pninv;
+            mrun = fmaxf(mrun, mn);
+            pow2_scale(mrun, pn, pninv);
+            scale_acc<NT>(acc, pn * pinv);
+            p = pn; pinv = pninv;
+        }
+        split8(xn, p, bhi, blo);
+        stream_sync();
+    }
+    if (row >= a.M) return;
+    scale_acc<NT>(acc, dW * pinv);
+    float* yrow = a.Y + row * a.N + 16 * tile0 + 4 * q4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+        *reinterpret_cast<float4*>(yrow + 16 * t) =
+            make_float4(fmaxf(acc[t][0], 0.0f), fmaxf(acc[t][1], 0.0f), fmaxf(acc[t][2], 0.0f), fmaxf(acc[t][3], 0.0f));
+}
+
+template <int NT>
+int launch_conv(const ConvArgs& a, hipStream_t st) {
+    const size_t lds_bytes = (size_t)2 * NT * kTile * sizeof(float);
+    static bool reserved[64] = {};                                     // the LDS reservation is a per-device attribute of the kernel
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !reserved[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) {
+            car_set_error("car_conv3x3: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e));
+            return CAR_E_LAUNCH;
+        }
+        if (dev >= 0 && dev < 64) reserved[dev] = true;
+    }
+    (void)hipGetLastError();
+    const int groups = a.tiles_total / NT;
+    hipLaunchKernelGGL((conv3x3_kernel<NT>), dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
+    CAR_CHECK_LAUNCH("car_conv3x3");
+    return CAR_OK;
+}
+
+// ---- first layer: 3 -> 64, fp32, scaling layer folded in ---------------------------------------------------------------------------
+// a wave = 64 output channels of one pixel at a time (the pixel is wave-uniform: its 27 inputs are scalar loads), 16 pixels per wave
+constexpr int kFirstPix = 16;
+__global__ void __launch_bounds__(256) conv_first_kernel(const float* __restrict__ X, const float* __restrict__ packed, float* __restrict__ Y,
+                                                         int H, int W, long M) {
+    constexpr float kShift[3] = CAR_LPIPS_SHIFT;
+    const int n = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float w[27];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) w[k] = packed[k * 64 + n];
+    const float b = packed[27 * 64 + n];
+    const long p0 = ((long)blockIdx.x * 4 + wave) * kFirstPix;
+    for (int i = 0; i < kFirstPix; ++i) {
+        const long p = p0 + i;
+        if (p >= M) return;
+        const int pix = (int)(p % ((long)H * W)), py = pix / W, px = pix % W;
+        float acc = b;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                const float* v = X + (p + (long)(t / 3 - 1) * W + (t % 3 - 1)) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc = fmaf(v[c] - kShift[c], w[3 * t + c], acc);
+            }
+        }
+        Y[p * 64 + n] = fmaxf(acc, 0.0f);
+    }
+}
+
+// ---- 2x2 max-pool, stride 2, floor ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) maxpool_kernel(const float* __restrict__ X, float* __restrict__ Y, int H, int W, int C4, long total) {
+    const int Ho = H / 2, Wo = W / 2;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % C4);
+        long r = idx / C4;
+        const int ox = (int)(r % Wo); r /= Wo;
+        const int oy = (int)(r % Ho);
+        const long img = r / Ho;
+        const float4* src = reinterpret_cast<const float4*>(X) + ((img * H + 2 * oy) * W + 2 * ox) * C4 + c;
+        const float4 a = src[0], b = src[C4], d = src[(long)W * C4], e = src[(long)W * C4 + C4];
+        reinterpret_cast<float4*>(Y)[idx] = make_float4(fmaxf(fmaxf(a.x, b.x), fmaxf(d.x, e.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(d.y, e.y)),
+                                                        fmaxf(fmaxf(a.z, b.z), fmaxf(d.z, e.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(d.w, e.w)));
+    }
+}
+
+// ---- packing -------------------------------------------------------------------------------------------------------------------------
+// max |w| of a layer as the bit pattern of a non-negative float, into scale[2] (zeroed by the caller): car_linear16.hip's absmax16_kernel
+__global__ void conv_absmax_kernel(const float* __restrict__ Wt, long total, float* __restrict__ scale) {
+    __shared__ float red[4];
+    float m = 0.0f;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(Wt[idx]));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x / 64); ++w) m = fmaxf(m, red[w]);
+        atomicMax(reinterpret_cast<unsigned*>(scale + 2), __float_as_uint(m));
+    }
+}
+// torch's [N][K][3][3] -> car_linear16.hip's tiles [K step][tile][hi | lo][lane][8 halves] with k = tap * K + channel: lane l carries
+// output 16 tile + l % 16 and k = 32 step + 8 (l >> 4) + e.  scale[0] = 2^shift, scale[1] = 2^-shift; the bias follows the 64 scale floats
+__global__ void conv_pack_kernel(const float* __restrict__ Wt, const float* __restrict__ bias, int K, int N, long total, float* __restrict__ scale,
+                                 _Float16* __restrict__ out) {
+    float p, inv;
+    pow2_scale(fmaxf(scale[2], 1e-30f), p, inv);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { scale[0] = p; scale[1] = inv; }
+    const int tiles = N / 16;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        if (idx < N) scale[64 + idx] = bias[idx];
+        const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
+        const long tile = idx >> 9;
+        const int t = (int)(tile % tiles), ks = (int)(tile / tiles);
+        const int n = 16 * t + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + e;
+        const int tap = k / K, ch = k % K;
+        const float w = Wt[((long)n * K + ch) * 9 + tap] * p;
+        const _Float16 hi = (_Float16)w;
+        _Float16* o = out + tile * 1024 + lane * 8 + e;
+        o[0] = hi;
+        o[512] = (_Float16)(w - (float)hi);
+    }
+}
+__global__ void first_pack_kernel(const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ out) {
+    constexpr double kScale[3] = CAR_LPIPS_SCALE;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 27 * 64) {
+        const int n = i % 64, k = i / 64, tap = k / 3, c = k % 3;
+        out[i] = (float)((double)Wt[(n * 3 + c) * 9 + tap] / kScale[c]);
+    } else if (i < kFirstFloats) out[i] = bias[i - 27 * 64];
+}
+
+// ---- the head ------------------------------------------------------------------------------------------------------------------------
+constexpr int kHeadPix = 64;                       // pixels per workgroup: 4 waves x 16
+struct HeadArgs {
+    const float* f[kTaps];                         // [2 B, npix, C]: images 0 .. B-1 against images B .. 2 B-1
+    const float* lin[kTaps];
+    int npix[kTaps], C[kTaps], blk0[kTaps + 1];    // blk0: first workgroup of a tap inside a pair's run of workgroups
+    int B;
+    double* partial;                               // [B, blk0[5]]
+};
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // a fixed butterfly: every lane ends with the same bits
+    return v;
+}
+__global__ void __launch_bounds__(256) lpips_head_kernel(const HeadArgs a) {
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per_pair = a.blk0[kTaps];
+    const int pair = blockIdx.x / per_pair, blk = blockIdx.x % per_pair;
+    int k = 0;
+#pragma unroll
+    for (int t = 1; t < kTaps; ++t) k += blk >= a.blk0[t] ? 1 : 0;
+    const int C = a.C[k], npix = a.npix[k], per = C / 64;
+    const int p0 = (blk - a.blk0[k]) * kHeadPix + wave * 16;
+    const float* f0 = a.f[k] + (size_t)pair * npix * C;
+    const float* f1 = a.f[k] + (size_t)(a.B + pair) * npix * C;
+    double w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = j < per ? (double)a.lin[k][lane + 64 * j] : 0.0;
+    double acc = 0.0;
+    for (int i = 0; i < 16; ++i) {
+        const int p = p0 + i;
+        if (p >= npix) break;                                          // wave-uniform
+        double u[8], v[8], s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            u[j] = j < per ? (double)f0[(size_t)p * C + lane + 64 * j] : 0.0;
+            v[j] = j < per ? (double)f1[(size_t)p * C + lane + 64 * j] : 0.0;
+            s0 += u[j] * u[j];
+            s1 += v[j] * v[j];
+        }
+        const double n0 = sqrt(wave_sum(s0)) + 1e-10, n1 = sqrt(wave_sum(s1)) + 1e-10;
+        double d = 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const double t = u[j] / n0 - v[j] / n1;
+            d += w[j] * (t * t);
+        }
+        acc += wave_sum(d);
+    }
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+// one wave per pair: lane l adds workgroups l, l + 64, ... of a tap in order, then the fixed butterfly
+__global__ void __launch_bounds__(64) lpips_mean_kernel(const HeadArgs a, double* lpips, double* per_tap) {
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    const double* part = a.partial + (size_t)pair * a.blk0[kTaps];
+    double total = 0.0;
+    for (int k = 0; k < kTaps; ++k) {
+        double s = 0.0;
+        for (int b = a.blk0[k] + lane; b < a.blk0[k + 1]; b += 64) s += part[b];
+        const double L = wave_sum(s) / (double)a.npix[k];
+        if (per_tap && lane == 0) per_tap[pair * kTaps + k] = L;
+        total += L;
+    }
+    if (lane == 0) lpips[pair] = total;
+}
+
+bool lpips_shape_ok(int B, int H, int W) {
+    return B >= 1 && H >= 16 && W >= 16 && 2.0 * B * H * W <= (double)kMaxPixels;
+}
+int head_blocks(int H, int W) {
+    int n = 0;
+    for (int k = 0; k < kTaps; ++k) n += ((H >> k) * (W >> k) + kHeadPix - 1) / kHeadPix;
+    return n;
+}
+size_t up64(size_t n) { return (n + 63) / 64 * 64; }
+size_t conv_tile_floats(int K, int N) { return (size_t)(9 * K / 32) * (N / 16) * kTile; }
+bool conv_shape_ok(int K, int N) {
+    return (K == 3 && N == 64) || ((K == 64 || K == 128 || K == 256 || K == 512) && (N == 64 || N == 128 || N == 256 || N == 512));
+}
+
+// the 13 convolutions and 4 pools over the workspace's buffers: 0..4 the taps, 5 and 6 two scratch maps, -1 the input images
+struct Step { bool pool; int layer, K, N, h, w, src, dst; };
+struct Plan { Step step[kLayers + 4]; int steps; size_t buf[7]; };
+Plan make_plan(int B, int H, int W) {
+    Plan pl{};
+    int cur = -1, h = H, w = W, K = 3, tap = 0;
+    auto need = [&](int b, size_t n) { if (pl.buf[b] < n) pl.buf[b] = n; };
+    for (int l = 0; l < kLayers; ++l) {
+        if (pool_in_front(l)) {
+            pl.step[pl.steps++] = Step{true, l, K, K, h, w, cur, 6};
+            h /= 2; w /= 2; cur = 6;
+            need(6, (size_t)2 * B * h * w * K);
+        }
+        const int N = kWidth[l], dst = layer_ends_block(l) ? tap++ : (cur == 5 ? 6 : 5);
+        pl.step[pl.steps++] = Step{false, l, K, N, h, w, cur, dst};
+        need(dst, (size_t)2 * B * h * w * N);
+        cur = dst; K = N;
+    }
+    for (int b = 0; b < 7; ++b) pl.buf[b] = up64(pl.buf[b]);
+    return pl;
+}
+size_t layer_offset(int l) {                                          // of layer l inside car_lpips_pack's array (l = 13: the lin weights)
+    size_t off = 0;
+    for (int i = 0, K = 3; i < l; K = kWidth[i], ++i) off += car_conv3x3_packed_floats(K, kWidth[i]);
+    return off;
+}
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int head(const float* const* feats, int B, int H, int W, const float* lin, double* lpips, double* per_tap, double* scratch, hipStream_t st,
+         const char* who) {
+    HeadArgs a;
+    int blk = 0, off = 0;
+    for (int k = 0; k < kTaps; ++k) {
+        a.f[k] = feats[k];
+        a.lin[k] = lin + off;
+        off += kTapWidth[k];
+        a.npix[k] = (H >> k) * (W >> k);
+        a.C[k] = kTapWidth[k];
+        a.blk0[k] = blk;
+        blk += (a.npix[k] + kHeadPix - 1) / kHeadPix;
+    }
+    a.blk0[kTaps] = blk;
+    a.B = B;
+    a.partial = scratch;
+    hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((long)B * blk)), dim3(256), 0, st, a);
+    CAR_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(lpips_mean_kernel, dim3((unsigned)B), dim3(64), 0, st, a, lpips, per_tap);
+    CAR_CHECK_LAUNCH(who);
+    return CAR_OK;
+}
+
+int conv(const float* X, int n, int H, int W, int K, int N, const float* packed, float* Y, hipStream_t st) {
+    const long M = (long)n * H * W;
+    if (K == 3) {
+        hipLaunchKernelGGL(conv_first_kernel, dim3(car_div_up(M, 4 * kFirstPix)), dim3(256), 0, st, X, packed, Y, H, W, M);
+        CAR_CHECK_LAUNCH("car_conv3x3");
+        return CAR_OK;
+    }
+    ConvArgs a;
+    a.X = X; a.Wp = packed; a.tiles_total = N / 16;
+    a.down = packed + conv_tile_floats(K, N) + 1;
+    a.bias = packed + conv_tile_floats(K, N) + 64;
+    a.Y = Y; a.H = H; a.W = W; a.K = K; a.N = N; a.chunks = 9 * K / 32; a.M = M;
+    a.lgk = K == 64 ? 1 : K == 128 ? 2 : K == 256 ? 3 : 4;
+    if (N == 64) return launch_conv<4>(a, st);
+    if (N == 128) return launch_conv<8>(a, st);
+    return launch_conv<16>(a, st);
+}
+
+int pool(const float* X, int n, int H, int W, int C, float* Y, hipStream_t st) {
+    const long total = (long)n * (H / 2) * (W / 2) * (C / 4);
+    const long blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, X, Y, H, W, C / 4, total);
+    CAR_CHECK_LAUNCH("car_maxpool2x2");
+    return CAR_OK;
+}
+
+}  // namespace
+
+// One layer's packed weights: K = 3 (N = 64; the network's first layer, scaling layer folded in) 27 x 64 fp32 weights and the bias;
+// otherwise 9 K / 32 x N / 16 tiles of 512 floats, 64 floats of scale, the bias.  0 for a shape car_conv3x3 refuses.
+extern "C" size_t car_conv3x3_packed_floats(int K, int N) {
+    if (!conv_shape_ok(K, N)) return 0;
+    return K == 3 ? (size_t)kFirstFloats : conv_tile_floats(K, N) + 64 + (size_t)N;
+}
+
+extern "C" int car_conv3x3_pack(const float* w, const float* bias, int K, int N, float* packed, void* stream) {
+    CAR_REQUIRE(w && bias && packed, "car_conv3x3_pack: null pointer");
+    CAR_REQUIRE(conv_shape_ok(K, N), "car_conv3x3_pack: %d -> %d channels, need 3 -> 64 or K and N among 64, 128, 256, 512", K, N);
+    CAR_REQUIRE(aligned16(packed), "car_conv3x3_pack: packed must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipGetLastError();
+    if (K == 3) {
+        hipLaunchKernelGGL(first_pack_kernel, dim3(car_div_up(kFirstFloats, 256)), dim3(256), 0, st, w, bias, packed);
+        CAR_CHECK_LAUNCH("car_conv3x3_pack");
+        return CAR_OK;
+    }
+    float* scale = packed + conv_tile_floats(K, N);
+    if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("car_conv3x3_pack: memset failed"); return CAR_E_LAUNCH; }
+    hipLaunchKernelGGL(conv_absmax_kernel, dim3(64), dim3(256), 0, st, w, (long)N * K * 9, scale);
+    hipLaunchKernelGGL(conv_pack_kernel, dim3(512), dim3(256), 0, st, w, bias, K, N, (long)(conv_tile_floats(K, N)), scale, reinterpret_cast<_Float16*>(packed));
+    CAR_CHECK_LAUNCH("car_conv3x3_pack");
+    return CAR_OK;
+}
+
+extern "C" int car_conv3x3(const float* X, int n, int H, int W, int K, int N, const float* packed, float* Y, void* stream) {
+    CAR_REQUIRE(X && packed && Y, "car_conv3x3: null pointer");
+    CAR_REQUIRE(conv_shape_ok(K, N), "car_conv3x3: %d -> %d channels, need 3 -> 64 or K and N among 64, 128, 256, 512", K, N);
+    CAR_REQUIRE(n >= 1 && H >= 1 && W >= 1, "car_conv3x3: %d images of %d x %d, need at least one pixel", n, H, W);
+    CAR_REQUIRE((double)n * H * W <= (double)kMaxPixels, "car_conv3x3: %d x %d x %d is too large", n, H, W);
+    CAR_REQUIRE(aligned16(X) && aligned16(packed) && aligned16(Y), "car_conv3x3: X, packed and Y must be 16-byte aligned");
+    return conv(X, n, H, W, K, N, packed, Y, (hipStream_t)stream);
+}
+
+extern "C" int car_maxpool2x2(const float* X, int n, int H, int W, int C, float* Y, void* stream) {
+    CAR_REQUIRE(X && Y, "car_maxpool2x2: null pointer");
+    CAR_REQUIRE(n >= 1 && H >= 2 && W >= 2 && C >= 4 && C % 4 == 0, "car_maxpool2x2: %d x %d x %d x %d, need H, W >= 2 and C a multiple of 4", n, H, W, C);
+    CAR_REQUIRE((double)n * H * W <= (double)kMaxPixels && C <= 4096, "car_maxpool2x2: %d x %d x %d x %d is too large", n, H, W, C);
+    CAR_REQUIRE(aligned16(X) && aligned16(Y), "car_maxpool2x2: X and Y must be 16-byte aligned");
+    return pool(X, n, H, W, C, Y, (hipStream_t)stream);
+}
+
+extern "C" size_t car_lpips_head_scratch_doubles(int B, int H, int W) {
+    return lpips_shape_ok(B, H, W) ? (size_t)B * head_blocks(H, W) : 0;
+}
+
+extern "C" int car_lpips_head(const float* const* feats, int B, int H, int W, const float* lin, double* lpips, double* per_tap, double* scratch,
+                              size_t scratch_doubles, void* stream) {
+    CAR_REQUIRE(feats && lin && lpips && scratch, "car_lpips_head: null pointer");
+    for (int k = 0; k < kTaps; ++k) CAR_REQUIRE(feats[k], "car_lpips_head: null pointer (tap %d)", k);
+    CAR_REQUIRE(B >= 1, "car_lpips_head: B = %d, need at least one image pair", B);
+    CAR_REQUIRE(H >= 16 && W >= 16, "car_lpips_head: %d x %d image, the last tap needs H >= 16 and W >= 16", H, W);
+    CAR_REQUIRE(lpips_shape_ok(B, H, W), "car_lpips_head: %d x %d x %d is too large", B, H, W);
+    const size_t need = car_lpips_head_scratch_doubles(B, H, W);
+    CAR_REQUIRE(scratch_doubles >= need, "car_lpips_head: scratch holds %zu doubles, need %zu (car_lpips_head_scratch_doubles)", scratch_doubles, need);
+    (void)hipGetLastError();
+    return head(feats, B, H, W, lin, lpips, per_tap, scratch, (hipStream_t)stream, "car_lpips_head");
+}
+
+extern "C" size_t car_lpips_packed_floats(void) { return layer_offset(kLayers) + kLinFloats; }
+
+extern "C" int car_lpips_pack(const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, float* packed, void* stream) {
+    CAR_REQUIRE(conv_w && conv_b && lin_w && packed, "car_lpips_pack: null pointer");
+    for (int l = 0; l < kLayers; ++l) CAR_REQUIRE(conv_w[l] && conv_b[l], "car_lpips_pack: null pointer (layer %d)", l);
+    for (int k = 0; k < kTaps; ++k) CAR_REQUIRE(lin_w[k], "car_lpips_pack: null pointer (lin%d)", k);
+    CAR_REQUIRE(aligned16(packed), "car_lpips_pack: packed must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    size_t off = 0;
+    for (int l = 0, K = 3; l < kLayers; K = kWidth[l], ++l) {
+        const int code = car_conv3x3_pack(conv_w[l], conv_b[l], K, kWidth[l], packed + off, stream);
+        if (code != CAR_OK) return code;
+        off += car_conv3x3_packed_floats(K, kWidth[l]);
+    }
+    for (int k = 0; k < kTaps; ++k) {
+        if (hipMemcpyAsync(packed + off, lin_w[k], kTapWidth[k] * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            car_set_error("car_lpips_pack: copying lin%d failed: %s", k, hipGetErrorString(hipGetLastError()));
+            return CAR_E_LAUNCH;
+        }
+        off += kTapWidth[k];
+    }
+    return CAR_OK;
+}
+
+extern "C" size_t car_lpips_workspace_bytes(int B, int H, int W) {
+    if (!lpips_shape_ok(B, H, W)) return 0;
+    const Plan pl = make_plan(B, H, W);
+    size_t floats = 0;
+    for (int b = 0; b < 7; ++b) floats += pl.buf[b];
+    return floats * sizeof(float) + up64(car_lpips_head_scratch_doubles(B, H, W)) * sizeof(double);
+}
+
+extern "C" int car_lpips(const float* x, const float* y, int B, int H, int W, const float* packed, double* lpips, double* per_tap, void* work,
+                         size_t work_bytes, void* stream) {
+    CAR_REQUIRE(x && y && packed && lpips && work, "car_lpips: null pointer");
+    CAR_REQUIRE(B >= 1, "car_lpips: B = %d, need at least one image pair", B);
+    CAR_REQUIRE(H >= 16 && W >= 16, "car_lpips: %d x %d image, the last tap needs H >= 16 and W >= 16", H, W);
+    CAR_REQUIRE(lpips_shape_ok(B, H, W), "car_lpips: %d x %d x %d is too large", B, H, W);
+    const size_t need = car_lpips_workspace_bytes(B, H, W);
+    CAR_REQUIRE(work_bytes >= need, "car_lpips: workspace holds %zu bytes, need %zu (car_lpips_workspace_bytes)", work_bytes, need);
+    CAR_REQUIRE(aligned16(packed) && aligned16(work), "car_lpips: packed and the workspace must be 16-byte aligned");
+
+    const Plan pl = make_plan(B, H, W);
+    float* buf[7];
+    float* at = static_cast<float*>(work);
+    for (int b = 0; b < 7; ++b) { buf[b] = at; at += pl.buf[b]; }
+    double* scratch = reinterpret_cast<double*>(at);
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipGetLastError();
+    for (int i = 0; i < pl.steps; ++i) {
+        const Step& s = pl.step[i];
+        int code;
+        if (s.pool) code = pool(buf[s.src], 2 * B, s.h, s.w, s.K, buf[s.dst], st);
+        else if (s.src < 0) {                                           // the two image stacks become one batch of 2 B here
+            code = conv(x, B, H, W, 3, 64, packed, buf[s.dst], st);
+            if (code == CAR_OK) code = conv(y, B, H, W, 3, 64, packed, buf[s.dst] + (size_t)B * H * W * 64, st);
+        } else code = conv(buf[s.src], 2 * B, s.h, s.w, s.K, s.N, packed + layer_offset(s.layer), buf[s.dst], st);
+        if (code != CAR_OK) return code;
+    }
+    return head(buf, B, H, W, packed + layer_offset(kLayers), lpips, per_tap, scratch, st, "car_lpips");
+}

@@ -111,6 +111,126 @@ def ssim(img: torch.Tensor, ref: torch.Tensor, data_range: float = 2.0) -> torch
     return out[0] if img.dim() == 3 else out
 
 
+# ---- LPIPS v0.1, net = 'vgg' (car_lpips, csrc/car_lpips.hip) ---------------------------------------------------------
+LPIPS_FEATURES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)      # torchvision vgg16().features indices of the 13 convolutions
+LPIPS_WIDTHS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+LPIPS_SLICE = (1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5)                   # the lpips package's net.slice{n} that holds each of them
+LPIPS_TAP_WIDTHS = (64, 128, 256, 512, 512)
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+
+
+def lpips_arrays(vgg_state, lin_state=None):
+    """The 13 convolutions' weights and biases and the five ``lin`` weights as float32 CPU tensors, from either layout of weight files:
+    a torchvision VGG16 state dict (``features.{i}.weight|bias``) plus the lpips package's linear file (``lin{k}.model.1.weight``), or
+    — with ``lin_state`` None — one ``lpips.LPIPS(net='vgg').state_dict()`` (``net.slice{n}.{i}.weight|bias``, ``lin{k}.model.1.weight``;
+    its duplicate ``lins.*`` keys are ignored, its ``scaling_layer.shift|scale`` checked against the constants).
+    Raises ValueError naming the key that is missing or has the wrong shape.  The sign of a lin weight is not checked."""
+    def take(state, key, shape):
+        if key not in state:
+            raise ValueError(f"lpips weights: key {key!r} is missing")
+        t = state[key]
+        if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"lpips weights: key {key!r} has shape {tuple(getattr(t, 'shape', ()))}, need {tuple(shape)}")
+        return t.detach().to("cpu", torch.float32).contiguous()
+    single = lin_state is None
+    lin_state = vgg_state if single else lin_state
+    conv_w, conv_b, k_in = [], [], 3
+    for i, n, sl in zip(LPIPS_FEATURES, LPIPS_WIDTHS, LPIPS_SLICE):
+        stem = f"net.slice{sl}.{i}" if single else f"features.{i}"
+        conv_w.append(take(vgg_state, stem + ".weight", (n, k_in, 3, 3)))
+        conv_b.append(take(vgg_state, stem + ".bias", (n,)))
+        k_in = n
+    lin = [take(lin_state, f"lin{k}.model.1.weight", (1, c, 1, 1)).reshape(c) for k, c in enumerate(LPIPS_TAP_WIDTHS)]
+    if single:
+        for key, want in (("scaling_layer.shift", LPIPS_SHIFT), ("scaling_layer.scale", LPIPS_SCALE)):
+            if key in vgg_state:
+                got = vgg_state[key]
+                if not torch.is_tensor(got) or got.numel() != 3 or (got.double().reshape(3) - torch.tensor(want, dtype=torch.float64)).abs().max() > 1e-6:
+                    raise ValueError(f"lpips weights: key {key!r} differs from LPIPS v0.1's constants {want}")
+    return conv_w, conv_b, lin
+
+
+class LpipsWeights:
+    """The caller's LPIPS weights: the float32 arrays, and per device their packed form (car_lpips_pack, made once) and the
+    workspaces of the shapes evaluated so far."""
+
+    def __init__(self, conv_w, conv_b, lin):
+        self.conv_w, self.conv_b, self.lin = conv_w, conv_b, lin
+        self._packed, self._work = {}, {}
+
+    def packed(self, device) -> torch.Tensor:
+        import ctypes
+        from . import _lib
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"lpips: the weights are packed on a ROCm device, not on {device}; there is no CPU fallback")
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._packed:
+            lib = _lib.load()
+            with torch.cuda.device(device):
+                dev = [[t.to(device) for t in group] for group in (self.conv_w, self.conv_b, self.lin)]
+                tables = [(ctypes.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in dev]
+                out = torch.empty(lib.car_lpips_packed_floats(), dtype=torch.float32, device=device)
+                code = lib.car_lpips_pack(*tables, out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                _lib.check(code, "car_lpips_pack")
+                torch.cuda.current_stream().synchronize()              # the float32 copies in `dev` are released on return
+            self._packed[key] = out
+        return self._packed[key]
+
+    def workspace(self, device, B, H, W, nbytes) -> torch.Tensor:
+        key = (str(device), B, H, W)
+        if key not in self._work:
+            self._work[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        return self._work[key]
+
+
+def load_lpips_weights(vgg_path: str, lin_path: Optional[str] = None) -> LpipsWeights:
+    """Reads the LPIPS weight files the caller names (``torch.load(..., weights_only=True)``): a torchvision VGG16 state dict and the
+    lpips package's ``vgg.pth``, or one file holding ``lpips.LPIPS(net='vgg').state_dict()``.  Validates every key (``lpips_arrays``);
+    packing happens once per device, on first use."""
+    vgg = torch.load(vgg_path, map_location="cpu", weights_only=True)
+    lin = torch.load(lin_path, map_location="cpu", weights_only=True) if lin_path else None
+    return LpipsWeights(*lpips_arrays(vgg, lin))
+
+
+def lpips(img: torch.Tensor, ref: torch.Tensor, weights: LpipsWeights, return_taps: bool = False):
+    """LPIPS v0.1 (net = 'vgg') of the reference's eval script (eval_realestate10k.py:184-191: ``loss_fn_vgg((x - 0.5) * 2, (y - 0.5) * 2)``)
+    on the device: ``car_lpips`` (csrc/car_lpips.hip) with the caller's weights (``load_lpips_weights``).
+
+    ``img`` and ``ref`` are (H, W, 3) or (B, H, W, 3) tensors in [0, 1] on a ROCm device, H and W >= 16; they are mapped to [-1, 1]
+    here, as the reference does.  Returns a float64 device tensor of shape () or (B,) (with ``return_taps`` also the five per-tap
+    terms, (5,) or (B, 5)).  Nothing waits for the launches.  Identical images give exactly 0.
+
+    Raises ValueError for CPU tensors (there is no CPU fallback), mismatched shapes and the shapes car_lpips refuses."""
+    import ctypes
+    from . import _lib
+    if not (torch.is_tensor(img) and torch.is_tensor(ref)):
+        raise ValueError("lpips: img and ref must be tensors")
+    if img.device.type != "cuda" or ref.device != img.device:
+        raise ValueError(f"lpips: needs both images on one ROCm device (got {img.device} and {ref.device}); there is no CPU fallback")
+    if img.shape != ref.shape or img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise ValueError(f"lpips: need two (H, W, 3) or (B, H, W, 3) images of one shape, got {tuple(img.shape)} and {tuple(ref.shape)}")
+    if not isinstance(weights, LpipsWeights):
+        raise ValueError("lpips: weights must come from load_lpips_weights")
+    x, y = (((t.to(torch.float32) - 0.5) * 2).contiguous() for t in (img, ref))
+    B, H, W, _ = x.shape if x.dim() == 4 else (1, *x.shape)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        packed = weights.packed(x.device)
+        n = lib.car_lpips_workspace_bytes(B, H, W)
+        work = weights.workspace(x.device, B, H, W, n)
+        out = torch.empty(max(B, 1), dtype=torch.float64, device=x.device)
+        taps = torch.empty(max(B, 1), 5, dtype=torch.float64, device=x.device)
+        code = lib.car_lpips(x.data_ptr(), y.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), taps.data_ptr(), work.data_ptr(), n,
+                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if code == -1:
+        raise ValueError(lib.car_last_error().decode())
+    _lib.check(code, "car_lpips")
+    out, taps = (out[0], taps[0]) if img.dim() == 3 else (out, taps)
+    return (out, taps) if return_taps else out
+
+
 def write_png(path: str, rgb: torch.Tensor) -> None:
     """(H, W, 3) float image in [-1, 1] -> 8-bit PNG (imageio is not available in this image)."""
     img = ((rgb.clamp(-1, 1) + 1) * 127.5).round().to(torch.uint8).cpu().numpy()

@@ -6,7 +6,8 @@ Differences from the reference, all additive:
                   identical replicas (eval_realestate10k.py:95-99);
   --synthetic     seeded synthetic stereo pair + feature pyramid (default when --data_root is absent: the datasets and the
                   DPT encoder weights are not available offline);
-  --out_dir       where frames (PNG + NPY) and metrics are written.
+  --out_dir       where frames (PNG + NPY) and metrics are written;
+  --lpips_weights VGG [LIN]   the caller's LPIPS weight files: with them the eval / render scripts report LPIPS too.
 """
 from __future__ import annotations
 
@@ -46,6 +47,10 @@ def parser(description: str) -> argparse.ArgumentParser:
                         "torch.inverse calls there (strict parity, no device sync; default); gpu = the whole input dict on the GPU as in the "
                         "reference's scripts, the engine downloads the matrices for the same host algebra (strict parity, one small sync per "
                         "new pose); device = car_pose_setup on the GPU (no host work per frame, last-ulp differences)")
+    p.add_argument("--lpips_weights", type=str, nargs="+", default=None, metavar=("VGG", "LIN"),
+                   help="report LPIPS (v0.1, net='vgg') computed on the device with these weight files: a torchvision VGG16 state dict and "
+                        "the lpips package's vgg.pth, or one file holding lpips.LPIPS(net='vgg').state_dict().  Without it LPIPS is not reported "
+                        "(no weights are shipped)")
     p.add_argument("--port", type=int, default=1492)          # the reference rendezvous port (eval_realestate10k.py:97)
     return p
 
@@ -89,6 +94,17 @@ def build_model(opt, device, with_encoder=None):
     model.pose_route = "device" if getattr(opt, "cameras", "host") == "device" else "host"
     model.render_precision = getattr(opt, "precision", "fp32")
     return model.to(device)
+
+
+def lpips_weights(opt):
+    """The weights named by --lpips_weights (harness.load_lpips_weights), or None without the option."""
+    paths = getattr(opt, "lpips_weights", None)
+    if not paths:
+        return None
+    if len(paths) > 2:
+        raise SystemExit("--lpips_weights takes one file (the lpips package's state dict) or two (VGG16 state dict, lin weights)")
+    from cross_attention_renderer_amd import harness
+    return harness.load_lpips_weights(paths[0], paths[1] if len(paths) == 2 else None)
 
 
 def spawn(fn, opt):

@@ -8,7 +8,8 @@ Per item (eval_realestate10k.py:131-199): ``z = model.get_z(model_input)`` on th
 chunks (18 for three views), MSE, PSNR and SSIM of the rendered against the ground-truth query frame.  Items come from
 ``dataio.RealEstate10kVis`` (the reference's reader, pinned in tests/test_dataio.py).  SSIM is the reference's scikit-image call
 (eval_realestate10k.py:192-194) computed on the device by ``harness.ssim``, with its default data_range of 2.
-LPIPS is not available: it needs the lpips package and VGG16 weights, neither of which can be installed offline.  With --gpus N
+LPIPS (eval_realestate10k.py:184-191: v0.1, net = 'vgg', images mapped to [-1, 1]) is reported with --lpips_weights VGG [LIN], computed on
+the device by ``harness.lpips`` from the weight files the caller names (no weights are shipped).  With --gpus N
 the rays of every item are banded over N processes instead of N replicas evaluating everything.
 --synthetic: a seeded pair and feature pyramid (no dataset, no encoder); the target is then the un-chunked render of the same frame,
 so the figures check chunk / shard invariance (inf or > 100 dB, SSIM 1), not image quality — and is labelled so."""
@@ -31,7 +32,8 @@ def evaluate(rank, opt, default_data=DEFAULT_DATA):
     real = not opt.synthetic and (opt.data_root or os.path.isdir(default_data[0]))
     model = common.build_model(opt, dev, with_encoder=True if real else None)
     n_chunks = 9 if opt.views < 3 else 18                    # eval_realestate10k.py:144-149
-    psnrs, mses, ssims = [], [], []
+    psnrs, mses, ssims, lpipss = [], [], [], []
+    lpips_w = common.lpips_weights(opt)
     if real:
         ds = dataio.RealEstate10kVis(opt.data_root or default_data[0], opt.pose_root or default_data[1], num_ctxt_views=opt.views,
                                      num_query_views=1, augment=False)
@@ -78,14 +80,20 @@ def evaluate(rank, opt, default_data=DEFAULT_DATA):
         psnrs.append(harness.psnr(rgb, target))
         mses.append(torch.mean((rgb - target) ** 2).item())                                  # img2mse (eval_realestate10k.py:183)
         ssims.append(harness.ssim(rgb.reshape(H, H, 3), target.reshape(H, H, 3)).item())     # eval_realestate10k.py:192-195
+        if lpips_w is not None:                                                              # eval_realestate10k.py:184-191
+            lpipss.append(harness.lpips(rgb.reshape(H, H, 3), target.reshape(H, H, 3), lpips_w).item())
         if rank == 0:
             print(f"item {k}: elapsed {elapsed:.3f} s, {what} {psnrs[-1]:.2f} dB, valid {tile[0, :, 4].mean().item():.3f}")
             print(f"item {k} ssim {ssims[-1]:.6f}, mse {mses[-1]:.3e}")
+            if lpipss:
+                print(f"item {k} lpips {lpipss[-1]:.6f}")
     if rank == 0 and psnrs:
         print("mean psnr", sum(min(p, 200.0) for p in psnrs) / len(psnrs))
         print("render precision", model.render_precision)
         print("mean mse", sum(mses) / len(mses))
         print("mean ssim", sum(ssims) / len(ssims))
+        if lpipss:
+            print("mean lpips", sum(lpipss) / len(lpipss))
 
 
 if __name__ == "__main__":

@@ -54,6 +54,7 @@ def render(rank, opt):
     from cross_attention_renderer_amd import harness
     dev = common.init_rank(rank, opt)
     model = common.build_model(opt, dev)
+    lpips_w = common.lpips_weights(opt)
     H = opt.img_sidelength
     out_root = opt.out_dir or os.path.join(opt.logging_root, opt.experiment_name, "renders")
     t0, n_done = time.time(), 0
@@ -74,6 +75,8 @@ def render(rank, opt):
                     img, ref = (rgb.clamp(-1, 1) + 1) / 2, (gt[0, 0].clamp(-1, 1) + 1) / 2
                     print(f"{scene} frame {i}: PSNR {harness.psnr(img, ref):.2f} dB")
                     print(f"{scene} frame {i}: SSIM {harness.ssim(img, ref.to(img.device)).item():.4f}")
+                    if lpips_w is not None:
+                        print(f"{scene} frame {i}: LPIPS {harness.lpips(img, ref.to(img.device), lpips_w).item():.4f}")
     torch.cuda.synchronize()
     if rank == 0:
         dt = time.time() - t0

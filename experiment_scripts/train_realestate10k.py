@@ -13,7 +13,8 @@ gradient clipping at norm 1 (training.py:130-134), parameters broadcast from ran
 Data: the RealEstate10K training set and its augmenting reader are not available offline, so scenes are synthetic (--synthetic, the
 default here: seeded stereo pairs with a smooth random target image per scene; every step draws new rays).  The encoder trains when the
 model is built with it (--with_encoder: the pyramid then comes from ``get_z`` under autograd); otherwise the pyramid itself is a leaf
-that receives gradients, standing in for the encoder's output.  LPIPS (--lpips) needs the lpips package, which is not installed."""
+that receives gradients, standing in for the encoder's output.  The LPIPS loss term (--lpips) is not built: a training loss
+needs the backward of the VGG16 convolutions; the forward metric is in the eval scripts (--lpips_weights, harness.lpips)."""
 import os
 import sys
 import time
@@ -42,7 +43,8 @@ def train(rank, opt):
     from cross_attention_renderer_amd import training
     from cross_attention_renderer_amd.training import average_gradients, render_train
     if opt.lpips:
-        raise SystemExit("--lpips needs the lpips package (not installed here)")
+        raise SystemExit("--lpips is not supported: a training loss needs LPIPS's backward, which is not built "
+                         "(the forward metric is reported by the eval scripts with --lpips_weights)")
     dev = common.init_rank(rank, opt)
     H, b, R = opt.img_sidelength, opt.batch_size, opt.query_sparsity
     model = common.build_model(opt, dev).train()

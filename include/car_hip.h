@@ -491,6 +491,37 @@ size_t car_ssim_scratch_doubles(int B, int H, int W, int C);
 int car_ssim(const float* x, const float* y, int B, int H, int W, int C, double data_range, double* mssim, double* scratch,
              size_t scratch_doubles, void* stream);
 
+/* ---- evaluation metric: LPIPS v0.1, net = 'vgg' (eval_realestate10k.py:184-199 prints mse, psnr, lpip, ssim).
+ * The weights are the caller's: 13 convolutions of VGG16's `features` (torch layout [N][K][3][3], biases [N]) and the five 1x1 `lin`
+ * layers (64, 128, 256, 512, 512 floats), all device arrays named by HOST arrays of pointers.  car_lpips_pack lays them out once
+ * (car_lpips_packed_floats floats, 16-byte aligned): the first layer as fp32 with the scaling layer's 1 / scale folded in, the other
+ * twelve as split-fp16 tiles, then the lin weights.
+ * car_lpips: x, y [B,H,W,3] fp32 channel-last in [-1, 1], H and W >= 16; lpips [B] fp64, per_tap [B,5] fp64 or NULL.  Both images of
+ * all B pairs run through the convolutions as one batch of 2 B; an image's features do not depend on its place in the batch, so
+ * identical images give exactly 0.  The head's arithmetic and sums are fp64 in a fixed order: bitwise reproducible, and a pair gives the
+ * same bits alone as inside a batch.  work: car_lpips_workspace_bytes bytes, 16-byte aligned, caller-owned (0 for a refused shape). */
+size_t car_lpips_packed_floats(void);
+int car_lpips_pack(const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, float* packed, void* stream);
+size_t car_lpips_workspace_bytes(int B, int H, int W);
+int car_lpips(const float* x, const float* y, int B, int H, int W, const float* packed, double* lpips, double* per_tap, void* work,
+              size_t work_bytes, void* stream);
+/* The stages, for tests and other hosts.
+ * car_conv3x3: Y [n,H,W,N] = relu(conv3x3(X [n,H,W,K]) + bias), stride 1, zero padding 1, channel-last fp32, as one implicit GEMM over
+ *   9 K on the f16 matrix pipe in split arithmetic (fp32-class accuracy); K and N among 64, 128, 256, 512.  K = 3 (N = 64) is the
+ *   network's first layer, an fp32 vector kernel that computes relu(conv3x3((X - shift) / scale) + bias) with the scaling layer's
+ *   constants, the padding being zeros of the SCALED image.  `packed` comes from car_conv3x3_pack (weights [N][K][3][3] and bias [N] on
+ *   the device; car_conv3x3_packed_floats floats, 0 for a refused shape).  X, Y and packed 16-byte aligned.
+ * car_maxpool2x2: Y [n,H/2,W/2,C] = the 2x2 / stride 2 maximum (floor), C a multiple of 4.
+ * car_lpips_head: feats = HOST array of five device maps [2 B, (H >> k)(W >> k), C_k] (images 0..B-1 against images B..2B-1), lin the
+ *   1472 lin weights in tap order; scratch: car_lpips_head_scratch_doubles doubles. */
+size_t car_conv3x3_packed_floats(int K, int N);
+int car_conv3x3_pack(const float* w, const float* bias, int K, int N, float* packed, void* stream);
+int car_conv3x3(const float* X, int n, int H, int W, int K, int N, const float* packed, float* Y, void* stream);
+int car_maxpool2x2(const float* X, int n, int H, int W, int C, float* Y, void* stream);
+size_t car_lpips_head_scratch_doubles(int B, int H, int W);
+int car_lpips_head(const float* const* feats, int B, int H, int W, const float* lin, double* lpips, double* per_tap, double* scratch,
+                   size_t scratch_doubles, void* stream);
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);

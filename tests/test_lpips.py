@@ -1,0 +1,506 @@
+"""LPIPS of the evaluation scripts (car_lpips, harness.lpips): the float64 restatement (tests/lpips_restatement.py) against closed forms,
+the weight loader, the C entries' argument checks and the wrapper's refusals on the CPU; on the GPU the head, the 3x3 convolution and the
+whole metric against the restatement with seeded random weights, the exact zero of identical images, determinism, and the eval script.
+
+Pinned against the restatement, NOT against the lpips package or the pretrained weights (neither exists offline):
+tests/golden/make_lpips_golden.py --lpips closes that pin where the package is installed."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import lpips_restatement as LR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCRIPTS = ("eval_realestate10k.py", "eval_acid.py", "render_realestate10k_traj.py", "render_unposed_traj.py", "train_realestate10k.py")
+
+# (B, H, W, seed) of the end-to-end cases and the three kinds of pair; the identical pair is a case of its own
+E2E_SHAPES = ((1, 256, 256, 11), (3, 256, 256, 12), (2, 50, 70, 13), (2, 16, 16, 14))
+KINDS = ("unrelated", "noisy", "near")
+# (K, N, side) of the nine distinct layer shapes of the network on a 256 x 256 image
+LAYER_SHAPES = ((3, 64, 256), (64, 64, 256), (64, 128, 128), (128, 128, 128), (128, 256, 64), (256, 256, 64), (256, 512, 32), (512, 512, 32),
+                (512, 512, 16))
+
+
+def _pair(kind, b, h, w, seed):
+    """Images in [0, 1]: x, and y unrelated / x + 0.05 normal / x + 1e-3 normal (not clamped: the reference's protocol clamps nothing)."""
+    x = LR.make_image(seed, b, h, w)
+    if kind == "unrelated":
+        return x, LR.make_image(seed + 1000, b, h, w)
+    g = torch.Generator().manual_seed(seed + 2000 + KINDS.index(kind))
+    return x, x + {"noisy": 0.05, "near": 1e-3}[kind] * torch.randn(x.shape, generator=g)
+
+
+def _to_pm1(img):
+    return ((img.to(torch.float32) - 0.5) * 2).contiguous()            # harness.lpips's mapping, in its arithmetic
+
+
+@pytest.fixture(scope="module")
+def weights():
+    return LR.seeded_weights(0)
+
+
+# ---- CPU: the restatement -----------------------------------------------------------------------------------------------------------
+
+def test_restatement_identical_images_give_exactly_zero(weights):
+    x = _to_pm1(LR.make_image(1, 2, 32, 40))
+    total, per_tap = LR.lpips(x, x.clone(), *weights)
+    assert (total == 0).all() and (per_tap == 0).all()
+
+
+def test_restatement_is_symmetric(weights):
+    x, y = (_to_pm1(t) for t in _pair("unrelated", 2, 32, 40, 2))
+    a, at = LR.lpips(x, y, *weights)
+    b, bt = LR.lpips(y, x, *weights)
+    assert (a > 0).all() and (a - b).abs().max() <= 1e-15 and (at - bt).abs().max() <= 1e-15
+
+
+def test_restatement_hand_computed_one_hot_case():
+    """Every convolution passes channels 0 and 1 through its centre tap, lin picks channel 0.  Image x is (0.6, 0.8) in the first two
+    SCALED channels times a positive per-pixel factor, image y likewise (0.8, 0.6): every layer and pool keeps the direction, the unit
+    vectors are (0.6, 0.8) and (0.8, 0.6) at every pixel of every tap, so each tap's term is (0.6 - 0.8)^2 = 0.04 and LPIPS is 0.2
+    (the 1e-10 in the denominators moves it by about 1e-10)."""
+    conv_w, conv_b, k = [], [], 3
+    for n in LR.WIDTHS:
+        w = torch.zeros(n, k, 3, 3, dtype=torch.float64)
+        w[0, 0, 1, 1] = w[1, 1, 1, 1] = 1.0
+        conv_w.append(w)
+        conv_b.append(torch.zeros(n, dtype=torch.float64))
+        k = n
+    lin = [F.one_hot(torch.tensor(0), c).double() for c in LR.TAP_WIDTHS]
+    g = torch.Generator().manual_seed(3)
+    factor = 0.5 + 0.5 * torch.rand(1, 16, 16, 1, generator=g, dtype=torch.float64)
+    shift, scale = torch.tensor(LR.SHIFT, dtype=torch.float64), torch.tensor(LR.SCALE, dtype=torch.float64)
+    x = torch.tensor([0.6, 0.8, 0.0], dtype=torch.float64) * factor * scale + shift
+    y = torch.tensor([0.8, 0.6, 0.0], dtype=torch.float64) * factor.flip(1) * scale + shift
+    total, per_tap = LR.lpips(x, y, conv_w, conv_b, lin)
+    assert per_tap.shape == (1, 5) and (per_tap - 0.04).abs().max() < 1e-8
+    assert abs(total.item() - 0.2) < 1e-8
+
+
+def test_inputs_reach_every_tap(weights):
+    """The condition on the test inputs: at every tap of every test image more than a quarter of the activations are non-zero and the
+    channel norm exceeds 1e-6 at every pixel — otherwise the deep taps would test nothing."""
+    for b, h, w, seed in E2E_SHAPES:
+        images = [("x", _pair(KINDS[0], b, h, w, seed)[0])] + [(kind, _pair(kind, b, h, w, seed)[1]) for kind in KINDS]
+        for name, img in images:
+            for k, t in enumerate(LR.taps(_to_pm1(img), weights[0], weights[1])):
+                for i in range(b):
+                    assert (t[i] != 0).double().mean().item() > 0.25, (b, h, w, name, k, i)
+                    assert t[i].pow(2).sum(0).sqrt().min().item() > 1e-6, (b, h, w, name, k, i)
+
+
+# ---- CPU: the loader ------------------------------------------------------------------------------------------------------------------
+
+def test_loader_reads_both_file_layouts(weights, tmp_path):
+    from cross_attention_renderer_amd import harness
+    vgg, lin = LR.state_dicts(*weights, "split")
+    single, _ = LR.state_dicts(*weights, "single")
+    a, b = harness.lpips_arrays(vgg, lin), harness.lpips_arrays(single)
+    for ga, gb, want in zip(a, b, weights):
+        assert len(ga) == len(gb) == len(want)
+        for ta, tb, tw in zip(ga, gb, want):
+            assert ta.dtype == torch.float32 and torch.equal(ta, tb) and torch.equal(ta, tw.reshape(ta.shape))
+    torch.save(vgg, tmp_path / "vgg16.pth")
+    torch.save(lin, tmp_path / "lin.pth")
+    torch.save(single, tmp_path / "lpips.pth")
+    w2, w1 = harness.load_lpips_weights(str(tmp_path / "vgg16.pth"), str(tmp_path / "lin.pth")), harness.load_lpips_weights(str(tmp_path / "lpips.pth"))
+    for ga, gb in zip((w2.conv_w, w2.conv_b, w2.lin), (w1.conv_w, w1.conv_b, w1.lin)):
+        assert all(torch.equal(ta, tb) for ta, tb in zip(ga, gb))
+
+
+def test_loader_names_the_malformed_key(weights):
+    from cross_attention_renderer_amd import harness
+    for layout in ("split", "single"):
+        def dicts():
+            return LR.state_dicts(*weights, layout)
+        stem = "features.10" if layout == "split" else "net.slice3.10"
+        vgg, lin = dicts()
+        del vgg[stem + ".weight"]
+        with pytest.raises(ValueError, match=stem.replace(".", r"\.") + r"\.weight"):
+            harness.lpips_arrays(vgg, lin)
+        vgg, lin = dicts()
+        vgg[stem + ".bias"] = torch.zeros(255)
+        with pytest.raises(ValueError, match=stem.replace(".", r"\.") + r"\.bias"):
+            harness.lpips_arrays(vgg, lin)
+        vgg, lin = dicts()
+        vgg[stem + ".weight"] = torch.zeros(256, 128, 1, 1)
+        with pytest.raises(ValueError, match=stem.replace(".", r"\.") + r"\.weight"):
+            harness.lpips_arrays(vgg, lin)
+        vgg, lin = dicts()
+        (lin if lin is not None else vgg)["lin3.model.1.weight"] = torch.zeros(1, 256, 1, 1)
+        with pytest.raises(ValueError, match=r"lin3\.model\.1\.weight"):
+            harness.lpips_arrays(vgg, lin)
+        vgg, lin = dicts()
+        del (lin if lin is not None else vgg)["lin0.model.1.weight"]
+        with pytest.raises(ValueError, match=r"lin0\.model\.1\.weight"):
+            harness.lpips_arrays(vgg, lin)
+    single, _ = LR.state_dicts(*weights, "single")
+    single["scaling_layer.scale"] = torch.tensor([0.5, 0.5, 0.5]).view(1, 3, 1, 1)
+    with pytest.raises(ValueError, match=r"scaling_layer\.scale"):
+        harness.lpips_arrays(single)
+    single, _ = LR.state_dicts(*weights, "single")
+    for k in range(5):
+        del single[f"lins.{k}.model.1.weight"]                         # the duplicates are ignored, present or not
+    del single["scaling_layer.shift"], single["scaling_layer.scale"]
+    harness.lpips_arrays(single)
+
+
+# ---- CPU: the C entries and the wrapper ---------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    ge.build()
+    from cross_attention_renderer_amd import _lib
+    return _lib.load()
+
+
+def test_car_lpips_sizes(lib):
+    conv = 9 * sum(k * n for k, n in zip((64,) + LR.WIDTHS[1:-1], LR.WIDTHS[1:]))           # one float per weight: fp16 hi | lo
+    assert lib.car_lpips_packed_floats() == (27 * 64 + 64) + conv + 12 * 64 + sum(LR.WIDTHS[1:]) + sum(LR.TAP_WIDTHS)
+    assert lib.car_conv3x3_packed_floats(3, 64) == 27 * 64 + 64 and lib.car_conv3x3_packed_floats(256, 512) == 9 * 256 * 512 + 64 + 512
+    for bad in ((3, 128), (64, 96), (32, 64), (1024, 64), (0, 0)):
+        assert lib.car_conv3x3_packed_floats(*bad) == 0, bad
+    assert lib.car_lpips_workspace_bytes(1, 16, 16) > 0 and lib.car_lpips_workspace_bytes(2, 50, 70) > 0
+    # the five taps of both images alone are (64 + 32 + 16 + 8 + 2) H W floats per image
+    assert lib.car_lpips_workspace_bytes(1, 256, 256) >= 2 * 122 * 256 * 256 * 4
+    assert lib.car_lpips_head_scratch_doubles(2, 16, 16) == 2 * (4 + 1 + 1 + 1 + 1)
+    for bad in ((0, 64, 64), (-1, 64, 64), (1, 15, 64), (1, 64, 15), (1 << 20, 256, 256), (1, 1 << 15, 1 << 15)):
+        assert lib.car_lpips_workspace_bytes(*bad) == 0, bad
+        assert lib.car_lpips_head_scratch_doubles(*bad) == 0, bad
+
+
+def test_car_lpips_entries_refuse_bad_arguments(lib):
+    """Every refusal happens before the device is touched, so host addresses stand in for the buffers (never dereferenced)."""
+    buf = (ctypes.c_double * 4096)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+    odd = p + 4
+
+    def check(fn, name, good, cases):
+        for kw, msg in cases:
+            a = dict(good, **kw)
+            assert fn(*a.values()) == -1, (name, kw)
+            err = lib.car_last_error()
+            assert err.startswith(name.encode() + b":") and msg in err, (name, kw, err)
+
+    need = lib.car_lpips_workspace_bytes(1, 64, 64)
+    good = dict(x=p, y=p, B=1, H=64, W=64, packed=p, lpips=p, per_tap=None, work=p, n=need, stream=None)
+    check(lib.car_lpips, "car_lpips", good,
+          [(dict(x=None), b"null pointer"), (dict(y=None), b"null pointer"), (dict(packed=None), b"null pointer"), (dict(lpips=None), b"null pointer"),
+           (dict(work=None), b"null pointer"), (dict(B=0), b"B = 0"), (dict(B=-3), b"B = -3"), (dict(H=15), b"H >= 16"), (dict(W=15), b"W >= 16"),
+           (dict(H=8, W=8), b"H >= 16"), (dict(n=need - 1), b"workspace"), (dict(B=1 << 20, H=256, W=256), b"too large"),
+           (dict(H=1 << 15, W=1 << 15), b"too large"), (dict(packed=odd), b"aligned"), (dict(work=odd), b"aligned")])
+
+    tables = (ctypes.c_void_p * 13)(*([p] * 13))
+    holes = (ctypes.c_void_p * 13)(*([p] * 12 + [None]))
+    lin5, lin_hole = (ctypes.c_void_p * 5)(*([p] * 5)), (ctypes.c_void_p * 5)(p, p, None, p, p)
+    good = dict(conv_w=tables, conv_b=tables, lin_w=lin5, packed=p, stream=None)
+    check(lib.car_lpips_pack, "car_lpips_pack", good,
+          [(dict(conv_w=None), b"null pointer"), (dict(conv_b=None), b"null pointer"), (dict(lin_w=None), b"null pointer"),
+           (dict(packed=None), b"null pointer"), (dict(conv_w=holes), b"layer 12"), (dict(conv_b=holes), b"layer 12"), (dict(lin_w=lin_hole), b"lin2"),
+           (dict(packed=odd), b"aligned")])
+
+    good = dict(X=p, n=1, H=8, W=8, K=64, N=64, packed=p, Y=p, stream=None)
+    check(lib.car_conv3x3, "car_conv3x3", good,
+          [(dict(X=None), b"null pointer"), (dict(packed=None), b"null pointer"), (dict(Y=None), b"null pointer"), (dict(K=3, N=128), b"3 -> 128"),
+           (dict(K=96), b"96 -> 64"), (dict(N=1024), b"64 -> 1024"), (dict(n=0), b"0 images"), (dict(H=0), b"at least one pixel"),
+           (dict(n=1 << 20, H=256, W=256), b"too large"), (dict(X=odd), b"aligned"), (dict(Y=odd), b"aligned")])
+    good = dict(w=p, bias=p, K=64, N=64, packed=p, stream=None)
+    check(lib.car_conv3x3_pack, "car_conv3x3_pack", good,
+          [(dict(w=None), b"null pointer"), (dict(bias=None), b"null pointer"), (dict(packed=None), b"null pointer"), (dict(K=5), b"5 -> 64"),
+           (dict(packed=odd), b"aligned")])
+    good = dict(X=p, n=1, H=8, W=8, C=64, Y=p, stream=None)
+    check(lib.car_maxpool2x2, "car_maxpool2x2", good,
+          [(dict(X=None), b"null pointer"), (dict(Y=None), b"null pointer"), (dict(H=1), b"H, W >= 2"), (dict(C=6), b"multiple of 4"),
+           (dict(n=1 << 20, H=256, W=256), b"too large"), (dict(X=odd), b"aligned")])
+
+    need = lib.car_lpips_head_scratch_doubles(1, 64, 64)
+    good = dict(feats=lin5, B=1, H=64, W=64, lin=p, lpips=p, per_tap=None, scratch=p, n=need, stream=None)
+    check(lib.car_lpips_head, "car_lpips_head", good,
+          [(dict(feats=None), b"null pointer"), (dict(feats=lin_hole), b"tap 2"), (dict(lin=None), b"null pointer"), (dict(lpips=None), b"null pointer"),
+           (dict(scratch=None), b"null pointer"), (dict(B=0), b"B = 0"), (dict(H=15), b"H >= 16"), (dict(W=15), b"W >= 16"),
+           (dict(n=need - 1), b"scratch"), (dict(B=1 << 20, H=256, W=256), b"too large")])
+
+
+def test_harness_lpips_refuses_cpu_tensors_and_bad_shapes(weights):
+    from cross_attention_renderer_amd import harness
+    w = harness.LpipsWeights(*weights)
+    x = torch.rand(16, 16, 3)
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        harness.lpips(x, x, w)
+    with pytest.raises(ValueError):
+        harness.lpips(x, x[:15], w)
+    with pytest.raises(ValueError):
+        harness.lpips(x.numpy(), x.numpy(), w)
+    with pytest.raises(ValueError):
+        harness.lpips(torch.rand(16, 16, 4), torch.rand(16, 16, 4), w)
+
+
+@pytest.mark.parametrize("script", SCRIPTS)
+def test_scripts_show_the_option(script):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "experiment_scripts", script), "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert "--lpips_weights VGG" in out.stdout, out.stdout
+
+
+def test_train_script_says_why_it_has_no_lpips_loss(tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "experiment_scripts", "train_realestate10k.py"), "--experiment_name", "t", "--lpips",
+                          "--logging_root", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode != 0 and "backward" in out.stderr and "not installed" not in out.stderr, out.stderr
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------------------
+
+def _dev():
+    return torch.device("cuda:0")
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _gpu_conv(lib, x_nhwc, w, b):
+    """car_conv3x3_pack + car_conv3x3 on a channel-last float32 device tensor; returns [n, H, W, N]."""
+    from cross_attention_renderer_amd import _lib
+    n, H, W, K = x_nhwc.shape
+    N = w.shape[0]
+    wd, bd = w.to(_dev()).contiguous(), b.to(_dev()).contiguous()
+    packed = torch.empty(lib.car_conv3x3_packed_floats(K, N), dtype=torch.float32, device=_dev())
+    _lib.check(lib.car_conv3x3_pack(wd.data_ptr(), bd.data_ptr(), K, N, packed.data_ptr(), _stream()), "car_conv3x3_pack")
+    y = torch.full((n, H, W, N), float("nan"), dtype=torch.float32, device=_dev())
+    _lib.check(lib.car_conv3x3(x_nhwc.data_ptr(), n, H, W, K, N, packed.data_ptr(), y.data_ptr(), _stream()), "car_conv3x3")
+    torch.cuda.synchronize()
+    return y
+
+
+def _ref_conv(x_nhwc, w, b, first):
+    """relu(conv2d) in float64 on the CPU, channel-last result; `first`: the scaling layer in front, as car_conv3x3 does for K = 3."""
+    x = x_nhwc.detach().cpu()
+    h = LR.scale_image(x) if first else x.double().permute(0, 3, 1, 2)
+    return F.relu(F.conv2d(h, w.double(), b.double(), stride=1, padding=1)).permute(0, 2, 3, 1).contiguous()
+
+
+def _assert_parity(got, want, what):
+    """|a - b| <= 1e-4 max(1, |b|) elementwise (tests/test_hip_parity.py's rule), the outermost rows and columns on their own."""
+    err = (got.detach().cpu().double() - want).abs() / want.abs().clamp_min(1.0)
+    assert torch.isfinite(err).all(), what
+    edge = torch.zeros(err.shape[1:3], dtype=torch.bool)
+    edge[0, :] = edge[-1, :] = edge[:, 0] = edge[:, -1] = True
+    worst_edge, worst = err[:, edge].max().item(), err.max().item()
+    print(f"{what}: worst |a - b| / max(1, |b|) = {worst:.3e} (outermost rows and columns {worst_edge:.3e}), max |b| = {want.abs().max().item():.3f}")
+    assert worst_edge <= 1e-4, (what, "border", worst_edge)
+    assert worst <= 1e-4, (what, worst)
+    return worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", LAYER_SHAPES, ids=lambda s: f"{s[0]}to{s[1]}at{s[2]}")
+def test_conv3x3_matches_float64_conv2d(lib, shape):
+    K, N, side = shape
+    g = torch.Generator().manual_seed(100 + LAYER_SHAPES.index(shape))
+    w = torch.randn(N, K, 3, 3, generator=g, dtype=torch.float64) * (2.0 / (9 * K)) ** 0.5
+    b = (0.01 * torch.randn(N, generator=g, dtype=torch.float64)).float()
+    if K == 3:
+        x = (torch.rand(2, side, side, 3, generator=g) * 2 - 1).float()
+        s = 5.0 / _ref_conv(x, w, b, True).max().item()               # the image stays in [-1, 1]: the first layer's weights take the scale
+        w = (w * s).float()
+    else:
+        x = torch.randn(2, side, side, K, generator=g).abs()          # rectified, like every input of these layers
+        w = w.float()
+        x = (x * (5.0 / _ref_conv(x, w, b, False).max().item())).float()
+    want = _ref_conv(x, w, b, K == 3)
+    assert 1.0 <= want.abs().max().item() <= 10.0
+    assert (want > 0).double().mean().item() > 0.25
+    _assert_parity(_gpu_conv(lib, x.to(_dev()).contiguous(), w, b), want, f"conv {K} -> {N} at {side} x {side}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", [(50, 70), (16, 16)])
+def test_conv_chain_matches_float64_layer_by_layer(lib, weights, hw):
+    """The 13 layers and 4 pools through the stage entries, each layer fed with the device's own previous map and held against float64
+    conv2d of that same map; the pools must be exact."""
+    from cross_attention_renderer_amd import _lib
+    conv_w, conv_b, _ = weights
+    cur = _to_pm1(LR.make_image(21, 2, *hw)).to(_dev())
+    for l in range(13):
+        if l in LR.POOL_BEFORE:
+            n, H, W, C = cur.shape
+            out = torch.full((n, H // 2, W // 2, C), float("nan"), dtype=torch.float32, device=_dev())
+            _lib.check(lib.car_maxpool2x2(cur.data_ptr(), n, H, W, C, out.data_ptr(), _stream()), "car_maxpool2x2")
+            torch.cuda.synchronize()
+            assert torch.equal(out.cpu(), F.max_pool2d(cur.cpu().permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1)), l
+            cur = out
+        want = _ref_conv(cur, conv_w[l], conv_b[l], l == 0)
+        nxt = _gpu_conv(lib, cur.contiguous(), conv_w[l], conv_b[l])
+        _assert_parity(nxt, want, f"{hw[0]} x {hw[1]} layer {l}")
+        cur = nxt
+    assert cur.shape == (2, hw[0] // 16, hw[1] // 16, 512)
+
+
+def _gpu_head(lib, f0, f1, lin, per_tap=True):
+    """car_lpips_head on lists of five [B, C, h, w] float32 CPU maps."""
+    from cross_attention_renderer_amd import _lib
+    B, H, W = f0[0].shape[0], f0[0].shape[2], f0[0].shape[3]
+    maps = [torch.cat([a, b]).permute(0, 2, 3, 1).contiguous().to(_dev()) for a, b in zip(f0, f1)]
+    table = (ctypes.c_void_p * 5)(*[m.data_ptr() for m in maps])
+    lin_d = torch.cat([w.float() for w in lin]).to(_dev())
+    n = lib.car_lpips_head_scratch_doubles(B, H, W)
+    scratch = torch.empty(n, dtype=torch.float64, device=_dev())
+    out, taps = torch.empty(B, dtype=torch.float64, device=_dev()), torch.empty(B, 5, dtype=torch.float64, device=_dev())
+    _lib.check(lib.car_lpips_head(table, B, H, W, lin_d.data_ptr(), out.data_ptr(), taps.data_ptr() if per_tap else None, scratch.data_ptr(), n,
+                                  _stream()), "car_lpips_head")
+    torch.cuda.synchronize()
+    return out.cpu(), taps.cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", [(256, 256), (50, 70)])
+def test_head_matches_the_float64_head(lib, weights, hw):
+    """<= 1e-9 relative per tap: fp64 arithmetic over at most 512 x 65 536 terms leaves about 1e-12, and 1e-9 separates that from any fp32
+    step inside the kernel.  Bitwise equal across two runs, and between a pair alone and the same pair inside a batch of 5."""
+    conv_w, conv_b, lin = weights
+    x, y = (_to_pm1(t) for t in _pair("noisy", 5, *hw, 31))
+    f0 = [t.float() for t in LR.taps(x, conv_w, conv_b)]
+    f1 = [t.float() for t in LR.taps(y, conv_w, conv_b)]
+    want, want_taps = LR.head(f0, f1, lin)
+    got, got_taps = _gpu_head(lib, f0, f1, lin)
+    rel = ((got_taps - want_taps).abs() / want_taps.abs()).max().item()
+    print(f"head {hw}: worst relative error per tap {rel:.3e}")
+    assert (want_taps > 0).all() and rel <= 1e-9
+    assert ((got - want).abs() / want).max().item() <= 1e-9
+    again, again_taps = _gpu_head(lib, f0, f1, lin)
+    assert torch.equal(got, again) and torch.equal(got_taps, again_taps)
+    for i in (0, 3):
+        one, one_taps = _gpu_head(lib, [t[i:i + 1] for t in f0], [t[i:i + 1] for t in f1], lin)
+        assert torch.equal(one[0], got[i]) and torch.equal(one_taps[0], got_taps[i]), i
+    assert torch.equal(_gpu_head(lib, f0, f1, lin, per_tap=False)[0], got)
+
+
+@pytest.fixture(scope="module")
+def dev_weights(weights):
+    from cross_attention_renderer_amd import harness
+    return harness.LpipsWeights(*weights)
+
+
+def _rel(a, b):
+    return ((a - b).abs() / b.abs()).max().item()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", E2E_SHAPES, ids=lambda s: f"B{s[0]}_{s[1]}x{s[2]}")
+def test_lpips_matches_the_restatement(weights, dev_weights, shape, kind):
+    """Bound: 1e-4 relative on the total and on each tap, and at most four times the deviation of the restatement itself run in float32
+    on the CPU from its float64 run on the same inputs (split fp16 x 3 keeps 22 bits to fp32's 24).  Should CPU float32 itself miss 1e-4
+    on the near-identical case, that case alone is bound by four times the CPU-float32 figure instead."""
+    from cross_attention_renderer_amd import harness
+    b, h, w, seed = shape
+    img, ref = _pair(kind, b, h, w, seed)
+    x, y = _to_pm1(img), _to_pm1(ref)
+    want, want_taps = LR.lpips(x, y, *weights)
+    cpu32, cpu32_taps = LR.lpips(x, y, *weights, dtype=torch.float32)
+    dev32 = max(_rel(cpu32.double(), want), _rel(cpu32_taps.double(), want_taps))
+    got, got_taps = harness.lpips(img.to(_dev()), ref.to(_dev()), dev_weights, return_taps=True)
+    assert got.shape == (b,) and got.dtype == torch.float64 and got_taps.shape == (b, 5)
+    dev_hip = max(_rel(got.cpu(), want), _rel(got_taps.cpu(), want_taps))
+    print(f"lpips {kind} B={b} {h}x{w}: value {want[0].item():.6e}, HIP vs float64 {dev_hip:.3e}, CPU float32 vs float64 {dev32:.3e}")
+    assert (want > 0).all()
+    bound = min(1e-4, 4 * dev32)
+    if kind == "near" and dev32 > 1e-4:
+        bound = 4 * dev32                                              # CPU float32 itself misses 1e-4 here: four times its figure binds alone
+    assert dev_hip <= bound, (kind, shape, dev_hip, dev32)
+
+
+@pytest.mark.gpu
+def test_lpips_of_identical_images_is_exactly_zero_and_batch_independent(dev_weights):
+    from cross_attention_renderer_amd import harness
+    w = dev_weights
+    for b, h, wd, seed in E2E_SHAPES:
+        img = LR.make_image(seed, b, h, wd).to(_dev())
+        got, taps = harness.lpips(img, img.clone(), w, return_taps=True)
+        assert (got == 0.0).all() and (taps == 0.0).all(), (b, h, wd, got)
+    img, ref = (t.to(_dev()) for t in _pair("noisy", 3, 50, 70, 41))
+    a, c = harness.lpips(img, ref, w), harness.lpips(img, ref, w)
+    assert torch.equal(a, c)
+    for i in range(3):
+        one = harness.lpips(img[i], ref[i], w)
+        assert one.shape == () and torch.equal(one, a[i]), i
+    # a pair against itself at another place in the batch: image i of x equals image i of y, whatever surrounds it
+    mixed = torch.stack([ref[0], img[1], ref[2]])
+    assert harness.lpips(img, mixed, w)[1].item() == 0.0
+    for bad in (torch.rand(15, 16, 3, device=_dev()), torch.rand(0, 16, 16, 3, device=_dev())):
+        with pytest.raises(ValueError):
+            harness.lpips(bad, bad, w)
+
+
+@pytest.mark.gpu
+def test_eval_script_reports_lpips_with_the_reference_protocol(weights, tmp_path):
+    """One synthetic frame through eval_realestate10k.py --lpips_weights <seeded files>: the script's `mean lpips` is harness.lpips of the
+    same mask-blended images, and the restatement's value for them, to the end-to-end bound.  Both file layouts; without the option
+    nothing about LPIPS is printed."""
+    from cross_attention_renderer_amd import harness
+    sys.path.insert(0, os.path.join(ROOT, "experiment_scripts"))
+    import common
+    vgg, lin = LR.state_dicts(*weights, "split")
+    single, _ = LR.state_dicts(*weights, "single")
+    torch.save(vgg, tmp_path / "vgg16.pth")
+    torch.save(lin, tmp_path / "lin.pth")
+    torch.save(single, tmp_path / "lpips.pth")
+    H = 64
+    base = [sys.executable, os.path.join(ROOT, "experiment_scripts", "eval_realestate10k.py"), "--experiment_name", "t", "--views", "2", "--synthetic",
+            "--img_sidelength", str(H), "--out_dir", str(tmp_path), "--logging_root", str(tmp_path), "--batch_size", "1"]
+    plain = subprocess.run(base, capture_output=True, text=True, timeout=600)
+    assert plain.returncode == 0 and "lpips" not in plain.stdout.lower(), plain.stdout + plain.stderr
+    outs = []
+    for files in ([str(tmp_path / "vgg16.pth"), str(tmp_path / "lin.pth")], [str(tmp_path / "lpips.pth")]):
+        out = subprocess.run(base + ["--lpips_weights", *files], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout + out.stderr
+        assert out.stdout.replace("item 0 lpips", "").count("lpips") == 1 and "mean ssim" in out.stdout, out.stdout
+        outs.append(float(out.stdout.split("mean lpips")[1].split()[0]))
+        assert len(out.stdout.splitlines()) == len(plain.stdout.splitlines()) + 2
+    assert outs[0] == outs[1]
+    # the script's images: the chunked render and the un-chunked render of the same frame, both blended over 0.5 grey with the valid mask
+    opt = common.add_precision(common.parser("t")).parse_args(base[2:])
+    dev = _dev()
+    model = common.build_model(opt, dev, with_encoder=None)
+    inp, z = harness.synthetic_pair(H, 2, seed=5)
+    inp, z = harness.to_device(inp, dev, opt.cameras), [t.to(dev) for t in z]
+    tile = harness.render_frame(model, inp, z, chunk_rays=-(-H * H // 9))
+    valid = tile[0, :, 4:5]
+
+    def composite(img):
+        return ((img + 1) * 0.5) * valid + 0.5 * (1 - valid)
+    rgb = composite(tile[0, :, :3]).reshape(H, H, 3)
+    target = composite(harness.render_frame(model, inp, z, chunk_rays=16384)[0, :, :3]).reshape(H, H, 3)
+    hw = harness.LpipsWeights(*weights)
+
+    def bound_for(x, y, want):
+        """The end-to-end bound of test_lpips_matches_the_restatement for one pair, with its rule for a near-identical pair."""
+        dev32 = abs(LR.lpips(x, y, *weights, dtype=torch.float32)[0].item() - want) / want
+        return dev32, (4 * dev32 if dev32 > 1e-4 else min(1e-4, 4 * dev32))
+    # the script's own pair: chunk invariance makes the two renders identical or nearly so (the near-identical case by construction)
+    mine = harness.lpips(rgb, target, hw).item()
+    x, y = _to_pm1(rgb.cpu()[None]), _to_pm1(target.cpu()[None])
+    want = LR.lpips(x, y, *weights)[0].item()
+    print(f"script's pair: mean lpips {outs[0]:.6e}, harness.lpips {mine:.6e}, restatement {want:.6e}")
+    if want == 0.0:
+        assert mine == 0.0 and outs[0] == 0.0
+    else:
+        dev32, bound = bound_for(x, y, want)
+        print(f"script's pair: CPU float32 vs float64 {dev32:.3e}")
+        assert abs(mine - want) / want <= bound and abs(outs[0] - want) / want <= bound, (outs[0], mine, want, dev32)
+    # the protocol on a pair that differs: the same frame against a perturbed copy, blended the same way
+    g = torch.Generator().manual_seed(7)
+    other = composite((tile[0, :, :3] + 0.1 * torch.randn(H * H, 3, generator=g).to(dev)).clamp(-1, 1)).reshape(H, H, 3)
+    got = harness.lpips(rgb, other, hw).item()
+    x, y = _to_pm1(rgb.cpu()[None]), _to_pm1(other.cpu()[None])
+    want = LR.lpips(x, y, *weights)[0].item()
+    dev32, bound = bound_for(x, y, want)
+    print(f"rendered frame: lpips {want:.6e}, HIP vs float64 {abs(got - want) / want:.3e}, CPU float32 vs float64 {dev32:.3e}")
+    assert want > 0 and valid.mean().item() > 0.1
+    assert abs(got - want) / want <= min(1e-4, 4 * dev32), (got, want, dev32)
