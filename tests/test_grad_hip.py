@@ -351,3 +351,76 @@ def test_model_call_in_train_mode_carries_gradients_and_channel_last_levels_are_
     with torch.no_grad():
         assert not m(inp, z=z_cl)["rgb"].requires_grad               # no_grad: the inference engine
     assert not m.eval()(inp, z=z_cl)["rgb"].requires_grad            # eval(): the inference engine (its forward never builds a graph)
+
+
+def test_two_backward_passes_accumulate_and_an_optimizer_step_follows():
+    """The parameter gradients of one backward are views of one flat buffer (training.py).  Two backward passes without zero_grad
+    (different cotangents) must leave the SUM of the two gradients taken separately in every p.grad, torch.optim.SGD must then move every
+    parameter by exactly -lr * p.grad, and a parameter whose grad was set to None must get the third gradient alone."""
+    from cross_attention_renderer_amd import synthetic as S
+    from cross_attention_renderer_amd.models import CrossAttentionRenderer
+    from cross_attention_renderer_amd.training import render_train
+    dev = torch.device("cuda:0")
+    H, P, R = 64, 16, 96
+    torch.manual_seed(0)
+    m = CrossAttentionRenderer(model="midas_vit", n_view=2, npoints=P, with_encoder=False).train()
+    S.perturb_parameters(m, seed=2)
+    m.H = m.W = H
+    m = m.to(dev)
+    inp = to_device(S.stereo_scene(H, b=2, uv=S.pixel_grid(H, H)[::43][:R].contiguous(), seed=6), dev, cameras_on_host=True)
+    base = [t.to(dev) for t in S.feature_maps(2, 2, H, seed=1)]
+    g = torch.Generator().manual_seed(1)
+    cots = [(torch.randn(2, 1, R, 3, generator=g).to(dev), torch.randn(2, R, 1, generator=g).to(dev)) for _ in range(3)]
+
+    def backward(i):
+        out = render_train(m, inp, z=[t.clone().requires_grad_(True) for t in base])
+        c_rgb, c_depth = cots[i]
+        ((out["rgb"] * c_rgb).sum() + (out["depth_ray"] * c_depth.reshape(out["depth_ray"].shape)).sum()).backward()
+    named = {k: p for k, p in m.named_parameters()}
+    separate = []
+    for i in range(3):                                                              # the three gradients, each taken alone and copied out
+        m.zero_grad(set_to_none=True)
+        backward(i)
+        separate.append({k: p.grad.clone() for k, p in named.items() if p.grad is not None})
+    assert len(separate[0]) == 42 and separate[0].keys() == separate[1].keys() == separate[2].keys()
+    m.zero_grad(set_to_none=True)
+    backward(0)
+    backward(1)                                                                     # no zero_grad in between
+    torch.cuda.synchronize()
+    worst = 0.0
+    for k, ga in separate[0].items():
+        want = ga.double().cpu() + separate[1][k].double().cpu()                  # summed on the host
+        got = named[k].grad.double().cpu()
+        scale = want.abs().max().item()
+        dev_k = (got - want).abs().max().item() / max(scale, 1e-30)
+        worst = max(worst, dev_k)
+        assert dev_k <= 4e-6, (k, dev_k)                                            # 2e-6 per run compared: the order of the fp32 atomics
+    print(f"two backward passes: worst deviation {worst:.2e} of a tensor's largest entry")
+    # one plain SGD step: p0 - lr * g with the measured g, to one fp32 rounding
+    lr = 0.125                                                                      # a power of two: lr * g is exact, the step one rounding
+    p0 = {k: p.detach().clone() for k, p in named.items()}
+    g_meas = {k: named[k].grad.detach().clone() for k in separate[0]}
+    torch.optim.SGD(m.parameters(), lr=lr).step()
+    torch.cuda.synchronize()
+    for k, p in named.items():
+        if k in g_meas:
+            want = (p0[k].double() - lr * g_meas[k].double()).float()
+            assert torch.equal(p.detach(), want), k
+            assert torch.equal(named[k].grad, g_meas[k]), k                      # the step left the gradients (and their neighbours in the buffer) alone
+        else:
+            assert torch.equal(p.detach(), p0[k]), k
+    # p.grad = None on one parameter, then a third backward: that parameter holds the third gradient alone, the others all three
+    with torch.no_grad():
+        for k, p in named.items():
+            p.copy_(p0[k])                                                          # back to the parameters the separate gradients belong to
+    lone = "key_map.weight"
+    assert lone in g_meas
+    named[lone].grad = None
+    backward(2)
+    torch.cuda.synchronize()
+    big = lambda t: max(t.abs().max().item(), 1e-30)
+    assert (named[lone].grad - separate[2][lone]).abs().max().item() <= 2e-6 * big(separate[2][lone])
+    for k in g_meas:
+        if k != lone:                                                               # what was there plus one more run's gradient
+            dev_k = (named[k].grad.double() - (g_meas[k].double() + separate[2][k].double())).abs().max().item()
+            assert dev_k <= 2e-6 * (big(g_meas[k]) + big(separate[2][k])), k
