@@ -1,4 +1,4 @@
-// car_common.h — error plumbing shared by the translation units of libcar_hip.so.
+// car_common.h — error plumbing and the library-internal prototypes shared by the translation units of libcar_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -36,3 +36,29 @@ void car_set_error(const char* fmt, ...);
 #endif
 
 static inline unsigned car_div_up(long a, long b) { return (unsigned)((a + b - 1) / b); }
+
+// a C++ function that one unit defines for another: kept out of the library's dynamic symbols
+#define CAR_INTERNAL __attribute__((visibility("hidden")))
+
+#define CAR_TRY(call)                 \
+    do {                              \
+        const int rc_ = (call);       \
+        if (rc_ != CAR_OK) return rc_; \
+    } while (0)
+
+// ---- library-internal functions that one unit defines and another calls.  Declared here and nowhere else: the defining and the calling
+// unit both include this header, so a parameter list that drifts on one side is a compile error, not a call that links and runs. ----
+// car_fused.hip: the fp16 instance of the fused per-sample kernel and its compact blob's size.  Reached through car_render_forward_f16;
+// exported (C linkage) for tools/bench_fused.py, not part of include/car_hip.h.  Arguments as car_fused_samples_parts.
+extern "C" size_t car_fused_blob16_floats(void);
+extern "C" int car_fused_samples_f16(const float* poses, const float* rays, const float* steps, const float* lattice, int lat_h, int lat_w,
+                                     int lat_pad, const float* gmeta, const float* wpt, const float* blob16, const float* bias, int b, int V, int R,
+                                     int P, int H, int W, int no_sample, float* e, float* g, float* logit, float* pt, float* pixel_val,
+                                     float* part, void* stream);
+// car_pack.hip: car_fused_pack with the compact (hi halves only) blob of the fp16 precision; same bias table and point table
+CAR_INTERNAL int car_fused_pack_hi(const car_weights* w, float* blob16, float* bias, float* wpt, void* stream);
+// car_lattice.hip: the common lattice of a pyramid's levels (only n_levels, level_h, level_w of d are read), and the merge onto it
+struct car_lattice { int h, w, pad, r[CAR_MAX_LEVELS]; bool ok; };
+CAR_INTERNAL car_lattice car_lattice_of(const car_dims& d);
+CAR_INTERNAL int car_launch_merge(const float* const* levels, const int* hs, const int* ws, const int* rs, int n_levels, int lh, int lw, int pad, int n_maps,
+                                  float* lattice, unsigned* gmax, hipStream_t st, const char* who);

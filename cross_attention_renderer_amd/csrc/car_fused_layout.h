@@ -1,5 +1,5 @@
 // car_fused_layout.h — sizes and the packed-weight layout of the fused per-sample kernel, shared by the kernel (car_fused.hip via
-// car_fused_mma.h) and by the host code that packs the weights (car_render.hip).  Plain constants only.
+// car_fused_mma.h) and by the host code that packs the weights (car_pack.hip) and lays out the plan (car_render.hip).  Plain constants only.
 #pragma once
 
 constexpr int kC = 576;            // feature channels = width of h

@@ -8,7 +8,8 @@ Two routes:
   * the reference's default configuration (n_view = 2, three pyramid levels, 576 channels; epipolar sampling or ``no_sample``'s depth
     sampling, with or without the second attention round) goes through the
     ONE-CALL C ABI — ``car_plan_build`` once per set of weights, ``car_project_maps`` once per stereo pair,
-    ``car_render_forward`` per batch of rays (csrc/car_render.hip: weight packing and the launch sequence are C++).  This
+    ``car_render_forward`` per batch of rays (csrc/car_render.hip over csrc/car_pack.hip and csrc/car_lattice.hip: weight packing, the
+    lattice merge and the launch sequence are C++).  This
     module only sizes the calls: rays (and, if need be, scenes) are chunked so that the per-call workspace fits the free device
     memory (rays and scenes are independent, so this changes nothing);
   * the other constructor variants (n_view 1 / 3, no_latent_concat, other widths) are sequenced here stage by stage
@@ -537,12 +538,17 @@ class RenderEngine:
         hm, wm = max(h for h, _ in sizes), max(w for _, w in sizes)
         return all(hm % h == 0 and wm % w == 0 and hm // h == wm // w for h, w in sizes)
 
+    def _lattice_shape(self, d) -> tuple:
+        """(lat_h, lat_w, lat_pad) of the common lattice of d's pyramid (car_lattice_shape)."""
+        lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(self.lib.car_lattice_shape(ctypes.byref(d), ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad)), "car_lattice_shape")
+        return lh.value, lw.value, lpad.value
+
     def _lattice_fits(self, b: int, R: int, z: List[Tensor]) -> bool:
         """car_fused_samples addresses the lattice of one (view, padding mode) with 32-bit byte offsets below 2 GiB (a finest level
         up to ~470 pixels wide at 576 channels); wider pyramids take the stage route, which has no such limit."""
-        lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(self.lib.car_lattice_shape(ctypes.byref(self._dims(b, R, z)), ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad)), "car_lattice_shape")
-        return lh.value * lw.value * 576 * 4 < 2**31
+        lh, lw, _ = self._lattice_shape(self._dims(b, R, z))
+        return lh * lw * 576 * 4 < 2**31
 
     def _free_budget(self, device) -> int:
         """85 % of what this engine could allocate now: free device memory, the caching allocator's idle blocks, and its own workspace
@@ -584,9 +590,8 @@ class RenderEngine:
         plan = self._plan_for(d_all, dev)
         f16 = self.render_precision == "fp16"
         plan16 = self._plan16_for(d_all, dev) if f16 else None
-        lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(lib.car_lattice_shape(ctypes.byref(d_all), ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad)), "car_lattice_shape")
-        lattice_scene = V * 2 * lh.value * lw.value * 576                                        # floats per scene
+        lh, lw, _ = self._lattice_shape(d_all)
+        lattice_scene = V * 2 * lh * lw * 576                                                    # floats per scene
 
         phases = 1 | 2 | (0 if self.first_round_parts else 4)
 
@@ -677,10 +682,7 @@ class RenderEngine:
                     if f16:
                         _lib.check(lib.car_render_forward_f16(ctypes.byref(d), _ptr(plan), _ptr(plan16), ctypes.byref(ci), ctypes.byref(co),
                                                               _ptr(work), work.numel() * 4, phases, st), "car_render_forward_f16")
-                    elif phases == 3:
-                        _lib.check(lib.car_render_forward(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co),
-                                                          _ptr(work), work.numel() * 4, st), "car_render_forward")
-                    else:
+                    else:                                       # phases == 3 is car_render_forward's own call
                         _lib.check(lib.car_render_forward_phase(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co),
                                                                 _ptr(work), work.numel() * 4, phases, st), "car_render_forward_phase")
                     if not whole:

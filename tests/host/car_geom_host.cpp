@@ -36,7 +36,7 @@ void host_bilinear_taps(const float* grid, int n, int W, int H, int mode, int* i
     for (int i = 0; i < n; ++i) car_bilinear_taps(grid[2 * i], grid[2 * i + 1], W, H, mode, idx + 4 * i, w + 4 * i);
 }
 
-// the merged lattice as car_project_maps' merge kernel builds it (csrc/car_render.hip merge_kernel): levels [n][h][w][C], r = how
+// the merged lattice as car_project_maps' merge kernel builds it (csrc/car_lattice.hip merge_kernel): levels [n][h][w][C], r = how
 // many times coarser than the widest level; lat [2 modes][lh][lw][C]
 void host_lattice_build(const float* const* g, const int* h, const int* w, const int* r, int n_levels, int C, int lh, int lw, int pad, float* lat) {
     for (int mode = 0; mode < 2; ++mode)

@@ -1,5 +1,5 @@
 """Reference (pure torch, CPU) statement of the operand packing the device packers ``car_fused_pack`` / ``car_round2_pack``
-(csrc/car_render.hip) must produce for csrc/car_fused.hip and csrc/car_round2.hip.  Test infrastructure: the product packs on the
+(csrc/car_pack.hip) must produce for csrc/car_fused.hip and csrc/car_round2.hip.  Test infrastructure: the product packs on the
 device; tests/test_fused_pack.py checks (on the CPU) that this layout reproduces the layers when walked the way the MFMA
 contracts it, and (on the GPU) that the device packers emit exactly these bytes."""
 from __future__ import annotations
@@ -60,7 +60,7 @@ LAYERS = ("W2", "Q1", "M", "K1")
 
 def bilinear_fold(wa: Tensor, ba: Tensor, wb: Tensor, bb: Tensor):
     """<Wa r + ba, Wb x + bb> = r^T (M x + v) + u^T x + c: M = Wa^T Wb, v = Wa^T bb, u = Wb^T ba, c = <ba, bb>, accumulated in fp64 in
-    ascending k exactly as bilinear_fold_kernel (csrc/car_render.hip) does, rounded once to fp32."""
+    ascending k exactly as bilinear_fold_kernel (csrc/car_pack.hip) does, rounded once to fp32."""
     wa, wb, ba, bb = wa.double(), wb.double(), ba.double(), bb.double()
     D = wa.shape[0]
     M = torch.zeros(D, D, dtype=torch.float64)

@@ -2,7 +2,7 @@
 
 CPU: evaluating a layer exactly the way the MFMA contracts the packed tiles (K step, tile, lane group, element) must reproduce
 W x for the standard, bias-folded and chained K mappings (tests/pack_reference.py is the layout's reference statement).
-GPU: the device packers of the C ABI (car_fused_pack / car_round2_pack, csrc/car_render.hip) must emit exactly those bytes."""
+GPU: the device packers of the C ABI (car_fused_pack / car_round2_pack, csrc/car_pack.hip) must emit exactly those bytes."""
 import ctypes
 
 import pytest
@@ -211,3 +211,63 @@ def test_device_packers_emit_the_reference_bytes(scale):
     torch.cuda.synchronize()
     assert torch.equal(dqw.cpu().view(torch.int32), r2qw.view(torch.int32))
     assert torch.equal(dqb.cpu(), r2qb)
+    # the fp16 precision's plan (car_plan_f16_build): compact blob | bias table | point table, each rounded up to 64 floats; the compact blob
+    # holds exactly the hi halves of car_fused_pack's tiles, in the same order (508 tiles, every one written).  The offsets restate
+    # car_render.hip's plan16_layout by hand (as tools/bench_fused.py does); the size query below checks the restatement
+    up64 = lambda n: (n + 63) & ~63
+    dims = _lib.CarDims()
+    dims.b, dims.V, dims.R, dims.P, dims.H, dims.W, dims.n_levels, dims.repeat_attention = 1, 2, 64, 8, 64, 64, 3, 1
+    for l, (c, h) in enumerate(((256, 16), (256, 32), (64, 64))):
+        dims.level_c[l], dims.level_h[l], dims.level_w[l] = c, h, h
+    n16 = lib.car_plan_f16_bytes(ctypes.byref(dims)) // 4
+    o_bias = up64(508 * 256)
+    o_wpt = o_bias + up64(bias.numel())
+    assert n16 == o_wpt + up64(576 * 4), lib.car_last_error()
+    p16 = torch.zeros(n16, device=dev)
+    rc = lib.car_plan_f16_build(ctypes.byref(dims), ctypes.byref(w), p16.data_ptr(), st)
+    assert rc == 0, lib.car_last_error()
+    torch.cuda.synchronize()
+    p16 = p16.cpu()
+    hi16 = p16[:508 * 256].view(torch.int16).view(508, 512)
+    assert torch.equal(hi16, dblob.cpu().view(torch.int16).view(508, 2, 512)[:, 0])
+    assert torch.equal(p16[o_bias:o_bias + bias.numel()].view(torch.int32), dbias.cpu().view(torch.int32))
+    assert torch.equal(p16[o_wpt:o_wpt + 576 * 4].view(torch.int32), dwpt.cpu().view(torch.int32))
+    # car_fused_pack_rows (the first two point-MLP layers alone) into zeroed buffers: W2's 324 tiles, the point table, b2 and the scale slots
+    # 0 (2^-shift of W2), 5 (the point / bias bound), 8 (2^shift of W2) as car_fused_pack leaves them; everything else it owns stays zero
+    rblob, rbias, rwpt = torch.zeros_like(dblob), torch.zeros_like(dbias), torch.zeros_like(dwpt)
+    rc = lib.car_fused_pack_rows(w.query_encode_latent_w, w.query_encode_latent_b, w.query_encode_latent_2_w, w.query_encode_latent_2_b,
+                                 rblob.data_ptr(), rbias.data_ptr(), rwpt.data_ptr(), st)
+    assert rc == 0, lib.car_last_error()
+    torch.cuda.synchronize()
+    want_blob = torch.zeros_like(blob).view(torch.int32)
+    want_blob[:324 * 512] = dblob.cpu().view(torch.int32)[:324 * 512]
+    assert torch.equal(rblob.cpu().view(torch.int32), want_blob)
+    assert torch.equal(rwpt.cpu().view(torch.int32), dwpt.cpu().view(torch.int32))
+    want_bias = torch.zeros_like(bias).view(torch.int32)
+    for lo, hi in ((0, 288), (672 + 0, 672 + 1), (672 + 5, 672 + 6), (672 + 8, 672 + 9)):
+        want_bias[lo:hi] = dbias.cpu().view(torch.int32)[lo:hi]
+    assert torch.equal(rbias.cpu().view(torch.int32), want_bias)
+    # car_kq_pack (the stage route's key / query chain): K2 (32 tiles) | Q1 (8) | Q2 (32) in the fused kernel's operand formats, K2 and Q2
+    # chained over the accumulator order of the layer before, Q1 standard with its bias folded in at k = 16;
+    # bias = bk2 | bq2 | 2^-shift of K2, Q1, Q2 (slots 0..2) and their 2^shift (slots 8..10, the packer's scratch), zeros between
+    f = lambda t: t.detach().float().cpu().reshape(t.shape[0], -1)
+    v = lambda t: t.detach().float().cpu()
+    k2, q1, q2 = f(m.key_map_2.weight), f(m.query_embed.weight), f(m.query_embed_2.weight)
+    pk2 = PR.pow2_scale(k2.abs().max().item())
+    pq1 = PR.pow2_scale(max(q1.abs().max().item(), v(m.query_embed.bias).abs().max().item()))
+    pq2 = PR.pow2_scale(q2.abs().max().item())
+    tail = torch.cat([PR.pack_tiles16(k2, None, 8, PR.chained16_k(4), pk2).reshape(-1),
+                      PR.pack_tiles16(q1, v(m.query_embed.bias), 8, PR.std16_k(1), pq1).reshape(-1),
+                      PR.pack_tiles16(q2, None, 8, PR.chained16_k(4), pq2).reshape(-1)])
+    scales = torch.zeros(16)
+    scales[0:3] = torch.tensor([1.0 / pk2, 1.0 / pq1, 1.0 / pq2])
+    scales[8:11] = torch.tensor([pk2, pq1, pq2])
+    kqb = torch.cat([v(m.key_map_2.bias), v(m.query_embed_2.bias), scales])
+    assert tail.numel() == lib.car_kq_tail_floats() and kqb.numel() == lib.car_kq_bias_floats()
+    dtail, dkqb = torch.empty_like(tail, device=dev), torch.empty_like(kqb, device=dev)
+    rc = lib.car_kq_pack(w.key_map_2_w, w.key_map_2_b, w.query_embed_w, w.query_embed_b, w.query_embed_2_w, w.query_embed_2_b,
+                         dtail.data_ptr(), dkqb.data_ptr(), st)
+    assert rc == 0, lib.car_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(dtail.cpu().view(torch.int32), tail.view(torch.int32))
+    assert torch.equal(dkqb.cpu().view(torch.int32), kqb.view(torch.int32))

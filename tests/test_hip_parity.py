@@ -812,7 +812,7 @@ def test_forward_on_device_made_poses(name):
 @pytest.mark.parametrize("sizes", [((8, 8), (16, 16), (32, 32)), ((6, 10), (24, 40)), ((16, 16),), ((4, 4), (8, 8), (16, 16), (32, 32)),
                                    ((64, 64), (128, 128), (256, 256)), ((4, 840),), ((2, 420), (4, 840))])
 def test_merged_lattice_kernel_matches_grid_sample(sizes):
-    """car_merge_lattice (csrc/car_render.hip merge_kernel: one 16-lane group per node writes both padding modes, zero-weight taps are
+    """car_merge_lattice (csrc/car_lattice.hip merge_kernel: one 16-lane group per node writes both padding modes, zero-weight taps are
     out-of-range buffer loads, the taps come from per-axis tables a workgroup keeps in LDS) against torch's grid_sample of every level at
     the lattice nodes, summed: border and zeros padding, interior, ring and corner nodes, several maps; the bench's pyramid; and lattices too
     wide for the tables (840-texel rows: the kernel's table-free form)."""

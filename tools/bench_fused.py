@@ -27,7 +27,7 @@ def _up64(n):
 
 def main():
     lib = _lib.load()
-    f16 = lib.car_fused_samples_f16                     # the engine reaches it through car_render_forward_f16 only: bound here
+    f16 = lib.car_fused_samples_f16                     # the engine reaches it through car_render_forward_f16 only: bound here (declared in csrc/car_common.h)
     f16.restype = ctypes.c_int
     f16.argtypes = _lib.SIGNATURES["car_fused_samples_parts"][1]
     lib.car_fused_blob16_floats.restype = ctypes.c_size_t
@@ -71,7 +71,7 @@ def main():
     wpt = torch.empty(576 * 4, device=dev)
     st = P_(torch.cuda.current_stream().cuda_stream)
     _lib.check(lib.car_fused_pack(ctypes.byref(w), blob.data_ptr(), bias.data_ptr(), wpt.data_ptr(), st), "car_fused_pack")
-    # the fp16 precision's plan (car_plan_f16_build): compact blob | bias table | point table, each rounded up to 64 floats (car_render.hip)
+    # the fp16 precision's plan (car_plan_f16_build): compact blob | bias table | point table, each rounded up to 64 floats (car_render.hip plan16_layout)
     plan16 = eng._plan16_for(d, dev)
     o_bias16 = _up64(lib.car_fused_blob16_floats())
     o_wpt16 = o_bias16 + _up64(lib.car_fused_bias_floats())
