@@ -142,6 +142,17 @@ SIGNATURES = {
     "car_maxpool2x2": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "car_lpips_head_scratch_doubles": (c_size_t, [c_int, c_int, c_int]),
     "car_lpips_head": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "car_lpips_backward_packed_floats": (c_size_t, []),
+    "car_lpips_pack_backward": (c_int, [_P, _P, _P]),
+    "car_lpips_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_lpips_train_layer_offset": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "car_lpips_forward_train": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "car_lpips_backward": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "car_conv3x3_backward_packed_floats": (c_size_t, [c_int, c_int]),
+    "car_conv3x3_backward_pack": (c_int, [_P, c_int, c_int, _P, _P]),
+    "car_conv3x3_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "car_maxpool2x2_backward": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_lpips_head_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

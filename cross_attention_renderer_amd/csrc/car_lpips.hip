@@ -1,4 +1,6 @@
-// car_lpips.hip — LPIPS v0.1, net = 'vgg' (include/car_hip.h: car_conv3x3, car_maxpool2x2, car_lpips_head, car_lpips).
+// car_lpips.hip — LPIPS v0.1, net = 'vgg' (include/car_hip.h: car_conv3x3, car_maxpool2x2, car_lpips_head, car_lpips),
+// and its gradient with respect to the images for the training loss (car_lpips_forward_train, car_lpips_backward and their stages: the
+// second half of this file).
 //
 // The metric is a fixed network: a per-channel scaling of the [-1, 1] image, the 13 3x3 convolutions of VGG16's `features` (ReLU behind
 // each, 2x2 max-pool in front of blocks 2-5), and at the five taps relu1_2 .. relu5_3 the channel-normalised squared difference of the two
@@ -46,14 +48,32 @@ constexpr long kMaxPixels = 1L << 27;              // 2 B H W: keeps every row c
 struct ConvArgs {
     const float* X;                        // [n, H, W, K]
     const float* Wp; int tiles_total;      // [K step][tiles_total][512]: k = tap * K + channel
-    const float* bias;                     // N floats
+    const float* bias;                     // N floats (forward only)
     const float* down;                     // 2^-shift of the packed layer
     float* Y;                              // [n, H, W, N]
+    const float* act;                      // data gradient only: [n, H, W, N] forward activation whose sign masks Y, or nullptr
+    const float* add;                      // data gradient only: [n, H, W, N] added in front of the mask, or nullptr
     int H, W, K, N, lgk, chunks;           // lgk = log2(K / 32)
     long M;                                // n H W output pixels
 };
 
-template <int NT>
+// pow2_scale with the exponent clamped far lower: a gradient row's largest magnitude is 1e-5 .. 1e-8 per unit of cotangent, and the
+// row's power of two has to follow it down so that a cotangent scaled by a power of two scales every result exactly.  p in [2^-90, 2^100]:
+// p and the weights' 2^shift are never multiplied into one float here (the data gradient undoes them in two steps).
+// When a later K step raises the row's maximum, the accumulators move by pn * pinv, a power of two as small as 2^-190: what was summed so
+// far may then lose low bits or flush to 0.  It is below 2^-150 of the row's new scale, so the accuracy bound is untouched, but "a
+// cotangent scaled by 2^k scales every entry exactly" holds only while no row's magnitude crosses the clamp span inside one sweep.
+__device__ __forceinline__ void pow2_scale_wide(float m, float& p, float& inv) {
+    int e = (int)((__float_as_uint(m) >> 23) & 0xffu);
+    e = e < 40 ? 40 : (e > 230 ? 230 : e);
+    p = __uint_as_float((unsigned)(267 - e) << 23);
+    inv = __uint_as_float((unsigned)(e - 13) << 23);
+}
+
+// BWD: the data gradient of the same convolution.  The same sweep over weights packed transposed and flipped
+// (conv_pack_kernel), no bias, a row's power of two from pow2_scale_wide, and the epilogue Y = (sum + add) * (act > 0) in the place of
+// bias + ReLU.  The forward instance's arithmetic is untouched by the parameter.
+template <int NT, bool BWD>
 __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];      // [2][NT][512]
     static_assert(kWaves * pieces_of(NT) <= 3 * 2 * NT, "stream_issue_piece wraps a piece index into the chunk with two subtractions");
@@ -126,10 +146,13 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         finish_x(0, raw, xc);
     }
     float mrun = fmaxf(row_max(xc), 1e-30f), p, pinv;
-    pow2_scale(mrun, p, pinv);
+    if constexpr (BWD) pow2_scale_wide(mrun, p, pinv); else pow2_scale(mrun, p, pinv);
 
     f32x4 acc[NT];
-    init_bias<NT>(acc, a.bias + 16 * tile0, q4, p / dW);
+    if constexpr (BWD) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    } else init_bias<NT>(acc, a.bias + 16 * tile0, q4, p / dW);
     half8 bhi, blo;
     split8(xc, p, bhi, blo);
     stream_sync();                                                     // weight chunk 0 landed
@@ -156,7 +179,7 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         if (__builtin_amdgcn_ballot_w64(mn > mrun) != 0) {
             float pn, pninv;
             mrun = fmaxf(mrun, mn);
-            pow2_scale(mrun, pn, pninv);
+            if constexpr (BWD) pow2_scale_wide(mrun, pn, pninv); else pow2_scale(mrun, pn, pninv);
             scale_acc<NT>(acc, pn * pinv);
             p = pn; pinv = pninv;
         }
@@ -164,32 +187,53 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         stream_sync();
     }
     if (row >= a.M) return;
-    scale_acc<NT>(acc, dW * pinv);
     float* yrow = a.Y + row * a.N + 16 * tile0 + 4 * q4;
+    if constexpr (BWD) {
+        scale_acc<NT>(acc, dW);                                        // two steps: dW * pinv may lie below fp32's normal range
+        scale_acc<NT>(acc, pinv);
+        const long at = row * a.N + 16 * tile0 + 4 * q4;
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
-        *reinterpret_cast<float4*>(yrow + 16 * t) =
-            make_float4(fmaxf(acc[t][0], 0.0f), fmaxf(acc[t][1], 0.0f), fmaxf(acc[t][2], 0.0f), fmaxf(acc[t][3], 0.0f));
+        for (int t = 0; t < NT; ++t) {
+            float4 v = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
+            if (a.add) {
+                CAR_BOUNDS_TRAP(at + 16 * t + 4 <= a.M * a.N);
+                const float4 d = *reinterpret_cast<const float4*>(a.add + at + 16 * t);
+                v.x += d.x; v.y += d.y; v.z += d.z; v.w += d.w;
+            }
+            if (a.act) {
+                CAR_BOUNDS_TRAP(at + 16 * t + 4 <= a.M * a.N);
+                const float4 m = *reinterpret_cast<const float4*>(a.act + at + 16 * t);
+                v.x = m.x > 0.0f ? v.x : 0.0f; v.y = m.y > 0.0f ? v.y : 0.0f; v.z = m.z > 0.0f ? v.z : 0.0f; v.w = m.w > 0.0f ? v.w : 0.0f;
+            }
+            *reinterpret_cast<float4*>(yrow + 16 * t) = v;
+        }
+    } else {
+        scale_acc<NT>(acc, dW * pinv);
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            *reinterpret_cast<float4*>(yrow + 16 * t) =
+                make_float4(fmaxf(acc[t][0], 0.0f), fmaxf(acc[t][1], 0.0f), fmaxf(acc[t][2], 0.0f), fmaxf(acc[t][3], 0.0f));
+    }
 }
 
-template <int NT>
+template <int NT, bool BWD = false>
 int launch_conv(const ConvArgs& a, hipStream_t st) {
     const size_t lds_bytes = (size_t)2 * NT * kTile * sizeof(float);
     static bool reserved[64] = {};                                     // the LDS reservation is a per-device attribute of the kernel
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !reserved[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<NT, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) {
-            car_set_error("car_conv3x3: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e));
+            car_set_error("%s: cannot reserve %zu bytes of LDS: %s", BWD ? "car_conv3x3_backward" : "car_conv3x3", lds_bytes, hipGetErrorString(e));
             return CAR_E_LAUNCH;
         }
         if (dev >= 0 && dev < 64) reserved[dev] = true;
     }
     (void)hipGetLastError();
     const int groups = a.tiles_total / NT;
-    hipLaunchKernelGGL((conv3x3_kernel<NT>), dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
-    CAR_CHECK_LAUNCH("car_conv3x3");
+    hipLaunchKernelGGL((conv3x3_kernel<NT, BWD>), dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
+    CAR_CHECK_LAUNCH(BWD ? "car_conv3x3_backward" : "car_conv3x3");
     return CAR_OK;
 }
 
@@ -255,21 +299,22 @@ __global__ void conv_absmax_kernel(const float* __restrict__ Wt, long total, flo
     }
 }
 // torch's [N][K][3][3] -> car_linear16.hip's tiles [K step][tile][hi | lo][lane][8 halves] with k = tap * K + channel: lane l carries
-// output 16 tile + l % 16 and k = 32 step + 8 (l >> 4) + e.  scale[0] = 2^shift, scale[1] = 2^-shift; the bias follows the 64 scale floats
+// output 16 tile + l % 16 and k = 32 step + 8 (l >> 4) + e.  scale[0] = 2^shift, scale[1] = 2^-shift; the bias follows the 64 scale floats.
+// flip (the data gradient's weights, no bias): Wt is the forward layer's [K][N][3][3] and the tile holds w'[n][k][tap] = Wt[k][n][8 - tap]
 __global__ void conv_pack_kernel(const float* __restrict__ Wt, const float* __restrict__ bias, int K, int N, long total, float* __restrict__ scale,
-                                 _Float16* __restrict__ out) {
+                                 _Float16* __restrict__ out, bool flip) {
     float p, inv;
     pow2_scale(fmaxf(scale[2], 1e-30f), p, inv);
     if (blockIdx.x == 0 && threadIdx.x == 0) { scale[0] = p; scale[1] = inv; }
     const int tiles = N / 16;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        if (idx < N) scale[64 + idx] = bias[idx];
+        if (!flip && idx < N) scale[64 + idx] = bias[idx];
         const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
         const long tile = idx >> 9;
         const int t = (int)(tile % tiles), ks = (int)(tile / tiles);
         const int n = 16 * t + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + e;
         const int tap = k / K, ch = k % K;
-        const float w = Wt[((long)n * K + ch) * 9 + tap] * p;
+        const float w = (flip ? Wt[((long)ch * N + n) * 9 + (8 - tap)] : Wt[((long)n * K + ch) * 9 + tap]) * p;
         const _Float16 hi = (_Float16)w;
         _Float16* o = out + tile * 1024 + lane * 8 + e;
         o[0] = hi;
@@ -395,9 +440,8 @@ size_t layer_offset(int l) {                                          // of laye
 }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-int head(const float* const* feats, int B, int H, int W, const float* lin, double* lpips, double* per_tap, double* scratch, hipStream_t st,
-         const char* who) {
-    HeadArgs a;
+HeadArgs head_args(const float* const* feats, int B, int H, int W, const float* lin) {
+    HeadArgs a{};
     int blk = 0, off = 0;
     for (int k = 0; k < kTaps; ++k) {
         a.f[k] = feats[k];
@@ -410,8 +454,13 @@ int head(const float* const* feats, int B, int H, int W, const float* lin, doubl
     }
     a.blk0[kTaps] = blk;
     a.B = B;
+    return a;
+}
+int head(const float* const* feats, int B, int H, int W, const float* lin, double* lpips, double* per_tap, double* scratch, hipStream_t st,
+         const char* who) {
+    HeadArgs a = head_args(feats, B, H, W, lin);
     a.partial = scratch;
-    hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((long)B * blk)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((long)B * a.blk0[kTaps])), dim3(256), 0, st, a);
     CAR_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(lpips_mean_kernel, dim3((unsigned)B), dim3(64), 0, st, a, lpips, per_tap);
     CAR_CHECK_LAUNCH(who);
@@ -444,6 +493,227 @@ int pool(const float* X, int n, int H, int W, int C, float* Y, hipStream_t st) {
     return CAR_OK;
 }
 
+
+// ==== the backward: d LPIPS / d image, weights frozen (profiles/lpips_backward.md) ============================
+// Every kernel is gather-form — an output element is written once, by the thread that summed it in a fixed order — so the gradient is
+// bit-reproducible and an image's gradient does not depend on where its pair sits in the batch.
+
+// ---- first layer's data gradient: 64 -> 3, fp32 ------------------------------------------------------------------------------------
+// gx[p][c] = sum over taps t and channels n of w[t][c][n] / scale[c] * D[p - offset(t)][n], over the taps whose output pixel lies inside
+// the image; `packed` is the forward's first-layer array, which already carries 1 / scale.  A wave takes one pixel at a time: lane n
+// holds channel n's 27 weights, the nine 64-float rows of D are coalesced loads, the three sums close with the fixed butterfly.
+__global__ void __launch_bounds__(256) conv_first_backward_kernel(const float* __restrict__ D, const float* __restrict__ packed, float* __restrict__ gx,
+                                                                  int H, int W, long M) {
+    const int n = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float w[27];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) w[k] = packed[k * 64 + n];
+    const long p0 = ((long)blockIdx.x * 4 + wave) * kFirstPix;
+    for (int i = 0; i < kFirstPix; ++i) {
+        const long p = p0 + i;
+        if (p >= M) return;
+        const int pix = (int)(p % ((long)H * W)), py = pix / W, px = pix % W;
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = py - (t / 3 - 1), xx = px - (t % 3 - 1);
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                const long src = p - ((long)(t / 3 - 1) * W + (t % 3 - 1));
+                CAR_BOUNDS_TRAP(src >= 0 && src < M);
+                const float d = D[src * 64 + n];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] = fmaf(d, w[3 * t + c], acc[c]);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o, 64);
+        if (n < 3) gx[p * 3 + n] = n == 0 ? acc[0] : n == 1 ? acc[1] : acc[2];
+    }
+}
+
+// ---- max-pool backward, gather form --------------------------------------------------------------------------------------------------
+// out[y][x] = (routed + add) * (act > 0): routed is the pooled gradient T[y / 2][x / 2] where (y, x) is the FIRST maximal element of its
+// window in row-major order (torch's rule), else 0; a last odd row or column lies in no window.  Four channels per thread.
+__device__ __forceinline__ float route1(float a, float b, float d, float e, int pos, float t) {
+    int arg = 0;
+    float m = a;
+    if (b > m) { m = b; arg = 1; }
+    if (d > m) { m = d; arg = 2; }
+    if (e > m) { m = e; arg = 3; }
+    return arg == pos ? t : 0.0f;
+}
+__global__ void __launch_bounds__(256) maxpool_backward_kernel(const float* __restrict__ T, const float* __restrict__ act, const float* __restrict__ add,
+                                                               float* __restrict__ out, int H, int W, int C4, long total) {
+    const int Ho = H / 2, Wo = W / 2;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % C4);
+        long r = idx / C4;
+        const int x = (int)(r % W); r /= W;
+        const int y = (int)(r % H);
+        const long img = r / H;
+        const float4 own = reinterpret_cast<const float4*>(act)[idx];
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const int oy = y >> 1, ox = x >> 1;
+        if (oy < Ho && ox < Wo) {
+            const long win = ((img * H + 2 * oy) * W + 2 * ox) * C4 + c, pooled = ((img * Ho + oy) * Wo + ox) * C4 + c;
+            // act holds `total` float4s, T only the pooled map's: total / (H W) = images x C4 of them per pooled pixel
+            CAR_BOUNDS_TRAP(win + (long)W * C4 + C4 < total && pooled < total / ((long)H * W) * Ho * Wo);
+            const float4* src = reinterpret_cast<const float4*>(act) + win;
+            const float4 a = src[0], b = src[C4], d = src[(long)W * C4], e = src[(long)W * C4 + C4];
+            const float4 t = reinterpret_cast<const float4*>(T)[pooled];
+            const int pos = 2 * (y & 1) + (x & 1);
+            v = make_float4(route1(a.x, b.x, d.x, e.x, pos, t.x), route1(a.y, b.y, d.y, e.y, pos, t.y), route1(a.z, b.z, d.z, e.z, pos, t.z),
+                            route1(a.w, b.w, d.w, e.w, pos, t.w));
+        }
+        if (add) {
+            const float4 g = reinterpret_cast<const float4*>(add)[idx];
+            v.x += g.x; v.y += g.y; v.z += g.z; v.w += g.w;
+        }
+        reinterpret_cast<float4*>(out)[idx] = make_float4(own.x > 0.0f ? v.x : 0.0f, own.y > 0.0f ? v.y : 0.0f, own.z > 0.0f ? v.z : 0.0f,
+                                                          own.w > 0.0f ? v.w : 0.0f);
+    }
+}
+// out = g * (act > 0): the last layer's ReLU, which no convolution's epilogue reaches
+__global__ void __launch_bounds__(256) relu_mask_kernel(const float* __restrict__ g, const float* __restrict__ act, float* __restrict__ out, long total4) {
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total4; idx += (long)gridDim.x * blockDim.x) {
+        const float4 v = reinterpret_cast<const float4*>(g)[idx], m = reinterpret_cast<const float4*>(act)[idx];
+        reinterpret_cast<float4*>(out)[idx] = make_float4(m.x > 0.0f ? v.x : 0.0f, m.y > 0.0f ? v.y : 0.0f, m.z > 0.0f ? v.z : 0.0f, m.w > 0.0f ? v.w : 0.0f);
+    }
+}
+
+// ---- the head's backward -----------------------------------------------------------------------------------------------------------------
+// Per pixel of a tap, in fp64 with the forward head's sums: u = f0 / (n0 + 1e-10), v = f1 / (n1 + 1e-10), q_c = 2 w_c (u_c - v_c),
+//   ds / df0_c =  q_c / (n0 + 1e-10) - (sum_j q_j f0_j) f0_c / (n0 (n0 + 1e-10)^2),
+//   ds / df1_c = -q_c / (n1 + 1e-10) + (sum_j q_j f1_j) f1_c / (n1 (n1 + 1e-10)^2),
+// times the pair's cotangent / npix, stored as fp32.  At n = 0 the norm's derivative is taken as 0.  Identical features give q = 0 exactly.
+struct HeadBwdArgs {
+    HeadArgs h;                                    // f, lin, npix, C, blk0, B as in the forward; partial unused
+    const double* g;                               // [B]
+    float* gf0[kTaps];                             // [B, npix, C] per tap, or all nullptr
+    float* gf1[kTaps];
+};
+__global__ void __launch_bounds__(256) lpips_head_backward_kernel(const HeadBwdArgs b) {
+    const HeadArgs& a = b.h;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per_pair = a.blk0[kTaps];
+    const int pair = blockIdx.x / per_pair, blk = blockIdx.x % per_pair;
+    int k = 0;
+#pragma unroll
+    for (int t = 1; t < kTaps; ++t) k += blk >= a.blk0[t] ? 1 : 0;
+    const int C = a.C[k], npix = a.npix[k], per = C / 64;
+    const int p0 = (blk - a.blk0[k]) * kHeadPix + wave * 16;
+    const float* f0 = a.f[k] + (size_t)pair * npix * C;
+    const float* f1 = a.f[k] + (size_t)(a.B + pair) * npix * C;
+    float* o0 = b.gf0[k] ? b.gf0[k] + (size_t)pair * npix * C : nullptr;
+    float* o1 = b.gf1[k] ? b.gf1[k] + (size_t)pair * npix * C : nullptr;
+    const double cot = b.g[pair] / (double)npix;
+    double w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = j < per ? (double)a.lin[k][lane + 64 * j] : 0.0;
+    for (int i = 0; i < 16; ++i) {
+        const int p = p0 + i;
+        if (p >= npix) break;                                          // wave-uniform
+        double u[8], v[8], s0 = 0.0, s1 = 0.0;
+        // a pixel's row of C floats, inside the pair's map and the pair inside the stack of 2 B images
+        CAR_BOUNDS_TRAP(pair < a.B && k < kTaps && (size_t)p * C + lane + 64 * (per - 1) < (size_t)npix * C);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            u[j] = j < per ? (double)f0[(size_t)p * C + lane + 64 * j] : 0.0;
+            v[j] = j < per ? (double)f1[(size_t)p * C + lane + 64 * j] : 0.0;
+            s0 += u[j] * u[j];
+            s1 += v[j] * v[j];
+        }
+        const double r0 = sqrt(wave_sum(s0)), r1 = sqrt(wave_sum(s1)), n0 = r0 + 1e-10, n1 = r1 + 1e-10;
+        double q[8], a0 = 0.0, a1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            q[j] = 2.0 * w[j] * (u[j] / n0 - v[j] / n1);
+            a0 += q[j] * u[j];
+            a1 += q[j] * v[j];
+        }
+        const double t0 = wave_sum(a0), t1 = wave_sum(a1);
+        const double c0 = r0 > 0.0 ? t0 / (r0 * (n0 * n0)) : 0.0, c1 = r1 > 0.0 ? t1 / (r1 * (n1 * n1)) : 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < per) {
+                if (o0) o0[(size_t)p * C + lane + 64 * j] = (float)((q[j] / n0 - c0 * u[j]) * cot);
+                if (o1) o1[(size_t)p * C + lane + 64 * j] = (float)((c1 * v[j] - q[j] / n1) * cot);
+            }
+    }
+}
+
+int head_backward(const float* const* feats, int B, int H, int W, const float* lin, const double* g, float* const* gf0, float* const* gf1,
+                  hipStream_t st, const char* who) {
+    HeadBwdArgs b;
+    b.h = head_args(feats, B, H, W, lin);
+    b.g = g;
+    for (int k = 0; k < kTaps; ++k) { b.gf0[k] = gf0 ? gf0[k] : nullptr; b.gf1[k] = gf1 ? gf1[k] : nullptr; }
+    hipLaunchKernelGGL(lpips_head_backward_kernel, dim3((unsigned)((long)B * b.h.blk0[kTaps])), dim3(256), 0, st, b);
+    CAR_CHECK_LAUNCH(who);
+    return CAR_OK;
+}
+
+// K, N: the FORWARD layer's channel counts; D [n, H, W, N] -> out [n, H, W, K]
+int conv_backward(const float* D, int n, int H, int W, int K, int N, const float* packed, const float* act, const float* add, float* out,
+                  hipStream_t st) {
+    const long M = (long)n * H * W;
+    if (K == 3) {
+        hipLaunchKernelGGL(conv_first_backward_kernel, dim3(car_div_up(M, 4 * kFirstPix)), dim3(256), 0, st, D, packed, out, H, W, M);
+        CAR_CHECK_LAUNCH("car_conv3x3_backward");
+        return CAR_OK;
+    }
+    ConvArgs a;
+    a.X = D; a.Wp = packed; a.tiles_total = K / 16;
+    a.down = packed + conv_tile_floats(N, K) + 1;
+    a.bias = nullptr;
+    a.Y = out; a.act = act; a.add = add;
+    a.H = H; a.W = W; a.K = N; a.N = K; a.chunks = 9 * N / 32; a.M = M;
+    a.lgk = N == 64 ? 1 : N == 128 ? 2 : N == 256 ? 3 : 4;
+    if (K == 64) return launch_conv<4, true>(a, st);
+    if (K == 128) return launch_conv<8, true>(a, st);
+    return launch_conv<16, true>(a, st);
+}
+int pool_backward(const float* T, const float* act, const float* add, int n, int H, int W, int C, float* out, hipStream_t st) {
+    const long total = (long)n * H * W * (C / 4);
+    const long blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(maxpool_backward_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, T, act, add, out, H, W, C / 4, total);
+    CAR_CHECK_LAUNCH("car_maxpool2x2_backward");
+    return CAR_OK;
+}
+bool conv_backward_shape_ok(int K, int N) { return conv_shape_ok(K, N) && K != 3; }
+size_t backward_layer_offset(int l) {                                  // of layer l >= 1 inside car_lpips_pack_backward's array
+    size_t off = 0;
+    for (int i = 1; i < l; ++i) off += car_conv3x3_backward_packed_floats(kWidth[i - 1], kWidth[i]);
+    return off;
+}
+
+// the training workspace (floats): the 13 retained activation maps [2 B, h, w, C] in layer order, the pooled map in flight, the head's
+// partial sums, then what only the backward touches: the five head gradients and two maps the gradient alternates between
+struct TrainPlan { size_t act[kLayers]; int h[kLayers], w[kLayers]; size_t pooled, scratch, hg[kTaps], ping[2], floats; };
+TrainPlan make_train_plan(int B, int H, int W) {
+    TrainPlan tp{};
+    size_t at = 0, pooled = 0;
+    int h = H, w = W;
+    for (int l = 0; l < kLayers; ++l) {
+        if (pool_in_front(l)) {
+            h /= 2; w /= 2;
+            const size_t n = (size_t)2 * B * h * w * kWidth[l - 1];
+            pooled = n > pooled ? n : pooled;
+        }
+        tp.act[l] = at; tp.h[l] = h; tp.w[l] = w;
+        at += up64((size_t)2 * B * h * w * kWidth[l]);
+    }
+    tp.pooled = at; at += up64(pooled);
+    tp.scratch = at; at += 2 * up64(car_lpips_head_scratch_doubles(B, H, W));
+    for (int k = 0; k < kTaps; ++k) { tp.hg[k] = at; at += up64((size_t)2 * B * (H >> k) * (W >> k) * kTapWidth[k]); }
+    for (int i = 0; i < 2; ++i) { tp.ping[i] = at; at += up64((size_t)2 * B * H * W * 64); }
+    tp.floats = at;
+    return tp;
+}
+constexpr int kTapLayer[kTaps] = {1, 3, 6, 9, 12};
+
 }  // namespace
 
 // One layer's packed weights: K = 3 (N = 64; the network's first layer, scaling layer folded in) 27 x 64 fp32 weights and the bias;
@@ -467,7 +737,7 @@ extern "C" int car_conv3x3_pack(const float* w, const float* bias, int K, int N,
     float* scale = packed + conv_tile_floats(K, N);
     if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("car_conv3x3_pack: memset failed"); return CAR_E_LAUNCH; }
     hipLaunchKernelGGL(conv_absmax_kernel, dim3(64), dim3(256), 0, st, w, (long)N * K * 9, scale);
-    hipLaunchKernelGGL(conv_pack_kernel, dim3(512), dim3(256), 0, st, w, bias, K, N, (long)(conv_tile_floats(K, N)), scale, reinterpret_cast<_Float16*>(packed));
+    hipLaunchKernelGGL(conv_pack_kernel, dim3(512), dim3(256), 0, st, w, bias, K, N, (long)(conv_tile_floats(K, N)), scale, reinterpret_cast<_Float16*>(packed), false);
     CAR_CHECK_LAUNCH("car_conv3x3_pack");
     return CAR_OK;
 }
@@ -566,4 +836,162 @@ extern "C" int car_lpips(const float* x, const float* y, int B, int H, int W, co
         if (code != CAR_OK) return code;
     }
     return head(buf, B, H, W, packed + layer_offset(kLayers), lpips, per_tap, scratch, st, "car_lpips");
+}
+
+// ---- the backward's entries (include/car_hip.h) ------------------------------------------------------------------------------------------
+// K, N are the FORWARD layer's channel counts throughout.  The data gradient's weights: 9 N / 32 x K / 16 tiles and 64 floats of scale;
+// 0 for a refused shape and for the first layer, whose data gradient reads car_conv3x3_pack's array.
+extern "C" size_t car_conv3x3_backward_packed_floats(int K, int N) {
+    return conv_backward_shape_ok(K, N) ? conv_tile_floats(N, K) + 64 : 0;
+}
+
+extern "C" int car_conv3x3_backward_pack(const float* w, int K, int N, float* packed, void* stream) {
+    CAR_REQUIRE(w && packed, "car_conv3x3_backward_pack: null pointer");
+    CAR_REQUIRE(conv_backward_shape_ok(K, N), "car_conv3x3_backward_pack: %d -> %d channels, need K and N among 64, 128, 256, 512", K, N);
+    CAR_REQUIRE(aligned16(packed), "car_conv3x3_backward_pack: packed must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipGetLastError();
+    float* scale = packed + conv_tile_floats(N, K);
+    if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("car_conv3x3_backward_pack: memset failed"); return CAR_E_LAUNCH; }
+    hipLaunchKernelGGL(conv_absmax_kernel, dim3(64), dim3(256), 0, st, w, (long)N * K * 9, scale);
+    hipLaunchKernelGGL(conv_pack_kernel, dim3(512), dim3(256), 0, st, w, (const float*)nullptr, N, K, (long)(conv_tile_floats(N, K)), scale,
+                       reinterpret_cast<_Float16*>(packed), true);
+    CAR_CHECK_LAUNCH("car_conv3x3_backward_pack");
+    return CAR_OK;
+}
+
+extern "C" int car_conv3x3_backward(const float* D, int n, int H, int W, int K, int N, const float* packed, const float* act, const float* add,
+                                    float* out, void* stream) {
+    CAR_REQUIRE(D && packed && out, "car_conv3x3_backward: null pointer");
+    CAR_REQUIRE(conv_shape_ok(K, N), "car_conv3x3_backward: %d -> %d channels, need 3 -> 64 or K and N among 64, 128, 256, 512", K, N);
+    CAR_REQUIRE(K != 3 || (!act && !add), "car_conv3x3_backward: the first layer's gradient lands on the image: act and add must be NULL");
+    CAR_REQUIRE(n >= 1 && H >= 1 && W >= 1, "car_conv3x3_backward: %d images of %d x %d, need at least one pixel", n, H, W);
+    CAR_REQUIRE((double)n * H * W <= (double)kMaxPixels, "car_conv3x3_backward: %d x %d x %d is too large", n, H, W);
+    CAR_REQUIRE(aligned16(D) && aligned16(packed) && aligned16(out) && aligned16(act) && aligned16(add),
+                "car_conv3x3_backward: D, packed, act, add and out must be 16-byte aligned");
+    (void)hipGetLastError();
+    return conv_backward(D, n, H, W, K, N, packed, act, add, out, (hipStream_t)stream);
+}
+
+extern "C" int car_maxpool2x2_backward(const float* T, const float* act, const float* add, int n, int H, int W, int C, float* out, void* stream) {
+    CAR_REQUIRE(T && act && out, "car_maxpool2x2_backward: null pointer");
+    CAR_REQUIRE(n >= 1 && H >= 2 && W >= 2 && C >= 4 && C % 4 == 0, "car_maxpool2x2_backward: %d x %d x %d x %d, need H, W >= 2 and C a multiple of 4", n, H, W, C);
+    CAR_REQUIRE((double)n * H * W <= (double)kMaxPixels && C <= 4096, "car_maxpool2x2_backward: %d x %d x %d x %d is too large", n, H, W, C);
+    CAR_REQUIRE(aligned16(T) && aligned16(act) && aligned16(add) && aligned16(out), "car_maxpool2x2_backward: T, act, add and out must be 16-byte aligned");
+    (void)hipGetLastError();
+    return pool_backward(T, act, add, n, H, W, C, out, (hipStream_t)stream);
+}
+
+extern "C" int car_lpips_head_backward(const float* const* feats, int B, int H, int W, const float* lin, const double* g, float* const* gf0,
+                                       float* const* gf1, void* stream) {
+    CAR_REQUIRE(feats && lin && g, "car_lpips_head_backward: null pointer");
+    CAR_REQUIRE(gf0 || gf1, "car_lpips_head_backward: null pointer (neither gf0 nor gf1 is given)");
+    for (int k = 0; k < kTaps; ++k)
+        CAR_REQUIRE(feats[k] && (!gf0 || gf0[k]) && (!gf1 || gf1[k]), "car_lpips_head_backward: null pointer (tap %d)", k);
+    CAR_REQUIRE(B >= 1, "car_lpips_head_backward: B = %d, need at least one image pair", B);
+    CAR_REQUIRE(H >= 16 && W >= 16, "car_lpips_head_backward: %d x %d image, the last tap needs H >= 16 and W >= 16", H, W);
+    CAR_REQUIRE(lpips_shape_ok(B, H, W), "car_lpips_head_backward: %d x %d x %d is too large", B, H, W);
+    (void)hipGetLastError();
+    return head_backward(feats, B, H, W, lin, g, gf0, gf1, (hipStream_t)stream, "car_lpips_head_backward");
+}
+
+extern "C" size_t car_lpips_backward_packed_floats(void) { return backward_layer_offset(kLayers); }
+
+extern "C" int car_lpips_pack_backward(const float* const* conv_w, float* packed, void* stream) {
+    CAR_REQUIRE(conv_w && packed, "car_lpips_pack_backward: null pointer");
+    for (int l = 0; l < kLayers; ++l) CAR_REQUIRE(conv_w[l], "car_lpips_pack_backward: null pointer (layer %d)", l);
+    CAR_REQUIRE(aligned16(packed), "car_lpips_pack_backward: packed must be 16-byte aligned");
+    for (int l = 1; l < kLayers; ++l)
+        CAR_TRY(car_conv3x3_backward_pack(conv_w[l], kWidth[l - 1], kWidth[l], packed + backward_layer_offset(l), stream));
+    return CAR_OK;
+}
+
+extern "C" size_t car_lpips_train_workspace_bytes(int B, int H, int W) {
+    return lpips_shape_ok(B, H, W) ? make_train_plan(B, H, W).floats * sizeof(float) : 0;
+}
+
+// byte offset of layer l's retained map [2 B, h, w, C_l] (h = H >> pools in front of l) in the training workspace; (size_t)-1 when refused
+extern "C" size_t car_lpips_train_layer_offset(int B, int H, int W, int l) {
+    if (!lpips_shape_ok(B, H, W) || l < 0 || l >= kLayers) return (size_t)-1;
+    return make_train_plan(B, H, W).act[l] * sizeof(float);
+}
+
+extern "C" int car_lpips_forward_train(const float* x, const float* y, int B, int H, int W, const float* packed, double* lpips, double* per_tap,
+                                       void* work, size_t work_bytes, void* stream) {
+    CAR_REQUIRE(x && y && packed && lpips && work, "car_lpips_forward_train: null pointer");
+    CAR_REQUIRE(B >= 1, "car_lpips_forward_train: B = %d, need at least one image pair", B);
+    CAR_REQUIRE(H >= 16 && W >= 16, "car_lpips_forward_train: %d x %d image, the last tap needs H >= 16 and W >= 16", H, W);
+    CAR_REQUIRE(lpips_shape_ok(B, H, W), "car_lpips_forward_train: %d x %d x %d is too large", B, H, W);
+    const size_t need = car_lpips_train_workspace_bytes(B, H, W);
+    CAR_REQUIRE(work_bytes >= need, "car_lpips_forward_train: workspace holds %zu bytes, need %zu (car_lpips_train_workspace_bytes)", work_bytes, need);
+    CAR_REQUIRE(aligned16(packed) && aligned16(work), "car_lpips_forward_train: packed and the workspace must be 16-byte aligned");
+
+    const TrainPlan tp = make_train_plan(B, H, W);
+    float* base = static_cast<float*>(work);
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipGetLastError();
+    CAR_TRY(conv(x, B, H, W, 3, 64, packed, base + tp.act[0], st));
+    CAR_TRY(conv(y, B, H, W, 3, 64, packed, base + tp.act[0] + (size_t)B * H * W * 64, st));
+    for (int l = 1; l < kLayers; ++l) {
+        const float* src = base + tp.act[l - 1];
+        if (pool_in_front(l)) {
+            CAR_TRY(pool(src, 2 * B, tp.h[l - 1], tp.w[l - 1], kWidth[l - 1], base + tp.pooled, st));
+            src = base + tp.pooled;
+        }
+        CAR_TRY(conv(src, 2 * B, tp.h[l], tp.w[l], kWidth[l - 1], kWidth[l], packed + layer_offset(l), base + tp.act[l], st));
+    }
+    const float* feats[kTaps];
+    for (int k = 0; k < kTaps; ++k) feats[k] = base + tp.act[kTapLayer[k]];
+    return head(feats, B, H, W, packed + layer_offset(kLayers), lpips, per_tap, reinterpret_cast<double*>(base + tp.scratch), st, "car_lpips_forward_train");
+}
+
+extern "C" int car_lpips_backward(const double* g, float* gx, float* gy, int B, int H, int W, const float* packed, const float* packed_backward,
+                                  void* work, size_t work_bytes, void* stream) {
+    CAR_REQUIRE(g && packed && packed_backward && work, "car_lpips_backward: null pointer");
+    CAR_REQUIRE(gx || gy, "car_lpips_backward: null pointer (neither gx nor gy is given)");
+    CAR_REQUIRE(B >= 1, "car_lpips_backward: B = %d, need at least one image pair", B);
+    CAR_REQUIRE(H >= 16 && W >= 16, "car_lpips_backward: %d x %d image, the last tap needs H >= 16 and W >= 16", H, W);
+    CAR_REQUIRE(lpips_shape_ok(B, H, W), "car_lpips_backward: %d x %d x %d is too large", B, H, W);
+    const size_t need = car_lpips_train_workspace_bytes(B, H, W);
+    CAR_REQUIRE(work_bytes >= need, "car_lpips_backward: workspace holds %zu bytes, need %zu (car_lpips_train_workspace_bytes)", work_bytes, need);
+    CAR_REQUIRE(aligned16(packed) && aligned16(packed_backward) && aligned16(work),
+                "car_lpips_backward: packed, packed_backward and the workspace must be 16-byte aligned");
+
+    const TrainPlan tp = make_train_plan(B, H, W);
+    float* base = static_cast<float*>(work);
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipGetLastError();
+    // the image stacks that need a gradient: images i0 .. i0 + n - 1 of every retained map
+    const int i0 = gx ? 0 : B, n = (gx && gy) ? 2 * B : B;
+    auto act = [&](int l) { return base + tp.act[l] + (size_t)i0 * tp.h[l] * tp.w[l] * kWidth[l]; };
+    const float* feats[kTaps];
+    float *hg0[kTaps], *hg1[kTaps];
+    for (int k = 0; k < kTaps; ++k) {
+        feats[k] = base + tp.act[kTapLayer[k]];
+        hg0[k] = base + tp.hg[k];
+        hg1[k] = base + tp.hg[k] + (gx ? (size_t)B * (H >> k) * (W >> k) * kTapWidth[k] : 0);
+    }
+    CAR_TRY(head_backward(feats, B, H, W, packed + layer_offset(kLayers), g, gx ? hg0 : nullptr, gy ? hg1 : nullptr, st, "car_lpips_backward"));
+    float* cur = base + tp.ping[0];
+    float* other = base + tp.ping[1];
+    {
+        const long total4 = (long)n * tp.h[12] * tp.w[12] * (kWidth[12] / 4), blocks = (total4 + 255) / 256;
+        hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, base + tp.hg[4], act(12), cur, total4);
+        CAR_CHECK_LAUNCH("car_lpips_backward");
+    }
+    int tap = kTaps - 2;
+    for (int l = kLayers - 1; l >= 1; --l) {                             // cur holds the gradient at layer l's pre-activation
+        const float* pk = packed_backward + backward_layer_offset(l);
+        if (pool_in_front(l)) {                                          // layer l - 1 is a tap: its head gradient joins behind the pool's routing
+            CAR_TRY(conv_backward(cur, n, tp.h[l], tp.w[l], kWidth[l - 1], kWidth[l], pk, nullptr, nullptr, other, st));
+            CAR_TRY(pool_backward(other, act(l - 1), base + tp.hg[tap--], n, tp.h[l - 1], tp.w[l - 1], kWidth[l - 1], cur, st));
+        } else {
+            CAR_TRY(conv_backward(cur, n, tp.h[l], tp.w[l], kWidth[l - 1], kWidth[l], pk, act(l - 1), nullptr, other, st));
+            float* t = cur; cur = other; other = t;
+        }
+    }
+    const size_t img = (size_t)B * H * W;
+    if (gx) CAR_TRY(conv_backward(cur, B, H, W, 3, 64, packed, nullptr, nullptr, gx, st));
+    if (gy) CAR_TRY(conv_backward(cur + (gx ? img * 64 : 0), B, H, W, 3, 64, packed, nullptr, nullptr, gy, st));
+    return CAR_OK;
 }

@@ -157,26 +157,36 @@ class LpipsWeights:
 
     def __init__(self, conv_w, conv_b, lin):
         self.conv_w, self.conv_b, self.lin = conv_w, conv_b, lin
-        self._packed, self._work = {}, {}
+        self._packed, self._packed_backward, self._work = {}, {}, {}
 
-    def packed(self, device) -> torch.Tensor:
+    def _pack_once(self, cache, device, groups, floats, pack) -> torch.Tensor:
+        """``cache[device]``, made on first use: the float32 tensor lists ``groups`` go to the device, entry ``pack`` (one table of
+        pointers per group, the output, the stream) writes entry ``floats``'s count of floats.  The one key rule of both packed forms."""
         import ctypes
         from . import _lib
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError(f"lpips: the weights are packed on a ROCm device, not on {device}; there is no CPU fallback")
         key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        if key not in self._packed:
+        if key not in cache:
             lib = _lib.load()
             with torch.cuda.device(device):
-                dev = [[t.to(device) for t in group] for group in (self.conv_w, self.conv_b, self.lin)]
+                dev = [[t.to(device) for t in group] for group in groups]
                 tables = [(ctypes.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in dev]
-                out = torch.empty(lib.car_lpips_packed_floats(), dtype=torch.float32, device=device)
-                code = lib.car_lpips_pack(*tables, out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-                _lib.check(code, "car_lpips_pack")
+                out = torch.empty(getattr(lib, floats)(), dtype=torch.float32, device=device)
+                code = getattr(lib, pack)(*tables, out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                _lib.check(code, pack)
                 torch.cuda.current_stream().synchronize()              # the float32 copies in `dev` are released on return
-            self._packed[key] = out
-        return self._packed[key]
+            cache[key] = out
+        return cache[key]
+
+    def packed(self, device) -> torch.Tensor:
+        return self._pack_once(self._packed, device, (self.conv_w, self.conv_b, self.lin), "car_lpips_packed_floats", "car_lpips_pack")
+
+    def packed_backward(self, device) -> torch.Tensor:
+        """The data gradients' weights (car_lpips_pack_backward: every layer but the first, transposed and flipped), made on the first
+        backward on a device."""
+        return self._pack_once(self._packed_backward, device, (self.conv_w,), "car_lpips_backward_packed_floats", "car_lpips_pack_backward")
 
     def workspace(self, device, B, H, W, nbytes) -> torch.Tensor:
         key = (str(device), B, H, W)
@@ -229,6 +239,74 @@ def lpips(img: torch.Tensor, ref: torch.Tensor, weights: LpipsWeights, return_ta
     _lib.check(code, "car_lpips")
     out, taps = (out[0], taps[0]) if img.dim() == 3 else (out, taps)
     return (out, taps) if return_taps else out
+
+
+class _LpipsLoss(torch.autograd.Function):
+    """car_lpips_forward_train / car_lpips_backward.  The workspace with the 13 retained activation maps belongs to the call (two losses
+    may be alive before either runs backward), so it is allocated here, not cached on the weights."""
+
+    @staticmethod
+    def forward(ctx, x, y, weights):
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        xc, yc = x.detach().contiguous(), y.detach().contiguous()
+        B, H, W, _ = xc.shape
+        with torch.cuda.device(xc.device):
+            packed = weights.packed(xc.device)
+            n = lib.car_lpips_train_workspace_bytes(B, H, W)
+            work = torch.empty(max(n, 16), dtype=torch.uint8, device=xc.device)
+            out = torch.empty(max(B, 1), dtype=torch.float64, device=xc.device)
+            code = lib.car_lpips_forward_train(xc.data_ptr(), yc.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), None, work.data_ptr(), n,
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if code == -1:
+            raise ValueError(lib.car_last_error().decode())
+        _lib.check(code, "car_lpips_forward_train")
+        ctx.weights, ctx.work, ctx.shape = weights, work, (B, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        B, H, W = ctx.shape
+        need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_y):
+            return None, None, None
+        dev = ctx.work.device
+        g = g.to(torch.float64).contiguous()
+        with torch.cuda.device(dev):
+            gx = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if need_x else None
+            gy = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if need_y else None
+            code = lib.car_lpips_backward(g.data_ptr(), gx.data_ptr() if need_x else None, gy.data_ptr() if need_y else None, B, H, W,
+                                          ctx.weights.packed(dev).data_ptr(), ctx.weights.packed_backward(dev).data_ptr(), ctx.work.data_ptr(),
+                                          ctx.work.numel(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(code, "car_lpips_backward")
+        return gx, gy, None
+
+
+def lpips_loss(x: torch.Tensor, y: torch.Tensor, weights: LpipsWeights) -> torch.Tensor:
+    """LPIPS v0.1 (net = 'vgg') as a training loss, the reference's ``LFLoss(lpips=True)`` term (loss_functions.py:102-118:
+    ``loss_fn_vgg(gt_rgb, pred_rgb)`` on the model's own rgb range): ``car_lpips_forward_train`` and, under autograd,
+    ``car_lpips_backward`` (csrc/car_lpips.hip).  The network's weights are frozen.
+
+    ``x`` and ``y`` are (B, H, W, 3) float32 tensors in [-1, 1] on one ROCm device, H and W >= 16; unlike ``lpips`` nothing is remapped.
+    Returns a float64 (B,) tensor, the same bits ``lpips`` gives for the same [-1, 1] images; its backward gives float32 gradients to
+    whichever of ``x``, ``y`` requires one and walks only that image stack.  Bit-reproducible; nothing waits for the launches.
+
+    Raises ValueError for CPU tensors (there is no CPU fallback), mismatched shapes and the shapes car_lpips refuses."""
+    if not (torch.is_tensor(x) and torch.is_tensor(y)):
+        raise ValueError("lpips_loss: x and y must be tensors")
+    if x.device.type != "cuda" or y.device != x.device:
+        raise ValueError(f"lpips_loss: needs both images on one ROCm device (got {x.device} and {y.device}); there is no CPU fallback")
+    if x.shape != y.shape or x.dim() != 4 or x.shape[-1] != 3:
+        raise ValueError(f"lpips_loss: need two (B, H, W, 3) images of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError(f"lpips_loss: need float32 images, got {x.dtype} and {y.dtype}")
+    if not isinstance(weights, LpipsWeights):
+        raise ValueError("lpips_loss: weights must come from load_lpips_weights")
+    return _LpipsLoss.apply(x, y, weights)
 
 
 def write_png(path: str, rgb: torch.Tensor) -> None:

@@ -5,7 +5,10 @@
 The reference's loop, with ``training.render_train`` (HIP forward + HIP backward, csrc/car_backward.hip) in the place of
 ``model(model_input)``: Adam(lr, betas=(0.99, 0.999)) (train_realestate10k.py:93), 192 random query rays per scene (query_sparsity,
 train_realestate10k.py:78), L1 image loss (loss_functions.image_loss; --depth adds the reference's per-patch depth-variance term on 32 x 32
-pixel patches, loss_functions.py:112-127, and samples the rays as such patches: --query_sparsity must then be a multiple of 1024),
+pixel patches, loss_functions.py:112-127, and samples the rays as such patches: --query_sparsity must then be a multiple of 1024; --lpips
+adds the reference's second-stage term, loss_functions.py:102-118: lpips_coeff x LPIPS_vgg(gt, pred) of the same 32 x 32 patches, masked
+per patch, its forward and backward on the device — harness.lpips_loss, csrc/car_lpips.hip — with the weight files named by
+--lpips_weights, since none are shipped),
 gradient clipping at norm 1 (training.py:130-134), parameters broadcast from rank 0 and gradients all-reduced when --gpus > 1
 (train_realestate10k.py:60-62, training.py:21-28: one process per GPU over RCCL), checkpoints ``{'model', 'optimizer'}`` as
 ``checkpoints/model_current.pth`` / ``model_final.pth`` (training.py:82-84, 244-246) that the eval / render scripts load.
@@ -13,8 +16,7 @@ gradient clipping at norm 1 (training.py:130-134), parameters broadcast from ran
 Data: the RealEstate10K training set and its augmenting reader are not available offline, so scenes are synthetic (--synthetic, the
 default here: seeded stereo pairs with a smooth random target image per scene; every step draws new rays).  The encoder trains when the
 model is built with it (--with_encoder: the pyramid then comes from ``get_z`` under autograd); otherwise the pyramid itself is a leaf
-that receives gradients, standing in for the encoder's output.  The LPIPS loss term (--lpips) is not built: a training loss
-needs the backward of the VGG16 convolutions; the forward metric is in the eval scripts (--lpips_weights, harness.lpips)."""
+that receives gradients, standing in for the encoder's output."""
 import os
 import sys
 import time
@@ -28,7 +30,9 @@ def _parser():
     p.add_argument("--lr", type=float, default=5e-5)
     p.add_argument("--l2_coeff", type=float, default=0.05)
     p.add_argument("--depth", action="store_true", default=False)
-    p.add_argument("--lpips", action="store_true", default=False)
+    p.add_argument("--lpips", action="store_true", default=False,
+                   help="add lpips_coeff x LPIPS (v0.1, net='vgg') of the 32 x 32 ray patches to the loss; needs --lpips_weights")
+    p.add_argument("--lpips_coeff", type=float, default=0.1)            # loss_functions.py:118 (its comment: 0.2 for realestate)
     p.add_argument("--max_steps", type=int, default=20)
     p.add_argument("--steps_til_summary", type=int, default=10)
     p.add_argument("--query_sparsity", type=int, default=192)
@@ -42,9 +46,6 @@ def train(rank, opt):
     from cross_attention_renderer_amd import harness, synthetic
     from cross_attention_renderer_amd import training
     from cross_attention_renderer_amd.training import average_gradients, render_train
-    if opt.lpips:
-        raise SystemExit("--lpips is not supported: a training loss needs LPIPS's backward, which is not built "
-                         "(the forward metric is reported by the eval scripts with --lpips_weights)")
     dev = common.init_rank(rank, opt)
     H, b, R = opt.img_sidelength, opt.batch_size, opt.query_sparsity
     model = common.build_model(opt, dev).train()
@@ -65,6 +66,8 @@ def train(rank, opt):
     if opt.depth and R % 1024:
         raise SystemExit("--depth: the reference's depth-variance term works on 32 x 32 pixel patches (loss_functions.py:112-127): "
                          "--query_sparsity must be a multiple of 1024")
+    lpips_w = common.lpips_weights(opt) if opt.lpips else None      # read once per rank; packed on the device at the first step
+    patches = opt.depth or opt.lpips
     # a smooth random target image per scene: low-frequency colours of the pixel coordinates
     coef = (torch.rand(b, 3, 4, generator=g) * 2 - 1).to(dev)
     ckpt_dir = os.path.join(opt.logging_root, opt.experiment_name, "checkpoints")
@@ -76,12 +79,12 @@ def train(rank, opt):
     base = harness.to_device(base, dev, opt.cameras)
     grid = synthetic.pixel_grid(H, H).to(dev)
     gdev = torch.Generator(device=dev).manual_seed(4321 + rank)
-    t0, losses, t_warm = time.time(), [], None
+    t0, losses, lpips_term, t_warm = time.time(), [], None, None
     for step in range(opt.max_steps):
         if step == min(2, opt.max_steps - 1):                     # steady-state clock: after the first steps' allocations and builds
             torch.cuda.synchronize()
             t_warm = (time.time(), step)
-        if opt.depth:                                            # 32 x 32 pixel patches at random corners, row-major inside a patch
+        if patches:                                              # 32 x 32 pixel patches at random corners, row-major inside a patch
             gi = grid.view(H, H, 2)
             corners = torch.randint(0, H - 31, (b, R // 1024, 2), generator=g).tolist()
             uv = torch.stack([torch.cat([gi[y0:y0 + 32, x0:x0 + 32].reshape(1024, 2) for y0, x0 in corners[sc]]) for sc in range(b)])[:, None]
@@ -99,6 +102,11 @@ def train(rank, opt):
             dist_ = opt.l2_coeff * torch.pow(d - mean, 2).mean(dim=-1).mean(dim=-1).mean(dim=-1)
             mask = torch.ones_like(dist_)                         # gt['mask']: every synthetic patch counts
             loss = loss + (dist_ * mask).mean()
+        if opt.lpips:                                            # loss_functions.py:102-118: LPIPS(gt, pred) per patch, masked per patch
+            gt_p, pred_p = gt_rgb.reshape(-1, 32, 32, 3), out["rgb"].reshape(-1, 32, 32, 3)       # channel-last, as car_lpips reads them
+            mask = torch.ones(gt_p.shape[0], device=dev)          # gt['mask']: every synthetic patch counts
+            lpips_term = harness.lpips_loss(gt_p * mask[:, None, None, None], pred_p * mask[:, None, None, None], lpips_w).mean()
+            loss = loss + opt.lpips_coeff * lpips_term.to(loss.dtype)
         optimizer.zero_grad()
         if z_optimizer is not None:
             z_optimizer.zero_grad()
@@ -111,7 +119,8 @@ def train(rank, opt):
             z_optimizer.step()
         losses.append(loss.detach())                              # no .item() here: that would drain the queue every step
         if rank == 0 and (step % opt.steps_til_summary == 0 or step == opt.max_steps - 1):
-            print(f"step {step}: loss {losses[-1].item():.5f}  ({(time.time() - t0) / (step + 1) * 1e3:.1f} ms/step since the start, {b} scenes x {R} rays)", flush=True)
+            term = f"  lpips {lpips_term.item():.5f} (x {opt.lpips_coeff:g})" if opt.lpips else ""
+            print(f"step {step}: loss {losses[-1].item():.5f}{term}  ({(time.time() - t0) / (step + 1) * 1e3:.1f} ms/step since the start, {b} scenes x {R} rays)", flush=True)
             torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict()}, os.path.join(ckpt_dir, "model_current.pth"))
     torch.cuda.synchronize()
     if rank == 0:
@@ -124,6 +133,19 @@ def train(rank, opt):
         dist.destroy_process_group()
 
 
+def _check(opt):
+    """Refusals that need no device: they happen before any process opens one."""
+    if not opt.lpips:
+        return
+    if not opt.lpips_weights:
+        raise SystemExit("--lpips needs --lpips_weights VGG [LIN]: the loss's forward and backward (harness.lpips_loss) run on the caller's "
+                         "LPIPS weight files, and none are shipped")
+    if opt.query_sparsity % 1024:
+        raise SystemExit("--lpips: the reference's LPIPS term works on 32 x 32 pixel patches (loss_functions.py:107-109): "
+                         "--query_sparsity must be a multiple of 1024")
+
+
 if __name__ == "__main__":
     opt = _parser().parse_args()
+    _check(opt)
     common.spawn(train, opt)

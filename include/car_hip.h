@@ -522,6 +522,39 @@ size_t car_lpips_head_scratch_doubles(int B, int H, int W);
 int car_lpips_head(const float* const* feats, int B, int H, int W, const float* lin, double* lpips, double* per_tap, double* scratch,
                    size_t scratch_doubles, void* stream);
 
+/* ---- training loss: the gradient of LPIPS with respect to either image, weights frozen (loss_functions.py:102-118).
+ * Gather-form kernels only, no float atomics: bitwise reproducible, and a pair's gradient does not depend on its place in the batch.
+ * car_lpips_forward_train: car_lpips with the same results, bit for bit, that retains all 13 activation maps in `work`
+ *   (car_lpips_train_workspace_bytes bytes, 16-byte aligned; 0 for a refused shape).  car_lpips_train_layer_offset is the byte offset
+ *   of layer l's map [2 B, h, w, C_l] (l = 0..12, channel-last fp32, x's images then y's) in it, (size_t)-1 when refused.
+ * car_lpips_backward: g [B] fp64 cotangent of lpips; gx, gy [B,H,W,3] fp32 or NULL (at least one): d sum_b(g_b lpips_b) / d x, / d y,
+ *   from the maps car_lpips_forward_train left in `work`.  Only the image stack(s) asked for are walked.  packed_backward comes from
+ *   car_lpips_pack_backward (conv_w as for car_lpips_pack; car_lpips_backward_packed_floats floats), packed from car_lpips_pack.
+ * The stages; K, N are the FORWARD layer's channel counts:
+ * car_conv3x3_backward: out [n,H,W,K] = (conv_transpose3x3(D [n,H,W,N]) + add) * (act > 0), the data gradient of car_conv3x3 in the
+ *   same split arithmetic on weights packed transposed and flipped (car_conv3x3_backward_pack from the layer's [N][K][3][3];
+ *   car_conv3x3_backward_packed_floats floats, 0 when refused).  act, add [n,H,W,K] or NULL.  K = 3: the first layer, fp32, with the
+ *   scaling layer's 1 / scale; `packed` is car_conv3x3_pack's array, act and add must be NULL.
+ * car_maxpool2x2_backward: out [n,H,W,C] = (routed + add) * (act > 0), where T [n,H/2,W/2,C] is routed to the first maximal element of
+ *   each 2x2 window of act in row-major order (torch's rule); add [n,H,W,C] or NULL.
+ * car_lpips_head_backward: gf0, gf1 = HOST arrays of five device maps [B, (H >> k)(W >> k), C_k] fp32, or NULL (at least one): the
+ *   head's gradient with respect to images 0..B-1 / B..2B-1 of feats, times g [B]; fp64 arithmetic, sums in a fixed order. */
+size_t car_lpips_backward_packed_floats(void);
+int car_lpips_pack_backward(const float* const* conv_w, float* packed, void* stream);
+size_t car_lpips_train_workspace_bytes(int B, int H, int W);
+size_t car_lpips_train_layer_offset(int B, int H, int W, int l);
+int car_lpips_forward_train(const float* x, const float* y, int B, int H, int W, const float* packed, double* lpips, double* per_tap,
+                            void* work, size_t work_bytes, void* stream);
+int car_lpips_backward(const double* g, float* gx, float* gy, int B, int H, int W, const float* packed, const float* packed_backward,
+                       void* work, size_t work_bytes, void* stream);
+size_t car_conv3x3_backward_packed_floats(int K, int N);
+int car_conv3x3_backward_pack(const float* w, int K, int N, float* packed, void* stream);
+int car_conv3x3_backward(const float* D, int n, int H, int W, int K, int N, const float* packed, const float* act, const float* add,
+                         float* out, void* stream);
+int car_maxpool2x2_backward(const float* T, const float* act, const float* add, int n, int H, int W, int C, float* out, void* stream);
+int car_lpips_head_backward(const float* const* feats, int B, int H, int W, const float* lin, const double* g, float* const* gf0,
+                            float* const* gf1, void* stream);
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
