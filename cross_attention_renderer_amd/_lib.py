@@ -153,6 +153,10 @@ SIGNATURES = {
     "car_conv3x3_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "car_maxpool2x2_backward": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "car_lpips_head_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "car_frames_table_ints": (c_size_t, []),
+    "car_frames_table_slot": (c_int, [c_int, c_int]),
+    "car_frames_resize_u8": (c_int, [_P, c_size_t, _P, _P, c_int, _P, _P, c_size_t, _P]),
+    "car_frames_resize_f32": (c_int, [_P, c_size_t, _P, _P, c_int, _P, _P, c_size_t, _P, _P, c_size_t, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,6 +1,7 @@
 """Training entry point (mirrors reference experiment_scripts/train_realestate10k.py + training.py:46-246).
 
     python experiment_scripts/train_realestate10k.py --experiment_name demo --views 2 --batch_size 12 --synthetic [--gpus N] [--max_steps K]
+    python experiment_scripts/train_realestate10k.py --experiment_name demo --views 2 --data_root DIR --pose_root FILE.mat [--no_data_aug] [--num_workers N]
 
 The reference's loop, with ``training.render_train`` (HIP forward + HIP backward, csrc/car_backward.hip) in the place of
 ``model(model_input)``: Adam(lr, betas=(0.99, 0.999)) (train_realestate10k.py:93), 192 random query rays per scene (query_sparsity,
@@ -13,10 +14,16 @@ gradient clipping at norm 1 (training.py:130-134), parameters broadcast from ran
 (train_realestate10k.py:60-62, training.py:21-28: one process per GPU over RCCL), checkpoints ``{'model', 'optimizer'}`` as
 ``checkpoints/model_current.pth`` / ``model_final.pth`` (training.py:82-84, 244-246) that the eval / render scripts load.
 
-Data: the RealEstate10K training set and its augmenting reader are not available offline, so scenes are synthetic (--synthetic, the
-default here: seeded stereo pairs with a smooth random target image per scene; every step draws new rays).  The encoder trains when the
-model is built with it (--with_encoder: the pyramid then comes from ``get_z`` under autograd); otherwise the pyramid itself is a leaf
-that receives gradients, standing in for the encoder's output."""
+Data.  With --data_root DIR --pose_root FILE.mat the script trains on the RealEstate10K reader (dataio.RealEstate10k: the reference's frame
+draw, augmentation unless --no_data_aug, and ray sampling, train_realestate10k.py:74-81) through dataio.TrainLoader: --num_workers threads
+read the scenes, the raw uint8 frames of a batch go to the device in one copy and the resize / flip / crop chain runs there
+(csrc/car_frames.hip).  The encoder is built and the pyramid comes from ``get_z`` under autograd; the L1 loss uses the batch's rgb;
+--lpips and --depth work on the reader's 1024 rays per scene and its per-scene mask (1 where the rays are one 32 x 32 patch), exactly as
+loss_functions.py:102-129, so --depth needs --lpips there (the reader only yields patches under lpips); with --gpus N every rank seeds
+its loader by its rank.
+Without --data_root scenes are synthetic (--synthetic, the default: seeded stereo pairs with a smooth random target image per scene;
+every step draws new rays).  There the encoder trains when the model is built with it (--with_encoder: the pyramid then comes from
+``get_z`` under autograd); otherwise the pyramid itself is a leaf that receives gradients, standing in for the encoder's output."""
 import os
 import sys
 import time
@@ -36,6 +43,10 @@ def _parser():
     p.add_argument("--max_steps", type=int, default=20)
     p.add_argument("--steps_til_summary", type=int, default=10)
     p.add_argument("--query_sparsity", type=int, default=192)
+    p.add_argument("--no_data_aug", action="store_true", default=False, help="--data_root: read the frames without flip / crop augmentation")
+    p.add_argument("--num_workers", type=int, default=8, help="--data_root: reader threads (capped at 16)")
+    p.add_argument("--replay_batch", action="store_true", default=False,
+                   help="--data_root: train on the first batch over and over (tools/train_loader_timing.py: the step without the data wait)")
     p.set_defaults(batch_size=12, synthetic=True)
     return p
 
@@ -48,13 +59,38 @@ def train(rank, opt):
     from cross_attention_renderer_amd.training import average_gradients, render_train
     dev = common.init_rank(rank, opt)
     H, b, R = opt.img_sidelength, opt.batch_size, opt.query_sparsity
-    model = common.build_model(opt, dev).train()
+    real = bool(opt.data_root)                                    # the RealEstate10K reader; otherwise synthetic scenes, as before
+    model = common.build_model(opt, dev, with_encoder=True if real else None).train()
     params = [p for p in model.parameters() if p.requires_grad]
     if opt.gpus > 1:                                              # sync_model (train_realestate10k.py:60-62)
         for p in params:
             dist.broadcast(p.data, 0)
     g = torch.Generator().manual_seed(1234 + rank)                 # every rank shuffles on its own (train_realestate10k.py:80-81)
-    base = synthetic.stereo_scene(H, b=b, seed=5 + rank, n_view=opt.views)
+    batches = None
+    if real:
+        from cross_attention_renderer_amd import dataio
+        ds = dataio.RealEstate10k(opt.data_root, opt.pose_root, num_ctxt_views=opt.views, num_query_views=1, query_sparsity=R,
+                                  augment=not opt.no_data_aug, lpips=opt.lpips)
+        loader = dataio.TrainLoader(ds, batch_size=b, seed=1234 + rank, num_workers=opt.num_workers, device=dev, cameras=opt.cameras)
+        if len(loader) == 0:
+            raise SystemExit(f"--data_root {opt.data_root}: {len(ds)} scenes do not fill one batch of {b}")
+        if opt.lpips:
+            R = dataio.LPIPS_RAYS                                 # the reader's sampling under lpips: 1024 rays per scene, patch or not
+        if rank == 0:
+            print(f"data: RealEstate10K reader on {opt.data_root} ({len(ds)} scenes, augment {'off' if opt.no_data_aug else 'on'}, "
+                  f"{loader.num_workers} reader threads, pixel chain on the device)", flush=True)
+
+        def forever():                                            # epoch after epoch, each shuffled anew
+            if opt.replay_batch:                                  # measurement: the step without any wait for data
+                epoch = iter(loader)
+                first = next(epoch)
+                epoch.close()                                     # stops the reader's threads now, not when the generator is collected
+                while True:
+                    yield first
+            while True:
+                yield from loader
+        batches = forever()
+    base = None if real else synthetic.stereo_scene(H, b=b, seed=5 + rank, n_view=opt.views)
     z = None
     if model.encoder.__class__.__name__ == "EncoderNotBuilt":
         # torch.channels_last memory: the renderer takes such a level as a view and returns its gradient in the same layout (no copies)
@@ -76,7 +112,8 @@ def train(rank, opt):
     # the scene (context images, cameras) goes to the device ONCE; every step only draws new rays there.  (Round 3's loop rebuilt the
     # input dict on the host every step — twelve 65 536-element permutations on the CPU and a 19 MB upload of the context images — and
     # spent 100 ms per step in it; render_train itself queues a step in ~33 ms and the GPU needs ~45 ms: profiles/round4_train_step.md.)
-    base = harness.to_device(base, dev, opt.cameras)
+    if not real:
+        base = harness.to_device(base, dev, opt.cameras)
     grid = synthetic.pixel_grid(H, H).to(dev)
     gdev = torch.Generator(device=dev).manual_seed(4321 + rank)
     t0, losses, lpips_term, t_warm = time.time(), [], None, None
@@ -84,27 +121,31 @@ def train(rank, opt):
         if step == min(2, opt.max_steps - 1):                     # steady-state clock: after the first steps' allocations and builds
             torch.cuda.synchronize()
             t_warm = (time.time(), step)
-        if patches:                                              # 32 x 32 pixel patches at random corners, row-major inside a patch
+        if real:                                                 # the batch is on the device already: rays, their colours, the mask
+            inp, gt = next(batches)
+            gt_rgb, mask_scene = gt["rgb"], gt["mask"].to(torch.float32)
+        elif patches:                                            # 32 x 32 pixel patches at random corners, row-major inside a patch
             gi = grid.view(H, H, 2)
             corners = torch.randint(0, H - 31, (b, R // 1024, 2), generator=g).tolist()
             uv = torch.stack([torch.cat([gi[y0:y0 + 32, x0:x0 + 32].reshape(1024, 2) for y0, x0 in corners[sc]]) for sc in range(b)])[:, None]
         else:                                                    # R distinct random pixels per scene (query_sparsity), drawn on the device
             uv = torch.stack([grid[torch.randperm(H * H, device=dev, generator=gdev)[:R]] for _ in range(b)])[:, None]   # (b, 1, R, 2)
-        inp = {"context": base["context"], "query": dict(base["query"], uv=uv)}
-        u = inp["query"]["uv"][:, 0] / (H - 1) * 3.14159
-        feats = torch.stack([torch.sin(u[..., 0]), torch.cos(u[..., 1]), torch.sin(u[..., 0] + u[..., 1]), torch.ones_like(u[..., 0])], dim=-1)
-        gt_rgb = torch.tanh(torch.einsum("brk,bck->brc", feats, coef))[:, None]                             # (b, 1, R, 3)
+        if not real:
+            inp = {"context": base["context"], "query": dict(base["query"], uv=uv)}
+            u = inp["query"]["uv"][:, 0] / (H - 1) * 3.14159
+            feats = torch.stack([torch.sin(u[..., 0]), torch.cos(u[..., 1]), torch.sin(u[..., 0] + u[..., 1]), torch.ones_like(u[..., 0])], dim=-1)
+            gt_rgb = torch.tanh(torch.einsum("brk,bck->brc", feats, coef))[:, None]                         # (b, 1, R, 3)
         out = model(inp, z=z)                                    # train() mode under autograd = training.render_train (the reference's call, training.py:92)
         loss = (gt_rgb - out["rgb"]).abs().mean()                                                           # loss_functions.image_loss
         if opt.depth:                                            # loss_functions.py:112-127: per-patch depth variance, masked per patch
             d = out["depth_ray"][..., 0].reshape(-1, 1, 32, 32)
             mean = d.mean(dim=-1).mean(dim=-1)[:, None, None]
             dist_ = opt.l2_coeff * torch.pow(d - mean, 2).mean(dim=-1).mean(dim=-1).mean(dim=-1)
-            mask = torch.ones_like(dist_)                         # gt['mask']: every synthetic patch counts
+            mask = mask_scene if real else torch.ones_like(dist_)  # gt['mask']: every synthetic patch counts
             loss = loss + (dist_ * mask).mean()
         if opt.lpips:                                            # loss_functions.py:102-118: LPIPS(gt, pred) per patch, masked per patch
             gt_p, pred_p = gt_rgb.reshape(-1, 32, 32, 3), out["rgb"].reshape(-1, 32, 32, 3)       # channel-last, as car_lpips reads them
-            mask = torch.ones(gt_p.shape[0], device=dev)          # gt['mask']: every synthetic patch counts
+            mask = mask_scene if real else torch.ones(gt_p.shape[0], device=dev)   # gt['mask']: every synthetic patch counts
             lpips_term = harness.lpips_loss(gt_p * mask[:, None, None, None], pred_p * mask[:, None, None, None], lpips_w).mean()
             loss = loss + opt.lpips_coeff * lpips_term.to(loss.dtype)
         optimizer.zero_grad()
@@ -123,6 +164,8 @@ def train(rank, opt):
             print(f"step {step}: loss {losses[-1].item():.5f}{term}  ({(time.time() - t0) / (step + 1) * 1e3:.1f} ms/step since the start, {b} scenes x {R} rays)", flush=True)
             torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict()}, os.path.join(ckpt_dir, "model_current.pth"))
     torch.cuda.synchronize()
+    if batches is not None:
+        batches.close()                                           # stops the reader's threads
     if rank == 0:
         if t_warm is not None and opt.max_steps - t_warm[1] > 0:
             print(f"steady state: {(time.time() - t_warm[0]) / (opt.max_steps - t_warm[1]) * 1e3:.1f} ms per step over the last {opt.max_steps - t_warm[1]} steps "
@@ -135,12 +178,18 @@ def train(rank, opt):
 
 def _check(opt):
     """Refusals that need no device: they happen before any process opens one."""
+    if opt.data_root:
+        if not opt.pose_root:
+            raise SystemExit("--data_root needs --pose_root FILE.mat: the reader takes the cameras from the .mat pose table (scene name -> rows)")
+        if opt.depth and not opt.lpips:
+            raise SystemExit("--depth on --data_root needs --lpips: the depth-variance term works on 32 x 32 pixel patches "
+                             "(loss_functions.py:120-129), and the reference's reader only yields patches under lpips")
     if not opt.lpips:
         return
     if not opt.lpips_weights:
         raise SystemExit("--lpips needs --lpips_weights VGG [LIN]: the loss's forward and backward (harness.lpips_loss) run on the caller's "
                          "LPIPS weight files, and none are shipped")
-    if opt.query_sparsity % 1024:
+    if opt.query_sparsity % 1024 and not opt.data_root:           # the reader samples 1024 rays per scene under lpips whatever it says
         raise SystemExit("--lpips: the reference's LPIPS term works on 32 x 32 pixel patches (loss_functions.py:107-109): "
                          "--query_sparsity must be a multiple of 1024")
 

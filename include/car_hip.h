@@ -555,6 +555,48 @@ int car_maxpool2x2_backward(const float* T, const float* act, const float* add, 
 int car_lpips_head_backward(const float* const* feats, int B, int H, int W, const float* lin, const double* g, float* const* gf0,
                             float* const* gf1, void* stream);
 
+/* ---- training input: the pixel chain of the RealEstate10K reader on raw uint8 frames (realestate10k_dataio.py:24-59, 353-376;
+ *      dataio.resize_linear_u8 is the host statement of the same arithmetic).
+ * A batch's frames lie in ONE device buffer `src` (uint8, H x W x 3, rows `src_pitch` bytes apart).  Every image has a record: its
+ * source rectangle is read (mirrored left-right with flip = 1), resized to dst_w x dst_h by OpenCV's 8-bit INTER_LINEAR fixed-point
+ * rule (11-bit coefficients, int32 horizontal pass, vertical pass ((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2, clip), and
+ * the columns win_x0 .. win_x0 + win_w - 1 of the result are written: dense (n_idx = 0) as [dst_h, win_w, 3] at element dst_off of
+ * dst, or sparse as [n_idx, 3], pixel k being index idx[idx_off + k] (row-major in the written window, < 65536) — the full frame is
+ * then never materialised.  A rectangle as large as its destination is copied without arithmetic (the rule is the identity there).
+ * The records and indices are read twice: `*_host` by the call itself, which validates every field against src_bytes, dst_elems and
+ * n_idx_total and launches nothing on a failure, and `*_dev`, the same bytes on the device (part of the same upload as the frames),
+ * by the kernel.  One launch per call, whatever the number of images.
+ * Coefficients come from the caller (dataio._linear_coefs), so the kernels hold no floating-point coordinate arithmetic:
+ * `tables` holds car_frames_table_ints ints: CAR_FRAMES_SLOTS slots of CAR_FRAMES_SLOT_ENTRIES entries {i0, i1, w0, w1}, entry d of slot
+ * car_frames_table_slot(n_src, n_dst) for destination index d; then 256 floats, the value written for each grey level by
+ * car_frames_resize_f32 (the host's uint8 -> float32 / 127.5 - 1, bit for bit).  Slots exist for n_src = 256 - 2 p -> 256 (p = 0..31),
+ * 360 -> 256 and 640 -> 455; any other pair has no table and is refused (slot -1).
+ * car_frames_resize_u8 writes uint8 (stage A: a 360-line frame to the 256 x 256 window the centre crop keeps of 256 x 455; dst may be
+ * another part of the allocation src lies in), car_frames_resize_f32 writes float32 through the table (stage B).  The dst_elems
+ * elements at dst must not overlap the src_bytes bytes at src (blocks read the one while others write the other): an overlapping call
+ * is refused, as is a record whose `reserved` is not 0.  win_w, dst_off and the dst pointer are multiples of 4 elements. */
+#define CAR_FRAMES_SLOTS 34
+#define CAR_FRAMES_SLOT_ENTRIES 512
+typedef struct car_frame_rec {
+    long long src_off;             /* byte offset of the stored image's first pixel in src                      */
+    long long dst_off;             /* element offset of this image's output in dst                              */
+    long long idx_off;             /* sparse: offset of this image's pixel indices in idx                       */
+    int src_h, src_w, src_pitch;   /* the stored image: rows, columns, bytes per row (>= 3 src_w)               */
+    int x0, y0, rw, rh;            /* the source rectangle, inside the stored image                             */
+    int flip;                      /* 1: the rectangle is read mirrored left-right                              */
+    int dst_w, dst_h;              /* the size the rectangle is resized to                                      */
+    int win_x0, win_w;             /* the columns of the result that are written                                */
+    int n_idx;                     /* 0: dense; otherwise the number of pixels of the sparse form               */
+    int reserved;                  /* 0                                                                         */
+} car_frame_rec;
+size_t car_frames_table_ints(void);
+int car_frames_table_slot(int n_src, int n_dst);
+int car_frames_resize_u8(const unsigned char* src, size_t src_bytes, const car_frame_rec* recs_host, const car_frame_rec* recs_dev,
+                         int n_images, const int* tables, unsigned char* dst, size_t dst_elems, void* stream);
+int car_frames_resize_f32(const unsigned char* src, size_t src_bytes, const car_frame_rec* recs_host, const car_frame_rec* recs_dev,
+                          int n_images, const int* idx_host, const int* idx_dev, size_t n_idx_total, const int* tables, float* dst,
+                          size_t dst_elems, void* stream);
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
