@@ -157,6 +157,12 @@ SIGNATURES = {
     "car_frames_table_slot": (c_int, [c_int, c_int]),
     "car_frames_resize_u8": (c_int, [_P, c_size_t, _P, _P, c_int, _P, _P, c_size_t, _P]),
     "car_frames_resize_f32": (c_int, [_P, c_size_t, _P, _P, c_int, _P, _P, c_size_t, _P, _P, c_size_t, _P]),
+    "car_attention_entropy_scratch_doubles": (c_size_t, [c_long, c_int]),
+    "car_attention_entropy": (c_int, [_P, c_long, c_int, c_int, _P, _P, c_size_t, _P]),
+    "car_colormap": (c_int, [_P, c_int, c_int, c_int, c_float, _P, _P, _P]),
+    "car_epipolar_overlay": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_image_grid_scratch_floats": (c_size_t, [c_int, c_int, c_int]),
+    "car_image_grid": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, c_size_t, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

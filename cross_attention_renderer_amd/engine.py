@@ -328,6 +328,27 @@ class RenderEngine:
                 torch.cuda.current_stream().wait_event(old["done"])
         self._pf = None
 
+    _PARAMETER_CACHES = ("_packed", "_gmaps", "_plan", "_plan16", "_pairs", "_xlat", "_layer_packs")
+
+    def park_parameter_caches(self) -> dict:
+        """Sets aside everything built from the module's parameters (packed layers, plans, projected levels, lattices) and starts from
+        empty caches; returns what was set aside for ``restore_parameter_caches``.  The keys see an in-place update through the tensor's
+        _version, and torch's fused optimizers (Adam(fused=True), training.make_adam) update parameters without advancing it: a render
+        that must see the parameters as they are now — the validation pass between optimizer steps — cannot trust the keys
+        (CrossAttentionRenderer.train parks on leaving train() mode and restores on returning, so the training loop's own caches are
+        exactly what they would have been without the pass)."""
+        parked = {n: getattr(self, n) for n in self._PARAMETER_CACHES}
+        for n in self._PARAMETER_CACHES:
+            setattr(self, n, collections.defaultdict(_Cached) if n == "_layer_packs" else _Cached())
+        self.drop_prefetched()
+        return parked
+
+    def restore_parameter_caches(self, parked: dict) -> None:
+        """Puts back what ``park_parameter_caches`` set aside; what was built in between is released."""
+        self.drop_prefetched()
+        for n in self._PARAMETER_CACHES:
+            setattr(self, n, parked[n])
+
     def _projected_maps(self, maps: List[Tensor], device):
         """G_l = query_encode_latent.weight[:, ch_l] F_l per pyramid level (channel-last, C wide), plus the [C,4]
         table (W1[:, C:C+3], b1).  Recomputed only when the pyramid or the layer's parameters change."""

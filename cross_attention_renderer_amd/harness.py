@@ -322,6 +322,32 @@ def write_png(path: str, rgb: torch.Tensor) -> None:
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+_JET_SEGMENTS = (((0.00, 0, 0), (0.35, 0, 0), (0.66, 1, 1), (0.89, 1, 1), (1.00, 0.5, 0.5)),                          # red
+                 ((0.000, 0, 0), (0.125, 0, 0), (0.375, 1, 1), (0.640, 1, 1), (0.910, 0, 0), (1.000, 0, 0)),        # green
+                 ((0.00, 0.5, 0.5), (0.11, 1, 1), (0.34, 1, 1), (0.65, 0, 0), (1.00, 0, 0)))                       # blue
+_jet_lut = None
+
+
+def jet_lut() -> torch.Tensor:
+    """The 256-entry "jet" table as a (256, 3) float32 CPU tensor, for ``car_colormap`` (summaries.colormap): matplotlib's lookup-table
+    construction restated — each channel's piecewise-linear segments (x, y below, y above) sampled at ``linspace(0, 1, 256)`` in
+    float64, the first and last entries taken from the end segments, clipped to [0, 1] — then cast to float32.  Equal to
+    ``matplotlib.pyplot.get_cmap("jet")``'s table entry for entry after the cast (tests/test_summaries_cpu.py)."""
+    global _jet_lut
+    if _jet_lut is None:
+        import numpy as np
+        n, cols = 256, []
+        for segments in _JET_SEGMENTS:
+            seg = np.array(segments, dtype=np.float64)
+            x, below, above = seg[:, 0] * (n - 1), seg[:, 1], seg[:, 2]
+            at = (n - 1) * np.linspace(0, 1, n)
+            hi = np.searchsorted(x, at)[1:-1]
+            frac = (at[1:-1] - x[hi - 1]) / (x[hi] - x[hi - 1])
+            cols.append(np.clip(np.concatenate([[above[0]], frac * (below[hi] - above[hi - 1]) + above[hi - 1], [below[-1]]]), 0.0, 1.0))
+        _jet_lut = torch.from_numpy(np.stack(cols, axis=-1).astype(np.float32))
+    return _jet_lut
+
+
 def synthetic_pair(H: int, n_view: int, seed: int = 5):
     """A seeded stereo pair + feature pyramid standing in for a dataset item and ``get_z`` (no dataset / encoder here)."""
     inp = synthetic.stereo_scene(H, b=1, seed=seed, n_view=n_view)

@@ -155,6 +155,19 @@ class CrossAttentionRenderer(nn.Module):
             raise ValueError(f"render_precision must be 'fp32' or 'fp16' (got {value!r})")
         self._render_precision = value
 
+    def train(self, mode: bool = True):
+        """Leaving train() mode for eval() — the validation pass between optimizer steps (summaries.render_full) — sets aside what the
+        engine built from the parameters and renders from empty caches: torch's fused optimizers update parameters without advancing
+        ``_version``, which the engine's cache keys rely on (engine.RenderEngine.park_parameter_caches).  Returning to train() mode puts
+        the training loop's caches back as they were.  A module that was never in train() mode is not touched."""
+        engine = getattr(self, "_engine", None)
+        if engine is not None and self.training and not mode:
+            self._parked_caches = engine.park_parameter_caches()
+        elif engine is not None and not self.training and mode and getattr(self, "_parked_caches", None) is not None:
+            engine.restore_parameter_caches(self._parked_caches)
+            self._parked_caches = None
+        return super().train(mode)
+
     # ------------------------------------------------------------------------------------------
     def get_z(self, input, val=False) -> List[Tensor]:
         """Feature pyramid of the context views, NCHW (models.py:148-188).  Stock PyTorch by design."""

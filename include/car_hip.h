@@ -597,6 +597,45 @@ int car_frames_resize_f32(const unsigned char* src, size_t src_bytes, const car_
                           int n_images, const int* idx_host, const int* idx_dev, size_t n_idx_total, const int* tables, float* dst,
                           size_t dst_elems, void* stream);
 
+/* ---- training summaries (training.py:110-115, summaries.py:15-141; csrc/car_summary.hip).  fp32 channel-last images,
+ * caller-owned scratch, no float atomics, sums in a fixed order: the same input gives the same bits.
+ *
+ * car_attention_entropy: at_wt [rows][S] fp32, 1 <= S <= 768.  Per row ent = -sum_j w_j * logf(w_j + 1e-5f), the terms formed in fp32
+ * as the reference's torch expression forms them and added in fp64; *sum (a DEVICE double) receives the sum over the rows — a caller
+ * that renders in chunks adds the sums and divides once.  nan_rows_zero = 1: a row whose entropy is NaN contributes 0 and still
+ * counts in the mean (training.py:112-114); 0: the NaN propagates (summaries.py:25-26).  Two launches; scratch:
+ * car_attention_entropy_scratch_doubles(rows, S) doubles (0, with a message, for a shape the entry refuses).
+ *
+ * car_colormap: x [N][H][W] fp32 -> out [N][H][W][3] through the caller's table lut [256][3], as matplotlib's Colormap.__call__ on a
+ * float array does with t = x / scale (an fp32 division): 0 <= t < 1 -> entry trunc(t * 256), t == 1 -> 255, t > 1 -> entry 255
+ * ("over"), t < 0 -> entry 0 ("under"), NaN -> (0, 0, 0) ("bad").
+ *
+ * car_epipolar_overlay: the epipolar panel of summaries.py:72-136.  trgt [B][H][W][3]; ctxt [B * V][H][W][3] scene-major, view-minor;
+ * pixel_val [B * V][rays][S][2]; at_wt_max [B * V][rays] int64; uv [B][rays][2]; only ray `probe` of each is read (0 <= probe <
+ * rays; the reference fixes 2065).  panel [B + B * V][H][W][3]: the B target tiles, then the context tiles view-major.  With
+ * pix = H / 64 + 1 a square around (x, y) spans rows [max(y - pix, 0), min(y + pix, H - 1)) and the matching columns.  A target
+ * pixel is -1 inside the square around (int(uv.x), int(uv.y)); a pixel of scene s's view-k tile is -1 inside the square of that
+ * view's arg-max sample, else 0 inside any of its samples' squares; every other pixel is the input's.  Sample centres are
+ * x = int(clip((v.x + 1) / 2, 0, 1) * (W - 1)), y likewise with H, in fp32.  A NaN sample or an arg-max index outside [0, S) paints
+ * nothing.
+ *
+ * car_image_grid: torchvision.utils.make_grid(x, normalize=True, scale_each=...) with nrow = 8, padding = 2, pad_value = 0, restated
+ * from its documented behaviour.  x [N][H][W][3], with clamp != 0 first clamped to [lo, hi]; out planar [3][Hg][Wg], where with
+ * xm = min(8, N), ym = ceil(N / xm): Hg = (H + 2) ym + 2, Wg = (W + 2) xm + 2 and image k starts at row (k / xm)(H + 2) + 2, column
+ * (k % xm)(W + 2) + 2; N == 1 gives the normalised image itself, [3][H][W].  low / high: the min / max of the clamped input over
+ * everything, or per image with scale_each; out = (clamp(x, low, high) - low) / max(high - low, 1e-5), the span formed in fp64 and
+ * rounded to fp32 as make_grid's Python floats are.  A NaN inside the reduced range makes the affected images NaN.  Two launches;
+ * scratch: car_image_grid_scratch_floats(N, H, W) floats (0, with a message, for a shape the entry refuses). */
+size_t car_attention_entropy_scratch_doubles(long rows, int S);
+int car_attention_entropy(const float* at_wt, long rows, int S, int nan_rows_zero, double* sum, double* scratch, size_t scratch_doubles,
+                          void* stream);
+int car_colormap(const float* x, int N, int H, int W, float scale, const float* lut, float* out, void* stream);
+int car_epipolar_overlay(const float* trgt, const float* ctxt, const float* pixel_val, const long long* at_wt_max, const float* uv, int B,
+                         int V, int H, int W, int rays, int probe, int S, float* panel, void* stream);
+size_t car_image_grid_scratch_floats(int N, int H, int W);
+int car_image_grid(const float* x, int N, int H, int W, int scale_each, int clamp, float lo, float hi, float* out, float* scratch,
+                   size_t scratch_floats, void* stream);
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
