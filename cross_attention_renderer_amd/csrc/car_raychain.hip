@@ -373,7 +373,11 @@ int launch_chain(bool tail, const float* arena, const unsigned* offs, const int*
     a.arena = arena; a.bias = bias; a.scale = scale; a.n_chunks = n_chunks;
     for (int i = 0; i < kMaxLayers; ++i) a.layer[i] = i < n_layers ? layers[i] : 0;
     for (int i = 0; i < n_layers; ++i) CAR_REQUIRE(layers[i] >= 0 && layers[i] < kMaxLayers, "car_ray_chain: bad scale slot");
-    for (int i = 0; i < n_chunks; ++i) { a.chunk[i].off = offs[i]; a.chunk[i].nt = nts[i]; }
+    for (int i = 0; i < n_chunks; ++i) {
+        // a buffer of the ring holds kMaxNT tiles, and Stream::landed counts the loads of a chunk of 1, 4 or 9 tiles
+        CAR_REQUIRE(nts[i] == 1 || nts[i] == 4 || nts[i] == 9, "car_ray_chain: chunk %d has %d tiles (1, 4 or 9)", i, nts[i]);
+        a.chunk[i].off = offs[i]; a.chunk[i].nt = nts[i];
+    }
     a.x0 = x0; a.ld0 = ld0; a.x1 = x1; a.ld1 = ld1; a.z1_in = z1_in; a.out0 = out0; a.out1 = out1; a.rays = (const CarRay*)rays;
     a.M = M; a.V = V; a.R = R; a.zscale = zscale;
     const size_t lds_bytes = (size_t)kRing * kBufFloats * sizeof(float);

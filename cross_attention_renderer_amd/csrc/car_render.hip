@@ -85,7 +85,7 @@ struct Work {
 // the buffers car_workspace_find hands out (include/car_hip.h lists them)
 const struct { const char* name; Span Work::*buf; } kFindable[] = {
     {"rays", &Work::rays}, {"e", &Work::e}, {"g", &Work::g}, {"logit", &Work::logit}, {"logit2", &Work::logit2}, {"pt", &Work::pt},
-    {"at_wt2", &Work::at_wt2}, {"ebar", &Work::ebar}, {"z1", &Work::z1}, {"uh", &Work::uh}, {"part", &Work::part}};
+    {"at_wt2", &Work::at_wt2}, {"ebar", &Work::ebar}, {"z1", &Work::z1}, {"uh", &Work::uh}, {"part", &Work::part}, {"phi_x", &Work::phi_x}};
 // step groups per (view, ray) of the first round's partial sums (car_fused_samples_parts)
 inline size_t step_groups(const car_dims& d) { const int ts = car_fused_tile_steps(); return (size_t)((d.P + ts - 1) / ts); }
 Work work_layout(const car_dims& d) {

@@ -467,7 +467,7 @@ int car_plan_f16_build(const car_dims* dims, const car_weights* weights, void* p
 int car_render_forward_f16(const car_dims* dims, const void* plan, const void* plan16, const car_inputs* in, const car_outputs* out,
                            void* workspace, size_t workspace_bytes, int phases, void* stream);
 /* Where a named intermediate lives inside the workspace after car_render_forward (tests, debugging, profiling): one of
- * "rays" "e" "g" "logit" "logit2" "pt" "at_wt2" "ebar" "z1" "uh" "part".  Returns 0 and the float offset / count. */
+ * "rays" "e" "g" "logit" "logit2" "pt" "at_wt2" "ebar" "z1" "uh" "part" "phi_x".  Returns 0 and the float offset / count. */
 int car_workspace_find(const car_dims* dims, const char* name, size_t* offset_floats, size_t* n_floats);
 
 /* ---- stage timing (the reference's only hooks are record_function labels, resnet_block_fc.py:54, 139, and one time.time() pair,
