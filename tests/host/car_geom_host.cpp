@@ -32,6 +32,24 @@ void host_sample_setup(const CarPose* poses, const CarRay* rays, const float* in
         }
 }
 
+// no_sample = 1 (sample_kernel of csrc/car_geometry.hip, the fused kernel's own geometry): a sample is the projection of the query ray's
+// point at depth steps[p]
+void host_sample_setup_depth(const CarPose* poses, const CarRay* rays, const float* steps, int b, int V, int R,
+                             int P, int H, int W, CarSample* out) {
+    for (int n = 0; n < b * V; ++n)
+        for (int r = 0; r < R; ++r) {
+            const CarRay& ray = rays[(size_t)n * R + r];
+            const CarPose& Ps = poses[n];
+            for (int p = 0; p < P; ++p) {
+                CarSample* S = out + ((size_t)n * R + r) * P + p;
+                const float s = steps[p];
+                const float q[3] = {Ps.q_rel[3] + s * ray.d[0], Ps.q_rel[7] + s * ray.d[1], Ps.q_rel[11] + s * ray.d[2]};
+                car_project_grid(Ps.kc, q, H, W, S->grid);
+                car_sample_setup(Ps, poses + (n / V) * V, ray, V, H, W, S);
+            }
+        }
+}
+
 void host_bilinear_taps(const float* grid, int n, int W, int H, int mode, int* idx, float* w) {
     for (int i = 0; i < n; ++i) car_bilinear_taps(grid[2 * i], grid[2 * i + 1], W, H, mode, idx + 4 * i, w + 4 * i);
 }
