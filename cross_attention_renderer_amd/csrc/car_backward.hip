@@ -631,6 +631,8 @@ extern "C" int car_gather_bilinear_backward(float* const* dmaps, const int* leve
     for (int l = n_levels; l < CAR_MAX_LEVELS; ++l) { L.map[l] = nullptr; L.c[l] = L.h[l] = L.w[l] = 0; if (l > n_levels) L.q0[l] = q; }
     CAR_REQUIRE(ld_out % 4 == 0 && col_out % 4 == 0 && col_out >= 0 && col_out + 4 * q <= ld_out,
                 "car_gather_bilinear_backward: window [%d,%d) must be float4-aligned inside a row of %d", col_out, col_out + 4 * q, ld_out);
+    for (int l = 0; l < n_levels; ++l)
+        CAR_REQUIRE((long)n_maps * level_h[l] * level_w[l] < 2147483647L, "car_gather_bilinear_backward: level %d too large for 32-bit texel indices", l);
     (void)hipGetLastError();
     hipLaunchKernelGGL(gather_bwd_kernel, dim3(grid_for((long)n_maps * pts * q * 4)), dim3(256), 0, (hipStream_t)stream, L, n_maps, grid, pts, mode, place, V,
                        dout, ld_out, col_out);

@@ -258,7 +258,8 @@ extern "C" int car_gather_bilinear(const float* const* maps, const int* level_c,
     for (int l = n_levels; l < CAR_MAX_LEVELS; ++l) { L.map[l] = nullptr; L.c[l] = L.h[l] = L.w[l] = 0; if (l > n_levels) L.q0[l] = q; }
     CAR_REQUIRE(ld_out % 4 == 0 && col_out % 4 == 0 && col_out >= 0 && col_out + 4 * q <= ld_out,
                 "car_gather_bilinear: output window [%d,%d) must be float4-aligned inside a row of %d", col_out, col_out + 4 * q, ld_out);
-    CAR_REQUIRE((long)n_maps * level_h[0] * level_w[0] < 2147483647L, "car_gather_bilinear: map too large for 32-bit texel indices");
+    for (int l = 0; l < n_levels; ++l)                                    // every level: a later one may be the larger
+        CAR_REQUIRE((long)n_maps * level_h[l] * level_w[l] < 2147483647L, "car_gather_bilinear: level %d too large for 32-bit texel indices", l);
     if (run < 1 || pts % run != 0) run = 1;
     return launch_gather(L, n_maps, grid, pts, run, mode, place, V, out, ld_out, col_out, stream);
 }

@@ -2,11 +2,16 @@
 //
 // All functions are `__host__ __device__` inline so that (a) the stand-alone stage kernels and the fused
 // kernels execute literally the same arithmetic and (b) the same code can be compiled by g++ into a tiny
-// host shim for CPU-side unit tests (tests/host/).  The translation units that include this header are
-// compiled with -ffp-contract=off: every fused multiply-add below is written explicitly (fmaf / fma) at
-// exactly the places where the reference's CPU kernels fuse (small MKL bmm chains, torch.cross,
-// vector_norm), so that the fp32 quantities feeding the fp64 Pluecker intersection are reproduced to the
-// last bit wherever IEEE arithmetic allows it.
+// host shim for CPU-side unit tests (tests/host/).  Every fused multiply-add below is written explicitly
+// (fmaf / fma) at exactly the places where the reference's CPU kernels fuse (small MKL bmm chains,
+// torch.cross, vector_norm), so that the fp32 quantities feeding the fp64 Pluecker intersection are
+// reproduced to the last bit wherever IEEE arithmetic allows it — in a unit built with -ffp-contract=off.
+// NOT every unit that includes this header is: the build gives the flag to car_geometry.hip,
+// car_gather.hip, car_fused.hip and car_scatter.hip (and the host shim); the other units that include
+// it, car_backward.hip, car_encode.hip, car_lattice.hip and car_linear16.hip among them, are built with
+// the compiler's default, which contracts.  Only the three tap functions (car_bilinear_taps_px, car_bilinear_taps, car_lattice_taps)
+// switch contraction off in their own bodies and so compute the same bits in every unit; everything else
+// here (car_sample_setup and the rest of the geometry) is bit-exact only under its unit's flag.
 //
 // Reference behaviour restated here (yilundu/cross_attention_renderer):
 //   query rays           geometry.py:236-245, 353-371, 409-433   (plucker_embedding / lift / get_ray_directions)
@@ -318,9 +323,14 @@ CAR_HD void car_sample_setup(const CarPose& P, const CarPose* poses_of_scene, co
 // Returns the four (clamped, always addressable) texel indices y*W+x and their weights; a tap that falls
 // outside the map has weight 0.  Coordinates may be ~1e10 (geometry.project scrubbing): the float->int
 // conversion is guarded.
+// The three tap functions switch contraction off themselves: a forward and a backward kernel must agree on ix to the last
+// bit (the scatter is the adjoint of the gather only with the gather's own weights), whatever flags their unit is built with.
 // ----------------------------------------------------------------------------------------------------
 // ... from texel coordinates (ix, iy): texel i has its centre at i
 CAR_HD void car_bilinear_taps_px(float ix, float iy, int W, int H, int mode, int* idx, float* w) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     if (mode == 0) {
         ix = fminf(fmaxf(ix, 0.0f), (float)(W - 1));
         iy = fminf(fmaxf(iy, 0.0f), (float)(H - 1));
@@ -343,6 +353,9 @@ CAR_HD void car_bilinear_taps_px(float ix, float iy, int W, int H, int mode, int
     idx[3] = cy1 * W + cx1; w[3] = (vx1 && vy1) ? wx1 * wy1 : 0.0f;    // se
 }
 CAR_HD void car_bilinear_taps(float gx, float gy, int W, int H, int mode, int* idx, float* w) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     car_bilinear_taps_px(((gx + 1.0f) * (float)W - 1.0f) / 2.0f, ((gy + 1.0f) * (float)H - 1.0f) / 2.0f, W, H, mode, idx, w);
 }
 
@@ -360,6 +373,9 @@ CAR_HD void car_bilinear_taps(float gx, float gy, int W, int H, int mode, int* i
 // Flag 4: on / beyond the outer ring.
 // ----------------------------------------------------------------------------------------------------
 CAR_HD void car_lattice_taps(float gx, float gy, int lw, int lh, int pad, float sx, float sy, int* node, int* flags, float* w) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     float ux = (gx + 1.0f) * sx - 1.0f, uy = (gy + 1.0f) * sy - 1.0f;
     const float lox = -(float)pad, hix = (float)(lw - 1 - pad), loy = -(float)pad, hiy = (float)(lh - 1 - pad);
     if (!(ux > lox)) ux = lox;                                         // also NaN

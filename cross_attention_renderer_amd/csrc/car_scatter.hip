@@ -229,6 +229,8 @@ extern "C" int car_gather_bilinear_backward_binned(float* const* dmaps, const in
         CAR_REQUIRE(places[j] == CAR_PLACE_PLAIN || places[j] == CAR_PLACE_OWN || (places[j] == CAR_PLACE_OTHER2 && V == 2 && n_maps % 2 == 0),
                     "car_gather_bilinear_backward_binned: bad placement %d for V=%d", places[j], V);
     }
+    for (int l = 0; l < n_levels; ++l)
+        CAR_REQUIRE((long)n_maps * level_h[l] * level_w[l] < 2147483647L, "car_gather_bilinear_backward_binned: level %d too large for 32-bit texel indices", l);
     const long n = (long)n_maps * t0 + 1;                                  // one counter per texel and a closing one
     const long recs = (long)n_gathers * n_maps * pts * n_levels * 4;
     CAR_REQUIRE(n < (1l << 31) && recs < (1l << 32) && (long)n_maps * pts * (V > 0 ? V : 1) < (1l << 31),
