@@ -87,6 +87,7 @@ SIGNATURES = {
     "car_round2q_packed_floats": (c_size_t, []),
     "car_round2q_bias_floats": (c_size_t, []),
     "car_round2_logits_from_g": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_attend_round2": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
     "car_round2q_pack": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "car_fused_pack": (c_int, [ctypes.POINTER(CarWeights), _P, _P, _P, _P]),
     "car_round2_pack": (c_int, [_P, _P, _P, _P, _P, _P, _P]),

@@ -62,3 +62,6 @@ struct car_lattice { int h, w, pad, r[CAR_MAX_LEVELS]; bool ok; };
 CAR_INTERNAL car_lattice car_lattice_of(const car_dims& d);
 CAR_INTERNAL int car_launch_merge(const float* const* levels, const int* hs, const int* ws, const int* rs, int n_levels, int lh, int lw, int pad, int n_maps,
                                   float* lattice, unsigned* gmax, hipStream_t st, const char* who);
+// car_round2_attend.hip: whether car_attend_round2 takes the shape (the one-call forward asks before it chooses between the merged second
+// round and the two launches)
+CAR_INTERNAL bool car_attend_round2_supports(int D, int V, int P);

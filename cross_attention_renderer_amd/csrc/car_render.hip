@@ -337,9 +337,10 @@ extern "C" int car_project_maps(const car_dims* dims, const void* plan, const fl
 // entry: the C entry's name, for the message about `phases`
 static int render_phases(const char* entry, const car_dims* dims, const void* plan, const car_inputs* in, const car_outputs* out,
                          void* workspace, size_t workspace_bytes, int phases, void* stream, const void* plan16 = nullptr) {
-    const int which = phases & ~CAR_PHASE_ROWS_FIRST_ROUND;
+    const int which = phases & ~(CAR_PHASE_ROWS_FIRST_ROUND | CAR_PHASE_SPLIT_SECOND_ROUND);
     CAR_REQUIRE(which == CAR_PHASE_SAMPLES || which == CAR_PHASE_RAYS || which == (CAR_PHASE_SAMPLES | CAR_PHASE_RAYS),
-                "%s: phases = %d (CAR_PHASE_SAMPLES, CAR_PHASE_RAYS or both, optionally | CAR_PHASE_ROWS_FIRST_ROUND)", entry, phases);
+                "%s: phases = %d (CAR_PHASE_SAMPLES, CAR_PHASE_RAYS or both, optionally | CAR_PHASE_ROWS_FIRST_ROUND | CAR_PHASE_SPLIT_SECOND_ROUND)",
+                entry, phases);
     CAR_TRY(check_dims(dims, "car_render_forward"));
     CAR_REQUIRE(plan && in && out && workspace, "car_render_forward: null pointer");
     CAR_REQUIRE(in->poses && in->uv && in->lattice && in->gmeta && out->rgb, "car_render_forward: poses, uv, lattice, gmeta and rgb are required");
@@ -413,15 +414,23 @@ static int render_phases(const char* entry, const car_dims* dims, const void* pl
             const int layers[3] = {0, 1, 2};
             CAR_TRY(car_ray_mid(pl, offs, nts, nch, pl + p.mid_bias, pl + p.chain_scale, layers, 3, ws + w.ebar.off, kC, ws + w.z1.off, ws + w.uh.off, BR, stream));
         }
-        {   // a15, per sample: second-round query and logits
-            Stage stage("round2_logits", st);
-            // no 128-wide query rows exist on this route: <q2, qry> is a bilinear form of two hidden vectors both made from g (car_round2.hip)
-            CAR_TRY(car_round2_logits_from_g(ws + w.g.off, ws + w.uh.off, pl + p.r2qw, pl + p.r2qb, b, V, R, P, ws + w.logit2.off, stream));
-        }
-        {
+        if (!(phases & CAR_PHASE_SPLIT_SECOND_ROUND) && car_attend_round2_supports(kC, V, P)) {
+            // a15 per sample + the second round's softmax and value average in one launch: the logits are made on the matrix pipe under the
+            // stream of e and never reach memory (car_round2_attend.hip; the workspace keeps its logit2 slot, unused here)
             Stage stage("attend_2", st);
-            CAR_TRY(car_attend(ws + w.logit2.off, nullptr, kD, ws + w.e.off, kC, b, V, R, P, nullptr, 0.0f, ws + w.at_wt2.off, ws + w.ebar.off, kC, 1, nullptr,
-                               nullptr, nullptr, nullptr, stream));
+            CAR_TRY(car_attend_round2(ws + w.g.off, ws + w.uh.off, pl + p.r2qw, pl + p.r2qb, ws + w.e.off, kC, b, V, R, P, ws + w.at_wt2.off, ws + w.ebar.off, kC,
+                                      nullptr, stream));
+        } else {
+            {   // a15, per sample: second-round query and logits
+                Stage stage("round2_logits", st);
+                // no 128-wide query rows exist on this route: <q2, qry> is a bilinear form of two hidden vectors both made from g (car_round2.hip)
+                CAR_TRY(car_round2_logits_from_g(ws + w.g.off, ws + w.uh.off, pl + p.r2qw, pl + p.r2qb, b, V, R, P, ws + w.logit2.off, stream));
+            }
+            {
+                Stage stage("attend_2", st);
+                CAR_TRY(car_attend(ws + w.logit2.off, nullptr, kD, ws + w.e.off, kC, b, V, R, P, nullptr, 0.0f, ws + w.at_wt2.off, ws + w.ebar.off, kC, 1, nullptr,
+                                   nullptr, nullptr, nullptr, stream));
+            }
         }
     } else if (hipMemsetAsync(ws + w.z1.off, 0, sizeof(float) * BR * kE, st) != hipSuccess) {       // no second round: z = Wv ebar1 + bv
         car_set_error("car_render_forward: memset failed");

@@ -142,6 +142,9 @@ class RenderEngine:
         # one-call route: the first attention round folds the fused kernel's per-step-group partial sums (default); False = it streams
         # the rows of e as in rounds 1-4 (CAR_PHASE_ROWS_FIRST_ROUND: A/B measurements and tests)
         self.first_round_parts = True
+        # one-call route: the second attention round in one launch (car_attend_round2, default wherever P % 32 == 0); False = logits and
+        # attention as two launches (CAR_PHASE_SPLIT_SECOND_ROUND: A/B measurements and tests)
+        self.second_round_merged = True
         self.wgrad_fp32 = False        # training: True keeps the wide layers' weight gradients on the fp32 matrix pipe (CAR_WGRAD_FP32) instead of bf16 x 3
         self.fuse_kq = True            # staged route: key / query chains and the first round's logits in one kernel (car_key_query_logits); False = five launches (A/B)
         # three-view exchange, first + second layer: "rows" = the fused per-sample kernel's source pass over the rows (car_fused_rows, default);
@@ -614,7 +617,7 @@ class RenderEngine:
         lh, lw, _ = self._lattice_shape(d_all)
         lattice_scene = V * 2 * lh * lw * 576                                                    # floats per scene
 
-        phases = 1 | 2 | (0 if self.first_round_parts else 4)
+        phases = 1 | 2 | (0 if self.first_round_parts else 4) | (0 if self.second_round_merged else 8)
 
         def ws_bytes(nb, nr):
             return lib.car_workspace_bytes(ctypes.byref(self._dims(nb, nr, z)))

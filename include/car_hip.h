@@ -276,6 +276,13 @@ size_t car_round2q_packed_floats(void);
 size_t car_round2q_bias_floats(void);
 int car_round2_logits_from_g(const float* g, const float* uh, const float* wpacked, const float* bias, int b, int V, int R, int P,
                              float* logit, void* stream);
+/* The whole second round in one launch: the logits of car_round2_logits_from_g, the softmax over the ray's V*P samples and
+ * z_out = sum_s w_s val_s, as car_attend (qb, zprev, pt NULL; reps = 1) computes them from those logits — w_out and z_out bit for bit.
+ * The logits are computed on the matrix pipe under the HBM stream of the value rows and never leave the chip: logit_out [b*V,R,P] may
+ * be NULL (tests pass a buffer to see them).  val [b*V,R,P,D]; w_out [b*V,R,P]; z_out [b,R,ld_z].  Takes D = 576, P % 32 == 0 and
+ * V*P within car_attend's limit; any other shape is refused (CAR_E_ARG) before anything is launched — the two entries above take it. */
+int car_attend_round2(const float* g, const float* uh, const float* wpacked, const float* bias, const float* val, int D, int b, int V,
+                      int R, int P, float* w_out, float* z_out, int ld_z, float* logit_out, void* stream);
 
 /* r[row, c] = relu(r[row, c] + u[ray(row), c]) with ray(row) = scene b, ray r of the sample row (models.py:549-553:
  * the z_embed half of query_repeat_embed is constant along the samples of a ray). r [b*V,R,P,C], u [b,R,C]. */
@@ -445,10 +452,14 @@ int car_render_forward(const car_dims* dims, const void* plan, const car_inputs*
  * workspaces are independent.  phases = both is car_render_forward.
  * CAR_PHASE_ROWS_FIRST_ROUND (a flag OR-ed onto both phases of a batch): the first attention round streams the rows of e
  * (car_fused_samples + car_attend, the form of rounds 1-4) instead of folding the fused kernel's per-step-group partial sums
- * (car_fused_samples_parts + car_attend_parts, the default) — kept for A/B measurements and tests; same results to fp32 rounding. */
+ * (car_fused_samples_parts + car_attend_parts, the default) — kept for A/B measurements and tests; same results to fp32 rounding.
+ * CAR_PHASE_SPLIT_SECOND_ROUND (a flag, OR-ed on the same way): the second round runs as car_round2_logits_from_g + car_attend, two
+ * launches with the logits in the workspace, instead of the one launch of car_attend_round2 (the default wherever it takes the shape:
+ * P % 32 == 0) — kept for A/B measurements and tests; the same results bit for bit. */
 #define CAR_PHASE_SAMPLES 1
 #define CAR_PHASE_RAYS 2
 #define CAR_PHASE_ROWS_FIRST_ROUND 4
+#define CAR_PHASE_SPLIT_SECOND_ROUND 8
 int car_render_forward_phase(const car_dims* dims, const void* plan, const car_inputs* in, const car_outputs* out,
                              void* workspace, size_t workspace_bytes, int phases, void* stream);
 /* Opt-in fp16 render precision of the same forward.  Off unless a host asks for it; the entries above are unchanged.
