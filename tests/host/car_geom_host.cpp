@@ -50,6 +50,81 @@ void host_sample_setup_depth(const CarPose* poses, const CarRay* rays, const flo
         }
 }
 
+// host_ray_setup_depth, host_xenc, host_project_points and host_exchange_rows below are HAND COPIES of kernel bodies of csrc/car_geometry.hip
+// (the loops around the header's functions live in the kernels, not in car_geom.h).  A CPU test through them pins the header's functions
+// they call and this copy of the loop — not the kernel's own loop, index arithmetic or strict comparisons: only tests/test_geometry_hip.py,
+// which runs the kernels against the same restatement, pins those.
+// no_sample = 1 of ray_kernel (csrc/car_geometry.hip): uniform depths on the query ray; overlaps = some sample strictly inside; the first and
+// the last sample are start and end
+void host_ray_setup_depth(const CarPose* poses, const float* uv, const float* depth_steps, int b, int V, int R, int H, int W, int P,
+                          CarRay* out) {
+    for (int n = 0; n < b * V; ++n)
+        for (int r = 0; r < R; ++r) {
+            const CarPose& Ps = poses[n];
+            const float* p2 = uv + 2 * ((n / V) * R + r);
+            CarRay ray;
+            car_pixel_ray(Ps.q_rel, Ps.kq, p2[0], p2[1], ray.d, ray.m);
+            const float o[3] = {Ps.q_rel[3], Ps.q_rel[7], Ps.q_rel[11]};
+            bool any_in = false;
+            float first[2] = {0, 0}, last[2] = {0, 0};
+            for (int p = 0; p < P; ++p) {
+                const float s = depth_steps[p];
+                const float q[3] = {o[0] + s * ray.d[0], o[1] + s * ray.d[1], o[2] + s * ray.d[2]};
+                float gg[2];
+                car_project_grid(Ps.kc, q, H, W, gg);
+                any_in = any_in || (gg[0] < 1.0f && gg[0] > -1.0f && gg[1] < 1.0f && gg[1] > -1.0f);
+                if (p == 0) { first[0] = gg[0]; first[1] = gg[1]; }
+                last[0] = gg[0]; last[1] = gg[1];
+            }
+            ray.start[0] = first[0]; ray.start[1] = first[1];
+            ray.end[0] = last[0]; ray.end[1] = last[1];
+            ray.overlaps = any_in ? 1.0f : 0.0f;
+            ray.pad = 0.0f;
+            out[(size_t)n * R + r] = ray;
+        }
+}
+
+// the xenc window of sample_kernel: V == 1: tanh(pt / 5), tanh(pt / 100) (6 wide); otherwise tanh(pt_in[s] / 5) per view (3 wide)
+void host_xenc(const CarSample* samples, long n, int V, float* xenc) {
+    for (long i = 0; i < n; ++i) {
+        const CarSample& S = samples[i];
+        if (V == 1) {
+            for (int k = 0; k < 3; ++k) { xenc[6 * i + k] = tanhf(S.pt[k] / 5.0f); xenc[6 * i + 3 + k] = tanhf(S.pt[k] / 100.0f); }
+        } else {
+            for (int s = 0; s < V; ++s)
+                for (int k = 0; k < 3; ++k) xenc[(i * V + s) * 3 + k] = tanhf(S.pt_in[s][k] / 5.0f);
+        }
+    }
+}
+
+// project_points_kernel
+void host_project_points(const CarPose* poses, const float* pts, int n_scenes, long npts, int V, int view, int H, int W, float* grid) {
+    for (long i = 0; i < (long)n_scenes * npts; ++i) {
+        const int sc = (int)(i / npts);
+        car_project_grid(poses[sc * V + view].kc, pts + 3 * i, H, W, grid + 2 * i);
+    }
+}
+
+// exchange_rows_kernel
+void host_exchange_rows(const CarPose* poses, const float* pixel_val, const float* pt_in, const float* ptenc, int n_scenes, int V, long pts,
+                        int H, int W, int* row_src, float* row_grid, float* row_pe) {
+    for (long idx = 0; idx < (long)n_scenes * V * pts * V; ++idx) {
+        const int k = (int)(idx % V);
+        const long sj = idx / V;
+        const long j = sj % pts;
+        const int n = (int)(sj / pts), c = n % V, sc = n / V;
+        const int o = k == 0 ? c : (k - 1 < c ? k - 1 : k);
+        const long so = ((long)(sc * V + o) * pts + j);
+        float g2[2];
+        if (k == 0) { g2[0] = pixel_val[2 * so]; g2[1] = pixel_val[2 * so + 1]; }
+        else car_project_grid(poses[sc * V + o].kc, pt_in + (so * V + c) * 3, H, W, g2);
+        row_src[idx] = (sc * V + o) | (k == 0 ? 0 : (1 << 30));
+        row_grid[2 * idx] = g2[0]; row_grid[2 * idx + 1] = g2[1];
+        const float* pe = ptenc + (so * V + c) * 4;
+        row_pe[4 * idx] = pe[0]; row_pe[4 * idx + 1] = pe[1]; row_pe[4 * idx + 2] = pe[2]; row_pe[4 * idx + 3] = 0.0f;
+    }
+}
+
 void host_bilinear_taps(const float* grid, int n, int W, int H, int mode, int* idx, float* w) {
     for (int i = 0; i < n; ++i) car_bilinear_taps(grid[2 * i], grid[2 * i + 1], W, H, mode, idx + 4 * i, w + 4 * i);
 }
