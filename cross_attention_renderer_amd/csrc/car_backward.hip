@@ -165,12 +165,8 @@ int launch_wgrad_tile(const float* dY, int ldy, const float* X, int ldx, long M,
     CAR_REQUIRE(gz <= 65535, "car_linear_wgrad: too many row slabs");
     const size_t lds_bytes = (size_t)2 * kWtRows * (WN + WK) * sizeof(float);
     auto kern = wgrad_tile_kernel<TN, TK>;
-    hipError_t e1 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e1 != hipSuccess) { car_set_error("car_linear_wgrad: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e1)); return CAR_E_LAUNCH; }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(gx, gy, gz), dim3(256), lds_bytes, (hipStream_t)stream, dY, ldy, X, ldx, M, N, K, (flags & CAR_LIN_RELU_IN) ? 1 : 0, slab,
+    CAR_LAUNCH_LDS("car_linear_wgrad", kern, dim3(gx, gy, gz), dim3(256), lds_bytes, (hipStream_t)stream, dY, ldy, X, ldx, M, N, K, (flags & CAR_LIN_RELU_IN) ? 1 : 0, slab,
                        dW, lddw, db);
-    CAR_CHECK_LAUNCH("car_linear_wgrad");
     return CAR_OK;
 }
 
@@ -371,17 +367,7 @@ int launch_wgrad16(const float* dY, int ldy, const float* X, int ldx, long M, in
     const size_t lds_bytes = (size_t)2 * kW16Buf * sizeof(float);
     const bool relu = (flags & CAR_LIN_RELU_IN) != 0;
     auto kern = relu ? wgrad16_kernel<true> : wgrad16_kernel<false>;
-    static bool reserved[2][64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !reserved[relu][dev]) {
-        hipError_t e1 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e1 != hipSuccess) { car_set_error("car_linear_wgrad: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e1)); return CAR_E_LAUNCH; }
-        if (dev >= 0 && dev < 64) reserved[relu][dev] = true;
-    }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(gx, gy, gz), dim3(kW16Threads), lds_bytes, (hipStream_t)stream, dY, ldy, X, ldx, M, N, K, slab, dW, lddw, db);
-    CAR_CHECK_LAUNCH("car_linear_wgrad");
+    CAR_LAUNCH_LDS("car_linear_wgrad", kern, dim3(gx, gy, gz), dim3(kW16Threads), lds_bytes, (hipStream_t)stream, dY, ldy, X, ldx, M, N, K, slab, dW, lddw, db);
     return CAR_OK;
 }
 

@@ -46,6 +46,19 @@ static inline unsigned car_div_up(long a, long b) { return (unsigned)((a + b - 1
         if (rc_ != CAR_OK) return rc_; \
     } while (0)
 
+// The launch of a kernel with dynamic LDS: reserve, clear the sticky error, launch, check (returns from the calling function on failure).
+// car_reserve_lds (car_api.hip): the reservation is a per-device attribute of the kernel, set once per (kernel, device) — not on each of
+// the dozens of launches of a step — and again when a call asks for more than the largest reserved so far.  Its refusal is CAR_E_LAUNCH
+// with the one error text worded there: a contract, engine._lds_refused lets a route step down to its next kernel on this code and text.
+CAR_INTERNAL int car_reserve_lds(const void* kernel, size_t bytes, const char* entry);
+#define CAR_LAUNCH_LDS(entry, kernel, grid, block, lds_bytes, stream, ...)            \
+    do {                                                                              \
+        CAR_TRY(car_reserve_lds((const void*)(kernel), lds_bytes, entry));            \
+        (void)hipGetLastError();                                                      \
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, __VA_ARGS__);      \
+        CAR_CHECK_LAUNCH(entry);                                                      \
+    } while (0)
+
 // ---- library-internal functions that one unit defines and another calls.  Declared here and nowhere else: the defining and the calling
 // unit both include this header, so a parameter list that drifts on one side is a compile error, not a call that links and runs. ----
 // car_fused.hip: the fp16 instance of the fused per-sample kernel and its compact blob's size.  Reached through car_render_forward_f16;
@@ -57,6 +70,17 @@ extern "C" int car_fused_samples_f16(const float* poses, const float* rays, cons
                                      float* part, void* stream);
 // car_pack.hip: car_fused_pack with the compact (hi halves only) blob of the fp16 precision; same bias table and point table
 CAR_INTERNAL int car_fused_pack_hi(const car_weights* w, float* blob16, float* bias, float* wpt, void* stream);
+// car_pack.hip: the layer maximum and the two tile writers that every packed layer goes through (formats: the kernels' comments there).
+// car_pack_scale says where a layer's power of two comes from and goes to.  max set: car_pack_absmax (any grid) raises *max, zeroed by
+// the caller, to the largest magnitude as a bit pattern; the tile writer derives p = 2^shift from it and stores p and 1 / p.  max null:
+// car_pack_absmax (ONE workgroup) stores p and 1 / p itself, and the tile writer reads *p (inv may then be null).
+struct car_pack_scale { float* max; float* p; float* inv; };
+CAR_INTERNAL void car_pack_absmax(hipStream_t st, int blocks, const float* W, int ldw, const float* W2, const float* bias, int N, int K, car_pack_scale s);
+CAR_INTERNAL void car_pack_rows16(hipStream_t st, int blocks, const float* W, int ldw, const float* bias, int N, int K, int n_tiles, int ksteps,
+                                  int chained, int kbase, car_pack_scale s, _Float16* out, bool hi_only = false);
+CAR_INTERNAL void car_pack_conv16(hipStream_t st, int blocks, const float* w, int K, int N, bool flip, car_pack_scale s, _Float16* out);
+CAR_INTERNAL void car_pack_tiles32(hipStream_t st, int blocks, const float* W, int ldw, const float* W2, int N, int K, int tiles, int chunks, int kgs,
+                                   int chained, car_pack_scale s, _Float16* out);
 // car_lattice.hip: the common lattice of a pyramid's levels (only n_levels, level_h, level_w of d are read), and the merge onto it
 struct car_lattice { int h, w, pad, r[CAR_MAX_LEVELS]; bool ok; };
 CAR_INTERNAL car_lattice car_lattice_of(const car_dims& d);

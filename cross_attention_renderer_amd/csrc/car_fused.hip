@@ -25,7 +25,6 @@
 // car_plan_f16_build, B operands rounded to nearest (car_fused_mma.h); geometry, gather, scaling and every output's layout are the same.
 #include "car_common.h"
 #include "car_geom.h"
-#include <type_traits>
 
 namespace {
 
@@ -417,7 +416,7 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
         }
     }
     if constexpr (ROWS) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the prefetched taps of a pass that does not exist
+        wait_vm<0>();                                                 // the prefetched taps of a pass that does not exist
         return;
     }
     // ---- k1 = Wk1 [e_0 ; e_1] + bk1: first the e_1 half, chained from the accumulators (each K step's two tiles are stored as soon
@@ -467,18 +466,12 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
                 const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_void*)(ebuf[m & 1] + it * 256));
                 const float* gsrc = esrc[it] + 32 * m;
                 CAR_BOUNDS_TRAP(gsrc >= a.e && gsrc + 4 <= a.e + a.S * kC);
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+                lds_dma16(gsrc, lds_dst);
             }
         };
-        auto wait_vm = [&](auto n) {                                   // at most n of this wave's vector memory operations outstanding
-            constexpr int N = decltype(n)::value;
-            if constexpr (N >= 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        };
+        // wait_vm<kept(n)>: at most n of this wave's vector memory operations outstanding; the counts this loop was tuned with are 5 (and
+        // above), 4 and 2, any other waits for all
+        constexpr auto kept = [](int n) { return n >= 5 ? 5 : (n == 4 || n == 2 ? n : 0); };
         constexpr int kSteps = kTE / 2;                                // 9 K steps, two per weight chunk
         issue_e0(0);
         issue_e0(1);
@@ -493,8 +486,8 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
                 if (m < kSteps) {
                     // vector memory operations issued after e_0(m)'s two: e_0(m + 1)'s, and for the second K step of a chunk the
                     // chunk's kP weight pieces in between
-                    if (kl == 0) { if (m + 1 < kSteps) wait_vm(std::integral_constant<int, 2>()); else wait_vm(std::integral_constant<int, 0>()); }
-                    else { if (m + 1 < kSteps) wait_vm(std::integral_constant<int, kP + 2>()); else wait_vm(std::integral_constant<int, kP>()); }
+                    if (kl == 0) { if (m + 1 < kSteps) wait_vm<2>(); else wait_vm<0>(); }
+                    else { if (m + 1 < kSteps) wait_vm<kept(kP + 2)>(); else wait_vm<kept(kP)>(); }
                     const float* eb = ebuf[m & 1] + s * 32;
                     const int rot = (s >> 1) & 7;
                     const float4 x0 = *reinterpret_cast<const float4*>(eb + 4 * (q4 ^ rot));
@@ -513,9 +506,9 @@ __global__ void __launch_bounds__(kThreads) fused_kernel(const FusedArgs a) {
                 }
             }
             // the weight pieces of the next chunk have landed: behind them only the e_0 rows issued after the K steps of this chunk
-            if (2 * c + 2 < kSteps && 2 * c + 3 < kSteps) wait_vm(std::integral_constant<int, 4>());
-            else if (2 * c + 2 < kSteps) wait_vm(std::integral_constant<int, 2>());
-            else wait_vm(std::integral_constant<int, 0>());
+            if (2 * c + 2 < kSteps && 2 * c + 3 < kSteps) wait_vm<4>();
+            else if (2 * c + 2 < kSteps) wait_vm<2>();
+            else wait_vm<0>();
             __syncthreads();
         }
     }
@@ -654,11 +647,7 @@ int launch_fused(const float* poses, const float* rays, const float* steps, cons
 #endif
     const long groups = (long)b * V * car_div_up(R, kTileRays) * car_div_up(P, kTileSteps);
     void (*kern)(const FusedArgs) = f16 ? fused_kernel<false, true> : fused_kernel<>;
-    hipError_t e1 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-    if (e1 != hipSuccess) { car_set_error("car_fused_samples: cannot reserve %zu bytes of LDS: %s", kLdsBytes, hipGetErrorString(e1)); return CAR_E_LAUNCH; }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(kThreads), kLdsBytes, (hipStream_t)stream, a);
-    CAR_CHECK_LAUNCH("car_fused_samples");
+    CAR_LAUNCH_LDS("car_fused_samples", kern, dim3((unsigned)groups), dim3(kThreads), kLdsBytes, (hipStream_t)stream, a);
     return CAR_OK;
 }
 
@@ -720,10 +709,6 @@ extern "C" int car_fused_rows(const float* lattice, int lat_h, int lat_w, int la
     a.row_src = row_src; a.row_grid = row_grid; a.row_pe = row_pe; a.ncomp = ncomp;
     const long groups = (long)n_sets * ncomp * car_div_up(R, kTileRays) * car_div_up(P, kTileSteps);
     void (*kern)(const FusedArgs) = fused_kernel<true>;
-    hipError_t e1 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-    if (e1 != hipSuccess) { car_set_error("car_fused_rows: cannot reserve %zu bytes of LDS: %s", kLdsBytes, hipGetErrorString(e1)); return CAR_E_LAUNCH; }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(kThreads), kLdsBytes, (hipStream_t)stream, a);
-    CAR_CHECK_LAUNCH("car_fused_rows");
+    CAR_LAUNCH_LDS("car_fused_rows", kern, dim3((unsigned)groups), dim3(kThreads), kLdsBytes, (hipStream_t)stream, a);
     return CAR_OK;
 }

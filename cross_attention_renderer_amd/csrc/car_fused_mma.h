@@ -20,7 +20,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
+#include "car_lds_dma.h"
 
 #include "car_fused_layout.h"
 
@@ -57,7 +57,7 @@ __device__ __forceinline__ NextChunk next_chunk(const float* __restrict__ blob, 
     return n;
 }
 // piece p of the next chunk: wave w copies KB number kWaves p + w (wrapped into the chunk: re-copying identical bytes is harmless).
-// LDS-DMA in inline asm, see car_linear.hip.  Must only run after the barrier that retired the buffer's previous chunk.
+// LDS-DMA: car_lds_dma.h.  Must only run after the barrier that retired the buffer's previous chunk.
 __device__ __forceinline__ void stream_issue_piece(const NextChunk& n, int p, int lane, int wave) {
     int kb = kWaves * p + wave;
     kb = kb < n.nkb ? kb : kb - n.nkb;
@@ -81,9 +81,7 @@ __device__ __forceinline__ void stream_issue_piece(const NextChunk& n, int p, in
     }
 #endif
     const unsigned voff = 16u * (unsigned)lane;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(gsrc) : "memory");
+    lds_dma16(gsrc, voff, lds_dst);
 }
 template <bool F16 = false>
 __device__ __forceinline__ void stream_issue_all(const float* __restrict__ blob, float* lds, int g, int lane, int wave) {
@@ -97,10 +95,7 @@ __device__ __forceinline__ void stream_issue_all(const float* __restrict__ blob,
 // order, so "at most KEEP outstanding" still means every DMA piece has landed).
 template <int KEEP = 0>
 __device__ __forceinline__ void stream_sync() {
-    if constexpr (KEEP == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if constexpr (KEEP == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (KEEP == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<(KEEP == 16 || KEEP == 8 || KEEP == 4 ? KEEP : 0)>();      // the counts the streams were tuned with; any other KEEP waits for all
     __syncthreads();
 }
 

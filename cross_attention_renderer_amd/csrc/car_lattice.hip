@@ -203,7 +203,6 @@ int car_launch_merge(const float* const* levels, const int* hs, const int* ws, c
     for (int l = 0; l < n_levels; ++l) widest = (long)hs[l] * ws[l] > widest ? (long)hs[l] * ws[l] : widest;
     const long per = 0x7fffffffL / (widest * kC * 4);
     CAR_REQUIRE(per >= 1, "%s: one map of the widest level exceeds 2 GiB", who);
-    (void)hipGetLastError();
     for (int m0 = 0; m0 < n_maps; m0 += (int)per) {
         const int nm = n_maps - m0 < per ? n_maps - m0 : (int)per;
         MergeArgs a{};
@@ -226,15 +225,8 @@ int car_launch_merge(const float* const* levels, const int* hs, const int* ws, c
 #define CAR_MERGE_KERNEL(T) (n_levels == 1 ? merge_kernel<1, T> : n_levels == 2 ? merge_kernel<2, T> : n_levels == 3 ? merge_kernel<3, T> : merge_kernel<4, T>)
         void (*kern)(const MergeArgs, unsigned*) = tables ? CAR_MERGE_KERNEL(true) : CAR_MERGE_KERNEL(false);
 #undef CAR_MERGE_KERNEL
-        if (tables) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab_bytes) != hipSuccess) {
-                car_set_error("%s: cannot reserve %zu bytes of LDS", who, tab_bytes);
-                return CAR_E_LAUNCH;
-            }
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), tables ? tab_bytes : 0, st, a, gmax);
+        CAR_LAUNCH_LDS(who, kern, dim3((unsigned)blocks), dim3(256), tables ? tab_bytes : 0, st, a, gmax);
     }
-    CAR_CHECK_LAUNCH(who);
     return CAR_OK;
 }
 // Every level is summed on the lattice: it must be an integer factor r_l coarser than the widest level, the same factor in both

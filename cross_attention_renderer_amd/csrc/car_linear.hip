@@ -14,8 +14,8 @@
 // take k = 32c + j, lanes 32-63 take k = 32c + 16 + j for MFMA step j = 0..15.  Each lane then reads its
 // sample's 16 consecutive floats straight from global memory as 4 x global_load_dwordx4 (no LDS round trip for
 // X), while the weights — shared by the four waves of a workgroup — are pre-packed on the host side
-// (car_linear_pack) in exactly the order the A operand wants them and streamed L2 -> LDS with
-// global_load_lds_dwordx4 (double buffered), then read back as one ds_read_b128 per four MFMAs.
+// (car_linear_pack) in exactly the order the A operand wants them and streamed L2 -> LDS by
+// LDS-DMA (car_lds_dma.h; double buffered), then read back as one ds_read_b128 per four MFMAs.
 //
 // Work decomposition: workgroup = 4 waves = 128 samples x (NT x 32) output channels; every wave owns 32 samples
 // and NT accumulator tiles (NT*16 VGPRs).  fp32 MFMA runs at the fp32 vector rate (64 cycles per 32x32x2), so
@@ -26,8 +26,8 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
+#include "car_lds_dma.h"
 
 constexpr int kChunkK = 32;            // K elements per chunk (16 MFMA steps)
 constexpr int kTileFloats = 1024;      // packed floats per (chunk, tile): 4 x 64 lanes x float4
@@ -89,18 +89,13 @@ linear_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ Wp
         for (int t = 0; t < NT; ++t) {
             const int f4 = t * 256 + tid;
             if constexpr (GLDS) {
-                // LDS-DMA: destination = M0 (wave-uniform LDS byte address) + lane*16, the global source is per lane.
-                // Issued through inline asm on purpose: hipcc orders every ds_read behind an LDS-DMA it knows about
-                // (s_waitcnt vmcnt(0) before the first ds_read of the chunk), which would serialise the weight stream
-                // with the MFMAs.  Hidden from the compiler, the DMA for chunk c+1 flies under the MFMAs of chunk c;
-                // the explicit vmcnt(0) + barrier at the end of the chunk orders it before the next chunk's reads.
+                // the DMA for chunk c+1 flies under the MFMAs of chunk c; the explicit wait + barrier at the end of the chunk orders it
+                // before the next chunk's reads (car_lds_dma.h)
                 const unsigned lds_dst = __builtin_amdgcn_readfirstlane(
                     (unsigned)(uintptr_t)(lds_void*)(dst + 4 * (t * 256 + wave * 64)));
                 const float* gsrc = src + 4 * f4;
                 CAR_BOUNDS_TRAP(gsrc >= Wp && gsrc + 4 <= Wp + (long)chunks * tiles_alloc * kTileFloats);     // debug build: inside the packed layer
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+                lds_dma16(gsrc, lds_dst);
             } else {
                 wreg[t] = *reinterpret_cast<const float4*>(src + 4 * f4);
             }
@@ -118,7 +113,7 @@ linear_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ Wp
     stage_issue(0, 0);
     load_x(0, xr);
     stage_commit(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
     fix_x(0, xr);
 
@@ -148,7 +143,7 @@ linear_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ Wp
 #pragma unroll
             for (int q = 0; q < 4; ++q) xr[q] = xn[q];
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
     }
 

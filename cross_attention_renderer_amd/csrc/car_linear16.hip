@@ -290,63 +290,11 @@ __global__ void __launch_bounds__(kThreads) linear16_kernel(const LinArgs a) {
     }
 }
 
-// max |W| over the layer, as the bit pattern of a non-negative float (orders like an integer), into scale[2] (zeroed by the caller): a grid
-// of workgroups, one atomic each.  (One workgroup reading the whole matrix took 25 us per layer: 0.9 ms of a training step, which re-packs
-// its ~36 forward and transposed layers after every optimizer step.)
-__global__ void absmax16_kernel(const float* __restrict__ W, int ldw, int K, int N, float* __restrict__ scale) {
-    __shared__ float red[4];
-    float m = 0.0f;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long)N * K; idx += (long)gridDim.x * blockDim.x)
-        m = fmaxf(m, fabsf(W[(idx / K) * ldw + idx % K]));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x / 64); ++w) m = fmaxf(m, red[w]);
-        atomicMax(reinterpret_cast<unsigned*>(scale + 2), __float_as_uint(m));
-    }
-}
-// [K step][tile][hi | lo][lane][8 halves]: lane l carries output 16 tile + l % 16 and k = 32 step + 8 (l >> 4) + e
-// scale[2] holds max |W| (absmax16_kernel): every thread derives the layer's power of two from it — scale[0] = 2^shift with
-// max |W| 2^shift in [2^13, 2^14), scale[1] = 2^-shift, written by the first thread for the consuming kernel
-__global__ void pack16x3_kernel(const float* __restrict__ W, int ldw, int K, int N, int tiles, long total, float* __restrict__ scale,
-                                _Float16* __restrict__ out) {
-    float p, inv;
-    pow2_scale(fmaxf(scale[2], 1e-30f), p, inv);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { scale[0] = p; scale[1] = inv; }
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
-        const long tile = idx >> 9;
-        const int t = (int)(tile % tiles), ks = (int)(tile / tiles);
-        const int n = 16 * t + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + e;
-        const float w = (n < N && k < K) ? W[(long)n * ldw + k] * p : 0.0f;
-        const _Float16 hi = (_Float16)w;
-        _Float16* o = out + tile * 1024 + lane * 8 + e;
-        o[0] = hi;
-        o[512] = (_Float16)(w - (float)hi);
-    }
-}
-
 template <int NT, bool GATHER = false, bool KQ = false>
 int launch16(const LinArgs& a, int groups, hipStream_t st) {
     const size_t lds_bytes = KQ ? (size_t)(2 * kChunkTiles * kTile + kTailBias) * sizeof(float)
                                 : (size_t)2 * NT * kTile * sizeof(float) + (GATHER ? (size_t)a.K * 4 * sizeof(float) : 0);
-    // the LDS reservation is a per-device attribute of the kernel: set it once per (instance, device), not on each of the dozens of
-    // launches of a staged forward or training step
-    static bool reserved[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !reserved[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)linear16_kernel<NT, GATHER, KQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) {
-            car_set_error("car_linear_x3: cannot reserve %zu bytes of LDS (a gfx950-class device has 160 KB per compute unit): %s", lds_bytes, hipGetErrorString(e));
-            return CAR_E_LAUNCH;
-        }
-        if (dev >= 0 && dev < 64) reserved[dev] = true;
-    }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((linear16_kernel<NT, GATHER, KQ>), dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
-    CAR_CHECK_LAUNCH("car_linear_x3");
+    CAR_LAUNCH_LDS("car_linear_x3", (linear16_kernel<NT, GATHER, KQ>), dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
     return CAR_OK;
 }
 
@@ -358,12 +306,13 @@ extern "C" int car_linear_x3_pack(const float* W, int ldw, int K, int N, float* 
     CAR_REQUIRE(W && packed && K > 0 && N > 0 && ldw >= K && N % 16 == 0, "car_linear_x3_pack: bad arguments (N must be a multiple of 16)");
     const int tiles = N / 16, ksteps = (K + 31) / 32;
     float* scale = packed + (size_t)ksteps * tiles * kTile;
+    hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
-    if (hipMemsetAsync(scale + 2, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) { car_set_error("car_linear_x3_pack: memset failed"); return CAR_E_LAUNCH; }
-    const long elems = (long)N * K;
-    hipLaunchKernelGGL(absmax16_kernel, dim3((unsigned)(elems < 65536 ? 8 : 64)), dim3(256), 0, (hipStream_t)stream, W, ldw, K, N, scale);
-    hipLaunchKernelGGL(pack16x3_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream, W, ldw, K, N, tiles, (long)ksteps * tiles * 512, scale,
-                       reinterpret_cast<_Float16*>(packed));
+    if (hipMemsetAsync(scale + 2, 0, sizeof(float), st) != hipSuccess) { car_set_error("car_linear_x3_pack: memset failed"); return CAR_E_LAUNCH; }
+    // scale[2]: the layer's largest magnitude (many workgroups: a training step re-packs every layer), scale[0] = 2^shift, scale[1] = 2^-shift
+    const car_pack_scale s{scale + 2, scale, scale + 1};
+    car_pack_absmax(st, (long)N * K < 65536 ? 8 : 64, W, ldw, nullptr, nullptr, N, K, s);
+    car_pack_rows16(st, 256, W, ldw, nullptr, N, K, tiles, ksteps, 0, 0, s, reinterpret_cast<_Float16*>(packed));
     CAR_CHECK_LAUNCH("car_linear_x3_pack");
     return CAR_OK;
 }

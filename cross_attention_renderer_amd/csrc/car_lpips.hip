@@ -57,21 +57,12 @@ struct ConvArgs {
     long M;                                // n H W output pixels
 };
 
-// pow2_scale with the exponent clamped far lower: a gradient row's largest magnitude is 1e-5 .. 1e-8 per unit of cotangent, and the
-// row's power of two has to follow it down so that a cotangent scaled by a power of two scales every result exactly.  p in [2^-90, 2^100]:
-// p and the weights' 2^shift are never multiplied into one float here (the data gradient undoes them in two steps).
+// A gradient row's power of two: pow2_scale with the exponent clamped far lower (car_split.h kPow2LoWide).
 // When a later K step raises the row's maximum, the accumulators move by pn * pinv, a power of two as small as 2^-190: what was summed so
 // far may then lose low bits or flush to 0.  It is below 2^-150 of the row's new scale, so the accuracy bound is untouched, but "a
 // cotangent scaled by 2^k scales every entry exactly" holds only while no row's magnitude crosses the clamp span inside one sweep.
-__device__ __forceinline__ void pow2_scale_wide(float m, float& p, float& inv) {
-    int e = (int)((__float_as_uint(m) >> 23) & 0xffu);
-    e = e < 40 ? 40 : (e > 230 ? 230 : e);
-    p = __uint_as_float((unsigned)(267 - e) << 23);
-    inv = __uint_as_float((unsigned)(e - 13) << 23);
-}
-
 // BWD: the data gradient of the same convolution.  The same sweep over weights packed transposed and flipped
-// (conv_pack_kernel), no bias, a row's power of two from pow2_scale_wide, and the epilogue Y = (sum + add) * (act > 0) in the place of
+// (car_pack.hip ConvSource), no bias, a row's power of two from pow2_scale<kPow2LoWide>, and the epilogue Y = (sum + add) * (act > 0) in the place of
 // bias + ReLU.  The forward instance's arithmetic is untouched by the parameter.
 template <int NT, bool BWD>
 __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
@@ -146,7 +137,7 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         finish_x(0, raw, xc);
     }
     float mrun = fmaxf(row_max(xc), 1e-30f), p, pinv;
-    if constexpr (BWD) pow2_scale_wide(mrun, p, pinv); else pow2_scale(mrun, p, pinv);
+    pow2_scale<BWD ? kPow2LoWide : kPow2Lo>(mrun, p, pinv);
 
     f32x4 acc[NT];
     if constexpr (BWD) {
@@ -179,7 +170,7 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         if (__builtin_amdgcn_ballot_w64(mn > mrun) != 0) {
             float pn, pninv;
             mrun = fmaxf(mrun, mn);
-            if constexpr (BWD) pow2_scale_wide(mrun, pn, pninv); else pow2_scale(mrun, pn, pninv);
+            pow2_scale<BWD ? kPow2LoWide : kPow2Lo>(mrun, pn, pninv);
             scale_acc<NT>(acc, pn * pinv);
             p = pn; pinv = pninv;
         }
@@ -219,21 +210,9 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
 template <int NT, bool BWD = false>
 int launch_conv(const ConvArgs& a, hipStream_t st) {
     const size_t lds_bytes = (size_t)2 * NT * kTile * sizeof(float);
-    static bool reserved[64] = {};                                     // the LDS reservation is a per-device attribute of the kernel
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !reserved[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<NT, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) {
-            car_set_error("%s: cannot reserve %zu bytes of LDS: %s", BWD ? "car_conv3x3_backward" : "car_conv3x3", lds_bytes, hipGetErrorString(e));
-            return CAR_E_LAUNCH;
-        }
-        if (dev >= 0 && dev < 64) reserved[dev] = true;
-    }
-    (void)hipGetLastError();
     const int groups = a.tiles_total / NT;
-    hipLaunchKernelGGL((conv3x3_kernel<NT, BWD>), dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
-    CAR_CHECK_LAUNCH(BWD ? "car_conv3x3_backward" : "car_conv3x3");
+    CAR_LAUNCH_LDS(BWD ? "car_conv3x3_backward" : "car_conv3x3", (conv3x3_kernel<NT, BWD>),
+                   dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
     return CAR_OK;
 }
 
@@ -285,41 +264,21 @@ __global__ void __launch_bounds__(256) maxpool_kernel(const float* __restrict__ 
 }
 
 // ---- packing -------------------------------------------------------------------------------------------------------------------------
-// max |w| of a layer as the bit pattern of a non-negative float, into scale[2] (zeroed by the caller): car_linear16.hip's absmax16_kernel
-__global__ void conv_absmax_kernel(const float* __restrict__ Wt, long total, float* __restrict__ scale) {
-    __shared__ float red[4];
-    float m = 0.0f;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(Wt[idx]));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x / 64); ++w) m = fmaxf(m, red[w]);
-        atomicMax(reinterpret_cast<unsigned*>(scale + 2), __float_as_uint(m));
+// A layer's tiles, 64 floats of scale (2^shift, 2^-shift, the largest magnitude, zeros) and, forward only, its bias: car_linear16.hip's
+// tiles [K step][tile][hi | lo][lane][8 halves] with k = tap * K + channel, written by car_pack.hip's 16-wide writer (ConvSource).
+// flip: the data gradient's weights, transposed and with the taps reversed.  K, N: the packed matrix's inputs per tap and outputs.
+int pack_conv(const float* w, const float* bias, int K, int N, bool flip, float* packed, hipStream_t st, const char* who) {
+    float* scale = packed + (size_t)9 * K * N;
+    if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("%s: memset failed", who); return CAR_E_LAUNCH; }
+    const car_pack_scale s{scale + 2, scale, scale + 1};
+    car_pack_absmax(st, 64, w, 9 * K * N, nullptr, nullptr, 1, 9 * K * N, s);
+    car_pack_conv16(st, 512, w, K, N, flip, s, reinterpret_cast<_Float16*>(packed));
+    if (bias && hipMemcpyAsync(scale + 64, bias, sizeof(float) * N, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        car_set_error("%s: bias copy failed", who);
+        return CAR_E_LAUNCH;
     }
-}
-// torch's [N][K][3][3] -> car_linear16.hip's tiles [K step][tile][hi | lo][lane][8 halves] with k = tap * K + channel: lane l carries
-// output 16 tile + l % 16 and k = 32 step + 8 (l >> 4) + e.  scale[0] = 2^shift, scale[1] = 2^-shift; the bias follows the 64 scale floats.
-// flip (the data gradient's weights, no bias): Wt is the forward layer's [K][N][3][3] and the tile holds w'[n][k][tap] = Wt[k][n][8 - tap]
-__global__ void conv_pack_kernel(const float* __restrict__ Wt, const float* __restrict__ bias, int K, int N, long total, float* __restrict__ scale,
-                                 _Float16* __restrict__ out, bool flip) {
-    float p, inv;
-    pow2_scale(fmaxf(scale[2], 1e-30f), p, inv);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { scale[0] = p; scale[1] = inv; }
-    const int tiles = N / 16;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        if (!flip && idx < N) scale[64 + idx] = bias[idx];
-        const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
-        const long tile = idx >> 9;
-        const int t = (int)(tile % tiles), ks = (int)(tile / tiles);
-        const int n = 16 * t + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + e;
-        const int tap = k / K, ch = k % K;
-        const float w = (flip ? Wt[((long)ch * N + n) * 9 + (8 - tap)] : Wt[((long)n * K + ch) * 9 + tap]) * p;
-        const _Float16 hi = (_Float16)w;
-        _Float16* o = out + tile * 1024 + lane * 8 + e;
-        o[0] = hi;
-        o[512] = (_Float16)(w - (float)hi);
-    }
+    CAR_CHECK_LAUNCH(who);
+    return CAR_OK;
 }
 __global__ void first_pack_kernel(const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ out) {
     constexpr double kScale[3] = CAR_LPIPS_SCALE;
@@ -734,12 +693,7 @@ extern "C" int car_conv3x3_pack(const float* w, const float* bias, int K, int N,
         CAR_CHECK_LAUNCH("car_conv3x3_pack");
         return CAR_OK;
     }
-    float* scale = packed + conv_tile_floats(K, N);
-    if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("car_conv3x3_pack: memset failed"); return CAR_E_LAUNCH; }
-    hipLaunchKernelGGL(conv_absmax_kernel, dim3(64), dim3(256), 0, st, w, (long)N * K * 9, scale);
-    hipLaunchKernelGGL(conv_pack_kernel, dim3(512), dim3(256), 0, st, w, bias, K, N, (long)(conv_tile_floats(K, N)), scale, reinterpret_cast<_Float16*>(packed), false);
-    CAR_CHECK_LAUNCH("car_conv3x3_pack");
-    return CAR_OK;
+    return pack_conv(w, bias, K, N, false, packed, st, "car_conv3x3_pack");
 }
 
 extern "C" int car_conv3x3(const float* X, int n, int H, int W, int K, int N, const float* packed, float* Y, void* stream) {
@@ -851,13 +805,7 @@ extern "C" int car_conv3x3_backward_pack(const float* w, int K, int N, float* pa
     CAR_REQUIRE(aligned16(packed), "car_conv3x3_backward_pack: packed must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
-    float* scale = packed + conv_tile_floats(N, K);
-    if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("car_conv3x3_backward_pack: memset failed"); return CAR_E_LAUNCH; }
-    hipLaunchKernelGGL(conv_absmax_kernel, dim3(64), dim3(256), 0, st, w, (long)N * K * 9, scale);
-    hipLaunchKernelGGL(conv_pack_kernel, dim3(512), dim3(256), 0, st, w, (const float*)nullptr, N, K, (long)(conv_tile_floats(N, K)), scale,
-                       reinterpret_cast<_Float16*>(packed), true);
-    CAR_CHECK_LAUNCH("car_conv3x3_backward_pack");
-    return CAR_OK;
+    return pack_conv(w, nullptr, N, K, true, packed, st, "car_conv3x3_backward_pack");
 }
 
 extern "C" int car_conv3x3_backward(const float* D, int n, int H, int W, int K, int N, const float* packed, const float* act, const float* add,

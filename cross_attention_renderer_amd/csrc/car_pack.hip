@@ -1,21 +1,20 @@
-// car_pack.hip — the device-side weight packers of the C ABI (include/car_hip.h: car_fused_pack, car_fused_pack_rows, car_kq_pack,
-// car_round2_pack, car_round2q_pack): small re-layout / reduction kernels that put a layer into the operand order of the kernel that
-// consumes it, every layer times its own power of two.  Asynchronous, device side only.  car_plan_build / car_plan_f16_build
-// (car_render.hip) and the stage route (engine.py) both pack through these entries.
+// car_pack.hip — every weight packer of the library.  The split-fp16 operand format is stated here once: a layer's largest magnitude
+// (absmax_kernel) gives its power of two (car_split.h pow2_scale), and one writer per MFMA tile shape (pack16_kernel, pack32_kernel) cuts the
+// scaled weights into fp16 hi/lo A-operand tiles.  The packers of the C ABI defined here (include/car_hip.h: car_fused_pack,
+// car_fused_pack_rows, car_kq_pack, car_round2_pack, car_round2q_pack) and the per-layer ones beside their kernels (car_linear_x3_pack,
+// car_chain_pack, car_conv3x3_pack, car_conv3x3_backward_pack) all go through the car_pack_* launchers below (declared in car_common.h).
+// Asynchronous, device side only.  car_plan_build / car_plan_f16_build (car_render.hip) and the stage route (engine.py) pack through these entries.
 #include "car_common.h"
 
 namespace {
 
 #include "car_fused_layout.h"
 
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+#include "car_split.h"
+
 constexpr int kTile16 = kTile;                     // floats per (K step, 16-channel tile) of the fused kernel's blob
 
-// power of two p with m p in [2^13, 2^14) (the window of the split-fp16 operands, car_fused_mma.h)
-__device__ __forceinline__ float pow2_for(float m) {
-    int e = (int)((__float_as_uint(m) >> 23) & 0xffu);
-    e = e < 97 ? 97 : (e > 230 ? 230 : e);          // p in [2^-90, 2^43]: an all-zero vector or matrix must not push p_x * p_W past fp32
-    return __uint_as_float((unsigned)(267 - e) << 23);
-}
 __device__ __forceinline__ float block_max(float v, float* red) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -27,42 +26,75 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 }
 
 // ---- re-layout kernels ---------------------------------------------------------------------------------------------
-// Scale of a packed layer: p = 2^shift from the largest |weight| (and |bias| where the bias is folded in as a column);
-// p goes to p_slot (read by the pack kernels), 1/p to down_slot (read by the consuming kernel).  One workgroup.
-__global__ void layer_scale_kernel(const float* __restrict__ W, int ldw, int N, int K, const float* __restrict__ bias,
-                                   float* __restrict__ p_slot, float* __restrict__ down_slot) {
+// Largest |W (+ W2)| of an [N][K] matrix with row stride ldw (and |bias| where the bias is folded in as a column).  A grid of workgroups
+// (s.max set): one atomicMax each into *s.max, zeroed by the caller — the bit pattern of a non-negative float orders like an integer.
+// (One workgroup reading the whole matrix took 25 us per layer: 0.9 ms of a training step, which re-packs its ~36 forward and
+// transposed layers after every optimizer step.)  One workgroup (s.max null; the plan-time packers): its maximum is the layer's, so it
+// stores p = 2^shift in *s.p and 1 / p in *s.inv itself.
+__global__ void absmax_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ W2, const float* __restrict__ bias, int N, int K,
+                              car_pack_scale s) {
     __shared__ float red[16];
     float m = 0.0f;
-    for (long idx = threadIdx.x; idx < (long)N * K; idx += blockDim.x) m = fmaxf(m, fabsf(W[(idx / K) * ldw + idx % K]));
-    if (bias) for (int n = threadIdx.x; n < N; n += blockDim.x) m = fmaxf(m, fabsf(bias[n]));
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long)N * K; idx += (long)gridDim.x * blockDim.x) {
+        const long at = (idx / K) * ldw + idx % K;
+        m = fmaxf(m, fabsf(W2 ? W[at] + W2[at] : W[at]));
+    }
+    if (bias) for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) m = fmaxf(m, fabsf(bias[n]));
     m = block_max(m, red);
-    if (threadIdx.x == 0) {
-        const float p = pow2_for(fmaxf(m, 1e-30f));
-        p_slot[0] = p;
-        down_slot[0] = 1.0f / p;
+    if (threadIdx.x != 0) return;
+    if (s.max) {
+        atomicMax(reinterpret_cast<unsigned*>(s.max), __float_as_uint(m));
+    } else {
+        pow2_scale(fmaxf(m, 1e-30f), *s.p, *s.inv);
     }
 }
-// A-operand tiles of v_mfma_f32_16x16x32_f16 with fp16 hi/lo halves: per (K step, tile) [hi|lo][lane][8 halves]; lane l carries
-// output 16 t + l % 16 and k = 32 ks + 8 (l >> 4) + e (mode 0) or the accumulator order base + 16 (2 ks + e / 4) + 4 (l >> 4) + e % 4
-// (mode 1); k == K selects the bias, k > K a zero.  Values are multiplied by the layer's power of two *p_slot.
+// The layer's power of two inside a tile writer: read from *s.p (stored by a one-workgroup absmax_kernel), or derived by every thread
+// from *s.max, the first thread of the grid storing it and its inverse for the consuming kernel (s.max never aliases s.p or s.inv).
+__device__ __forceinline__ float layer_pow2(const car_pack_scale& s) {
+    if (!s.max) return *s.p;
+    float p, inv;
+    pow2_scale(fmaxf(*s.max, 1e-30f), p, inv);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { *s.p = p; *s.inv = inv; }
+    return p;
+}
+
+// The scaled weight stays a value of its own in front of its rounding to fp16: left to the compiler, some instances of the writers fuse
+// multiplication and rounding into v_fma_mixlo_f16 (x, p, +0), which packs a weight of -0.0 as +0.0, and some do not.
+__device__ __forceinline__ void keep_product(float& w) { asm("" : "+v"(w)); }
+
+// Where element (output n; K step ks, lane group q = lane >> 4, element e) of a 16-wide tile comes from.
+// Rows of a matrix with stride ldw: k = 32 ks + 8 q + e, or chained over the accumulator order of the layer before,
+// k = base + 16 (2 ks + e / 4) + 4 q + e % 4; k == K selects the bias, k > K and n >= N a zero.
+struct RowSource {
+    const float* W; int ldw; const float* bias; int N, K, chained, base;
+    __device__ float operator()(int n, int ks, int q, int e) const {
+        const int k = chained ? base + 16 * (2 * ks + e / 4) + 4 * q + e % 4 : 32 * ks + 8 * q + e;
+        if (n >= N) return 0.0f;
+        return k < K ? W[(long)n * ldw + k] : (k == K && bias ? bias[n] : 0.0f);
+    }
+};
+// torch's [N][K][3][3] convolution weights with k = tap * K + channel.  flip (the data gradient's weights): Wt is the forward layer's
+// [K][N][3][3] and the tile holds w'[n][k][tap] = Wt[k][n][8 - tap]
+struct ConvSource {
+    const float* Wt; int K, N; bool flip;
+    __device__ float operator()(int n, int ks, int q, int e) const {
+        const int k = 32 * ks + 8 * q + e, tap = k / K, ch = k % K;
+        return flip ? Wt[((long)ch * N + n) * 9 + (8 - tap)] : Wt[((long)n * K + ch) * 9 + tap];
+    }
+};
+// A-operand tiles of v_mfma_f32_16x16x32_f16 with fp16 hi/lo halves: [K step][tile][hi|lo][lane][8 halves]; lane l carries output
+// 16 t + l % 16 and the eight k its source gives (K step, l >> 4, e).  Values are multiplied by the layer's power of two first.
 // HI_ONLY: the compact tiles of the fp16 precision (car_plan_f16_build): the same values and order as the full instance's hi halves
 // (rounded to nearest after the layer's power of two), without the lo halves: per (K step, tile) [lane][8 halves], 1 KB.
-template <bool HI_ONLY>
-__global__ void pack16_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ bias, int N, int K, int n_tiles,
-                              int ksteps, int mode, int base, const float* __restrict__ p_slot, _Float16* __restrict__ out) {
-    const long total = (long)ksteps * n_tiles * 512;
-    const float p = p_slot[0];
+template <bool HI_ONLY, class Source>
+__global__ void pack16_kernel(const Source src, int n_tiles, long total, car_pack_scale s, _Float16* __restrict__ out) {
+    const float p = layer_pow2(s);
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
         const long tile = idx >> 9;
         const int t = (int)(tile % n_tiles), ks = (int)(tile / n_tiles);
-        const int n = 16 * t + (lane & 15), q = lane >> 4;
-        const int k = mode == 0 ? 32 * ks + 8 * q + e : base + 16 * (2 * ks + e / 4) + 4 * q + e % 4;
-        float w = 0.0f;
-        if (n < N) {
-            if (k < K) w = W[(long)n * ldw + k] * p;
-            else if (k == K && bias) w = bias[n] * p;
-        }
+        float w = src(16 * t + (lane & 15), ks, lane >> 4, e) * p;
+        keep_product(w);
         const _Float16 hi = (_Float16)w;
         if constexpr (HI_ONLY) {
             out[idx] = hi;
@@ -101,21 +133,26 @@ __global__ void bilinear_fold_kernel(const float* __restrict__ Wa, const float* 
         }
     }
 }
-// A-operand tiles of v_mfma_f32_32x32x16_f16 for car_round2.hip: [chunk][tile 4][K group kgs][hi|lo][lane][8 halves], output
-// 32 t + l % 32; chained = 1: k = 32 c + (e & 3) + 8 (2 kg + (e >> 2)) + 4 (l >> 5) (the accumulator order of the layer before),
-// chained = 0: k = 16 c + 8 (l >> 5) + e with one K group per chunk.
-__global__ void pack32_kernel(const float* __restrict__ W, int ldw, int chunks, int kgs, int chained, const float* __restrict__ p_slot,
-                              _Float16* __restrict__ out) {
-    const int total = chunks * 4 * kgs * 2 * 64 * 8;
-    const float p = p_slot[0];
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int e = idx & 7, lane = (idx >> 3) & 63, hl = (idx >> 9) & 1;
-        int rest = idx >> 10;
-        const int kg = rest % kgs; rest /= kgs;
-        const int t = rest & 3, c = rest >> 2;
+// A-operand tiles of v_mfma_f32_32x32x16_f16 (car_round2.hip: 4 tiles; car_raychain.hip: kgs = 2): [chunk][tile][K group kgs][hi|lo][lane]
+// [8 halves]; lane l carries output 32 t + l % 32 and, chained, k = 32 c + (e & 3) + 8 (2 kg + (e >> 2)) + 4 (l >> 5) (the accumulator
+// order of the layer before), else k = 16 kgs c + 16 kg + 8 (l >> 5) + e.  W2 (optional, same shape and stride) is added element-wise;
+// outputs >= N and inputs >= K are zero.
+__global__ void pack32_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ W2, int N, int K, int tiles, int kgs, int chained,
+                              long total, car_pack_scale s, _Float16* __restrict__ out) {
+    const float p = layer_pow2(s);
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63), hl = (int)((idx >> 9) & 1);
+        long rest = idx >> 10;
+        const int kg = (int)(rest % kgs); rest /= kgs;
+        const int t = (int)(rest % tiles), c = (int)(rest / tiles);
         const int n = 32 * t + (lane & 31);
-        const int k = chained ? 32 * c + (e & 3) + 8 * (2 * kg + (e >> 2)) + 4 * (lane >> 5) : 16 * c + 8 * (lane >> 5) + e;
-        const float w = W[n * ldw + k] * p;
+        const int k = chained ? 32 * c + (e & 3) + 8 * (2 * kg + (e >> 2)) + 4 * (lane >> 5) : 16 * kgs * c + 16 * kg + 8 * (lane >> 5) + e;
+        float w = 0.0f;
+        if (n < N && k < K) {
+            const long at = (long)n * ldw + k;
+            w = (W2 ? W[at] + W2[at] : W[at]) * p;
+        }
+        keep_product(w);
         const _Float16 hi = (_Float16)w;
         out[idx] = hl == 0 ? hi : (_Float16)(w - (float)hi);
     }
@@ -135,23 +172,47 @@ __global__ void wpt_kernel(const float* __restrict__ w1, const float* __restrict
     if (threadIdx.x == 0) bound[0] = m;
 }
 
-// ---- what the five packers share: zero the bias table, one layer_scale_kernel per layer, the pack launches, CAR_CHECK_LAUNCH, then
-// device-to-device bias copies -------------------------------------------------------------------------------------------------------
+}  // namespace
+
+// ---- the launchers every packer goes through (car_common.h) ----------------------------------------------------------------------------
+void car_pack_absmax(hipStream_t st, int blocks, const float* W, int ldw, const float* W2, const float* bias, int N, int K, car_pack_scale s) {
+    hipLaunchKernelGGL(absmax_kernel, dim3(blocks), dim3(blocks == 1 ? 1024 : 256), 0, st, W, ldw, W2, bias, N, K, s);
+}
+void car_pack_rows16(hipStream_t st, int blocks, const float* W, int ldw, const float* bias, int N, int K, int n_tiles, int ksteps, int chained,
+                     int kbase, car_pack_scale s, _Float16* out, bool hi_only) {
+    const RowSource src{W, ldw, bias, N, K, chained, kbase};
+    const long total = (long)ksteps * n_tiles * 512;
+    if (hi_only) hipLaunchKernelGGL((pack16_kernel<true, RowSource>), dim3(blocks), dim3(256), 0, st, src, n_tiles, total, s, out);
+    else hipLaunchKernelGGL((pack16_kernel<false, RowSource>), dim3(blocks), dim3(256), 0, st, src, n_tiles, total, s, out);
+}
+void car_pack_conv16(hipStream_t st, int blocks, const float* w, int K, int N, bool flip, car_pack_scale s, _Float16* out) {
+    hipLaunchKernelGGL((pack16_kernel<false, ConvSource>), dim3(blocks), dim3(256), 0, st, ConvSource{w, K, N, flip}, N / 16, (long)9 * K * N, s, out);
+}
+void car_pack_tiles32(hipStream_t st, int blocks, const float* W, int ldw, const float* W2, int N, int K, int tiles, int chunks, int kgs, int chained,
+                      car_pack_scale s, _Float16* out) {
+    hipLaunchKernelGGL(pack32_kernel, dim3(blocks), dim3(256), 0, st, W, ldw, W2, N, K, tiles, kgs, chained, (long)chunks * tiles * kgs * 1024, s, out);
+}
+
+namespace {
+
+// ---- what the five packers here share: zero the bias table, one single-workgroup maximum per layer, the pack launches, CAR_CHECK_LAUNCH,
+// then device-to-device bias copies ---------------------------------------------------------------------------------------------------
 int zero_table(float* bias, size_t n, hipStream_t st, const char* who) {
     if (hipMemsetAsync(bias, 0, sizeof(float) * n, st) != hipSuccess) { car_set_error("%s: memset failed", who); return CAR_E_LAUNCH; }
     (void)hipGetLastError();
     return CAR_OK;
 }
+// the plan-time forms: one workgroup stores p = 2^shift in p_slot (read by the writers) and 1 / p in down_slot (read by the consuming kernel)
 void layer_scale(hipStream_t st, const float* W, int ldw, int N, int K, const float* b, float* p_slot, float* down_slot) {
-    hipLaunchKernelGGL(layer_scale_kernel, dim3(1), dim3(1024), 0, st, W, ldw, N, K, b, p_slot, down_slot);
+    car_pack_absmax(st, 1, W, ldw, nullptr, b, N, K, {nullptr, p_slot, down_slot});
 }
 template <bool HI_ONLY = false>
-void pack16(hipStream_t st, int blocks, const float* W, int ldw, const float* b, int N, int K, int n_tiles, int ksteps, int mode, int kbase,
-            const float* p_slot, _Float16* out) {
-    hipLaunchKernelGGL(pack16_kernel<HI_ONLY>, dim3(blocks), dim3(256), 0, st, W, ldw, b, N, K, n_tiles, ksteps, mode, kbase, p_slot, out);
+void pack16(hipStream_t st, int blocks, const float* W, int ldw, const float* b, int N, int K, int n_tiles, int ksteps, int chained, int kbase,
+            float* p_slot, _Float16* out) {
+    car_pack_rows16(st, blocks, W, ldw, b, N, K, n_tiles, ksteps, chained, kbase, {nullptr, p_slot, nullptr}, out, HI_ONLY);
 }
-void pack32(hipStream_t st, int blocks, const float* W, int ldw, int chunks, int kgs, int chained, const float* p_slot, _Float16* out) {
-    hipLaunchKernelGGL(pack32_kernel, dim3(blocks), dim3(256), 0, st, W, ldw, chunks, kgs, chained, p_slot, out);
+void pack32(hipStream_t st, int blocks, const float* W, int ldw, int chunks, int kgs, int chained, float* p_slot, _Float16* out) {
+    car_pack_tiles32(st, blocks, W, ldw, nullptr, kD, 16 * kgs * chunks, 4, chunks, kgs, chained, {nullptr, p_slot, nullptr}, out);
 }
 int copy_bias(float* dst, const float* src, int n, hipStream_t st, const char* who) {
     if (hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, st) != hipSuccess) { car_set_error("%s: bias copy failed", who); return CAR_E_LAUNCH; }

@@ -24,7 +24,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
+#include "car_lds_dma.h"
 
 constexpr int kTileFloats = 1024;                  // packed floats per (chunk, tile): [kg (2)][hi | lo][lane (64)][8 halves]
 constexpr int kMaxNT = 9;
@@ -65,9 +65,7 @@ struct Stream {
         for (int t = 0; t < c.nt; ++t) {
             const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_void*)(dst + 4 * (t * 256 + wave * 64)));
             const float* gsrc = src + 4 * (t * 256 + tid);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+            lds_dma16(gsrc, lds_dst);
         }
     }
     // chunk gi has landed, in every wave's view: this wave's pieces of it are older than the one chunk issued behind it (gi + 1: a chunk is
@@ -76,10 +74,10 @@ struct Stream {
     __device__ __forceinline__ void landed(int gi) const {
         const int n = __builtin_amdgcn_readfirstlane(gi + 1 < a.n_chunks ? a.chunk[gi + 1].nt : 0);
         switch (n) {
-            case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-            case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-            case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-            default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+            case 1: wait_vm<1>(); break;
+            case 4: wait_vm<4>(); break;
+            case 9: wait_vm<9>(); break;
+            default: wait_vm<0>(); break;
         }
         __syncthreads();
     }
@@ -306,44 +304,6 @@ __global__ void __launch_bounds__(256, 1) ray_tail_kernel(const ChainArgs a) {
     }
 }
 
-// scale[slot] = 2^shift with max |W (+ W2)| 2^shift in [2^13, 2^14), scale[kMaxLayers + slot] = 2^-shift.  One workgroup.
-__global__ void chain_scale_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ W2, int K, int N, float* __restrict__ scale, int slot) {
-    __shared__ float red[16];
-    float m = 0.0f;
-    for (long idx = threadIdx.x; idx < (long)N * K; idx += blockDim.x) {
-        const long at = (idx / K) * ldw + idx % K;
-        m = fmaxf(m, fabsf(W[at] + (W2 ? W2[at] : 0.0f)));
-    }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x / 64); ++w) m = fmaxf(m, red[w]);
-        float p, inv;
-        pow2_scale(fmaxf(m, 1e-30f), p, inv);
-        scale[slot] = p;
-        scale[kMaxLayers + slot] = inv;
-    }
-}
-// [chunk = 32 input channels][tile = 32 outputs][kg][hi | lo][lane][8 halves]; lane l carries output 32 tile + l % 32 and
-// chained: k = 32 chunk + (e & 3) + 8 (2 kg + (e >> 2)) + 4 (l >> 5) (the accumulator order of the layer before), else
-// k = 32 chunk + 16 kg + 8 (l >> 5) + e; outputs >= N and inputs >= K are zero
-__global__ void pack_chain_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ W2, int K, int N, int tiles, int chained,
-                                  long total, const float* __restrict__ scale, int slot, _Float16* __restrict__ packed) {
-    const float p = scale[slot];
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63), hl = (int)((idx >> 9) & 1), kg = (int)((idx >> 10) & 1);
-        const long ct = idx >> 11;
-        const int tile = (int)(ct % tiles), chunk = (int)(ct / tiles);
-        const int n = 32 * tile + (lane & 31);
-        const int k = chained ? 32 * chunk + (e & 3) + 8 * (2 * kg + (e >> 2)) + 4 * (lane >> 5) : 32 * chunk + 16 * kg + 8 * (lane >> 5) + e;
-        float v = 0.0f;
-        if (n < N && k < K) v = (W[(long)n * ldw + k] + (W2 ? W2[(long)n * ldw + k] : 0.0f)) * p;
-        const _Float16 hi = (_Float16)v;
-        packed[idx] = hl == 0 ? hi : (_Float16)(v - (float)hi);
-    }
-}
-
 }  // namespace
 
 // Split-fp16 tiles of one layer for the chain kernels: ceil(K/32) * ceil(N/32) * 1024 floats, [chunk][tile][kg][hi | lo][lane][8 halves].
@@ -355,11 +315,10 @@ extern "C" int car_chain_pack(const float* W, int ldw, const float* W2, int K, i
                               void* stream) {
     CAR_REQUIRE(W && packed && scale && K > 0 && N > 0 && ldw >= K && slot >= 0 && slot < kMaxLayers, "car_chain_pack: bad arguments");
     const int tiles = (N + 31) / 32;
-    const long total = (long)car_chain_packed_floats(K, N) * 2;              // halves
+    const car_pack_scale s{nullptr, scale + slot, scale + kMaxLayers + slot};
     (void)hipGetLastError();
-    hipLaunchKernelGGL(chain_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, W, ldw, W2, K, N, scale, slot);
-    hipLaunchKernelGGL(pack_chain_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream, W, ldw, W2, K, N, tiles, chained, total, scale, slot,
-                       reinterpret_cast<_Float16*>(packed));
+    car_pack_absmax((hipStream_t)stream, 1, W, ldw, W2, nullptr, N, K, s);
+    car_pack_tiles32((hipStream_t)stream, 256, W, ldw, W2, N, K, tiles, (K + 31) / 32, 2, chained, s, reinterpret_cast<_Float16*>(packed));
     CAR_CHECK_LAUNCH("car_chain_pack");
     return CAR_OK;
 }
@@ -382,11 +341,7 @@ int launch_chain(bool tail, const float* arena, const unsigned* offs, const int*
     a.M = M; a.V = V; a.R = R; a.zscale = zscale;
     const size_t lds_bytes = (size_t)kRing * kBufFloats * sizeof(float);
     auto kern = tail ? ray_tail_kernel : ray_mid_kernel;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { car_set_error("car_ray_chain: cannot reserve LDS: %s", hipGetErrorString(e)); return CAR_E_LAUNCH; }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(car_div_up(M, 128)), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    CAR_CHECK_LAUNCH("car_ray_chain");
+    CAR_LAUNCH_LDS("car_ray_chain", kern, dim3(car_div_up(M, 128)), dim3(256), lds_bytes, (hipStream_t)stream, a);
     return CAR_OK;
 }
 }  // namespace

@@ -245,14 +245,9 @@ static int launch_round2(bool qg, const float* g, const float* uh, const float* 
     void (*kern)(const float*, const float*, const float*, const float*, const float*, int, int, int, long, float*) =
         qg ? round2_kernel<true> : round2_kernel<false>;
     const size_t lds_bytes = qg ? kLdsBytesG : kLdsBytes;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { car_set_error("%s: cannot reserve LDS: %s", who, hipGetErrorString(e)); return CAR_E_LAUNCH; }
     const long groups = (S + 255) / 256;
     const unsigned blocks = (unsigned)(groups < 1024 ? groups : 1024);       // one 8-wave workgroup per CU x 256 CUs x 4: grid-stride
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream, g, uh, qry, wpacked, bias, V, R, P, S, logit);
-    hipError_t e_ = hipGetLastError();
-    if (e_ != hipSuccess) { car_set_error("%s: launch failed: %s", who, hipGetErrorString(e_)); return CAR_E_LAUNCH; }
+    CAR_LAUNCH_LDS(who, kern, dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream, g, uh, qry, wpacked, bias, V, R, P, S, logit);
     return CAR_OK;
 }
 

@@ -338,11 +338,7 @@ extern "C" int car_attend_round2(const float* g, const float* uh, const float* w
     }
     const long nbatch = ((long)b * R + 1) / 2;
     const size_t lds_bytes = (size_t)kLdsFloats * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void*)round2_attend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { car_set_error("car_attend_round2: cannot reserve LDS: %s", hipGetErrorString(e)); return CAR_E_LAUNCH; }
     const Args a{g, uh, wpacked, bias, val, b, V, R, P, w_out, z_out, ld_z, logit_out};
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(round2_attend_kernel, dim3((unsigned)(nbatch < cus ? nbatch : cus)), dim3(kThreads), lds_bytes, (hipStream_t)stream, a);
-    CAR_CHECK_LAUNCH("car_attend_round2");
+    CAR_LAUNCH_LDS("car_attend_round2", round2_attend_kernel, dim3((unsigned)(nbatch < cus ? nbatch : cus)), dim3(kThreads), lds_bytes, (hipStream_t)stream, a);
     return CAR_OK;
 }

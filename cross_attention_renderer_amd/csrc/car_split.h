@@ -1,4 +1,5 @@
-// car_split.h — the split-fp16 operand helpers shared by the matrix kernels (car_fused_mma.h, car_round2.hip, car_raychain.hip).
+// car_split.h — the split-fp16 operand helpers shared by the matrix kernels (car_fused_mma.h, car_round2.hip,
+// car_raychain.hip) and the packers (car_pack.hip).
 // Included INSIDE the including file's anonymous namespace, after its half8 typedef.
 #pragma once
 
@@ -33,10 +34,17 @@ __device__ __forceinline__ void split8(const float (&x)[8], float p, half8& hi, 
     }
     split8_scaled(y, hi, lo);
 }
-// power of two p with m p in [2^13, 2^14) for m > 0 (exponent clamped for tiny / huge m), and inv = 1 / p
+// power of two p with m p in [2^13, 2^14) for m > 0, and inv = 1 / p; the biased exponent of m is clamped to [LO, 230].
+// kPow2Lo: p in [2^-90, 2^43] — an all-zero vector or matrix (callers pass max(m, 1e-30)) must not push p_x * p_W, or a folded
+// bias * 2^43 * 2^shift, past fp32.
+// kPow2LoWide (car_lpips.hip's data gradient): p in [2^-90, 2^100] — a gradient row's largest magnitude is 1e-5 .. 1e-8 per unit of
+// cotangent, and the row's power of two has to follow it down so that a cotangent scaled by a power of two scales every result
+// exactly; p and the weights' 2^shift are never multiplied into one float there (the data gradient undoes them in two steps).
+constexpr int kPow2Lo = 97, kPow2LoWide = 40, kPow2Hi = 230;
+template <int LO = kPow2Lo>
 __device__ __forceinline__ void pow2_scale(float m, float& p, float& inv) {
     int e = (int)((__float_as_uint(m) >> 23) & 0xffu);
-    e = e < 97 ? 97 : (e > 230 ? 230 : e);          // p in [2^-90, 2^43]: an all-zero vector or matrix must not push p_x * p_W past fp32
+    e = e < LO ? LO : (e > kPow2Hi ? kPow2Hi : e);
     p = __uint_as_float((unsigned)(267 - e) << 23);
     inv = __uint_as_float((unsigned)(e - 13) << 23);
 }

@@ -13,9 +13,10 @@ Tensor = torch.Tensor
 
 
 def pow2_scale(m: float) -> float:
-    """2^k with m * 2^k in [2^13, 2^14): the window the split-fp16 operands are moved into (car_fused_mma.h pow2_scale)."""
-    _, ex = math.frexp(max(m, 1e-30))          # m = f * 2^ex, f in [0.5, 1)
-    return 2.0 ** (14 - ex)
+    """2^k with m * 2^k in [2^13, 2^14): the window the split-fp16 operands are moved into (csrc/car_split.h pow2_scale), with that
+    function's clamp 2^k in [2^-90, 2^43]: an all-zero layer gets 2^43."""
+    _, ex = math.frexp(max(m, 1e-30))          # m = f * 2^ex, f in [0.5, 1): the biased fp32 exponent is ex + 126
+    return 2.0 ** (14 - min(max(ex, 97 - 126), 230 - 126))
 
 
 def std16_k(ksteps: int) -> Tensor:
@@ -106,18 +107,23 @@ def pack_fused(m):
     return blob, bias, wpt
 
 
-def pack_tiles32(W: Tensor, chunks: int, kgs: int, chained: bool, p: float) -> Tensor:
-    """A-operand tiles of v_mfma_f32_32x32x16_f16 for csrc/car_round2.hip: [chunk][tile 4][K group][hi|lo][lane][8 halves];
-    lane l carries output 32 t + l % 32; chained: k = 32 c + (e & 3) + 8 (2 kg + (e >> 2)) + 4 (l >> 5), else k = 16 c + 8 (l >> 5) + e."""
+def pack_tiles32(W: Tensor, chunks: int, kgs: int, chained: bool, p: float, tiles: int = 4, W2: Optional[Tensor] = None) -> Tensor:
+    """A-operand tiles of v_mfma_f32_32x32x16_f16 for csrc/car_round2.hip (kgs = 1 or 2, 4 tiles) and csrc/car_raychain.hip (kgs = 2):
+    [chunk][tile][K group][hi|lo][lane][8 halves]; lane l carries output 32 t + l % 32; chained: k = 32 c + (e & 3) + 8 (2 kg + (e >> 2))
+    + 4 (l >> 5), else k = 16 kgs c + 16 kg + 8 (l >> 5) + e.  W2 (same shape) is added element-wise in fp32 before the power of two p;
+    outputs >= N and inputs >= K are zero."""
+    N, K = W.shape
     c = torch.arange(chunks)[:, None, None, None, None]
-    t = torch.arange(4)[None, :, None, None, None]
+    t = torch.arange(tiles)[None, :, None, None, None]
     kg = torch.arange(kgs)[None, None, :, None, None]
     lane = torch.arange(64)[None, None, None, :, None]
     e = torch.arange(8)[None, None, None, None, :]
-    n = (32 * t + lane % 32).expand(chunks, 4, kgs, 64, 8)
-    k = (32 * c + (e & 3) + 8 * (2 * kg + (e >> 2)) + 4 * (lane // 32)) if chained else (16 * c + 8 * (lane // 32) + e + 0 * kg)
-    k = k.expand(chunks, 4, kgs, 64, 8)
-    w = (W * p)[n, k]
+    n = (32 * t + lane % 32).expand(chunks, tiles, kgs, 64, 8)
+    k = (32 * c + (e & 3) + 8 * (2 * kg + (e >> 2)) + 4 * (lane // 32)) if chained else (16 * kgs * c + 16 * kg + 8 * (lane // 32) + e)
+    k = k.expand(chunks, tiles, kgs, 64, 8)
+    Wext = torch.zeros(32 * tiles, max(K, int(k.max()) + 1), dtype=torch.float32)
+    Wext[:N, :K] = (W if W2 is None else W + W2) * p
+    w = Wext[n, k]
     hi = w.half()
     lo = (w - hi.float()).half()
     return torch.stack([hi, lo], dim=3).contiguous().view(torch.float32).reshape(-1)      # (c, t, kg, hl, lane, 8 halves)

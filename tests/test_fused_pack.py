@@ -2,7 +2,8 @@
 
 CPU: evaluating a layer exactly the way the MFMA contracts the packed tiles (K step, tile, lane group, element) must reproduce
 W x for the standard, bias-folded and chained K mappings (tests/pack_reference.py is the layout's reference statement).
-GPU: the device packers of the C ABI (car_fused_pack / car_round2_pack, csrc/car_pack.hip) must emit exactly those bytes."""
+GPU: the device packers of the C ABI (car_fused_pack / car_round2_pack and the per-layer entries car_linear_x3_pack, car_chain_pack,
+car_conv3x3_pack, car_conv3x3_backward_pack, all through the kernels of csrc/car_pack.hip) must emit exactly those bytes."""
 import ctypes
 
 import pytest
@@ -163,15 +164,18 @@ def test_round2q_fold_reproduces_the_two_layers():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("scale", [1.0, 2e-4, 5e3])
+@pytest.mark.parametrize("scale", [1.0, 2e-4, 5e3, 0.0])
 def test_device_packers_emit_the_reference_bytes(scale):
     from cross_attention_renderer_amd import _lib
     lib = _lib.load()
     dev = torch.device("cuda:0")
     m = _module(4)
     with torch.no_grad():
-        for p_ in (m.query_encode_latent_2.weight, m.key_map.weight, m.query_embed.bias, m.query_repeat_embed_2.weight):
-            p_.mul_(scale)
+        if scale == 0.0:                       # an all-zero layer: the clamp of the power-of-two rule (2^43, not 2^113)
+            m.query_encode_latent_2.weight.zero_()
+        else:
+            for p_ in (m.query_encode_latent_2.weight, m.key_map.weight, m.query_embed.bias, m.query_repeat_embed_2.weight):
+                p_.mul_(scale)
     blob, bias, wpt = PR.pack_fused(m)
     r2w, r2b = PR.pack_round2(m)
     keep = []
@@ -271,3 +275,101 @@ def test_device_packers_emit_the_reference_bytes(scale):
     torch.cuda.synchronize()
     assert torch.equal(dtail.cpu().view(torch.int32), tail.view(torch.int32))
     assert torch.equal(dkqb.cpu().view(torch.int32), kqb.view(torch.int32))
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scale", [1.0, 2e-4, 5e3, 0.0])
+@pytest.mark.parametrize("K,N,ldw", [(64, 32, 64), (72, 48, 80), (576, 288, 579)])
+def test_linear_x3_pack_emits_the_reference_bytes(K, N, ldw, scale):
+    """car_linear_x3_pack: ceil(K / 32) x N / 16 standard tiles of the 16-wide format read out of a matrix with row stride ldw (K no
+    multiple of 32: zeros behind it), then 2^shift, 2^-shift.  scale 0.0: an all-zero matrix, the clamp of the power-of-two rule."""
+    from cross_attention_renderer_amd import _lib
+    lib = _lib.load()
+    W = torch.randn(N, ldw, generator=torch.Generator().manual_seed(K + N)) * scale
+    p = PR.pow2_scale(W[:, :K].abs().max().item())
+    ksteps = (K + 31) // 32
+    want = PR.pack_tiles16(W[:, :K], None, N // 16, PR.std16_k(ksteps), p).reshape(-1)
+    n = int(lib.car_linear_x3_packed_floats(K, N))
+    assert n == want.numel() + 64
+    dW, packed = W.to("cuda:0"), torch.full((n,), float("nan"), device="cuda:0")
+    rc = lib.car_linear_x3_pack(dW.data_ptr(), ldw, K, N, packed.data_ptr(), _stream())
+    assert rc == 0, lib.car_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(packed[:want.numel()]), _bits(want))
+    assert torch.equal(_bits(packed[want.numel():want.numel() + 2]), _bits(torch.tensor([p, 1.0 / p])))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K,N,chained,twice", [(18, 128, 0, False), (128, 3, 1, False), (288, 128, 1, True)])
+def test_chain_pack_emits_the_reference_bytes(K, N, chained, twice):
+    """car_chain_pack: ceil(K / 32) x ceil(N / 32) tiles of the 32-wide format with two K groups, standard or chained K order, outputs
+    >= N and inputs >= K zero; twice: W2 = the matrix's second K columns (row stride 2 K) added before the power of two, as lin_z is
+    packed.  The layer's 2^shift / 2^-shift land in its slot of the 32 shared floats and nowhere else."""
+    from cross_attention_renderer_amd import _lib
+    lib = _lib.load()
+    ldw = 2 * K if twice else K
+    Wfull = torch.randn(N, ldw, generator=torch.Generator().manual_seed(K + N))
+    W, W2 = Wfull[:, :K], (Wfull[:, K:] if twice else None)
+    p = PR.pow2_scale((W + W2 if twice else W).abs().max().item())
+    chunks, tiles, slot = (K + 31) // 32, (N + 31) // 32, 5
+    want = PR.pack_tiles32(W, chunks, 2, bool(chained), p, tiles=tiles, W2=W2)
+    assert want.numel() == int(lib.car_chain_packed_floats(K, N))
+    dW = Wfull.to("cuda:0")
+    packed = torch.full((want.numel(),), float("nan"), device="cuda:0")
+    scales = torch.full((32,), float("nan"), device="cuda:0")
+    rc = lib.car_chain_pack(dW.data_ptr(), ldw, dW.data_ptr() + 4 * K if twice else None, K, N, chained, packed.data_ptr(), scales.data_ptr(), slot,
+                            _stream())
+    assert rc == 0, lib.car_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(packed), _bits(want))
+    scales = scales.cpu()
+    assert scales[slot].item() == p and scales[16 + slot].item() == 1.0 / p
+    others = torch.ones(32, dtype=torch.bool)
+    others[[slot, 16 + slot]] = False
+    assert bool(torch.isnan(scales[others]).all())
+
+
+@pytest.mark.gpu
+def test_conv3x3_packs_emit_the_reference_bytes():
+    """car_conv3x3_pack (K, N) = (64, 64): standard 16-wide tiles over k = tap * K + channel of torch's [N][K][3][3], 64 scale floats
+    (2^shift, 2^-shift, the largest magnitude, zeros), the bias.  car_conv3x3_backward_pack (64, 128): the data gradient's matrix
+    w'[k][tap * N + n] = w[n][k][8 - tap] (transposed, taps flipped) in the same tiles, then its 64 scale floats."""
+    from cross_attention_renderer_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(7)
+
+    def scale_floats(Wm):
+        p = PR.pow2_scale(Wm.abs().max().item())
+        s = torch.zeros(64)
+        s[0], s[1], s[2] = p, 1.0 / p, Wm.abs().max()
+        return p, s
+    K, N = 64, 64
+    w, b = torch.randn(N, K, 3, 3, generator=g) * 0.05, torch.randn(N, generator=g)
+    Wm = w.permute(0, 2, 3, 1).reshape(N, 9 * K)
+    p, s = scale_floats(Wm)
+    want = torch.cat([PR.pack_tiles16(Wm, None, N // 16, PR.std16_k(9 * K // 32), p).reshape(-1), s, b])
+    assert want.numel() == int(lib.car_conv3x3_packed_floats(K, N))
+    dw, db, packed = w.to("cuda:0"), b.to("cuda:0"), torch.full((want.numel(),), float("nan"), device="cuda:0")
+    rc = lib.car_conv3x3_pack(dw.data_ptr(), db.data_ptr(), K, N, packed.data_ptr(), _stream())
+    assert rc == 0, lib.car_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(packed), _bits(want))
+    K, N = 64, 128
+    w = torch.randn(N, K, 3, 3, generator=g) * 0.05
+    Wm = w.flip(2, 3).permute(1, 2, 3, 0).reshape(K, 9 * N)
+    p, s = scale_floats(Wm)
+    want = torch.cat([PR.pack_tiles16(Wm, None, K // 16, PR.std16_k(9 * N // 32), p).reshape(-1), s])
+    assert want.numel() == int(lib.car_conv3x3_backward_packed_floats(K, N))
+    dw, packed = w.to("cuda:0"), torch.full((want.numel(),), float("nan"), device="cuda:0")
+    rc = lib.car_conv3x3_backward_pack(dw.data_ptr(), K, N, packed.data_ptr(), _stream())
+    assert rc == 0, lib.car_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(packed), _bits(want))

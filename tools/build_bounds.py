@@ -37,10 +37,12 @@ def build(reintroduce: bool = False):
         assert old != cur and old.count("kPieces; ++p") >= 1, "car_linear16.hip no longer has the lines commit 0d74f26 changed"
         srcf = os.path.join(DEV, "linear16_with_0d74f26_reverted.hip")
         open(srcf, "w").write(old)
+        # beside it: car_api.hip (errors, the LDS reservation), car_pack.hip (the kernels car_linear_x3_pack launches) and car_round2.hip (size
+        # queries car_pack.hip calls) — a library of its own with no symbol left undefined
         for tag, flags in (("", []), ("_bounds", ["-DCAR_BOUNDS"])):
             so = os.path.join(DEV, f"liboldlin16{tag}.so")
             subprocess.check_call([ge._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *flags, "-I", os.path.join(ROOT, "include"),
-                                   "-I", ge.CSRC, srcf, os.path.join(ge.CSRC, "car_api.hip"), "-o", so])
+                                   "-I", ge.CSRC, srcf, *(os.path.join(ge.CSRC, u) for u in ("car_api.hip", "car_pack.hip", "car_round2.hip")), "-Wl,-z,defs", "-o", so])
             out.append(so)
     return out
 
