@@ -164,6 +164,11 @@ SIGNATURES = {
     "car_epipolar_overlay": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "car_image_grid_scratch_floats": (c_size_t, [c_int, c_int, c_int]),
     "car_image_grid": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, c_size_t, _P]),
+    "car_essential_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "car_essential_solve": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, _P]),
+    "car_essential_score": (c_int, [_P, _P, c_int, _P, _P, c_int, c_double, _P, _P, _P]),
+    "car_essential_select": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_double, _P, _P, _P, _P]),
+    "car_essential_ransac": (c_int, [_P, _P, c_int, _P, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -309,6 +309,117 @@ def lpips_loss(x: torch.Tensor, y: torch.Tensor, weights: LpipsWeights) -> torch
     return _LpipsLoss.apply(x, y, weights)
 
 
+# ---- relative pose of an unposed pair (car_essential_ransac, csrc/car_pose.hip) -----------------------------------------
+def pose_sample_table(n: int, hypotheses: int, seed: int = 0):
+    """The five-point sample table: ``hypotheses`` rows of five distinct indices below ``n`` as int32, uniform over ordered 5-tuples,
+    from ``numpy.random.default_rng(seed)`` (one ``integers`` call; the k-th index of a row is drawn among the n - k values its row
+    has not taken yet)."""
+    import numpy as np
+    g = np.random.default_rng(seed)
+    draws = g.integers(0, np.array([n, n - 1, n - 2, n - 3, n - 4]), size=(hypotheses, 5))
+    out = np.empty((hypotheses, 5), dtype=np.int64)
+    for k in range(5):
+        idx = draws[:, k].copy()
+        prev = np.sort(out[:, :k], axis=1)
+        for j in range(k):
+            idx += idx >= prev[:, j]
+        out[:, k] = idx
+    return out.astype(np.int32)
+
+
+def recover_pose(E, x0, x1, mask, dist: float = 1e9):
+    """OpenCV's ``recoverPose`` written down from its documented procedure, in float64 on the host (a few KB once per pair).  SVD of E
+    with U and V^T sign-fixed to determinant +1; R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2]; the combinations (R1, t), (R2, t),
+    (R1, -t), (R2, -t) in this order; for each the matches of ``mask`` are triangulated linearly with P0 = [I | 0], P1 = [R | t] and
+    those with 0 < z < ``dist`` in both cameras counted; the first combination with the largest count wins.  Returns (count, R, t,
+    mask of the matches that passed for the winner).  Not pinned against cv2, which is not available offline."""
+    import numpy as np
+    E = np.asarray(E, dtype=np.float64).reshape(3, 3)
+    U, _, Vt = np.linalg.svd(E)
+    U = -U if np.linalg.det(U) < 0 else U
+    Vt = -Vt if np.linalg.det(Vt) < 0 else Vt
+    W = np.array([[0.0, 1.0, 0.0], [-1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    R1, R2, t = U @ W @ Vt, U @ W.T @ Vt, U[:, 2]
+    mask = np.asarray(mask).astype(bool)
+    sel = np.nonzero(mask)[0]
+    a, b = np.asarray(x0, dtype=np.float64)[sel], np.asarray(x1, dtype=np.float64)[sel]
+    best = None
+    for R, tt in ((R1, t), (R2, t), (R1, -t), (R2, -t)):
+        P1 = np.concatenate([R, tt[:, None]], axis=1)
+        A = np.zeros((len(sel), 4, 4))                                  # x (P row 3) - (P row 1), y (P row 3) - (P row 2), both views
+        A[:, 0, 0], A[:, 0, 2] = -1.0, a[:, 0]
+        A[:, 1, 1], A[:, 1, 2] = -1.0, a[:, 1]
+        A[:, 2] = b[:, 0, None] * P1[2][None] - P1[0][None]
+        A[:, 3] = b[:, 1, None] * P1[2][None] - P1[1][None]
+        Q = np.linalg.svd(A)[2][:, 3] if len(sel) else np.zeros((0, 4))
+        with np.errstate(all="ignore"):
+            X = Q[:, :3] / Q[:, 3:4]
+            z0, z1 = X[:, 2], (X @ R.T + tt)[:, 2]
+            good = (z0 > 0) & (z0 < dist) & (z1 > 0) & (z1 < dist)
+        if best is None or int(good.sum()) > best[0]:
+            best = (int(good.sum()), R, tt, good)
+    out = np.zeros(mask.shape[0], dtype=bool)
+    out[sel] = best[3]
+    return best[0], best[1], best[2], out
+
+
+def estimate_pose(kpts0, kpts1, K0, K1, thresh, hypotheses: int = 8192, seed: int = 0, device=None):
+    """Relative pose of the second view from keypoint matches, the reference's ``estimate_pose`` (dataset/load_video_superglue.py:
+    114-138) with its signature and conventions: ``kpts0``, ``kpts1`` (N, 2) matched pixels, ``K0``, ``K1`` intrinsics, ``thresh`` in
+    pixels; ``norm_thresh = thresh / mean(K0[0,0], K1[1,1], K0[0,0], K1[1,1])``, points normalised with ``K[[0,1],[2,2]]`` and
+    ``K[[0,1],[0,1]]``.  Returns ``(R, t, inlier_mask)`` with x_2 = R x_1 + t, |t| = 1 and the mask as cv2 leaves it after recoverPose
+    (the winner's inliers that triangulate in front of both cameras), or None below five matches or when no hypothesis gives a pose.
+
+    The essential matrix comes from ``car_essential_ransac`` on the device (csrc/car_pose.hip), all fp64.  In place of cv2's
+    ``prob=0.99999`` stop rule (at most 1000 iterations) there is a FIXED BUDGET: ``hypotheses`` five-point samples, drawn on the host
+    from ``numpy.random.default_rng(seed)`` (``pose_sample_table``), uploaded once, every one solved and scored against every match.
+    Scoring a superset of hypotheses can never return fewer inliers, so a larger budget only helps; the result is a function of the
+    inputs, ``hypotheses`` and ``seed`` alone (ties: lowest hypothesis, then lowest candidate).  The default of 8192 is no measured
+    optimum: at 30-40 % inliers 300 hypotheses are too few and 4000 are enough (profiles/pose_estimate.md).  recoverPose runs on the
+    host in float64 (``recover_pose``).  Neither stage is pinned against cv2.
+
+    Raises ValueError for shapes the device entry refuses, RuntimeError without a ROCm device (there is no CPU fallback)."""
+    import ctypes
+    import numpy as np
+    from . import _lib
+    kpts0, kpts1 = np.asarray(kpts0, dtype=np.float64), np.asarray(kpts1, dtype=np.float64)
+    if kpts0.ndim != 2 or kpts0.shape[1] != 2 or kpts0.shape != kpts1.shape:
+        raise ValueError(f"estimate_pose: need two (N, 2) arrays of matched keypoints, got {kpts0.shape} and {kpts1.shape}")
+    if len(kpts0) < 5:
+        return None
+    K0, K1 = np.asarray(K0, dtype=np.float64), np.asarray(K1, dtype=np.float64)
+    f_mean = np.mean([K0[0, 0], K1[1, 1], K0[0, 0], K1[1, 1]])
+    norm_thresh = float(thresh / f_mean)
+    x0 = np.ascontiguousarray((kpts0 - K0[[0, 1], [2, 2]][None]) / K0[[0, 1], [0, 1]][None])
+    x1 = np.ascontiguousarray((kpts1 - K1[[0, 1], [2, 2]][None]) / K1[[0, 1], [0, 1]][None])
+    if not torch.cuda.is_available():
+        raise RuntimeError("estimate_pose: needs a ROCm device; there is no CPU fallback")
+    dev = torch.device(device if device is not None else "cuda")
+    N, H = len(x0), int(hypotheses)
+    lib = _lib.load()
+    nbytes = lib.car_essential_workspace_bytes(N, H)
+    if nbytes == 0:
+        raise ValueError(lib.car_last_error().decode())
+    with torch.cuda.device(dev):
+        d0, d1 = torch.from_numpy(x0).to(dev), torch.from_numpy(x1).to(dev)
+        table = torch.from_numpy(pose_sample_table(N, H, seed)).to(dev)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        E = torch.empty(9, dtype=torch.float64, device=dev)
+        best = torch.empty(3, dtype=torch.int32, device=dev)
+        inl = torch.empty(N, dtype=torch.uint8, device=dev)
+        code = lib.car_essential_ransac(d0.data_ptr(), d1.data_ptr(), N, table.data_ptr(), H, ctypes.c_double(norm_thresh), E.data_ptr(),
+                                        best.data_ptr(), inl.data_ptr(), work.data_ptr(), nbytes,
+                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if code == -1:
+            raise ValueError(lib.car_last_error().decode())
+        _lib.check(code, "car_essential_ransac")
+        E, best, inl = E.cpu().numpy(), best.cpu().numpy(), inl.cpu().numpy()
+    if best[0] < 1:
+        return None
+    n, R, t, mask = recover_pose(E, x0, x1, inl)
+    return (R, t, mask) if n > 0 else None
+
+
 def write_png(path: str, rgb: torch.Tensor) -> None:
     """(H, W, 3) float image in [-1, 1] -> 8-bit PNG (imageio is not available in this image)."""
     img = ((rgb.clamp(-1, 1) + 1) * 127.5).round().to(torch.uint8).cpu().numpy()

@@ -3,9 +3,10 @@
 Behaviour of the reference's ``dataset/load_video_superglue.py``: ``linear_interpolate`` (:33-54), ``make_circle`` (:57-82),
 ``rotate_interpolate`` (:85-111) and the input dict assembled by its ``get_camera_pose`` (:462-506) once the relative pose (R, t)
 of the second image is known.  The reference gets (R, t) from a SuperPoint + SuperGlue matcher followed by
-``cv2.findEssentialMat`` / ``recoverPose`` (:114-139, 421-460); that matcher's weights are not part of the reference tree and the
-estimate is made once per image pair, so here (R, t) is an input.  Rotations are interpolated with ``roma.rotmat_slerp`` in the
-reference (roma is not installed here): unit-quaternion spherical interpolation along the shorter arc, restated below.
+``cv2.findEssentialMat`` / ``recoverPose`` (:114-139, 421-460); that matcher's weights are not part of the reference tree, so here the
+matcher's output file is an input (``read_matches``; ``harness.estimate_pose`` makes (R, t) from it), or (R, t) itself.  Rotations
+are interpolated with ``roma.rotmat_slerp`` in the reference (roma is not installed here): unit-quaternion spherical interpolation
+along the shorter arc, restated below.
 tests/test_trajectory.py replays vectors produced by the reference's own functions (tests/golden/make_trajectory_golden.py)."""
 from __future__ import annotations
 
@@ -99,6 +100,20 @@ def rotate_interpolate(poses: np.ndarray, n: int) -> np.ndarray:
 
 
 UNPOSED_K = np.array([[225.0, 0.0, 128.0, 0.0], [0.0, 225.0, 128.0, 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]])
+
+
+def read_matches(path: str):
+    """The matches of one image pair as SuperGlue's published ``match_pairs.py`` writes them: an .npz with ``keypoints0`` (n0, 2),
+    ``keypoints1`` (n1, 2), ``matches`` (n0,) — the index into keypoints1 or -1 — and ``match_confidence`` (n0,).  Keeps the pairs
+    with ``matches > -1`` and returns ``mkpts0, mkpts1, mconf`` (load_video_superglue.py:459-463).  Raises ValueError for a file
+    without the four arrays."""
+    with np.load(path) as f:
+        missing = [k for k in ("keypoints0", "keypoints1", "matches", "match_confidence") if k not in f.files]
+        if missing:
+            raise ValueError(f"{path}: not a SuperGlue matches file, {missing} missing (need keypoints0, keypoints1, matches, match_confidence)")
+        kpts0, kpts1, matches, conf = f["keypoints0"], f["keypoints1"], f["matches"], f["match_confidence"]
+    valid = matches > -1
+    return kpts0[valid], kpts1[matches[valid]], conf[valid]
 
 
 def center_crop_square(im: np.ndarray) -> np.ndarray:

@@ -1,15 +1,26 @@
 """Novel views from two images of unknown pose (mirrors reference experiment_scripts/render_unposed_traj.py).
 
+    python experiment_scripts/render_unposed_traj.py --experiment_name demo --checkpoint_path model.pth --im1 a.png --im2 b.png --matches m.npz
     python experiment_scripts/render_unposed_traj.py --experiment_name demo --checkpoint_path model.pth --im1 a.png --im2 b.png --pose rt.npz
 
-The reference estimates the relative pose of the second image with SuperPoint + SuperGlue + ``cv2.findEssentialMat`` /
-``recoverPose`` (dataset/load_video_superglue.py:114-139, 421-460); the matcher's weights are not part of the reference tree and cv2
-is not installed here, so (R, t) — ``recoverPose``'s convention, x_2 = R x_1 + t — comes from ``--pose`` (an .npz with ``R`` (3, 3) and
-``t`` (3,)).  Everything after that is the reference's path: the two images centre-cropped to squares and scaled to [-1, 1], first camera =
+The reference gets the relative pose of the second image in two steps (dataset/load_video_superglue.py:419-479): SuperPoint + SuperGlue
+match keypoints of the two 256 x 256 crops, then ``estimate_pose`` (:114-138) runs ``cv2.findEssentialMat`` (RANSAC) and
+``cv2.recoverPose`` on the matches.  The first step is NOT here: the matcher's weights are not part of the reference tree.  The second
+step is: ``--matches`` takes the .npz that SuperGlue's published ``match_pairs.py`` writes for the pair (``keypoints0``, ``keypoints1``,
+``matches``, ``match_confidence``; ``trajectory.read_matches``) and ``harness.estimate_pose`` estimates (R, t) from it on the device,
+with K = ``trajectory.UNPOSED_K`` and a threshold of 1 pixel as the reference sets them, and prints the inlier count.  The keypoints are
+pixels of the 256 x 256 CROPS: run the matcher on the centre-cropped, resized images, as the reference does, not on the photographs.
+The estimator is not cv2's: a fixed budget of ``--pose_hypotheses`` five-point samples, all scored, replaces cv2's early stop, and
+neither it nor the host's recoverPose is pinned against cv2.  ``--pose`` instead takes (R, t) —
+``recoverPose``'s convention, x_2 = R x_1 + t — from an .npz with ``R`` (3, 3) and ``t`` (3,) estimated elsewhere.  With --im1 / --im2
+exactly one of the two is required.
+
+Everything after that is the reference's path: the two images centre-cropped to squares and scaled to [-1, 1], first camera =
 world frame, second at inv([R | t]) with its position divided by 1.2, fixed RealEstate10K intrinsics, 76 query poses on a helix
 between the two (``trajectory.unposed_pair_input``, pinned in tests/test_trajectory.py), ``get_z`` once, one chunked forward per
 pose, frames written as PNG.  Images must already be 256 pixels high (the reference resizes with skimage, not installed here).
---synthetic renders the same trajectory over the seeded synthetic pair and feature pyramid."""
+--synthetic renders the same trajectory over the seeded synthetic pair and feature pyramid; with --matches its pose is the
+estimator's too, and the pose used is written to ``pose.npz`` beside the frames."""
 import os
 import sys
 
@@ -40,23 +51,43 @@ def render(rank, opt):
     H = 256
     opt.img_sidelength = H
     uv = synthetic.pixel_grid(H, H)
-    if opt.synthetic or not (opt.im1 and opt.im2 and opt.pose):
+    if opt.im1 and opt.im2 and not opt.synthetic and bool(opt.pose) == bool(opt.matches):
+        raise SystemExit("--im1 / --im2 need exactly one of --matches (SuperGlue's .npz for the pair) and --pose (an .npz with R, t)")
+    estimated = None
+    if opt.matches:
+        mkpts0, mkpts1, _ = trajectory.read_matches(opt.matches)
+        K = trajectory.UNPOSED_K[:3, :3]
+        estimated = harness.estimate_pose(mkpts0, mkpts1, K, K, 1.0, hypotheses=opt.pose_hypotheses, device=dev)
+        if estimated is None:
+            raise SystemExit(f"{opt.matches}: no relative pose from its {len(mkpts0)} matches (at least five good ones are needed)")
+        if rank == 0:
+            print(f"pose from {len(mkpts0)} matches, {opt.pose_hypotheses} hypotheses: {int(estimated[2].sum())} inliers")
+    if opt.synthetic or not (opt.im1 and opt.im2 and (opt.pose or opt.matches)):
         model = common.build_model(opt, dev)
         g = np.random.default_rng(0)
         yaw = np.deg2rad(-12.0)
         R = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]]).T
-        inp = trajectory.unposed_pair_input(g.random((H, H, 3)), g.random((H, H, 3)), R, -R @ np.array([0.6, 0.03, 0.05]), uv)
+        t = -R @ np.array([0.6, 0.03, 0.05])
+        if estimated is not None:
+            R, t = estimated[:2]
+        inp = trajectory.unposed_pair_input(g.random((H, H, 3)), g.random((H, H, 3)), R, t, uv)
         z = [t.to(dev) for t in synthetic.feature_maps(1, 2, H, seed=1)]
         inp = harness.to_device(inp, dev, opt.cameras)
     else:
         model = common.build_model(opt, dev, with_encoder=True)
-        rt = np.load(opt.pose)
-        inp = harness.to_device(trajectory.unposed_pair_input(_read_image(opt.im1), _read_image(opt.im2), rt["R"], rt["t"], uv), dev, opt.cameras)
+        if estimated is not None:
+            R, t = estimated[:2]
+        else:
+            rt = np.load(opt.pose)
+            R, t = rt["R"], rt["t"]
+        inp = harness.to_device(trajectory.unposed_pair_input(_read_image(opt.im1), _read_image(opt.im2), R, t, uv), dev, opt.cameras)
         with torch.no_grad():
             z = model.get_z(inp)
     out_dir = opt.out_dir or os.path.join(opt.logging_root, opt.experiment_name, "unposed")
     if rank == 0:
         os.makedirs(out_dir, exist_ok=True)
+        if estimated is not None:
+            np.savez(os.path.join(out_dir, "pose.npz"), R=estimated[0], t=estimated[1], inliers=estimated[2])
     nq = inp["query"]["cam2world"].shape[1] if not opt.n_frames else min(opt.n_frames, inp["query"]["cam2world"].shape[1])
     for i in range(nq):
         frame = {"context": inp["context"], "query": {"cam2world": inp["query"]["cam2world"][:, i:i + 1], "intrinsics": inp["query"]["intrinsics"][:, i:i + 1],
@@ -74,5 +105,9 @@ if __name__ == "__main__":
     p.add_argument("--im1", type=str, default=None)
     p.add_argument("--im2", type=str, default=None)
     p.add_argument("--pose", type=str, default=None, help=".npz with R (3,3), t (3,) of the second camera relative to the first")
+    p.add_argument("--matches", type=str, default=None,
+                   help=".npz of SuperGlue's match_pairs.py for the pair (keypoints0, keypoints1, matches, match_confidence; pixels of the "
+                        "256x256 crops): the relative pose is estimated from it on the device")
+    p.add_argument("--pose_hypotheses", type=int, default=8192, help="five-point hypotheses the pose estimator solves and scores (--matches)")
     opt = p.parse_args()
     common.spawn(render, opt)

@@ -647,6 +647,35 @@ size_t car_image_grid_scratch_floats(int N, int H, int W);
 int car_image_grid(const float* x, int N, int H, int W, int scale_each, int clamp, float lo, float hi, float* out, float* scratch,
                    size_t scratch_floats, void* stream);
 
+/* ---- relative pose of an unposed pair from keypoint matches (dataset/load_video_superglue.py:114-138: cv2.findEssentialMat(RANSAC)
+ *      + cv2.recoverPose; csrc/car_pose.hip).  All arithmetic fp64.  x0, x1 [N][2]: the matches' normalised image points
+ * (kpt - c) / f in the first and second view; samples [H][5] int32: the caller's table of five-point samples; cand [H][10][9]: up to ten
+ * real essential matrices per hypothesis, row-major, unit Frobenius norm, x1^T E x0 = 0 on the five points, in ascending order of the
+ * solver's last unknown, unused slots zero; nsol [H] their number.
+ * car_essential_solve: Nister's five-point solver, one lane per hypothesis: null space of the 5 x 9 system (complete pivoting), the ten
+ *   cubic constraints eliminated on a 10 x 20 matrix (partial pivoting), the degree-10 polynomial's real roots bracketed through its chain
+ *   of derivatives and bisected (every loop has a fixed bound).  nsol = 0, and nothing is read through the row, when an index lies
+ *   outside [0, N), is repeated, names a non-finite point, an elimination meets a zero pivot (at most 1e-13 of the matrix's scale), or
+ *   the polynomial's leading coefficient is so small that the bound on its roots reaches 2^70 (the bisection could not resolve them).
+ * car_essential_score: counts [H][10] = the matches whose Sampson error (x1^T E x0)^2 / ((E x0)_1^2 + (E x0)_2^2 + (E^T x1)_1^2 +
+ *   (E^T x1)_2^2), cv2's error for this model, is below thresh^2 (a non-finite error is no inlier; slots >= nsol count 0);
+ *   hyp_best [H] = the largest count of each hypothesis.  Any N >= 5: the matches pass through LDS 512 at a time.
+ * car_essential_select: the winner is the candidate with the largest count; ties go to the lowest hypothesis, then to the lowest
+ *   candidate, so the result depends on the inputs alone, never on the schedule (integer maxima, no float atomics).  E [9] its matrix,
+ *   best [3] = {count, hypothesis, candidate}, inliers [N] uint8 its inlier mask; {0, -1, -1}, zeros when no hypothesis has a candidate.
+ * car_essential_ransac: the three stages on `work` (car_essential_workspace_bytes(N, H) bytes, 16-byte aligned, caller-owned; 0 for a
+ *   refused shape).  Bitwise reproducible.
+ * Refusals (CAR_E_ARG, nothing launched): N < 5, H < 1, N or H above 2^24, a null pointer, thresh <= 0 or not finite, a workspace that
+ * is too small.  recoverPose is the host's (harness.estimate_pose). */
+size_t car_essential_workspace_bytes(int N, int H);
+int car_essential_solve(const double* x0, const double* x1, int N, const int* samples, int H, double* cand, int* nsol, void* stream);
+int car_essential_score(const double* x0, const double* x1, int N, const double* cand, const int* nsol, int H, double thresh, int* counts,
+                        int* hyp_best, void* stream);
+int car_essential_select(const double* x0, const double* x1, int N, const double* cand, const int* nsol, const int* counts, int H,
+                         double thresh, double* E, int* best, unsigned char* inliers, void* stream);
+int car_essential_ransac(const double* x0, const double* x1, int N, const int* samples, int H, double thresh, double* E, int* best,
+                         unsigned char* inliers, void* work, size_t work_bytes, void* stream);
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
