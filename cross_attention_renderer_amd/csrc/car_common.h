@@ -46,6 +46,15 @@ static inline unsigned car_div_up(long a, long b) { return (unsigned)((a + b - 1
         if (rc_ != CAR_OK) return rc_; \
     } while (0)
 
+// A HIP runtime call (memset, copy, event) that must succeed: the error text is the caller's
+#define CAR_CHECK_HIP(call, ...)              \
+    do {                                      \
+        if ((call) != hipSuccess) {           \
+            car_set_error(__VA_ARGS__);       \
+            return CAR_E_LAUNCH;              \
+        }                                     \
+    } while (0)
+
 // The launch of a kernel with dynamic LDS: reserve, clear the sticky error, launch, check (returns from the calling function on failure).
 // car_reserve_lds (car_api.hip): the reservation is a per-device attribute of the kernel, set once per (kernel, device) — not on each of
 // the dozens of launches of a step — and again when a call asks for more than the largest reserved so far.  Its refusal is CAR_E_LAUNCH

@@ -25,33 +25,28 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 #include "car_lds_dma.h"
-
-constexpr int kTileFloats = 1024;                  // packed floats per (chunk, tile): [kg (2)][hi | lo][lane (64)][8 halves]
-constexpr int kMaxNT = 9;
-constexpr int kBufFloats = kMaxNT * kTileFloats;   // one weight buffer: 36 KB
-constexpr int kMaxChunks = 96;
-constexpr int kMaxLayers = 16;
+#include "car_fused_layout.h"
+#include "car_chain_layout.h"                      // tile geometry, the layers with their scale slots, both kernels' sequences and bias tables
 
 struct Chunk { unsigned off; int nt; };            // float offset of the chunk's tiles inside the weight arena, tiles in the chunk
 struct ChainArgs {
     const float* arena;                            // every layer's packed tiles
     const float* bias;                             // biases of the layers, back to back in consumption order
-    const float* scale;                            // [2 kMaxLayers]: 2^shift of every packed layer, then 2^-shift (car_chain_pack)
+    const float* scale;                            // [kScaleFloats]: 2^shift of every packed layer, then 2^-shift (car_chain_pack)
     int layer[kMaxLayers];                         // scale slot of the kernel's i-th layer
     Chunk chunk[kMaxChunks];
     int n_chunks;
-    const float* x0; int ld0;                      // first layer's input rows (ebar), K0 = 576
-    const float* x1; int ld1;                      // tail: decoder ray input (phi_x), K = 18
-    const float* z1_in;                            // tail: z1 [rays, 288]
-    float* out0;                                   // mid: z1 [rays, 288];  tail: rgb [rays, 3]
-    float* out1;                                   // mid: uh [rays, 128];  tail: valid [rays]
+    const float* x0; int ld0;                      // first layer's input rows (ebar), K0 = kC
+    const float* x1; int ld1;                      // tail: decoder ray input (phi_x), K = kPhiIn
+    const float* z1_in;                            // tail: z1 [rays, kE]
+    float* out0;                                   // mid: z1 [rays, kE];  tail: rgb [rays, 3]
+    float* out1;                                   // mid: uh [rays, kD];  tail: valid [rays]
     const CarRay* rays;                            // tail: overlaps of every view
     long M;                                        // rays
     int V, R;
     float zscale;                                  // tail: V
 };
 
-constexpr int kRing = 3;                           // weight buffers: the chunk being multiplied and the two behind it
 struct Stream {
     const ChainArgs& a;
     float* lds;
@@ -69,14 +64,14 @@ struct Stream {
         }
     }
     // chunk gi has landed, in every wave's view: this wave's pieces of it are older than the one chunk issued behind it (gi + 1: a chunk is
-    // nt loads per thread, nt in {1, 4, 9}), which may stay in flight.  Loads the compiler issued in between (a layer's input rows) only
+    // nt loads per thread, nt in kTileCounts), which may stay in flight.  Loads the compiler issued in between (a layer's input rows) only
     // make the count stricter; its own waits never know of these loads and are stricter for that
     __device__ __forceinline__ void landed(int gi) const {
         const int n = __builtin_amdgcn_readfirstlane(gi + 1 < a.n_chunks ? a.chunk[gi + 1].nt : 0);
         switch (n) {
-            case 1: wait_vm<1>(); break;
-            case 4: wait_vm<4>(); break;
-            case 9: wait_vm<9>(); break;
+            case kTileCounts[0]: wait_vm<kTileCounts[0]>(); break;
+            case kTileCounts[1]: wait_vm<kTileCounts[1]>(); break;
+            case kTileCounts[2]: wait_vm<kTileCounts[2]>(); break;
             default: wait_vm<0>(); break;
         }
         __syncthreads();
@@ -224,7 +219,15 @@ __device__ __forceinline__ void store_rows(const f32x16 (&acc)[NT], float* row, 
         }
 }
 
-// bias layout — mid: latent_value (288), encode_latent (128);  layers: 0 latent_value, 1 encode_latent, 2 query_repeat_embed[:, :128]
+// Both kernels spell their layers out; the table they are checked against, dW's positions (kMidSeq, kTailSeq) and the bias offsets:
+// car_chain_layout.h
+static_assert(chain_tiles(kSlotLatentValue) == 9 && chain_tiles(kSlotEncodeLatent) == 4 && chain_tiles(kSlotQueryRepeat) == 4 &&
+              chain_tiles(kSlotLinIn) == 4 && chain_tiles(chain_block_slot(0, 0)) == 4 && chain_tiles(chain_block_slot(0, 1)) == 4 &&
+              chain_tiles(chain_block_slot(0, 2)) == 4 && chain_tiles(kSlotLinOut) == 1, "the kernels' <9>, <4>, <1> are the table's tile counts");
+static_assert(tail_block_bias(0, 0) == kTailBiasLinIn + kD && tail_block_bias(0, 2) == kTailBiasLinIn + 3 * kD && tail_block_bias(1, 0) == kTailBiasLinIn + 4 * kD &&
+              tail_block_pos(0, 2) == kTailPosBlocks + 2 && tail_block_pos(1, 0) == kTailPosBlocks + 3, "the tail's spelled-out offsets and positions");
+constexpr int kLvK = kChainLayer[kSlotLatentValue].K, kLvChunks = chain_chunks(kSlotLatentValue);
+constexpr int kInK = kChainLayer[kSlotLinIn].K, kInChunks = chain_chunks(kSlotLinIn);
 __global__ void __launch_bounds__(256, 1) ray_mid_kernel(const ChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = lane & 31, h = lane >> 5;
@@ -238,20 +241,18 @@ __global__ void __launch_bounds__(256, 1) ray_mid_kernel(const ChainArgs a) {
     f32x16 z1[9];
     zero<9>(z1);
     add_bias<9>(z1, a.bias, h);
-    layer_global<9>(z1, a.x0 + lrow * a.ld0, 576, 18, dW(0), st, tid, lane, wave);            // z1 = Wv ebar + bv
-    if (row < a.M) store_rows<9>(z1, a.out0 + row * 288, 288, h);
+    layer_global<9>(z1, a.x0 + lrow * a.ld0, kLvK, kLvChunks, dW(0), st, tid, lane, wave);    // z1 = Wv ebar + bv
+    if (row < a.M) store_rows<9>(z1, a.out0 + row * kE, kE, h);
     f32x16 hb[4];
     zero<4>(hb);
-    add_bias<4>(hb, a.bias + 288, h);                                                         // encode_latent.bias
+    add_bias<4>(hb, a.bias + kMidBiasEncodeLatent, h);
     layer_chained<9, 4, false>(hb, z1, dW(1), st, tid, lane, wave);
     f32x16 uh[4];
     zero<4>(uh);
     layer_chained<4, 4, false>(uh, hb, dW(2), st, tid, lane, wave);                           // Wr1[:, :128], no bias (it rides with the local half)
-    if (row < a.M) store_rows<4>(uh, a.out1 + row * 128, 128, h);
+    if (row < a.M) store_rows<4>(uh, a.out1 + row * kD, kD, h);
 }
 
-// bias layout — tail: latent_value (288), lin_in (128), 3 x { lin_z, fc_0, fc_1 } (128 each), lin_out (padded to 32);
-// layers: 0 latent_value, 1 lin_in, 2 + 3 i lin_z_i, 3 + 3 i fc_0_i, 4 + 3 i fc_1_i, 11 lin_out
 __global__ void __launch_bounds__(256, 1) ray_tail_kernel(const ChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = lane & 31, h = lane >> 5;
@@ -268,31 +269,33 @@ __global__ void __launch_bounds__(256, 1) ray_tail_kernel(const ChainArgs a) {
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const float4 v = *reinterpret_cast<const float4*>(a.z1_in + lrow * 288 + 32 * t + 8 * g + 4 * h);
+            const float4 v = *reinterpret_cast<const float4*>(a.z1_in + lrow * kE + 32 * t + 8 * g + 4 * h);
             z[t][4 * g] = a.zscale * v.x; z[t][4 * g + 1] = a.zscale * v.y; z[t][4 * g + 2] = a.zscale * v.z; z[t][4 * g + 3] = a.zscale * v.w;
         }
     add_bias<9>(z, a.bias, h);
-    layer_global<9>(z, a.x0 + lrow * a.ld0, 576, 18, dW(0), st, tid, lane, wave);
+    layer_global<9>(z, a.x0 + lrow * a.ld0, kLvK, kLvChunks, dW(0), st, tid, lane, wave);
     // light-field decoder (resnet_block_fc.py:132-168)
-    const float* bias = a.bias + 288;
+    // the decoder's part of the table; bias + (3 i + j + 1) kD is tail_block_bias(i, j) and kTailPosBlocks + j + 3 i is tail_block_pos(i, j),
+    // both spelled out: a call with the loop's i gives another schedule
+    const float* bias = a.bias + kTailBiasLinIn;
     f32x16 x[4], net[4];
     zero<4>(x);
     add_bias<4>(x, bias, h);
-    layer_global<4>(x, a.x1 + lrow * a.ld1, 18, 1, dW(1), st, tid, lane, wave);               // lin_in
+    layer_global<4>(x, a.x1 + lrow * a.ld1, kInK, kInChunks, dW(1), st, tid, lane, wave);     // lin_in
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        add_bias<4>(x, bias + (3 * i + 1) * 128, h);
-        layer_chained<9, 4, false>(x, z, dW(2 + 3 * i), st, tid, lane, wave);                 // x += lin_z_i([z, z])
+    for (int i = 0; i < kBlocks; ++i) {
+        add_bias<4>(x, bias + (3 * i + 1) * kD, h);
+        layer_chained<9, 4, false>(x, z, dW(kTailPosBlocks + 0 + 3 * i), st, tid, lane, wave);      // x += lin_z_i([z, z])
         zero<4>(net);
-        add_bias<4>(net, bias + (3 * i + 2) * 128, h);
-        layer_chained<4, 4, true>(net, x, dW(3 + 3 * i), st, tid, lane, wave);                // net = fc_0(relu(x))
-        add_bias<4>(x, bias + (3 * i + 3) * 128, h);
-        layer_chained<4, 4, true>(x, net, dW(4 + 3 * i), st, tid, lane, wave);                // x += fc_1(relu(net))
+        add_bias<4>(net, bias + (3 * i + 2) * kD, h);
+        layer_chained<4, 4, true>(net, x, dW(kTailPosBlocks + 1 + 3 * i), st, tid, lane, wave);     // net = fc_0(relu(x))
+        add_bias<4>(x, bias + (3 * i + 3) * kD, h);
+        layer_chained<4, 4, true>(x, net, dW(kTailPosBlocks + 2 + 3 * i), st, tid, lane, wave);     // x += fc_1(relu(net))
     }
     f32x16 o[1];
     zero<1>(o);
-    add_bias<1>(o, bias + 10 * 128, h);                                                       // lin_out.bias (padded to 32)
-    layer_chained<4, 1, true>(o, x, dW(11), st, tid, lane, wave);
+    add_bias<1>(o, bias + (kTailBiasLinOut - kTailBiasLinIn), h);                             // lin_out.bias (padded to a tile)
+    layer_chained<4, 1, true>(o, x, dW(kTailPosLinOut), st, tid, lane, wave);
     // a18: rgb valid + (1 - valid), valid = any view's epipolar segment overlaps its image (models.py:614-617)
     if (row < a.M && h == 0) {
         const long sc = row / a.R, r = row % a.R;
@@ -310,15 +313,14 @@ __global__ void __launch_bounds__(256, 1) ray_tail_kernel(const ChainArgs a) {
 // chained != 0: the layer's input is another layer's accumulator set (its K order); 0: input rows from memory.  W2 (optional, same
 // shape and stride) is added element-wise (lin_z sees its latent twice).  The layer's power of two goes to scale[slot] (and its
 // inverse to scale[16 + slot]): `scale` is a device array of 32 floats shared by the layers of a plan.
-extern "C" size_t car_chain_packed_floats(int K, int N) { return (size_t)((K + 31) / 32) * ((N + 31) / 32) * kTileFloats; }
+extern "C" size_t car_chain_packed_floats(int K, int N) { return chain_packed_floats(K, N); }
 extern "C" int car_chain_pack(const float* W, int ldw, const float* W2, int K, int N, int chained, float* packed, float* scale, int slot,
                               void* stream) {
     CAR_REQUIRE(W && packed && scale && K > 0 && N > 0 && ldw >= K && slot >= 0 && slot < kMaxLayers, "car_chain_pack: bad arguments");
-    const int tiles = (N + 31) / 32;
     const car_pack_scale s{nullptr, scale + slot, scale + kMaxLayers + slot};
     (void)hipGetLastError();
     car_pack_absmax((hipStream_t)stream, 1, W, ldw, W2, nullptr, N, K, s);
-    car_pack_tiles32((hipStream_t)stream, 256, W, ldw, W2, N, K, tiles, (K + 31) / 32, 2, chained, s, reinterpret_cast<_Float16*>(packed));
+    car_pack_tiles32((hipStream_t)stream, 256, W, ldw, W2, N, K, chain_tiles_of(N), chain_chunks_of(K), 2, chained, s, reinterpret_cast<_Float16*>(packed));
     CAR_CHECK_LAUNCH("car_chain_pack");
     return CAR_OK;
 }
@@ -327,14 +329,14 @@ namespace {
 int launch_chain(bool tail, const float* arena, const unsigned* offs, const int* nts, int n_chunks, const float* bias, const float* scale,
                  const int* layers, int n_layers, const float* x0, int ld0, const float* x1, int ld1, const float* z1_in, float* out0, float* out1,
                  const float* rays, long M, int V, int R, float zscale, void* stream) {
-    CAR_REQUIRE(n_chunks > 0 && n_chunks <= kMaxChunks && n_layers == (tail ? 12 : 3), "car_ray_chain: %d weight chunks, %d layers", n_chunks, n_layers);
+    CAR_REQUIRE(n_chunks > 0 && n_chunks <= kMaxChunks && n_layers == (tail ? kTailLayers : kMidLayers), "car_ray_chain: %d weight chunks, %d layers", n_chunks, n_layers);
     ChainArgs a;
     a.arena = arena; a.bias = bias; a.scale = scale; a.n_chunks = n_chunks;
     for (int i = 0; i < kMaxLayers; ++i) a.layer[i] = i < n_layers ? layers[i] : 0;
     for (int i = 0; i < n_layers; ++i) CAR_REQUIRE(layers[i] >= 0 && layers[i] < kMaxLayers, "car_ray_chain: bad scale slot");
     for (int i = 0; i < n_chunks; ++i) {
-        // a buffer of the ring holds kMaxNT tiles, and Stream::landed counts the loads of a chunk of 1, 4 or 9 tiles
-        CAR_REQUIRE(nts[i] == 1 || nts[i] == 4 || nts[i] == 9, "car_ray_chain: chunk %d has %d tiles (1, 4 or 9)", i, nts[i]);
+        // a buffer of the ring holds kMaxNT tiles, and Stream::landed counts the loads of a chunk of kTileCounts tiles
+        CAR_REQUIRE(chain_tile_count_ok(nts[i]), "car_ray_chain: chunk %d has %d tiles (1, 4 or 9)", i, nts[i]);
         a.chunk[i].off = offs[i]; a.chunk[i].nt = nts[i];
     }
     a.x0 = x0; a.ld0 = ld0; a.x1 = x1; a.ld1 = ld1; a.z1_in = z1_in; a.out0 = out0; a.out1 = out1; a.rays = (const CarRay*)rays;
@@ -351,7 +353,7 @@ int launch_chain(bool tail, const float* arena, const unsigned* offs, const int*
 // its slot in it (car_render.hip builds all of it next to the arena).
 extern "C" int car_ray_mid(const float* arena, const unsigned* offs, const int* nts, int n_chunks, const float* bias, const float* scale,
                            const int* layers, int n_layers, const float* ebar, int ld_ebar, float* z1, float* uh, long M, void* stream) {
-    CAR_REQUIRE(arena && offs && nts && bias && scale && layers && ebar && z1 && uh && M > 0 && ld_ebar >= 576 && ld_ebar % 4 == 0,
+    CAR_REQUIRE(arena && offs && nts && bias && scale && layers && ebar && z1 && uh && M > 0 && ld_ebar >= kC && ld_ebar % 4 == 0,
                 "car_ray_mid: bad arguments");
     return launch_chain(false, arena, offs, nts, n_chunks, bias, scale, layers, n_layers, ebar, ld_ebar, nullptr, 0, nullptr, z1, uh, nullptr, M, 0, 1,
                         0.0f, stream);
@@ -360,7 +362,7 @@ extern "C" int car_ray_tail(const float* arena, const unsigned* offs, const int*
                             const int* layers, int n_layers, const float* ebar, int ld_ebar, const float* phi_x, int ld_phi, const float* z1,
                             const float* rays, int b, int V, int R, float* rgb, float* valid, void* stream) {
     CAR_REQUIRE(arena && offs && nts && bias && scale && layers && ebar && phi_x && z1 && rays && rgb && valid, "car_ray_tail: null pointer");
-    CAR_REQUIRE(b > 0 && V > 0 && R > 0 && ld_ebar >= 576 && ld_ebar % 4 == 0 && ld_phi >= 20 && ld_phi % 4 == 0, "car_ray_tail: bad sizes");
+    CAR_REQUIRE(b > 0 && V > 0 && R > 0 && ld_ebar >= kC && ld_ebar % 4 == 0 && ld_phi >= kPhiLd && ld_phi % 4 == 0, "car_ray_tail: bad sizes");
     return launch_chain(true, arena, offs, nts, n_chunks, bias, scale, layers, n_layers, ebar, ld_ebar, phi_x, ld_phi, z1, rgb, valid, rays, (long)b * R, V,
                         R, (float)V, stream);
 }

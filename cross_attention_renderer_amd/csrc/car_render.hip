@@ -14,18 +14,15 @@
 namespace {
 
 #include "car_fused_layout.h"
-
-constexpr int kPhiIn = 18, kPhiLd = 20, kBlocks = 3;
+#include "car_chain_layout.h"
 
 inline size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 // ---- plan layout ---------------------------------------------------------------------------------------------------
 struct Plan {
-    // offsets in floats.  latent_value ... lout_c: car_chain_pack tiles of the per-ray chains (car_raychain.hip; latent_value and lin_in
-    // read their input rows from memory, the *_c layers the previous layer's accumulators); chain_scale: their powers of two;
-    // mid_bias / tail_bias: their biases in consumption order
-    size_t steps, blob, fbias, wpt, r2qw, r2qb, proj[CAR_MAX_LEVELS], proj16[CAR_MAX_LEVELS], latent_value, lin_in, enc_c, qreh_c, lz_c[kBlocks], fc0_c[kBlocks],
-        fc1_c[kBlocks], lout_c, chain_scale, mid_bias, tail_bias, total;
+    // offsets in floats.  chain[slot]: car_chain_pack tiles of the per-ray chains' layers (car_chain_layout.h); chain_scale: their powers
+    // of two; mid_bias / tail_bias: their biases in consumption order
+    size_t steps, blob, fbias, wpt, r2qw, r2qb, proj[CAR_MAX_LEVELS], proj16[CAR_MAX_LEVELS], chain[kChainLayers], chain_scale, mid_bias, tail_bias, total;
 };
 // car_linear_x3 wants rows of whole float4s and a K worth its 32-wide chunks; narrower levels stay on car_linear
 inline bool level_on_f16_pipe(int c) { return c % 4 == 0 && c >= 32; }
@@ -42,19 +39,10 @@ Plan plan_layout(const car_dims& d) {
     for (int l = 0; l < CAR_MAX_LEVELS; ++l) p.proj[l] = l < d.n_levels ? take(car_linear_packed_floats(d.level_c[l], kC)) : 0;
     // the same slices for the split-fp16 kernel (car_linear_x3), which car_project_maps takes for the levels it serves
     for (int l = 0; l < CAR_MAX_LEVELS; ++l) p.proj16[l] = (l < d.n_levels && level_on_f16_pipe(d.level_c[l])) ? take(car_linear_x3_packed_floats(d.level_c[l], kC)) : 0;
-    p.latent_value = take(car_chain_packed_floats(kC, kE));
-    p.lin_in = take(car_chain_packed_floats(kPhiIn, kD));
-    p.enc_c = take(car_chain_packed_floats(kE, kD));
-    p.qreh_c = take(car_chain_packed_floats(kD, kD));
-    for (int i = 0; i < kBlocks; ++i) {
-        p.lz_c[i] = take(car_chain_packed_floats(kE, kD));
-        p.fc0_c[i] = take(car_chain_packed_floats(kD, kD));
-        p.fc1_c[i] = take(car_chain_packed_floats(kD, kD));
-    }
-    p.lout_c = take(car_chain_packed_floats(kD, 3));
-    p.chain_scale = take(32);
-    p.mid_bias = take(kE + kD);
-    p.tail_bias = take(kE + kD + 3 * kBlocks * kD + 32);
+    for (int slot : kPlanOrder) p.chain[slot] = take(chain_floats(slot));
+    p.chain_scale = take(kScaleFloats);
+    p.mid_bias = take(kMidBiasFloats);
+    p.tail_bias = take(kTailBiasFloats);
     p.total = o;
     return p;
 }
@@ -155,10 +143,8 @@ extern "C" int car_profile_count(void) { return (int)g_prof.recs.size(); }
 extern "C" int car_profile_read(int i, const char** name, float* ms) {
     CAR_REQUIRE(i >= 0 && i < (int)g_prof.recs.size() && name && ms, "car_profile_read: no stage %d", i);
     const StageRec& r = g_prof.recs[i];
-    if (hipEventSynchronize(r.stop) != hipSuccess || hipEventElapsedTime(ms, r.start, r.stop) != hipSuccess) {
-        car_set_error("car_profile_read: %s", hipGetErrorString(hipGetLastError()));
-        return CAR_E_LAUNCH;
-    }
+    CAR_CHECK_HIP(hipEventSynchronize(r.stop), "car_profile_read: %s", hipGetErrorString(hipGetLastError()));
+    CAR_CHECK_HIP(hipEventElapsedTime(ms, r.start, r.stop), "car_profile_read: %s", hipGetErrorString(hipGetLastError()));
     *name = r.name;
     return CAR_OK;
 }
@@ -231,11 +217,9 @@ extern "C" int car_plan_build(const car_dims* dims, const car_weights* w, void* 
         float steps[1024];
         CAR_REQUIRE(dims->P <= 1024, "car_plan_build: P too large");
         car_linspace(0.0f, 1.0f, dims->P, steps);
-        if (hipMemcpyAsync(base + p.steps, steps, sizeof(float) * dims->P, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            car_set_error("car_plan_build: upload failed: %s", hipGetErrorString(hipGetLastError()));
-            return CAR_E_LAUNCH;
-        }
+        CAR_CHECK_HIP(hipMemcpyAsync(base + p.steps, steps, sizeof(float) * dims->P, hipMemcpyHostToDevice, st), "car_plan_build: upload failed: %s",
+                      hipGetErrorString(hipGetLastError()));
+        CAR_CHECK_HIP(hipStreamSynchronize(st), "car_plan_build: upload failed: %s", hipGetErrorString(hipGetLastError()));
     }
     // split-fp16 operand tiles of the fused per-sample kernel and of the round-2 kernel
     CAR_TRY(car_fused_pack(w, base + p.blob, base + p.fbias, base + p.wpt, stream));
@@ -249,31 +233,34 @@ extern "C" int car_plan_build(const car_dims* dims, const car_weights* w, void* 
             CAR_TRY(car_linear_x3_pack(w->query_encode_latent_w + coff, kC + 3, dims->level_c[l], kC, base + p.proj16[l], stream));
         coff += dims->level_c[l];
     }
-    // the per-ray chains (car_raychain.hip), split-fp16 tiles; scale slots: 0 latent_value, 1 encode_latent, 2 query_repeat_embed[:, :128],
-    // 3 lin_in, 4 + 3 i lin_z_i, 5 + 3 i fc_0_i, 6 + 3 i fc_1_i, 13 lin_out
-    float* cs = base + p.chain_scale;
-    CAR_TRY(car_chain_pack(w->latent_value_w, kC, nullptr, kC, kE, 0, base + p.latent_value, cs, 0, stream));
-    CAR_TRY(car_chain_pack(w->encode_latent_w, kE, nullptr, kE, kD, 1, base + p.enc_c, cs, 1, stream));
-    CAR_TRY(car_chain_pack(w->query_repeat_embed_w, kD + 16, nullptr, kD, kD, 1, base + p.qreh_c, cs, 2, stream));
-    CAR_TRY(car_chain_pack(w->phi_lin_in_w, kPhiIn, nullptr, kPhiIn, kD, 0, base + p.lin_in, cs, 3, stream));
+    // the per-ray chains (car_raychain.hip), split-fp16 tiles: where each layer of car_chain_layout.h's table finds its weight rows, their
+    // stride and its bias
+    struct { const float* W; int ldw; const float* bias; } src[kChainLayers];
+    src[kSlotLatentValue] = {w->latent_value_w, kC, w->latent_value_b};
+    src[kSlotEncodeLatent] = {w->encode_latent_w, kE, w->encode_latent_b};
+    src[kSlotQueryRepeat] = {w->query_repeat_embed_w, kD + 16, nullptr};
+    src[kSlotLinIn] = {w->phi_lin_in_w, kPhiIn, w->phi_lin_in_b};
     for (int i = 0; i < kBlocks; ++i) {
-        CAR_TRY(car_chain_pack(w->phi_lin_z_w[i], 2 * kE, w->phi_lin_z_w[i] + kE, kE, kD, 1, base + p.lz_c[i], cs, 4 + 3 * i, stream));   // [z, z]: halves added
-        CAR_TRY(car_chain_pack(w->phi_fc_0_w[i], kD, nullptr, kD, kD, 1, base + p.fc0_c[i], cs, 5 + 3 * i, stream));
-        CAR_TRY(car_chain_pack(w->phi_fc_1_w[i], kD, nullptr, kD, kD, 1, base + p.fc1_c[i], cs, 6 + 3 * i, stream));
+        src[chain_block_slot(i, 0)] = {w->phi_lin_z_w[i], 2 * kE, w->phi_lin_z_b[i]};
+        src[chain_block_slot(i, 1)] = {w->phi_fc_0_w[i], kD, w->phi_fc_0_b[i]};
+        src[chain_block_slot(i, 2)] = {w->phi_fc_1_w[i], kD, w->phi_fc_1_b[i]};
     }
-    CAR_TRY(car_chain_pack(w->phi_lin_out_w, kD, nullptr, kD, 3, 1, base + p.lout_c, cs, 13, stream));
-    const int tail_floats = kE + kD + 3 * kBlocks * kD + 32;
-    if (hipMemsetAsync(base + p.tail_bias, 0, sizeof(float) * tail_floats, st) != hipSuccess) { car_set_error("car_plan_build: memset failed"); return CAR_E_LAUNCH; }
-    auto d2d = [&](float* dst, const float* src, int n) { return hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, st) == hipSuccess; };
-    bool ok = d2d(base + p.mid_bias, w->latent_value_b, kE) && d2d(base + p.mid_bias + kE, w->encode_latent_b, kD);
-    float* tb = base + p.tail_bias;
-    ok = ok && d2d(tb, w->latent_value_b, kE) && d2d(tb + kE, w->phi_lin_in_b, kD);
-    tb += kE + kD;
-    for (int i = 0; i < kBlocks; ++i)
-        ok = ok && d2d(tb + (3 * i + 0) * kD, w->phi_lin_z_b[i], kD) && d2d(tb + (3 * i + 1) * kD, w->phi_fc_0_b[i], kD) &&
-             d2d(tb + (3 * i + 2) * kD, w->phi_fc_1_b[i], kD);
-    ok = ok && d2d(tb + 3 * kBlocks * kD, w->phi_lin_out_b, 3);
-    if (!ok) { car_set_error("car_plan_build: bias copy failed"); return CAR_E_LAUNCH; }
+    src[kSlotLinOut] = {w->phi_lin_out_w, kD, w->phi_lin_out_b};
+    for (int slot = 0; slot < kChainLayers; ++slot) {
+        const ChainLayer& L = kChainLayer[slot];
+        CAR_TRY(car_chain_pack(src[slot].W, src[slot].ldw, L.halves ? src[slot].W + L.K : nullptr, L.K, L.N, L.chained, base + p.chain[slot],
+                               base + p.chain_scale, slot, stream));
+    }
+    CAR_CHECK_HIP(hipMemsetAsync(base + p.tail_bias, 0, sizeof(float) * kTailBiasFloats, st), "car_plan_build: memset failed");
+    auto biases = [&](float* table, const int* seq, int n) {
+        for (int pos = 0; pos < n; ++pos)
+            if (kChainLayer[seq[pos]].bias)
+                CAR_CHECK_HIP(hipMemcpyAsync(table + chain_bias_at(seq, pos), src[seq[pos]].bias, sizeof(float) * kChainLayer[seq[pos]].N, hipMemcpyDeviceToDevice, st),
+                              "car_plan_build: bias copy failed");
+        return CAR_OK;
+    };
+    CAR_TRY(biases(base + p.mid_bias, kMidSeq, kMidLayers));
+    CAR_TRY(biases(base + p.tail_bias, kTailSeq, kTailLayers));
     return CAR_OK;
 }
 
@@ -310,7 +297,7 @@ extern "C" int car_project_maps(const car_dims* dims, const void* plan, const fl
     const float* base = static_cast<const float*>(plan);
     hipStream_t st = (hipStream_t)stream;
     float* gmeta = gmaps + car_gmeta_offset(dims);
-    if (hipMemsetAsync(gmeta, 0, sizeof(float) * CAR_MAX_LEVELS, st) != hipSuccess) { car_set_error("car_project_maps: memset failed"); return CAR_E_LAUNCH; }
+    CAR_CHECK_HIP(hipMemsetAsync(gmeta, 0, sizeof(float) * CAR_MAX_LEVELS, st), "car_project_maps: memset failed");
     const car_lattice L = car_lattice_of(*dims);
     const float* lv[CAR_MAX_LEVELS];
     for (int l = 0; l < dims->n_levels; ++l) {
@@ -367,7 +354,7 @@ static int render_phases(const char* entry, const car_dims* dims, const void* pl
     if (phases & CAR_PHASE_SAMPLES) {
     {   // a4-a6: rays, their epipolar segments, the decoder's ray input (columns 18, 19 of phi_x stay zero)
         Stage stage("ray_setup", st);
-        if (hipMemsetAsync(ws + w.phi_x.off, 0, sizeof(float) * BR * kPhiLd, st) != hipSuccess) { car_set_error("car_render_forward: memset failed"); return CAR_E_LAUNCH; }
+        CAR_CHECK_HIP(hipMemsetAsync(ws + w.phi_x.off, 0, sizeof(float) * BR * kPhiLd, st), "car_render_forward: memset failed");
         CAR_TRY(car_ray_setup(in->poses, in->uv, b, V, R, d.H, d.W, P, d.no_sample != 0, steps, ws + w.rays.off, coords, ws + w.phi_x.off, kPhiLd, stream));
     }
     {   // a6-a13 + round-1 logits: the fused per-sample kernel
@@ -399,20 +386,22 @@ static int render_phases(const char* entry, const car_dims* dims, const void* pl
             CAR_TRY(car_attend_parts(ws + w.logit.off, ws + w.part.off, car_fused_tile_steps(), kC, b, V, R, P, at_wt, ws + w.ebar.off, kC, 1, ws + w.pt.off, in->poses,
                                      depth, amax, stream));
     }
-    // weight-chunk tables of the two per-ray chains (car_raychain.hip): float offset inside the plan and tile count of every K = 32
-    // chunk, in the order the kernels consume them
-    unsigned offs[96];
-    int nts[96];
-    int nch = 0;
-    auto chunks = [&](size_t at, int n, int nt) { for (int c = 0; c < n; ++c) { offs[nch] = (unsigned)(at + (size_t)c * nt * 1024); nts[nch++] = nt; } };
+    // weight-chunk tables of the two per-ray chains (car_raychain.hip): float offset inside the plan and tile count of every chunk of
+    // the sequence's layers, in the order the kernel consumes them
+    unsigned offs[kMaxChunks];
+    int nts[kMaxChunks];
+    auto chunks = [&](const int* seq, int n) {
+        int nch = 0;
+        for (int i = 0; i < n; ++i)
+            for (int c = 0, nt = chain_tiles(seq[i]); c < chain_chunks(seq[i]); ++c) { offs[nch] = (unsigned)(p.chain[seq[i]] + (size_t)c * nt * kTileFloats); nts[nch++] = nt; }
+        return nch;
+    };
     CAR_REQUIRE(p.total < (1ull << 32), "car_render_forward: plan too large");
     if (d.repeat_attention) {
         {   // a15, per ray: z1 = Wv ebar + bv; uh = Wr1[:, :128] encode_latent(z1)
             Stage stage("ray_layers_1", st);
-            nch = 0;
-            chunks(p.latent_value, 18, 9); chunks(p.enc_c, 9, 4); chunks(p.qreh_c, 4, 4);
-            const int layers[3] = {0, 1, 2};
-            CAR_TRY(car_ray_mid(pl, offs, nts, nch, pl + p.mid_bias, pl + p.chain_scale, layers, 3, ws + w.ebar.off, kC, ws + w.z1.off, ws + w.uh.off, BR, stream));
+            const int nch = chunks(kMidSeq, kMidLayers);
+            CAR_TRY(car_ray_mid(pl, offs, nts, nch, pl + p.mid_bias, pl + p.chain_scale, kMidSeq, kMidLayers, ws + w.ebar.off, kC, ws + w.z1.off, ws + w.uh.off, BR, stream));
         }
         if (!(phases & CAR_PHASE_SPLIT_SECOND_ROUND) && car_attend_round2_supports(kC, V, P)) {
             // a15 per sample + the second round's softmax and value average in one launch: the logits are made on the matrix pipe under the
@@ -432,18 +421,12 @@ static int render_phases(const char* entry, const car_dims* dims, const void* pl
                                    nullptr, nullptr, nullptr, stream));
             }
         }
-    } else if (hipMemsetAsync(ws + w.z1.off, 0, sizeof(float) * BR * kE, st) != hipSuccess) {       // no second round: z = Wv ebar1 + bv
-        car_set_error("car_render_forward: memset failed");
-        return CAR_E_LAUNCH;
-    }
+    } else                                                                                          // no second round: z = Wv ebar1 + bv
+        CAR_CHECK_HIP(hipMemsetAsync(ws + w.z1.off, 0, sizeof(float) * BR * kE, st), "car_render_forward: memset failed");
     {   // z = (Wv ebar + bv) + V z1 (models.py:561-565), light-field decoder (resnet_block_fc.py:132-168), valid mask / white background
         Stage stage("ray_layers_2", st);
-        nch = 0;
-        chunks(p.latent_value, 18, 9); chunks(p.lin_in, 1, 4);
-        for (int i = 0; i < kBlocks; ++i) { chunks(p.lz_c[i], 9, 4); chunks(p.fc0_c[i], 4, 4); chunks(p.fc1_c[i], 4, 4); }
-        chunks(p.lout_c, 4, 1);
-        const int layers[12] = {0, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13};
-        CAR_TRY(car_ray_tail(pl, offs, nts, nch, pl + p.tail_bias, pl + p.chain_scale, layers, 12, ws + w.ebar.off, kC, ws + w.phi_x.off, kPhiLd, ws + w.z1.off,
+        const int nch = chunks(kTailSeq, kTailLayers);
+        CAR_TRY(car_ray_tail(pl, offs, nts, nch, pl + p.tail_bias, pl + p.chain_scale, kTailSeq, kTailLayers, ws + w.ebar.off, kC, ws + w.phi_x.off, kPhiLd, ws + w.z1.off,
                              ws + w.rays.off, b, V, R, out->rgb, valid, stream));
     }
     return CAR_OK;

@@ -160,3 +160,30 @@ def test_one_call_abi_host_side(lib):
         assert (got - want).abs().max() <= 6e-8, n
         if n < 8:
             assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("levels, P, total", [(((256, 64), (256, 128), (64, 256)), 64, 5897472),
+                                              (((560, 8), (12, 16), (4, 32)), 33, 5823232)])      # two levels off the split-fp16 path
+def test_plan_bytes_are_the_sum_of_the_slices(lib, levels, P, total):
+    """car_plan_bytes exactly: every slice of the plan rounded up to 64 floats, the per-ray chains' layers taken from raychain_reference's
+    own statement of them (layer_specs, PLAN_SLOTS), not from the library's table."""
+    import raychain_reference as RC
+    from cross_attention_renderer_amd import _lib
+    d = _lib.CarDims()
+    d.b, d.V, d.R, d.P, d.H, d.W, d.n_levels, d.repeat_attention = 1, 2, 64, P, 256, 256, 3, 1
+    for l, (c, h) in enumerate(levels):
+        d.level_c[l], d.level_h[l], d.level_w[l] = c, h, h
+    chain = {}
+    for which in ("mid", "tail"):
+        for slot, (_, _, _, k, n, _) in zip(RC.PLAN_SLOTS[which], RC.layer_specs(which)):
+            assert chain.setdefault(slot, (k, n)) == (k, n)
+    assert sorted(chain) == list(range(14))
+    terms = [P, lib.car_fused_blob_floats(), lib.car_fused_bias_floats(), 576 * 4, lib.car_round2q_packed_floats(), lib.car_round2q_bias_floats()]
+    terms += [lib.car_linear_packed_floats(c, 576) for c, _ in levels]
+    terms += [lib.car_linear_x3_packed_floats(c, 576) for c, _ in levels if c % 4 == 0 and c >= 32]
+    terms += [lib.car_chain_packed_floats(k, n) for k, n in chain.values()]
+    terms += [32, 288 + 128, 288 + 128 + 9 * 128 + 32]
+    want = 4 * sum((int(t) + 63) // 64 * 64 for t in terms)
+    got = lib.car_plan_bytes(ctypes.byref(d))
+    assert got == want, (got, want, lib.car_last_error())
+    assert got == total
