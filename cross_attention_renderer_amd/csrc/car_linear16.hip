@@ -318,12 +318,12 @@ extern "C" int car_linear_x3_pack(const float* W, int ldw, int K, int N, float* 
 }
 
 namespace {
-int linear_x3(const float* X, int ldx, const float* packed, const float* bias, int K, int N, float* Y, int ldy, long M, int flags, const float* act,
-              int lda, void* stream);
+int linear_x3(const char* who, const float* X, int ldx, const float* packed, const float* bias, int K, int N, float* Y, int ldy, long M, int flags,
+              const float* act, int lda, void* stream);
 }
 extern "C" int car_linear_x3(const float* X, int ldx, const float* packed, const float* bias, int K, int N, float* Y, int ldy, long M, int flags,
                              void* stream) {
-    return linear_x3(X, ldx, packed, bias, K, N, Y, ldy, M, flags, nullptr, 0, stream);
+    return linear_x3("car_linear_x3", X, ldx, packed, bias, K, N, Y, ldy, M, flags, nullptr, 0, stream);
 }
 // car_linear_x3 with car_relu_mask applied to the result as it is stored: Y[m][n] = act[m][n] > 0 ? (X W^T + bias (+ Y))[m][n] : 0 — the data
 // gradient dX = dY W of a layer whose input went through a ReLU (torch autograd's threshold_backward over models.py:333-341, 487-491, 529),
@@ -332,15 +332,16 @@ extern "C" int car_linear_x3_masked(const float* X, int ldx, const float* packed
                                     const float* act, int lda, void* stream) {
     CAR_REQUIRE(act && lda >= N && lda % 4 == 0 && ((uintptr_t)act & 15) == 0,
                 "car_linear_x3_masked: act must be 16-byte aligned with a row stride (%d) that is a multiple of 4 and holds N = %d", lda, N);
-    return linear_x3(X, ldx, packed, bias, K, N, Y, ldy, M, flags, act, lda, stream);
+    return linear_x3("car_linear_x3_masked", X, ldx, packed, bias, K, N, Y, ldy, M, flags, act, lda, stream);
 }
 namespace {
-int linear_x3(const float* X, int ldx, const float* packed, const float* bias, int K, int N, float* Y, int ldy, long M, int flags, const float* act,
-              int lda, void* stream) {
-    CAR_REQUIRE(X && packed && Y && M > 0 && K > 0 && N > 0, "car_linear_x3: bad arguments");
+// `who`: the entry that was called — a refusal names it, not the entry whose checks it shares
+int linear_x3(const char* who, const float* X, int ldx, const float* packed, const float* bias, int K, int N, float* Y, int ldy, long M, int flags,
+              const float* act, int lda, void* stream) {
+    CAR_REQUIRE(X && packed && Y && M > 0 && K > 0 && N > 0, "%s: bad arguments", who);
     CAR_REQUIRE(N % 32 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= ((K + 3) & ~3) && ldy >= N,
-                "car_linear_x3: N = %d must be a multiple of 32, ldx = %d / ldy = %d multiples of 4 that hold a row", N, ldx, ldy);
-    CAR_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0), "car_linear_x3: X, Y and bias must be 16-byte aligned");
+                "%s: N = %d must be a multiple of 32, ldx = %d / ldy = %d multiples of 4 that hold a row", who, N, ldx, ldy);
+    CAR_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0), "%s: X, Y and bias must be 16-byte aligned", who);
     const int tiles = N / 16, ksteps = (K + 31) / 32;
     LinArgs a;
     a.X = X; a.ldx = ldx; a.Wp = packed; a.tiles_total = tiles; a.bias = bias;
