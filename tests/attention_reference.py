@@ -15,6 +15,8 @@ Every result comes with the magnitude its rounding error scales with (the sum of
 """
 import torch
 
+from parity_rule import gen  # noqa: F401
+
 F64 = torch.float64
 PT_CLAMP = 100.0
 DEPTH_MAX = 10.0
@@ -136,10 +138,6 @@ def backward(w, val, dz, V, ddepth=None, pt=None, inv_q=None):
 
 
 # ---- seeded inputs ---------------------------------------------------------------------------------------------------------------
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 def make_logits(b, V, R, P, spread, seed):
     """fp32 logits [b*V, R, P] = spread * N(0, 1), with two kinds of planted rays (by ray index r, scene sc):
       (r + sc) % 3 == 0  "planted": in every view v one step gets the ray's largest logit + 1 + v / 2 — the view's argmax, by a margin of

@@ -14,7 +14,7 @@ value comes with its sum of magnitudes, always float64:
     B_lat = sum_l sum_t |w| |G_l|                      B_h = sum |w| |G| (or sum |w| B_lat) + |wpt[:, :3]| |pe| + |wpt[:, 3]|
     B_y   = |W2| B_h + |b2|   (h's magnitudes carried through, as fused_reference does)
 
-A comparison divides an error by that bound (gather_reference.ratio / fused_reference.ratio); tolerance = 8 max(r32, 2^-22)."""
+A comparison divides an error by that bound (parity_rule.ratio); tolerance = 8 max(r32, 2^-22)."""
 from __future__ import annotations
 
 import functools
@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 import fused_reference as FR
 import gather_reference as GR
+import parity_rule as PR
 
 F32, F64 = torch.float32, torch.float64
 MODE_BIT = 30
@@ -32,7 +33,7 @@ RELU_IN, RELU_OUT, ACCUM = 1, 2, 4                  # CAR_LIN_* of include/car_h
 ROW_BLOCK = 16                                      # rows of a workgroup of csrc/car_encode.hip
 TABLE_LDS = 52 * 1024                               # csrc/car_lattice.hip car_launch_merge: larger axis tables take the table-free kernel
 
-ratio, tolerance, fp16_linear = FR.ratio, FR.tolerance, FR.fp16_linear
+ratio, tolerance, fp16_linear = PR.ratio, PR.tolerance, FR.fp16_linear
 
 
 def fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:

@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from cross_attention_renderer_amd import synthetic as S
+from parity_rule import FACTOR, FLOOR, gen, ratio, tolerance  # noqa: F401  (the suites' rule: max |got - ref64| / bound, 8 x max(r, 2^-22))
 
 C, E, D, G = 576, 288, 128, 16
 TILE_RAYS, TILE_STEPS = 24, 8                            # a workgroup of csrc/car_fused.hip: 24 rays x 8 steps
@@ -31,26 +32,6 @@ SHAPES = {"query_encode_latent": (C, C + 3), "query_encode_latent_2": (E, C), "k
           "query_embed": (D, G), "query_embed_2": (D, D)}
 F64 = torch.float64
 FMAX = 3.4028234663852886e38
-
-FLOOR = 2.0 ** -22
-FACTOR = 8.0       # 4: the kernel's operands keep 22 bits against fp32's 24 (car_split.h); 2: spread of a maximum (tests/raychain_reference.py)
-
-
-def tolerance(ratio_yardstick: float) -> float:
-    """What the kernel's ratio may reach: 8 x max(the yardstick's ratio on the same inputs, 2^-22)."""
-    return FACTOR * max(ratio_yardstick, FLOOR)
-
-
-def ratio(got, ref64, bound):
-    """max over entries |got - ref64| / bound; a zero bound demands a zero error; a non-finite result is infinitely wrong."""
-    err = (got.double() - ref64).abs()
-    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
-    return r.max().item()
-
-
-def gen(seed: int) -> torch.Generator:
-    return torch.Generator().manual_seed(seed)
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------

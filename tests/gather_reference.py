@@ -21,6 +21,8 @@ from typing import List, Sequence, Tuple
 
 import torch
 
+import parity_rule as PR
+
 PLAIN, OWN, OTHER2 = 0, 1, 2                      # CAR_PLACE_* of include/car_hip.h
 MAX_LEVELS, MAX_GATHERS = 4, 4
 SCAN_BLOCK, SCAN_THREADS = 1024, 1024             # csrc/car_scatter.hip: counters per scan block, threads of the block-sum scan
@@ -162,25 +164,16 @@ def record_counts(shapes, n_maps: int, gathers) -> torch.Tensor:
     return cnt
 
 
-def ratio(x: torch.Tensor, ref64: torch.Tensor, bound: torch.Tensor) -> float:
-    """max |x - ref| / bound over the elements with a bound; where the bound is 0 the value must be exactly 0 (inf otherwise)."""
-    err = (x.double() - ref64).abs()
-    dead = bound == 0
-    if bool((err[dead] != 0).any()) or not bool(torch.isfinite(x).all()):
-        return INF
-    live = ~dead
-    return float((err[live] / bound[live]).max()) if bool(live.any()) else 0.0
-
-
-def tolerance(r32: float) -> float:
-    return 8.0 * max(r32, 2.0 ** -22)
+# max |x - ref| / bound over the elements with a bound, every non-zero bound one; where the bound is 0 the value must be exactly 0, and a
+# non-finite x anywhere fails the whole comparison
+ratio = functools.partial(PR.ratio, bound_ok="nonzero", all_finite=True)
+tolerance = PR.tolerance
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # input sets (shared by test_gather_reference.py, which asserts the edges they exist for, and test_gather_hip.py)
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def gen(seed: int) -> torch.Generator:
-    return torch.Generator().manual_seed(seed)
+gen = PR.gen
 
 
 def centre(x: int, W: int) -> float:

@@ -35,13 +35,13 @@ from typing import Dict, Optional
 
 import torch
 
+import parity_rule as PR
+
 F32, F64 = torch.float32, torch.float64
 POSE_FLOATS, RAY_FLOATS, G_DIM, MAX_VIEWS = 96, 12, 16, 3
 FMAX = 3.4028234663852886e38
 INF = float("inf")
 
-FLOOR = 2.0 ** -22
-FACTOR = 8.0            # the rule of the fused, raychain and gather suites
 MARGIN = 2.0 ** -14     # decided: further than this x the summed magnitudes from a threshold: 1024 x fp32's unit roundoff
 BIG = 1e30              # a finite intermediate below this cannot overflow fp32 in the header's one or two further operations
 CAP_UNDECIDED = 0.02    # the share of a set's rays or samples that may lie outside a decided mask
@@ -54,26 +54,9 @@ R32_CEILING_OTHER = 1e-6            # with it the GPU tolerance 8 x max(r32, 2^-
 Q_REL, C_REL, T0, KC, K01, KQ, INV_Q, PAD = 0, 12, 24, 60, 64, 73, 77, 89
 
 
-def tolerance(r32: float) -> float:
-    return FACTOR * max(r32, FLOOR)
-
-
-def ratio(got, ref64, bound, mask=None) -> float:
-    """max over the masked entries of |got - ref64| / bound; equal infinities agree; a zero bound demands a zero error; a non-finite error
-    is infinitely wrong."""
-    got, ref64 = got.double(), ref64.double()
-    err = torch.where(got == ref64, torch.zeros_like(ref64), (got - ref64).abs())
-    err = torch.where(torch.isfinite(err), err, torch.full_like(err, INF))
-    bound = bound.expand_as(err)
-    ok = torch.isfinite(bound) & (bound > 0)
-    r = torch.where(ok, err / torch.where(ok, bound, torch.ones_like(bound)), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, INF)))
-    if mask is not None:
-        r = r[mask.expand_as(r)]
-    return r.max().item() if r.numel() else 0.0
-
-
-def gen(seed: int) -> torch.Generator:
-    return torch.Generator().manual_seed(seed)
+# max over the masked entries of |got - ref64| / bound; equal infinities agree; a bound that is zero or not finite demands a zero error
+ratio = functools.partial(PR.ratio, equal_inf=True, bound_ok="finite")
+tolerance, gen = PR.tolerance, PR.gen
 
 
 # ---- arithmetic --------------------------------------------------------------------------------------------------------------------------

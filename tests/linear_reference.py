@@ -13,8 +13,8 @@ checker; no GPU code, no ctypes.
                  negative throughout, B_key is |bk2| alone.  This only ever lowers the bound.
     wgrad   dW = dW0 + dY^T act(X), db = db0 + sum_m dY                     B = |dW0| + |dY|^T |act(X)|,  |db0| + sum |dY|
 
-Every bound is float64.  A comparison divides an error by its bound (fused_reference.ratio); tolerance = 8 max(r, 2^-22), r the worst
-ratio of a yardstick on the same inputs (fused_reference.tolerance).  Yardsticks: the float32 run of the same formula (torch float32 on
+Every bound is float64.  A comparison divides an error by its bound (parity_rule.ratio); tolerance = 8 max(r, 2^-22), r the worst
+ratio of a yardstick on the same inputs (parity_rule.tolerance).  Yardsticks: the float32 run of the same formula (torch float32 on
 the CPU); x3_linear, the three-product split-fp16 arithmetic of csrc/car_split.h / car_linear16.hip; wgrad_bf16, the three-product bf16
 arithmetic of csrc/car_backward.hip w16_piece.  Both emulations sum in float64: they state which products the kernel forms from which
 operand halves, not the order or width of its accumulation."""
@@ -26,14 +26,13 @@ from typing import Callable, Dict, Optional
 import torch
 import torch.nn.functional as F
 
-import fused_reference as FR
 import pack_reference as PR
+from parity_rule import FACTOR, FLOOR, gen, ratio, tolerance  # noqa: F401
 
 F32, F64 = torch.float32, torch.float64
 RELU_IN, RELU_OUT, ACCUM, NO_GLDS, WGRAD_FP32 = 1, 2, 4, 8, 16          # CAR_LIN_*, CAR_WGRAD_FP32 of include/car_hip.h
 NAN, INF = float("nan"), float("inf")
 
-ratio, tolerance, FLOOR, FACTOR, gen = FR.ratio, FR.tolerance, FR.FLOOR, FR.FACTOR, FR.gen
 GATE = 2.0 ** -12                                                      # see the module docstring: the ReLU's dead entries
 
 

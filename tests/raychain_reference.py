@@ -16,6 +16,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
+from parity_rule import FACTOR, FLOOR, gen, ratio, tolerance  # noqa: F401  (the suites' rule: max |got - ref64| / bound, 8 x max(r, 2^-22))
+
 C, E, D, PHI = 576, 288, 128, 18                       # ebar / e width, latent width, hidden width, decoder ray input
 BLOCKS = 3
 SHAPES = {"latent_value": (E, C), "encode_latent": (D, E), "query_repeat_embed": (D, D + 16), "phi.lin_in": (D, PHI), "phi.lin_out": (3, D)}
@@ -25,10 +27,6 @@ MID_LAYERS = ("latent_value", "encode_latent", "query_repeat_embed")
 TAIL_LAYERS = ("latent_value", "phi.lin_in") + tuple(n for i in range(BLOCKS) for n in (f"phi.lin_z.{i}", f"phi.blocks.{i}.fc_0", f"phi.blocks.{i}.fc_1")) \
     + ("phi.lin_out",)
 PLAN_SLOTS = {"mid": (0, 1, 2), "tail": (0, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13)}      # what car_plan_build / car_render_forward use
-
-
-def gen(seed: int) -> torch.Generator:
-    return torch.Generator().manual_seed(seed)
 
 
 def gaussian_params(seed: int) -> Dict[str, torch.Tensor]:
@@ -303,23 +301,6 @@ def integer_case(seed: int = 5, M: int = 161):
         phi_x[r] = 0.0
         z1[r] = -params["latent_value.bias"] / INT_V
     return params, ebar, z1, phi_x
-
-
-def ratio(got, ref64, bound):
-    """max over entries |got - ref64| / bound; a zero bound demands a zero error; a non-finite result is infinitely wrong."""
-    err = (got.double() - ref64).abs()
-    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
-    return r.max().item()
-
-
-FLOOR = 2.0 ** -22
-FACTOR = 8.0       # 4: the kernels' operands keep 22 bits against fp32's 24 (car_split.h: |x - hi - lo| < 2^-21 |x|); 2: spread of a maximum
-
-
-def tolerance(ratio_fp32: float) -> float:
-    """What the kernel's ratio may reach: 8 x max(the float32 restatement's ratio on the same inputs, 2^-22)."""
-    return FACTOR * max(ratio_fp32, FLOOR)
 
 
 def mid_tags():

@@ -7,69 +7,24 @@ Tolerance of every fp32-sum comparison: |got - want| <= 2e-5 * bound, entry by e
 plain implementation's roundings (at most 56 sequential terms per lane, a handful of tree steps, |l - M| <= 88 in front of exp) stays
 under 1e-5.  Every test prints its worst error / (2e-5 * bound) as a ``[parity]`` line (profiles/attention_parity.md).
 Every output lies inside a larger NaN-filled buffer: the margins and the row padding must come back untouched."""
-import ctypes
 import math
 
 import pytest
 import torch
 
+import abi_harness as abi
 import attention_reference as A
+from abi_harness import CAR_E_ARG, NAN, Guarded
+from parity_rule import error_ratio as _ratio
 
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5
 EPS = 2.0 ** -23
-NAN = float("nan")
-MARGIN = 64                                  # floats in front of and behind every output (keeps the 16-byte alignment)
-CAR_E_ARG = -1
-
-
-def _lib():
-    from cross_attention_renderer_amd import _lib as L
-    return L.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _up(t):
-    return None if t is None else t.contiguous().to(_dev())
-
-
-class Guarded:
-    """A [rows, cols] result with row stride ld inside a buffer filled with `fill` (NaN; a sentinel for integers)."""
-
-    def __init__(self, rows, cols, ld=None, dtype=torch.float32, fill=NAN, init=None, offset=0):
-        self.rows, self.cols, self.ld, self.fill, self.offset = rows, cols, ld or cols, fill, offset
-        self.full = torch.full((MARGIN + offset + rows * self.ld + MARGIN,), fill, dtype=dtype, device=_dev())
-        self.view = self.full[MARGIN + offset:MARGIN + offset + rows * self.ld].view(rows, self.ld)
-        if init is not None:
-            self.view[:, :cols] = init.reshape(rows, cols).to(_dev())
-
-    @property
-    def ptr(self):
-        return ctypes.c_void_p(self.view.data_ptr())
-
-    def _untouched(self, t):
-        return bool(torch.isnan(t).all()) if self.fill != self.fill else bool((t == self.fill).all())
-
-    def get(self, what=""):
-        """The result on the host, after checking that nothing around it was written."""
-        f = self.full.cpu()
-        n = MARGIN + self.offset
-        assert self._untouched(f[:n]) and self._untouched(f[n + self.rows * self.ld:]), f"{what}: wrote outside the buffer"
-        v = f[n:n + self.rows * self.ld].view(self.rows, self.ld)
-        assert self._untouched(v[:, self.cols:]), f"{what}: wrote into the row padding"
-        return v[:, :self.cols].clone()
+    return None if t is None else t.contiguous().to(abi.dev())
 
 
 def _poses(inv_q, V):
@@ -78,12 +33,6 @@ def _poses(inv_q, V):
     p = torch.full((b * V, 96), NAN)
     p[::V, 77:89] = inv_q.reshape(b, 12)
     return p
-
-
-def _ratio(err, bound):
-    """max err / bound; a zero bound demands a zero error."""
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
-    return r.max().item()
 
 
 def _report(test, case, **ratios):
@@ -101,15 +50,15 @@ def attend(lib, logit, val, V, qb=None, zprev=None, scale=0.0, reps=1, ld_z=None
     dq = logit.shape[3] if qb is not None else 0
     d = dict(qa=_up(logit), qb=_up(qb), val=_up(part if part is not None else val), zprev=_up(zprev), pt=_up(pt),
              poses=_up(_poses(inv_q, V)) if pt is not None else None)
-    w, z = Guarded(bV * R, P), Guarded(b * R, reps * D, ld_z)
-    depth = Guarded(b * R, 1) if pt is not None else None
-    am = Guarded(bV * R, 1, dtype=torch.int32, fill=-7777) if (pt is not None and argmax) else None
+    w, z = Guarded((bV * R, P)), Guarded((b * R, reps * D), ld_z)
+    depth = Guarded((b * R, 1)) if pt is not None else None
+    am = Guarded((bV * R, 1), dtype=torch.int32) if (pt is not None and argmax) else None
     if part is not None:
-        rc = lib.car_attend_parts(_ptr(d["qa"]), _ptr(d["val"]), tile, D, b, V, R, P, w.ptr, z.ptr, ld_z, reps, _ptr(d["pt"]), _ptr(d["poses"]),
-                                  depth.ptr if depth else None, am.ptr if am else None, _stream())
+        rc = lib.car_attend_parts(abi.ptr(d["qa"]), abi.ptr(d["val"]), tile, D, b, V, R, P, w.ptr, z.ptr, ld_z, reps, abi.ptr(d["pt"]), abi.ptr(d["poses"]),
+                                  depth.ptr if depth else None, am.ptr if am else None, abi.stream())
     else:
-        rc = lib.car_attend(_ptr(d["qa"]), _ptr(d["qb"]), dq, _ptr(d["val"]), D, b, V, R, P, _ptr(d["zprev"]), scale, w.ptr, z.ptr, ld_z, reps,
-                            _ptr(d["pt"]), _ptr(d["poses"]), depth.ptr if depth else None, am.ptr if am else None, _stream())
+        rc = lib.car_attend(abi.ptr(d["qa"]), abi.ptr(d["qb"]), dq, abi.ptr(d["val"]), D, b, V, R, P, abi.ptr(d["zprev"]), scale, w.ptr, z.ptr, ld_z, reps,
+                            abi.ptr(d["pt"]), abi.ptr(d["poses"]), depth.ptr if depth else None, am.ptr if am else None, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     out = {"w": w.get("w").view(bV, R, P), "z": z.get("z").view(b, R, reps * D)}
@@ -156,7 +105,7 @@ FORWARD_SHAPES = ((1, 1, 7, 1, 4), (1, 2, 6, 5, 64), (2, 2, 37, 13, 576), (1, 2,
 def test_attend_with_given_logits_matches_fp64(shape):
     """Both compiled instances (D <= 576 / D <= 896), the streaming path with a full, a partial and a one-float4 last segment, the scalar
     fallback (D < 64, D > 896, D % 4 != 0), S from 1 to 768, at logit spreads 1, 30 and 1e3."""
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P, D = shape
     for spread in (1.0, 30.0, 1e3):
         logit, val, pt, inv_q, cls, decided, winner = _case_inputs(b, V, R, P, D, spread, seed=100 + int(spread))
@@ -173,7 +122,7 @@ SPECIAL_SHAPES = ((1, 2, 6, 5, 64), (2, 2, 37, 13, 576), (1, 3, 19, 64, 864), (1
 def test_attend_one_hot_and_constant_logits_are_exact(shape):
     """One logit 1e3 above the rest: w is exactly 1 and 0 and z is the winner's value row bit for bit (as values).  Constant logits:
     every weight is fp32(1) / fp32(S)."""
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P, D = shape
     val = torch.randn(b * V, R, P, D, generator=A.gen(7))
     logit, hot = A.one_hot_logits(b, V, R, P, seed=8)
@@ -192,7 +141,7 @@ def test_attend_one_hot_and_constant_logits_are_exact(shape):
 @pytest.mark.parametrize("shape", ((2, 2, 37, 13, 576), (1, 3, 19, 64, 864), (1, 2, 11, 33, 62)), ids=("narrow", "wide", "fallback"))
 def test_attend_adds_zprev_and_replicates_into_padded_rows(shape):
     """zprev, zprev_scale, reps > 1 and ld_z > reps * D: the header's contract, which no caller in the project uses."""
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P, D = shape
     logit, val, pt, inv_q, cls, decided, winner = _case_inputs(b, V, R, P, D, 3.0, seed=40)
     zprev = torch.randn(b, R, D, generator=A.gen(41)) * 3
@@ -207,7 +156,7 @@ def test_attend_adds_zprev_and_replicates_into_padded_rows(shape):
 
 @pytest.mark.parametrize("shape", ((2, 2, 37, 13, 576), (1, 3, 19, 64, 864), (1, 2, 11, 33, 62)), ids=("narrow", "wide", "fallback"))
 def test_attend_optional_outputs_do_not_change_the_others(shape):
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P, D = shape
     logit, val, pt, inv_q, _, _, _ = _case_inputs(b, V, R, P, D, 3.0, seed=50)
     full = attend(lib, logit, val, V, pt=pt, inv_q=inv_q)
@@ -222,7 +171,7 @@ def test_attend_with_dot_product_logits_matches_fp64(shape):
     """logit = <qa, qb> / 16 inside the kernel.  An fp32 dot product is off by a few 2^-24 L1 (L1 = sum |qa||qb| / 16), and exp carries an
     absolute error of the logits into a relative one of the weights, on the ray's largest logit and on the sample's own: the weights'
     tolerance is 2e-5 (1 + 2 max_t L1_t) relative, with max L1 <= 8; z and depth inherit the weights' error, so they get the same factor."""
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P, D = shape
     _, val, _, _, _, _, _ = _case_inputs(b, V, R, P, D, 1.0, seed=60)
     for dq in (4, 16, 68, 128, 192):
@@ -241,7 +190,7 @@ def test_attend_parts_matches_fp64_on_the_raw_rows(D):
     """car_attend_parts fed with fp64-made partial sums, against forward() on the sample rows themselves (not against car_attend): P
     below, at and across the group size, one to three views, a group 200 below its ray's largest logit (its factor underflows to 0) and a
     one-hot ray."""
-    lib = _lib()
+    lib = abi.lib()
     tile = lib.car_fused_tile_steps()
     R = 7                                                     # rays 0, 3, 6 planted, 1, 4 ties, 2 and 5 free (scene 0)
     for V in (1, 2, 3):
@@ -271,10 +220,10 @@ def attend_backward(lib, w, val, V, dz, ld_dz, ddepth=None, pt=None, inv_q=None,
     dzb[:, :D] = dz.reshape(b * R, D)
     d = dict(w=_up(w), val=_up(val), dz=_up(dzb), dd=_up(ddepth), pt=_up(pt) if ddepth is not None else None,
              poses=_up(_poses(inv_q, V)) if ddepth is not None else None)
-    dval = Guarded(bV * R * P, D, init=prior)
-    dlogit = Guarded(bV * R, P)
-    rc = lib.car_attend_backward(_ptr(d["w"]), _ptr(d["val"]), D, b, V, R, P, _ptr(d["dz"]), ld_dz, _ptr(d["dd"]), _ptr(d["pt"]), _ptr(d["poses"]),
-                                 dval.ptr, 0 if prior is None else 1, dlogit.ptr, _stream())
+    dval = Guarded((bV * R * P, D), init=prior)
+    dlogit = Guarded((bV * R, P))
+    rc = lib.car_attend_backward(abi.ptr(d["w"]), abi.ptr(d["val"]), D, b, V, R, P, abi.ptr(d["dz"]), ld_dz, abi.ptr(d["dd"]), abi.ptr(d["pt"]), abi.ptr(d["poses"]),
+                                 dval.ptr, 0 if prior is None else 1, dlogit.ptr, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return dlogit.get("dlogit").view(bV, R, P), dval.get("dval").view(bV, R, P, D)
@@ -291,7 +240,7 @@ def backward_ratios(dlogit, ref, V):
 def test_attend_backward_matches_the_closed_form(D):
     """dlogit and dval of one round from given weights (the fp64 softmax rounded to fp32): one sample per ray up to S = 768 (three trips
     of the 256-thread strides), padded dz rows, with and without the depth read-out's term over all three depth classes."""
-    lib = _lib()
+    lib = abi.lib()
     for V, P in ((1, 1), (2, 5), (2, 64), (3, 64), (3, 256), (1, 70)):
         b, R = (2, 9) if V * P <= 128 else (1, 7)
         logit, val, _, _, _, _, _ = _case_inputs(b, V, R, P, D, 3.0, seed=80 + P)
@@ -323,7 +272,7 @@ def test_attend_backward_matches_the_closed_form(D):
 
 def test_attend_then_backward_matches_fp64_autograd_from_the_logits():
     """The chained case: car_attend's own weights fed to car_attend_backward, against fp64 autograd through the reference forward."""
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P, D = 2, 2, 37, 64, 576
     logit, val, pt, inv_q, cls, _, _ = _case_inputs(b, V, R, P, D, 3.0, seed=90)
     g = A.gen(91)
@@ -344,11 +293,11 @@ def test_attend_then_backward_matches_fp64_autograd_from_the_logits():
 def _scale_rows_case(lib, M, N, ldx, ldo, group, scale, accumulate, seed, offset=0):
     """out[m, :] (+)= scale * s[m // group] * x[m, :], compared on the device in fp64 chunk by chunk (the large cases do not fit twice; the
     prior contents of an accumulating call are a pattern of the indices, exact in fp32, so that no copy of them is kept either)."""
-    dev = _dev()
+    dev = abi.dev()
     g = torch.Generator(device=dev).manual_seed(seed)
     x = torch.randn(M, ldx, generator=g, device=dev)
     s = torch.randn((M + group - 1) // group, generator=g, device=dev)
-    out = Guarded(M, N, ldo, offset=offset)
+    out = Guarded((M, N), ldo, offset=offset)
     chunk = max(1, (1 << 23) // N)
     cols = torch.arange(N, device=dev)
 
@@ -358,7 +307,7 @@ def _scale_rows_case(lib, M, N, ldx, ldo, group, scale, accumulate, seed, offset
     if accumulate:
         for m0 in range(0, M, chunk):
             out.view[m0:min(M, m0 + chunk), :N] = prior_of(m0, min(M, m0 + chunk))
-    rc = lib.car_scale_rows(out.ptr, ldo, _ptr(x), ldx, _ptr(s), group, scale, M, N, int(accumulate), _stream())
+    rc = lib.car_scale_rows(out.ptr, ldo, abi.ptr(x), ldx, abi.ptr(s), group, scale, M, N, int(accumulate), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     worst, exact = 0.0, True
@@ -376,15 +325,14 @@ def _scale_rows_case(lib, M, N, ldx, ldo, group, scale, accumulate, seed, offset
         got = out.view[m0:m1, :N]
         exact = exact and torch.equal(got, want.float())
         worst = max(worst, _ratio((got.double() - want).abs(), EPS * bound))
-    n = MARGIN + offset
-    assert bool(torch.isnan(out.full[:n]).all()) and bool(torch.isnan(out.full[n + M * ldo:]).all()) and bool(torch.isnan(out.view[:, N:]).all())
+    assert out.margins_untouched() and bool(torch.isnan(out.view[:, N:]).all())
     return worst, exact
 
 
 def test_scale_rows_matches_fp64():
     """The decoder's call (N = 3, ldx = 3, ldo = 4: the scalar path), the key / query gradients (N = 128, scale 1 / 16, written and
     accumulated: the float4 path), row groups, an `out` that is 4- but not 16-byte aligned, and both paths beyond the 65 536-block grid cap."""
-    lib = _lib()
+    lib = abi.lib()
     P = 64
     cases = [("decoder", 2304, 3, 3, 4, 1, 1.0, False, 0), ("key", 4736, 128, 128, 128, 1, 1.0 / 16.0, False, 0),
              ("key_acc", 4736, 128, 128, 128, 1, 1.0 / 16.0, True, 0), ("group7", 1001, 128, 132, 136, 7, 0.3, True, 0),
@@ -403,49 +351,49 @@ def test_scale_rows_matches_fp64():
 def test_add_matches_fp64():
     """out = alpha a + beta b: b = NULL (one rounding: bit for bit), in place (out == a), b a column-offset view of a wider matrix, three
     different row strides."""
-    lib = _lib()
+    lib = abi.lib()
     g = A.gen(5)
     M, Dl, V = 777, 288, 2
     zrep = torch.randn(M, V * Dl, generator=g)
     a = torch.randn(M, Dl + 4, generator=g)
     # b = NULL, alpha = V (engine.py / training.py: zrep = V z1)
-    out = Guarded(M, Dl, V * Dl)
+    out = Guarded((M, Dl), V * Dl)
     ad = _up(a)
-    assert lib.car_add(out.ptr, V * Dl, _ptr(ad), Dl + 4, float(V), None, 0, 0.0, M, Dl, _stream()) == 0, lib.car_last_error()
+    assert lib.car_add(out.ptr, V * Dl, abi.ptr(ad), Dl + 4, float(V), None, 0, 0.0, M, Dl, abi.stream()) == 0, lib.car_last_error()
     torch.cuda.synchronize()
     assert torch.equal(out.get("add"), (float(V) * a[:, :Dl].double()).float())
-    out = Guarded(M, Dl, Dl + 8)
-    assert lib.car_add(out.ptr, Dl + 8, _ptr(ad), Dl + 4, -0.37, None, 0, 0.0, M, Dl, _stream()) == 0
+    out = Guarded((M, Dl), Dl + 8)
+    assert lib.car_add(out.ptr, Dl + 8, abi.ptr(ad), Dl + 4, -0.37, None, 0, 0.0, M, Dl, abi.stream()) == 0
     torch.cuda.synchronize()
     assert torch.equal(out.get("add"), (torch.tensor(-0.37, dtype=torch.float32).double() * a[:, :Dl].double()).float())
     # b a column-offset view (d_zrep[:, Dl:]), all strides different, alpha and beta not 1
     zd = _up(zrep)
     for alpha, beta in ((1.0, 1.0), (0.75, -1.3)):
-        out = Guarded(M, Dl, Dl + 12)
+        out = Guarded((M, Dl), Dl + 12)
         bview = zd[:, Dl:]
-        assert lib.car_add(out.ptr, Dl + 12, _ptr(ad), Dl + 4, alpha, _ptr(bview), V * Dl, beta, M, Dl, _stream()) == 0
+        assert lib.car_add(out.ptr, Dl + 12, abi.ptr(ad), Dl + 4, alpha, abi.ptr(bview), V * Dl, beta, M, Dl, abi.stream()) == 0
         torch.cuda.synchronize()
         fa, fb = torch.tensor(alpha, dtype=torch.float32).double(), torch.tensor(beta, dtype=torch.float32).double()
         want = fa * a[:, :Dl].double() + fb * zrep[:, Dl:].double()
         bound = (fa * a[:, :Dl].double()).abs() + (fb * zrep[:, Dl:].double()).abs()
         _report("add", f"view alpha {alpha} beta {beta}", err=_ratio((out.get("add").double() - want).abs(), EPS * bound))
     # in place: out == a (training.py: d_x = d_x + tmp, d_zf = d_zf + d_zrep[:, v Dl:])
-    acc = Guarded(M, Dl, Dl + 4, init=a[:, :Dl])
-    assert lib.car_add(acc.ptr, Dl + 4, acc.ptr, Dl + 4, 1.0, _ptr(zd[:, Dl:]), V * Dl, 1.0, M, Dl, _stream()) == 0
+    acc = Guarded((M, Dl), Dl + 4, init=a[:, :Dl])
+    assert lib.car_add(acc.ptr, Dl + 4, acc.ptr, Dl + 4, 1.0, abi.ptr(zd[:, Dl:]), V * Dl, 1.0, M, Dl, abi.stream()) == 0
     torch.cuda.synchronize()
     assert torch.equal(acc.get("add in place"), (a[:, :Dl].double() + zrep[:, Dl:].double()).float())
 
 
 def test_reduce_samples_matches_fp64():
-    lib = _lib()
+    lib = abi.lib()
     for V in (1, 2, 3):
         for P in (1, 13, 64):
             for C in (4, 128, 300):
                 b, R = 2, 11
                 d = torch.randn(b * V, R, P, C, generator=A.gen(V * 1000 + P * 10 + C)) + 0.5
-                du = Guarded(b * R, C)
+                du = Guarded((b * R, C))
                 dd = _up(d)
-                assert lib.car_reduce_samples(_ptr(dd), b, V, R, P, C, du.ptr, _stream()) == 0, lib.car_last_error()
+                assert lib.car_reduce_samples(abi.ptr(dd), b, V, R, P, C, du.ptr, abi.stream()) == 0, lib.car_last_error()
                 torch.cuda.synchronize()
                 dr = A.ray_major(d.double(), b, V)
                 _report("reduce_samples", f"V {V} P {P} C {C}",
@@ -454,7 +402,7 @@ def test_reduce_samples_matches_fp64():
 
 def test_relu_mask_is_exact_on_special_values():
     """grad = act > 0 ? grad : 0 — +0, -0 and NaN activations pass nothing, denormals and +inf do; different row strides."""
-    lib = _lib()
+    lib = abi.lib()
     g = A.gen(6)
     M, N, ldg, lda = 513, 37, 40, 44
     act = torch.randn(M, lda, generator=g)
@@ -463,9 +411,9 @@ def test_relu_mask_is_exact_on_special_values():
     flat[::7] = specials[torch.arange(flat[::7].numel()) % len(specials)]
     act[:, :N] = flat.view(M, N)
     grad = torch.randn(M, N, generator=g)
-    gb = Guarded(M, N, ldg, init=grad)
+    gb = Guarded((M, N), ldg, init=grad)
     ad = _up(act)
-    assert lib.car_relu_mask(gb.ptr, ldg, _ptr(ad), lda, M, N, _stream()) == 0, lib.car_last_error()
+    assert lib.car_relu_mask(gb.ptr, ldg, abi.ptr(ad), lda, M, N, abi.stream()) == 0, lib.car_last_error()
     torch.cuda.synchronize()
     want = torch.where(act[:, :N].double() > 0, grad, torch.zeros_like(grad))
     got = gb.get("relu_mask")
@@ -477,24 +425,24 @@ def test_relu_mask_is_exact_on_special_values():
 
 def test_add_ray_bias_relu_is_exact():
     """r = relu(r + u[scene, ray]) in place, one rounding: bit for bit; the last size runs beyond the 16 384-block grid cap."""
-    lib = _lib()
+    lib = abi.lib()
     for b, V, R, P, C in ((1, 1, 5, 3, 4), (2, 2, 37, 13, 128), (3, 3, 10, 7, 16), (1, 2, 1100, 64, 128)):
         assert (b, V, R, P, C) != (1, 2, 1100, 64, 128) or b * V * R * P * C // 4 > 16384 * 256
         g = A.gen(C)
         r = torch.randn(b * V, R, P, C, generator=g)
         u = torch.randn(b, R, C, generator=g)
-        rb = Guarded(b * V * R * P, C, init=r)
+        rb = Guarded((b * V * R * P, C), init=r)
         ud = _up(u)
-        assert lib.car_add_ray_bias_relu(rb.ptr, _ptr(ud), b, V, R, P, C, _stream()) == 0, lib.car_last_error()
+        assert lib.car_add_ray_bias_relu(rb.ptr, abi.ptr(ud), b, V, R, P, C, abi.stream()) == 0, lib.car_last_error()
         torch.cuda.synchronize()
         want = (r.double().view(b, V, R, P, C) + u.double()[:, None, :, None, :]).clamp_min(0.0).float().view(-1, C)
         assert torch.equal(rb.get("add_ray_bias_relu"), want), (b, V, R, P, C)
 
 
 def test_bad_arguments_are_refused_before_anything_is_launched():
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P, D = 1, 2, 4, 8, 64
-    dev = _dev()
+    dev = abi.dev()
     w = torch.rand(b * V, R, P, device=dev)
     val = torch.randn(b * V, R, P, D + 4, device=dev)
     dz = torch.randn(b, R, D + 8, device=dev)
@@ -502,16 +450,16 @@ def test_bad_arguments_are_refused_before_anything_is_launched():
     dd = torch.randn(b, R, device=dev)
     poses = torch.zeros(b * V, 96, device=dev)
     qa = torch.randn(b * V, R, P, 8, device=dev)
-    dval, dlogit, z = Guarded(b * V * R * P, D + 4), Guarded(b * V * R, P), Guarded(b * R, 2 * D)
-    depth, wout = Guarded(b * R, 1), Guarded(b * V * R, P)
+    dval, dlogit, z = Guarded((b * V * R * P, D + 4)), Guarded((b * V * R, P)), Guarded((b * R, 2 * D))
+    depth, wout = Guarded((b * R, 1)), Guarded((b * V * R, P))
 
     def bwd(D_=D, ld=D, V_=V, P_=P, ddepth=None, pt_=None):
-        return lib.car_attend_backward(_ptr(w), _ptr(val), D_, b, V_, R, P_, _ptr(dz), ld, _ptr(ddepth), _ptr(pt_), _ptr(poses), dval.ptr, 0,
-                                       dlogit.ptr, _stream())
+        return lib.car_attend_backward(abi.ptr(w), abi.ptr(val), D_, b, V_, R, P_, abi.ptr(dz), ld, abi.ptr(ddepth), abi.ptr(pt_), abi.ptr(poses), dval.ptr, 0,
+                                       dlogit.ptr, abi.stream())
 
     def fwd(dq=8, qb=None, ld_z=D, reps=1):
-        return lib.car_attend(_ptr(qa), _ptr(qb), dq, _ptr(val), D, b, V, R, P, None, 0.0, wout.ptr, z.ptr, ld_z, reps, None, None, None, None,
-                              _stream())
+        return lib.car_attend(abi.ptr(qa), abi.ptr(qb), dq, abi.ptr(val), D, b, V, R, P, None, 0.0, wout.ptr, z.ptr, ld_z, reps, None, None, None, None,
+                              abi.stream())
     assert bwd(D_=D + 2) == CAR_E_ARG                       # D % 4 != 0
     assert bwd(ld=D - 4) == CAR_E_ARG                       # ld_dz < D
     assert bwd(V_=3, P_=257) == CAR_E_ARG                   # V P > 768
@@ -519,8 +467,8 @@ def test_bad_arguments_are_refused_before_anything_is_launched():
     assert lib.car_last_error()
     assert fwd(ld_z=2 * D - 4, reps=2) == CAR_E_ARG         # ld_z < reps D
     assert fwd(dq=6, qb=qa) == CAR_E_ARG                    # qb given, dq % 4 != 0
-    r = Guarded(b * V * R * P, 6)
-    assert lib.car_add_ray_bias_relu(r.ptr, _ptr(dz), b, V, R, P, 6, _stream()) == CAR_E_ARG       # C % 4 != 0
+    r = Guarded((b * V * R * P, 6))
+    assert lib.car_add_ray_bias_relu(r.ptr, abi.ptr(dz), b, V, R, P, 6, abi.stream()) == CAR_E_ARG       # C % 4 != 0
     torch.cuda.synchronize()
     for buf in (dval, dlogit, z, depth, wout, r):
         assert bool(torch.isnan(buf.full).all()), "a refused call wrote something"

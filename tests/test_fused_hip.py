@@ -17,14 +17,12 @@ import functools
 import pytest
 import torch
 
+import abi_harness as abi
 import fused_reference as FR
+from abi_harness import CAR_E_ARG, NAN, Guarded
+from parity_rule import judge
 
 pytestmark = pytest.mark.gpu
-
-NAN = float("nan")
-MARGIN = 256
-CAR_E_ARG = -1
-P_ = ctypes.c_void_p
 
 
 def _L():
@@ -33,9 +31,8 @@ def _L():
 
 
 @functools.lru_cache(maxsize=None)
-def _lib():
-    L = _L()
-    lib = L.load()
+def _fused_lib():
+    L, lib = _L(), abi.lib()
     f16 = lib.car_fused_samples_f16                       # declared in csrc/car_common.h, reached by the engine through car_render_forward_f16 only
     f16.restype = ctypes.c_int
     f16.argtypes = L.SIGNATURES["car_fused_samples_parts"][1]
@@ -43,61 +40,22 @@ def _lib():
     return lib
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return None if t is None else P_(t.data_ptr())
-
-
-def _stream():
-    return P_(torch.cuda.current_stream().cuda_stream)
-
-
-class Guarded:
-    """n floats inside a NaN-filled buffer."""
-
-    def __init__(self, *shape):
-        self.shape = shape
-        self.n = 1
-        for s in shape:
-            self.n *= s
-        self.full = torch.full((2 * MARGIN + self.n,), NAN, dtype=torch.float32, device=_dev())
-
-    @property
-    def ptr(self):
-        return P_(self.full.data_ptr() + 4 * MARGIN)
-
-    def untouched(self):
-        return bool(torch.isnan(self.full).all())
-
-    def get(self, what=""):
-        f = self.full.cpu()
-        assert bool(torch.isnan(f[:MARGIN]).all()) and bool(torch.isnan(f[MARGIN + self.n:]).all()), f"{what}: wrote outside the buffer"
-        return f[MARGIN:MARGIN + self.n].reshape(self.shape).clone()
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
 # ---- setup ---------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _packed(kind):
     """(params, blob, bias, wpt, CarWeights, the tensors it points into) of a weight set, packed once by car_fused_pack."""
-    L, lib = _L(), _lib()
+    L, lib = _L(), _fused_lib()
     params = FR.weights(kind)
     w, keep = L.CarWeights(), []
     for n in FR.SHAPES:
         for k, suffix in (("weight", "w"), ("bias", "b")):
-            t = params[f"{n}.{k}"].float().contiguous().to(_dev())
+            t = params[f"{n}.{k}"].float().contiguous().to(abi.dev())
             keep.append(t)
             setattr(w, f"{n}_{suffix}", t.data_ptr())
-    blob = torch.full((lib.car_fused_blob_floats(),), NAN, device=_dev())
-    bias = torch.full((lib.car_fused_bias_floats(),), NAN, device=_dev())
-    wpt = torch.full((FR.C * 4,), NAN, device=_dev())
-    rc = lib.car_fused_pack(ctypes.byref(w), _ptr(blob), _ptr(bias), _ptr(wpt), _stream())
+    blob = torch.full((lib.car_fused_blob_floats(),), NAN, device=abi.dev())
+    bias = torch.full((lib.car_fused_bias_floats(),), NAN, device=abi.dev())
+    wpt = torch.full((FR.C * 4,), NAN, device=abi.dev())
+    rc = lib.car_fused_pack(ctypes.byref(w), abi.ptr(blob), abi.ptr(bias), abi.ptr(wpt), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return params, blob, bias, wpt, w, keep
@@ -107,7 +65,7 @@ def _packed(kind):
 def _plan16(kind):
     """blob16 | bias | wpt of the fp16 instance: car_plan_f16_build's plan (compact blob, bias table, point table, each rounded up to 64
     floats: csrc/car_render.hip plan16_layout, as tests/test_fused_pack.py restates it)."""
-    L, lib = _L(), _lib()
+    L, lib = _L(), _fused_lib()
     w = _packed(kind)[4]
     up64 = lambda n: (n + 63) & ~63
     dims = L.CarDims()
@@ -118,8 +76,8 @@ def _plan16(kind):
     o_bias = up64(lib.car_fused_blob16_floats())
     o_wpt = o_bias + up64(lib.car_fused_bias_floats())
     assert n16 == o_wpt + up64(FR.C * 4), "car_plan_f16_build's layout changed"
-    p16 = torch.zeros(n16, device=_dev())
-    rc = lib.car_plan_f16_build(ctypes.byref(dims), ctypes.byref(w), _ptr(p16), _stream())
+    p16 = torch.zeros(n16, device=abi.dev())
+    rc = lib.car_plan_f16_build(ctypes.byref(dims), ctypes.byref(w), abi.ptr(p16), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return p16, p16[:o_bias], p16[o_bias:o_wpt], p16[o_wpt:]
@@ -130,7 +88,7 @@ class Setup:
 
     def __init__(self, c, rays_edit=FR.patch_rays, device_poses=False):
         from cross_attention_renderer_amd.poses import pack_poses
-        lib, dev, st = _lib(), _dev(), _stream()
+        lib, dev, st = _fused_lib(), abi.dev(), abi.stream()
         self.c = c
         b, R, P, H, W = c["b"], c["R"], c["P"], c["H"], c["W"]
         self.n_sets, self.S = 2 * b, 2 * b * R * P
@@ -139,44 +97,44 @@ class Setup:
             f = lambda t: t.float().contiguous().to(dev)
             cc, cq, kc, kq = f(inp["context"]["cam2world"]), f(inp["query"]["cam2world"]), f(inp["context"]["intrinsics"]), f(inp["query"]["intrinsics"])
             self.poses = torch.empty(2 * b, 96, device=dev)
-            assert lib.car_pose_setup(_ptr(cc), _ptr(cq), _ptr(kc), _ptr(kq), b, 2, H, _ptr(self.poses), st) == 0, lib.car_last_error()
+            assert lib.car_pose_setup(abi.ptr(cc), abi.ptr(cq), abi.ptr(kc), abi.ptr(kq), b, 2, H, abi.ptr(self.poses), st) == 0, lib.car_last_error()
         else:
             self.poses = pack_poses(inp, H).contiguous().to(dev)
         self.steps = steps.to(dev)
         uvd = inp["query"]["uv"].float().contiguous().to(dev)
         self.rays = torch.empty(2 * b, R, 12, device=dev)
-        rc = lib.car_ray_setup(_ptr(self.poses), _ptr(uvd), b, 2, R, H, W, P, c["no_sample"], _ptr(self.steps), _ptr(self.rays), None, None, 0, st)
+        rc = lib.car_ray_setup(abi.ptr(self.poses), abi.ptr(uvd), b, 2, R, H, W, P, c["no_sample"], abi.ptr(self.steps), abi.ptr(self.rays), None, None, 0, st)
         assert rc == 0, lib.car_last_error()
         rays_edit(self.rays)
         S = self.S
         pv, pt, g = torch.empty(S, 2, device=dev), torch.empty(S, 3, device=dev), torch.empty(S, 16, device=dev)
         gi, pi = torch.empty(S, 2, 2, device=dev), torch.empty(S, 2, 3, device=dev)
-        rc = lib.car_sample_setup(_ptr(self.poses), _ptr(self.rays), _ptr(self.steps), b, 2, R, P, H, W, c["no_sample"], _ptr(pv), _ptr(pt), _ptr(g),
-                                  _ptr(gi), None, 0, 0, _ptr(pi), st)
+        rc = lib.car_sample_setup(abi.ptr(self.poses), abi.ptr(self.rays), abi.ptr(self.steps), b, 2, R, P, H, W, c["no_sample"], abi.ptr(pv), abi.ptr(pt), abi.ptr(g),
+                                  abi.ptr(gi), None, 0, 0, abi.ptr(pi), st)
         assert rc == 0, lib.car_last_error()
         torch.cuda.synchronize()
         self.rec = {"grid": pv.cpu(), "pt": pt.cpu(), "g": g.cpu(), "grid_in": gi.cpu(), "pt_in": pi.cpu()}
 
 
 def _lattice_dev(lat):
-    d = lat.contiguous().to(_dev())
-    return d, lat.abs().max().reshape(1).float().to(_dev())
+    d = lat.contiguous().to(abi.dev())
+    return d, lat.abs().max().reshape(1).float().to(abi.dev())
 
 
 def run_samples(su, lat, gmeta, wpt, blob, bias, entry="parts", dims=None):
     """One launch of car_fused_samples / _parts / _f16 into guarded buffers: dict of host tensors."""
-    lib, c = _lib(), su.c
+    lib, c = _fused_lib(), su.c
     S, R, P = su.S, c["R"], c["P"]
     pgs = -(-P // lib.car_fused_tile_steps())
-    out = {"e": Guarded(S, FR.C), "g": Guarded(S, 16), "logit": Guarded(S), "pt": Guarded(S, 3), "pixel_val": Guarded(S, 2)}
+    out = {"e": Guarded((S, FR.C)), "g": Guarded((S, 16)), "logit": Guarded((S,)), "pt": Guarded((S, 3)), "pixel_val": Guarded((S, 2))}
     lh, lw = lat.shape[2:4]
-    args = [_ptr(su.poses), _ptr(su.rays), _ptr(su.steps), _ptr(lat), lh, lw, c["pad"], _ptr(gmeta), _ptr(wpt), _ptr(blob), _ptr(bias), c["b"], 2, R, P,
+    args = [abi.ptr(su.poses), abi.ptr(su.rays), abi.ptr(su.steps), abi.ptr(lat), lh, lw, c["pad"], abi.ptr(gmeta), abi.ptr(wpt), abi.ptr(blob), abi.ptr(bias), c["b"], 2, R, P,
             c["H"], c["W"], c["no_sample"], out["e"].ptr, out["g"].ptr, out["logit"].ptr, out["pt"].ptr, out["pixel_val"].ptr]
     if entry == "plain":
-        rc = lib.car_fused_samples(*args, _stream())
+        rc = lib.car_fused_samples(*args, abi.stream())
     else:
-        out["part"] = Guarded(su.n_sets, R, pgs, FR.C)
-        rc = (lib.car_fused_samples_parts if entry == "parts" else lib.car_fused_samples_f16)(*args, out["part"].ptr, _stream())
+        out["part"] = Guarded((su.n_sets, R, pgs, FR.C))
+        rc = (lib.car_fused_samples_parts if entry == "parts" else lib.car_fused_samples_f16)(*args, out["part"].ptr, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return {k: v.get(k) for k, v in out.items()}
@@ -195,29 +153,20 @@ def _case(tag):
 
 
 def _judge(test, case, got, ref, yard, keys=("e", "logit"), what="fp32"):
-    parts, bad = [], []
-    for k in keys:
-        assert bool(torch.isfinite(got[k]).all()), (test, case, k, "not finite")
-        ry = FR.ratio(yard[k], ref[k], ref["B_" + k])
-        rk = FR.ratio(got[k], ref[k], ref["B_" + k])
-        tol = FR.tolerance(ry)
-        parts.append(f"{k}={rk / tol:.3f} (kernel {rk:.2e} {what} {ry:.2e})")
-        if not rk <= tol:
-            bad.append((k, rk, tol))
-    print(f"[parity] {test} {case}: " + " ".join(parts))
-    assert not bad, (test, case, bad)
+    """Every output finite and held to the yardstick run's own ratio against the same float64 run and bound."""
+    judge(test, case, {k: ((got[k], ref[k], ref["B_" + k]), FR.ratio(yard[k], ref[k], ref["B_" + k])) for k in keys}, what=what, finite=True)
 
 
 def _judge_part(test, case, got, su):
     c = su.c
-    want, mag = FR.part(got["e"], got["logit"], su.n_sets, c["R"], c["P"], _lib().car_fused_tile_steps())
-    y32, _ = FR.part(got["e"], got["logit"], su.n_sets, c["R"], c["P"], _lib().car_fused_tile_steps(), dtype=torch.float32)
+    want, mag = FR.part(got["e"], got["logit"], su.n_sets, c["R"], c["P"], _fused_lib().car_fused_tile_steps())
+    y32, _ = FR.part(got["e"], got["logit"], su.n_sets, c["R"], c["P"], _fused_lib().car_fused_tile_steps(), dtype=torch.float32)
     _judge(test, case, {"part": got["part"]}, {"part": want, "B_part": mag}, {"part": y32}, keys=("part",))
 
 
 def _geometry_equals_sample_setup(got, su):
     for k, r in (("pixel_val", "grid"), ("pt", "pt"), ("g", "g")):
-        assert torch.equal(_bits(got[k]), _bits(su.rec[r].reshape(got[k].shape))), f"{k} differs from car_sample_setup's"
+        assert torch.equal(abi.bits(got[k]), abi.bits(su.rec[r].reshape(got[k].shape))), f"{k} differs from car_sample_setup's"
 
 
 def _check(test, tag):
@@ -240,7 +189,7 @@ def test_fused_samples_match_fp64_at_the_tile_edges(shape):
     su, ref, got, (dlat, gmeta, wpt, blob, bias) = _check("tile_edges", tag)
     plain = run_samples(su, dlat, gmeta, wpt, blob, bias, "plain")
     for k in ("e", "g", "logit", "pt", "pixel_val"):
-        assert torch.equal(_bits(plain[k]), _bits(got[k])), f"{k}: car_fused_samples differs from car_fused_samples_parts"
+        assert torch.equal(abi.bits(plain[k]), abi.bits(got[k])), f"{k}: car_fused_samples differs from car_fused_samples_parts"
 
 
 # ---- 2. geometry variants ------------------------------------------------------------------------------------------------------------------
@@ -286,13 +235,13 @@ def test_fused_samples_integer_case_is_bit_exact_in_e():
 # ---- 5. the rows instance ------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _packed_rows():
-    lib = _lib()
+    lib = _fused_lib()
     params, _, _, _, w, _ = _packed("gauss")
-    blob = torch.zeros(lib.car_fused_blob_floats(), device=_dev())
-    bias = torch.zeros(lib.car_fused_bias_floats(), device=_dev())
-    wpt = torch.zeros(FR.C * 4, device=_dev())
-    rc = lib.car_fused_pack_rows(w.query_encode_latent_w, w.query_encode_latent_b, w.query_encode_latent_2_w, w.query_encode_latent_2_b, _ptr(blob),
-                                 _ptr(bias), _ptr(wpt), _stream())
+    blob = torch.zeros(lib.car_fused_blob_floats(), device=abi.dev())
+    bias = torch.zeros(lib.car_fused_bias_floats(), device=abi.dev())
+    wpt = torch.zeros(FR.C * 4, device=abi.dev())
+    rc = lib.car_fused_pack_rows(w.query_encode_latent_w, w.query_encode_latent_b, w.query_encode_latent_2_w, w.query_encode_latent_2_b, abi.ptr(blob),
+                                 abi.ptr(bias), abi.ptr(wpt), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return params, blob, bias, wpt
@@ -302,7 +251,7 @@ def _packed_rows():
 def test_fused_rows_match_fp64(tag):
     """car_fused_rows over explicit rows, ncomp 1 and 3, ragged and whole tiles; every (set, component) its own (map, mode); mode-1 rows on
     and beyond the ring; e [rows][288] NaN-guarded."""
-    lib, c = _lib(), FR.ROWS_CASES[tag]
+    lib, c = _fused_lib(), FR.ROWS_CASES[tag]
     su = Setup(c)
     src, grid, pe = FR.rows_lists(c, su.rec)
     lat = FR.case_lattice(c)
@@ -311,11 +260,11 @@ def test_fused_rows_match_fp64(tag):
     f32 = FR.rows(params, lat, c["pad"], src, grid, pe, dtype=torch.float32)
     dlat, gmeta = _lattice_dev(lat)
     nc = c["rows_comp"]
-    e = Guarded(su.S * nc, FR.E)
-    dsrc, dgrid, dpe = src.to(_dev()), grid.to(_dev()), pe.to(_dev())
+    e = Guarded((su.S * nc, FR.E))
+    dsrc, dgrid, dpe = src.to(abi.dev()), grid.to(abi.dev()), pe.to(abi.dev())
     lh, lw = lat.shape[2:4]
-    rc = lib.car_fused_rows(_ptr(dlat), lh, lw, c["pad"], _ptr(gmeta), _ptr(wpt), _ptr(blob), _ptr(bias), _ptr(dsrc), _ptr(dgrid), _ptr(dpe), su.n_sets,
-                            c["R"], c["P"], nc, e.ptr, _stream())
+    rc = lib.car_fused_rows(abi.ptr(dlat), lh, lw, c["pad"], abi.ptr(gmeta), abi.ptr(wpt), abi.ptr(blob), abi.ptr(bias), abi.ptr(dsrc), abi.ptr(dgrid), abi.ptr(dpe), su.n_sets,
+                            c["R"], c["P"], nc, e.ptr, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     _judge("rows", tag, {"e": e.get("e")}, ref, f32, keys=("e",))
@@ -333,7 +282,7 @@ def test_fused_samples_f16_is_held_to_the_fp16_emulation(tag):
     got = run_samples(su, dlat, gmeta, wpt16, blob16, bias16, "f16")
     fp32 = run_samples(su, dlat, gmeta, wpt, blob, bias, "parts")
     for k in ("g", "pt", "pixel_val"):
-        assert torch.equal(_bits(got[k]), _bits(fp32[k])), k
+        assert torch.equal(abi.bits(got[k]), abi.bits(fp32[k])), k
     _judge("f16", tag, got, ref, emu, what="fp16-emulation")
     _judge_part("f16", tag, got, su)
     assert not torch.equal(got["e"], fp32["e"]), "the fp16 instance did not run"
@@ -345,11 +294,11 @@ def _refusal_args():
     _, blob, bias, wpt, _, _ = _packed("gauss")
     c = su.c
     lh, lw = lat.shape[2:4]
-    out = {k: Guarded(*s) for k, s in (("e", (su.S, FR.C)), ("g", (su.S, 16)), ("logit", (su.S,)), ("pt", (su.S, 3)), ("pixel_val", (su.S, 2)),
+    out = {k: Guarded(s) for k, s in (("e", (su.S, FR.C)), ("g", (su.S, 16)), ("logit", (su.S,)), ("pt", (su.S, 3)), ("pixel_val", (su.S, 2)),
                                        ("part", (su.n_sets, c["R"], 1, FR.C)))}
     names = ["poses", "rays", "steps", "lattice", "lat_h", "lat_w", "lat_pad", "gmeta", "wpt", "blob", "bias", "b", "V", "R", "P", "H", "W", "no_sample",
              "e", "g", "logit", "pt", "pixel_val", "part"]
-    vals = [_ptr(su.poses), _ptr(su.rays), _ptr(su.steps), _ptr(dlat), lh, lw, c["pad"], _ptr(gmeta), _ptr(wpt), _ptr(blob), _ptr(bias), c["b"], 2, c["R"],
+    vals = [abi.ptr(su.poses), abi.ptr(su.rays), abi.ptr(su.steps), abi.ptr(dlat), lh, lw, c["pad"], abi.ptr(gmeta), abi.ptr(wpt), abi.ptr(blob), abi.ptr(bias), c["b"], 2, c["R"],
             c["P"], c["H"], c["W"], 0, out["e"].ptr, out["g"].ptr, out["logit"].ptr, out["pt"].ptr, out["pixel_val"].ptr, out["part"].ptr]
     return dict(zip(names, vals)), out
 
@@ -363,7 +312,7 @@ SAMPLE_REFUSALS = [(k, None) for k in ("poses", "rays", "steps", "lattice", "gme
 def test_fused_samples_refusals(field, value):
     """Null inputs and outputs; V of 1 and 3; non-positive b / R / P; H or W of 1; pad below 2; even lat - 2 pad; a lattice too small for
     its pad; 967 x 967 nodes (2 GiB per map, no such allocation: refused from lat_h, lat_w alone); null `part` for _parts.  Nothing is written."""
-    lib = _lib()
+    lib = _fused_lib()
     args, out = _refusal_args()
     if field == "lat_h+w":
         args["lat_h"] = args["lat_w"] = value
@@ -371,17 +320,17 @@ def test_fused_samples_refusals(field, value):
         args[field] = value
     a = list(args.values())
     for fn, n in ((lib.car_fused_samples, 23), (lib.car_fused_samples_parts, 24), (lib.car_fused_samples_f16, 24)):
-        assert fn(*a[:n], _stream()) == CAR_E_ARG, (fn.__name__, field, value)
+        assert fn(*a[:n], abi.stream()) == CAR_E_ARG, (fn.__name__, field, value)
         assert lib.car_last_error()
     torch.cuda.synchronize()
     assert all(g.untouched() for g in out.values())
 
 
 def test_fused_samples_parts_refuses_a_null_part():
-    lib = _lib()
+    lib = _fused_lib()
     args, out = _refusal_args()
     args["part"] = None
-    assert lib.car_fused_samples_parts(*args.values(), _stream()) == CAR_E_ARG
+    assert lib.car_fused_samples_parts(*args.values(), abi.stream()) == CAR_E_ARG
     torch.cuda.synchronize()
     assert all(g.untouched() for g in out.values())
 
@@ -392,21 +341,21 @@ ROWS_REFUSALS = [(k, None) for k in ("lattice", "gmeta", "wpt", "blob", "bias", 
 
 @pytest.mark.parametrize("field,value", ROWS_REFUSALS, ids=lambda v: str(v))
 def test_fused_rows_refusals(field, value):
-    lib = _lib()
+    lib = _fused_lib()
     su, lat, (dlat, gmeta), _, _ = _case("edge-24-8-1")
     _, blob, bias, wpt = _packed_rows()
     c = su.c
     rows = su.S
-    src, grid, pe = torch.zeros(rows, dtype=torch.int32, device=_dev()), torch.zeros(rows, 2, device=_dev()), torch.zeros(rows, 4, device=_dev())
-    e = Guarded(rows, FR.E)
+    src, grid, pe = torch.zeros(rows, dtype=torch.int32, device=abi.dev()), torch.zeros(rows, 2, device=abi.dev()), torch.zeros(rows, 4, device=abi.dev())
+    e = Guarded((rows, FR.E))
     lh, lw = lat.shape[2:4]
-    args = dict(lattice=_ptr(dlat), lat_h=lh, lat_w=lw, lat_pad=c["pad"], gmeta=_ptr(gmeta), wpt=_ptr(wpt), blob=_ptr(blob), bias=_ptr(bias),
-                row_src=_ptr(src), row_grid=_ptr(grid), row_pe=_ptr(pe), n_sets=su.n_sets, R=c["R"], P=c["P"], ncomp=1, e=e.ptr)
+    args = dict(lattice=abi.ptr(dlat), lat_h=lh, lat_w=lw, lat_pad=c["pad"], gmeta=abi.ptr(gmeta), wpt=abi.ptr(wpt), blob=abi.ptr(blob), bias=abi.ptr(bias),
+                row_src=abi.ptr(src), row_grid=abi.ptr(grid), row_pe=abi.ptr(pe), n_sets=su.n_sets, R=c["R"], P=c["P"], ncomp=1, e=e.ptr)
     if field == "lat_h+w":
         args["lat_h"] = args["lat_w"] = value
     else:
         args[field] = value
-    assert lib.car_fused_rows(*args.values(), _stream()) == CAR_E_ARG, (field, value)
+    assert lib.car_fused_rows(*args.values(), abi.stream()) == CAR_E_ARG, (field, value)
     assert lib.car_last_error()
     torch.cuda.synchronize()
     assert e.untouched()

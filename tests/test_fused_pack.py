@@ -9,6 +9,7 @@ import ctypes
 import pytest
 import torch
 
+import abi_harness as abi
 import pack_reference as PR
 from cross_attention_renderer_amd import synthetic as S
 from cross_attention_renderer_amd.models import CrossAttentionRenderer
@@ -277,14 +278,6 @@ def test_device_packers_emit_the_reference_bytes(scale):
     assert torch.equal(dkqb.cpu().view(torch.int32), kqb.view(torch.int32))
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("scale", [1.0, 2e-4, 5e3, 0.0])
 @pytest.mark.parametrize("K,N,ldw", [(64, 32, 64), (72, 48, 80), (576, 288, 579)])
@@ -300,11 +293,11 @@ def test_linear_x3_pack_emits_the_reference_bytes(K, N, ldw, scale):
     n = int(lib.car_linear_x3_packed_floats(K, N))
     assert n == want.numel() + 64
     dW, packed = W.to("cuda:0"), torch.full((n,), float("nan"), device="cuda:0")
-    rc = lib.car_linear_x3_pack(dW.data_ptr(), ldw, K, N, packed.data_ptr(), _stream())
+    rc = lib.car_linear_x3_pack(dW.data_ptr(), ldw, K, N, packed.data_ptr(), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
-    assert torch.equal(_bits(packed[:want.numel()]), _bits(want))
-    assert torch.equal(_bits(packed[want.numel():want.numel() + 2]), _bits(torch.tensor([p, 1.0 / p])))
+    assert torch.equal(abi.bits(packed[:want.numel()].cpu()), abi.bits(want))
+    assert torch.equal(abi.bits(packed[want.numel():want.numel() + 2].cpu()), abi.bits(torch.tensor([p, 1.0 / p])))
 
 
 @pytest.mark.gpu
@@ -326,10 +319,10 @@ def test_chain_pack_emits_the_reference_bytes(K, N, chained, twice):
     packed = torch.full((want.numel(),), float("nan"), device="cuda:0")
     scales = torch.full((32,), float("nan"), device="cuda:0")
     rc = lib.car_chain_pack(dW.data_ptr(), ldw, dW.data_ptr() + 4 * K if twice else None, K, N, chained, packed.data_ptr(), scales.data_ptr(), slot,
-                            _stream())
+                            abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
-    assert torch.equal(_bits(packed), _bits(want))
+    assert torch.equal(abi.bits(packed.cpu()), abi.bits(want))
     scales = scales.cpu()
     assert scales[slot].item() == p and scales[16 + slot].item() == 1.0 / p
     others = torch.ones(32, dtype=torch.bool)
@@ -358,10 +351,10 @@ def test_conv3x3_packs_emit_the_reference_bytes():
     want = torch.cat([PR.pack_tiles16(Wm, None, N // 16, PR.std16_k(9 * K // 32), p).reshape(-1), s, b])
     assert want.numel() == int(lib.car_conv3x3_packed_floats(K, N))
     dw, db, packed = w.to("cuda:0"), b.to("cuda:0"), torch.full((want.numel(),), float("nan"), device="cuda:0")
-    rc = lib.car_conv3x3_pack(dw.data_ptr(), db.data_ptr(), K, N, packed.data_ptr(), _stream())
+    rc = lib.car_conv3x3_pack(dw.data_ptr(), db.data_ptr(), K, N, packed.data_ptr(), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
-    assert torch.equal(_bits(packed), _bits(want))
+    assert torch.equal(abi.bits(packed.cpu()), abi.bits(want))
     K, N = 64, 128
     w = torch.randn(N, K, 3, 3, generator=g) * 0.05
     Wm = w.flip(2, 3).permute(1, 2, 3, 0).reshape(K, 9 * N)
@@ -369,7 +362,7 @@ def test_conv3x3_packs_emit_the_reference_bytes():
     want = torch.cat([PR.pack_tiles16(Wm, None, K // 16, PR.std16_k(9 * N // 32), p).reshape(-1), s])
     assert want.numel() == int(lib.car_conv3x3_backward_packed_floats(K, N))
     dw, packed = w.to("cuda:0"), torch.full((want.numel(),), float("nan"), device="cuda:0")
-    rc = lib.car_conv3x3_backward_pack(dw.data_ptr(), K, N, packed.data_ptr(), _stream())
+    rc = lib.car_conv3x3_backward_pack(dw.data_ptr(), K, N, packed.data_ptr(), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
-    assert torch.equal(_bits(packed), _bits(want))
+    assert torch.equal(abi.bits(packed.cpu()), abi.bits(want))

@@ -16,58 +16,16 @@ import functools
 import pytest
 import torch
 
+import abi_harness as abi
 import gather_reference as GR
+from abi_harness import CAR_E_ARG, INF, NAN, Guarded
+from parity_rule import judge
 
 pytestmark = pytest.mark.gpu
 
-NAN, INF = float("nan"), float("inf")
-MARGIN = 64
-CAR_E_ARG = -1
-
-
-def _lib():
-    from cross_attention_renderer_amd import _lib as L
-    return L.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*v)
-
-
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
 
 def _levels(shapes):
-    return _ints([s[2] for s in shapes]), _ints([s[0] for s in shapes]), _ints([s[1] for s in shapes])
-
-
-class Guarded:
-    """A contiguous float32 tensor of `shape` filled with `fill`, inside a NaN-filled buffer."""
-
-    def __init__(self, shape, fill=NAN):
-        n = 1
-        for d in shape:
-            n *= d
-        self.n = n
-        self.full = torch.full((MARGIN + n + MARGIN,), NAN, dtype=torch.float32, device=_dev())
-        self.view = self.full[MARGIN:MARGIN + n].view(*shape)
-        self.view.fill_(fill)
-
-    def margins_untouched(self):
-        return bool(torch.isnan(self.full[:MARGIN]).all()) and bool(torch.isnan(self.full[MARGIN + self.n:]).all())
+    return abi.ints([s[2] for s in shapes]), abi.ints([s[0] for s in shapes]), abi.ints([s[1] for s in shapes])
 
 
 def _named_rows(n_maps, pts, V, places):
@@ -77,18 +35,16 @@ def _named_rows(n_maps, pts, V, places):
 def _dout(values, ld, col_out, named):
     """values [rows, C] on the device inside rows of stride ld: padding columns hold inf, rows outside `named` NaN."""
     rows, C = values.shape
-    d = Guarded((rows, ld), INF)
+    d = Guarded((rows, ld), fill=INF)
     d.view[:, col_out:col_out + C] = NAN
-    d.view[named.to(_dev()), col_out:col_out + C] = values.to(_dev())[named.to(_dev())]
+    d.view[named.to(abi.dev()), col_out:col_out + C] = values.to(abi.dev())[named.to(abi.dev())]
     return d
 
 
 def _judge(test, case, pairs, r32):
-    """pairs: [(got, ref64, bound)] on one device.  Prints the [parity] line and holds the worst ratio to 8 x max(r32, 2^-22)."""
-    rk = max(GR.ratio(g, r, b) for g, r, b in pairs)
-    tol = GR.tolerance(r32)
-    print(f"[parity] {test} {case}: {rk / tol:.3f} (kernel {rk:.2e} fp32 {r32:.2e} tol {tol:.2e})" + ("  ABOVE HALF THE TOLERANCE" if rk > tol / 2 else ""))
-    assert rk <= tol, (test, case, rk, tol)
+    """pairs: [(got, ref64, bound)] on one device, one per level; the worst of them is held to the float32 run's ratio r32 by
+    gather_reference.ratio's reading of a bound and of a non-finite value."""
+    judge(test, case, {"": (pairs, r32)}, ratio=GR.ratio)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -98,15 +54,15 @@ def run_forward(lib, s, mode):
     shapes, n_maps, pts, place, V = s["shapes"], s["n_maps"], s["pts"], s["place"], s["V"]
     C = sum(c for _, _, c in shapes)
     rows, ld, col_out = GR.n_rows(place, V, n_maps, pts), s["ld"], s["col_out"]
-    maps = [t.to(_dev()) for t in s["maps"]]
-    grid = s["grid"].to(_dev())
+    maps = [t.to(abi.dev()) for t in s["maps"]]
+    grid = s["grid"].to(abi.dev())
     out = Guarded((rows, ld))
     cs, hs, ws = _levels(shapes)
-    rc = lib.car_gather_bilinear(_ptrs(maps), cs, hs, ws, len(shapes), n_maps, _ptr(grid), pts, s["run"], mode, place, V, _ptr(out.view), ld, col_out,
-                                 _stream())
+    rc = lib.car_gather_bilinear(abi.ptrs(maps), cs, hs, ws, len(shapes), n_maps, abi.ptr(grid), pts, s["run"], mode, place, V, abi.ptr(out.view), ld, col_out,
+                                 abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
-    named = GR.rows_of(place, V, n_maps, pts).flatten().to(_dev())
+    named = GR.rows_of(place, V, n_maps, pts).flatten().to(abi.dev())
     got = out.view[named, col_out:col_out + C].clone()
     out.view[named, col_out:col_out + C] = NAN
     assert out.margins_untouched() and bool(torch.isnan(out.view).all()), "wrote outside the rows' windows"
@@ -115,8 +71,8 @@ def run_forward(lib, s, mode):
 
 def _forward_case(lib, test, case, s, mode):
     got = run_forward(lib, s, mode)
-    ref, bound = GR.gather_ref(s["maps"], s["grid"], mode, device=_dev())
-    f32, _ = GR.gather_ref(s["maps"], s["grid"], mode, torch.float32, device=_dev())
+    ref, bound = GR.gather_ref(s["maps"], s["grid"], mode, device=abi.dev())
+    f32, _ = GR.gather_ref(s["maps"], s["grid"], mode, torch.float32, device=abi.dev())
     _judge(test, case, [(got, ref, bound)], GR.ratio(f32, ref, bound))
 
 
@@ -125,7 +81,7 @@ def _forward_case(lib, test, case, s, mode):
 def test_forward_edge_sets(name, mode):
     """Four levels with a 512-channel one (wave tasks, two segments), (256, 64, 8) (wave tasks), (8, 12, 4) and (4,) (the per-float4 kernel);
     levels of 1 x 1, 1 x 7, 5 x 3 and 16 x 16; plain, own with V = 2 and 3, other2; run = 1, 4 over 37 rays, and a non-divisor."""
-    _forward_case(_lib(), "forward", f"{name} mode={mode}", GR.edge_set(name), mode)
+    _forward_case(abi.lib(), "forward", f"{name} mode={mode}", GR.edge_set(name), mode)
 
 
 @pytest.mark.parametrize("mode", [0, 1])
@@ -134,7 +90,7 @@ def test_forward_group_stride(kernel, mode):
     """2 200 000 rows, more groups of 32 than the grid's 65536 work groups, so that the group loop takes a second trip: in the wave-task
     kernel (one 8-channel level, 68 750 groups) and in the per-float4 kernel (one 12-channel level, 275 000 rays x 4 steps: 68 752 groups
     with a ragged last ray block)."""
-    _forward_case(_lib(), "forward", f"group-stride {kernel} mode={mode}", GR.forward_stride_set(kernel), mode)
+    _forward_case(abi.lib(), "forward", f"group-stride {kernel} mode={mode}", GR.forward_stride_set(kernel), mode)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -154,10 +110,10 @@ def _scatter_reference(key, mode, on_device):
     """(ref64, bound, r32) of a set shared by the two scatters, computed once: on the CPU (the float32 run then adds in row order), or on the
     device for the sets too large for that."""
     s = _SETS[key]() if key in _SETS else GR.edge_set(key)
-    dev = _dev() if on_device else torch.device("cpu")
+    dev = abi.dev() if on_device else torch.device("cpu")
     args = (s["shapes"], s["n_maps"], _gathers_of(s, mode), s["V"], s["dout"], 0)
     ref, bound, r32 = GR.scatter_ref_r32(*args, device=dev)
-    return [r.to(_dev()) for r in ref], [b.to(_dev()) for b in bound], r32
+    return [r.to(abi.dev()) for r in ref], [b.to(abi.dev()) for b in bound], r32
 
 
 _SETS = {"deep": GR.deep_set, "integer": GR.integer_set, "odd": GR.odd_set, "atomic-stride": GR.atomic_stride_set}
@@ -166,18 +122,18 @@ _SETS = {"deep": GR.deep_set, "integer": GR.integer_set, "odd": GR.odd_set, "ato
 def _device_inputs(s, gathers):
     named = _named_rows(s["n_maps"], s["pts"], s["V"], [p for _, _, p in gathers])
     dout = _dout(s["dout"], s["ld"], s["col_out"], named)
-    return dout, [g.to(_dev()) for g, _, _ in gathers]
+    return dout, [g.to(abi.dev()) for g, _, _ in gathers]
 
 
 def run_atomic(lib, s, gathers, dmaps=None):
     """One call per gather into zeroed (or the given) maps."""
     shapes, n_maps = s["shapes"], s["n_maps"]
     dout, grids = _device_inputs(s, gathers)
-    dmaps = dmaps or [Guarded((n_maps, H, W, C), 0.0) for H, W, C in shapes]
+    dmaps = dmaps or [Guarded((n_maps, H, W, C), fill=0.0) for H, W, C in shapes]
     cs, hs, ws = _levels(shapes)
     for grid, (_, mode, place) in zip(grids, gathers):
-        rc = lib.car_gather_bilinear_backward(_ptrs([d.view for d in dmaps]), cs, hs, ws, len(shapes), n_maps, _ptr(grid), s["pts"], mode, place, s["V"],
-                                              _ptr(dout.view), s["ld"], s["col_out"], _stream())
+        rc = lib.car_gather_bilinear_backward(abi.ptrs([d.view for d in dmaps]), cs, hs, ws, len(shapes), n_maps, abi.ptr(grid), s["pts"], mode, place, s["V"],
+                                              abi.ptr(dout.view), s["ld"], s["col_out"], abi.stream())
         assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     assert all(d.margins_untouched() for d in dmaps), "wrote outside a map"
@@ -193,11 +149,11 @@ def run_binned(lib, s, gathers, dmaps=None, misalign=0, short=0):
     G = len(gathers)
     nbytes = lib.car_scatter_workspace_bytes(hs, ws, len(shapes), n_maps, s["pts"], G)
     assert nbytes > 0
-    work = torch.empty(nbytes + 16, dtype=torch.uint8, device=_dev())
+    work = torch.empty(nbytes + 16, dtype=torch.uint8, device=abi.dev())
     assert work.data_ptr() % 16 == 0
-    rc = lib.car_gather_bilinear_backward_binned(_ptrs([d.view for d in dmaps]), cs, hs, ws, len(shapes), n_maps, _ptrs(grids), _ints([m for _, m, _ in gathers]),
-                                                 _ints([p for _, _, p in gathers]), G, s["pts"], s["V"], _ptr(dout.view), s["ld"], s["col_out"],
-                                                 ctypes.c_void_p(work.data_ptr() + misalign), nbytes - short, _stream())
+    rc = lib.car_gather_bilinear_backward_binned(abi.ptrs([d.view for d in dmaps]), cs, hs, ws, len(shapes), n_maps, abi.ptrs(grids), abi.ints([m for _, m, _ in gathers]),
+                                                 abi.ints([p for _, _, p in gathers]), G, s["pts"], s["V"], abi.ptr(dout.view), s["ld"], s["col_out"],
+                                                 ctypes.c_void_p(work.data_ptr() + misalign), nbytes - short, abi.stream())
     torch.cuda.synchronize()
     if misalign or short:
         return rc, dmaps
@@ -211,7 +167,7 @@ RUN = {"atomic": run_atomic, "binned": run_binned}
 
 def _scatter_case(entry, case, key, mode=None, on_device=False):
     s = _SETS[key]() if key in _SETS else GR.edge_set(key)
-    dmaps = RUN[entry](_lib(), s, _gathers_of(s, mode))
+    dmaps = RUN[entry](abi.lib(), s, _gathers_of(s, mode))
     ref, bound, r32 = _scatter_reference(key, mode, on_device)
     _judge(entry, case, [(d.view, r, b) for d, r, b in zip(dmaps, ref, bound)], r32)
     return s, dmaps, ref, bound, r32
@@ -237,7 +193,7 @@ def test_scatter_integer_set_bit_for_bit(entry):
     """Every partial sum is exact in fp32 (tests/test_gather_reference.py asserts it): whatever the order of the additions, the result is the
     float64 reference to the last bit.  Two gathers (own border, other2 zeros) reading one dout."""
     s = GR.integer_set()
-    dmaps = RUN[entry](_lib(), s, _gathers_of(s))
+    dmaps = RUN[entry](abi.lib(), s, _gathers_of(s))
     ref, _, _ = _scatter_reference("integer", None, False)
     for l, (d, r) in enumerate(zip(dmaps, ref)):
         assert torch.equal(d.view.double(), r), (entry, l, int((d.view.double() != r).sum()))
@@ -259,7 +215,7 @@ def test_scatter_stride_set(entry):
 def test_atomic_scatter_accumulates():
     """A second call into the first call's result: the sum of the two references."""
     s = GR.edge_set("wave3")
-    lib = _lib()
+    lib = abi.lib()
     dmaps = run_atomic(lib, s, _gathers_of(s, 0))
     dmaps = run_atomic(lib, s, _gathers_of(s, 1), dmaps)
     (r0, b0, a), (r1, b1, b) = _scatter_reference("wave3", 0, False), _scatter_reference("wave3", 1, False)
@@ -269,7 +225,7 @@ def test_atomic_scatter_accumulates():
 def test_binned_scatter_overwrites():
     """A second call into the first call's result: the second reference alone."""
     s = GR.edge_set("wave3")
-    lib = _lib()
+    lib = abi.lib()
     dmaps = run_binned(lib, s, _gathers_of(s, 0))
     dmaps = run_binned(lib, s, _gathers_of(s, 1), dmaps)
     ref, bound, r32 = _scatter_reference("wave3", 1, False)
@@ -281,17 +237,17 @@ def test_binned_scatter_mixed_gathers(n_gathers):
     """One, two and four (kMaxGathers) gathers with their own grids, padding modes and placements reading one dout (GR.mixed_set)."""
     s = GR.mixed_set(n_gathers)
     gathers = _gathers_of(s)
-    dmaps = run_binned(_lib(), s, gathers)
+    dmaps = run_binned(abi.lib(), s, gathers)
     args = (s["shapes"], s["n_maps"], gathers, s["V"], s["dout"], 0)
     ref, bound, r32 = GR.scatter_ref_r32(*args)
-    _judge("binned", f"{n_gathers} gathers", [(d.view, r.to(_dev()), b.to(_dev())) for d, r, b in zip(dmaps, ref, bound)], r32)
+    _judge("binned", f"{n_gathers} gathers", [(d.view, r.to(abi.dev()), b.to(abi.dev())) for d, r, b in zip(dmaps, ref, bound)], r32)
 
 
 def _big_binned_case(case, s):
     gathers = _gathers_of(s)
-    dmaps = run_binned(_lib(), s, gathers)
+    dmaps = run_binned(abi.lib(), s, gathers)
     args = (s["shapes"], s["n_maps"], gathers, s["V"], s["dout"], 0)
-    ref, bound, r32 = GR.scatter_ref_r32(*args, device=_dev())
+    ref, bound, r32 = GR.scatter_ref_r32(*args, device=abi.dev())
     _judge("binned", case, [(d.view, r, b) for d, r, b in zip(dmaps, ref, bound)], r32)
 
 
@@ -310,7 +266,7 @@ def test_binned_scatter_bin_stride():
 
 def test_binned_scatter_refuses_a_bad_workspace():
     s = GR.edge_set("quad1")
-    lib = _lib()
+    lib = abi.lib()
     for kw in ({"short": 1}, {"misalign": 8}):
         rc, dmaps = run_binned(lib, s, _gathers_of(s, 0), **kw)
         assert rc == CAR_E_ARG and b"workspace" in lib.car_last_error(), kw
@@ -330,17 +286,17 @@ def _refusal_args(entry, **kw):
     shapes, null_map, null_grid = kw.pop("shapes", _SHAPES), kw.pop("null_map", None), kw.pop("null_grid", None)
     n_maps, pts, V, C = 2, 8, 2, sum(c for _, _, c in shapes)
     maps = [Guarded((2, 5, 3, 8)), Guarded((2, 4, 4, 4))]
-    grid, out = torch.zeros(n_maps, pts, 2, device=_dev()), Guarded((n_maps * pts * V, C + 4))
+    grid, out = torch.zeros(n_maps, pts, 2, device=abi.dev()), Guarded((n_maps * pts * V, C + 4))
     cs, hs, ws = _levels(shapes)
-    a = {"maps": _ptrs([m.view for m in maps]), "c": cs, "h": hs, "w": ws, "n_levels": len(shapes), "n_maps": n_maps}
+    a = {"maps": abi.ptrs([m.view for m in maps]), "c": cs, "h": hs, "w": ws, "n_levels": len(shapes), "n_maps": n_maps}
     if entry == "forward":
-        a.update(grid=_ptr(grid), pts=pts, run=1, mode=0, place=GR.OWN, V=V, out=_ptr(out.view), ld=C + 4, col_out=4)
+        a.update(grid=abi.ptr(grid), pts=pts, run=1, mode=0, place=GR.OWN, V=V, out=abi.ptr(out.view), ld=C + 4, col_out=4)
     elif entry == "atomic":
-        a.update(grid=_ptr(grid), pts=pts, mode=0, place=GR.OWN, V=V, out=_ptr(out.view), ld=C + 4, col_out=4)
+        a.update(grid=abi.ptr(grid), pts=pts, mode=0, place=GR.OWN, V=V, out=abi.ptr(out.view), ld=C + 4, col_out=4)
     else:
-        work = torch.empty(1 << 16, dtype=torch.uint8, device=_dev())
-        a.update(grids=_ptrs([grid, grid]), modes=_ints([0, 1]), places=_ints([GR.OWN, GR.OTHER2]), n_gathers=2, pts=pts, V=V, out=_ptr(out.view), ld=C + 4,
-                 col_out=4, work=_ptr(work), nbytes=1 << 16)
+        work = torch.empty(1 << 16, dtype=torch.uint8, device=abi.dev())
+        a.update(grids=abi.ptrs([grid, grid]), modes=abi.ints([0, 1]), places=abi.ints([GR.OWN, GR.OTHER2]), n_gathers=2, pts=pts, V=V, out=abi.ptr(out.view), ld=C + 4,
+                 col_out=4, work=abi.ptr(work), nbytes=1 << 16)
     if null_map is not None:                                    # one element of the array of map pointers
         a["maps"][null_map] = None
     if null_grid is not None:
@@ -353,17 +309,17 @@ def _refusal_args(entry, **kw):
 
 _ENTRY_FN = {"forward": "car_gather_bilinear", "atomic": "car_gather_bilinear_backward", "binned": "car_gather_bilinear_backward_binned"}
 _COMMON = [("bad sizes", {"n_levels": 0}), ("bad sizes", {"n_levels": 5}), ("bad sizes", {"n_maps": 0}), ("bad sizes", {"pts": 0}),
-           ("multiple of 4", {"c": _ints([8, 6])}), ("multiple of 4", {"h": _ints([5, 0])}), ("multiple of 4", {"w": _ints([0, 4])}),
+           ("multiple of 4", {"c": abi.ints([8, 6])}), ("multiple of 4", {"h": abi.ints([5, 0])}), ("multiple of 4", {"w": abi.ints([0, 4])}),
            ("float4-aligned", {"ld": 18}), ("float4-aligned", {"col_out": 2}), ("float4-aligned", {"col_out": -4}), ("float4-aligned", {"col_out": 8}),
            ("multiple of 4", {"null_map": 1}), ("32-bit texel indices", {"shapes": _BIG})]
 _SINGLE = [("null pointer", {"grid": None}), ("null pointer", {"out": None}), ("null pointer", {"maps": None}), ("mode must be", {"mode": 2}),
            ("bad placement", {"place": 3}), ("bad placement", {"place": GR.OTHER2, "V": 3}), ("bad placement", {"place": GR.OTHER2, "n_maps": 3})]
-_BINNED = [("bad sizes", {"n_gathers": 0}), ("bad sizes", {"n_gathers": 5}), ("mode must be", {"modes": _ints([0, 2])}),
-           ("bad placement", {"places": _ints([GR.OWN, 3])}), ("bad placement", {"V": 3}), ("bad placement", {"n_maps": 3}),
+_BINNED = [("bad sizes", {"n_gathers": 0}), ("bad sizes", {"n_gathers": 5}), ("mode must be", {"modes": abi.ints([0, 2])}),
+           ("bad placement", {"places": abi.ints([GR.OWN, 3])}), ("bad placement", {"V": 3}), ("bad placement", {"n_maps": 3}),
            ("mode must be", {"null_grid": 1}),
            # each term of the counter check alone: 32 pts records and 4 pts rows; one gather of one level with V = 8: 8 pts records, 16 pts
            # rows; two levels whose counters together pass 2^31
-           ("32-bit counters", {"pts": 1 << 27}), ("32-bit counters", {"n_gathers": 1, "n_levels": 1, "V": 8, "places": _ints([GR.OWN]), "pts": 1 << 27}),
+           ("32-bit counters", {"pts": 1 << 27}), ("32-bit counters", {"n_gathers": 1, "n_levels": 1, "V": 8, "places": abi.ints([GR.OWN]), "pts": 1 << 27}),
            ("32-bit counters", {"shapes": _SUM}), ("workspace", {"nbytes": 64})]
 _REFUSALS = [(e, m, kw) for e in ("forward", "atomic") for m, kw in _COMMON + _SINGLE] + [("binned", m, kw) for m, kw in _COMMON + _BINNED]
 
@@ -371,9 +327,9 @@ _REFUSALS = [(e, m, kw) for e in ("forward", "atomic") for m, kw in _COMMON + _S
 @pytest.mark.parametrize("entry,message,kw", _REFUSALS, ids=[f"{e}-{m.split()[0]}-{'-'.join(kw)}-{i}" for i, (e, m, kw) in enumerate(_REFUSALS)])
 def test_refusals(entry, message, kw):
     """CAR_E_ARG, the message of the CAR_REQUIRE that fired, and buffers that are still NaN."""
-    lib = _lib()
+    lib = abi.lib()
     a, guarded, _keep = _refusal_args(entry, **dict(kw))
-    rc = getattr(lib, _ENTRY_FN[entry])(*a.values(), _stream())
+    rc = getattr(lib, _ENTRY_FN[entry])(*a.values(), abi.stream())
     torch.cuda.synchronize()
     assert rc == CAR_E_ARG, (entry, kw, rc)
     assert message.encode() in lib.car_last_error(), (entry, kw, lib.car_last_error())
@@ -381,8 +337,8 @@ def test_refusals(entry, message, kw):
 
 
 def test_binned_scatter_refuses_a_misaligned_dout():
-    lib = _lib()
+    lib = abi.lib()
     a, guarded, _keep = _refusal_args("binned")
     a["out"] = ctypes.c_void_p(a["out"].value + 4)
-    assert lib.car_gather_bilinear_backward_binned(*a.values(), _stream()) == CAR_E_ARG and b"float4-aligned" in lib.car_last_error()
+    assert lib.car_gather_bilinear_backward_binned(*a.values(), abi.stream()) == CAR_E_ARG and b"float4-aligned" in lib.car_last_error()
     assert all(bool(torch.isnan(g.full).all()) for g in guarded)

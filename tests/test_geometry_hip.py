@@ -13,114 +13,55 @@ Stage by stage: every entry is fed the fp32 records of the stage before it — t
 
 Every output lies inside a larger NaN-filled buffer whose margins must come back untouched.  Every test prints ratio / tolerance as a
 ``[parity]`` line (profiles/geometry_parity.md)."""
-import ctypes
 import functools
 
 import pytest
 import torch
 
+import abi_harness as abi
 import geometry_reference as GR
+from abi_harness import CAR_E_ARG, Guarded
 from geometry_reference import F32, F64
+from parity_rule import judge
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-MARGIN = 256
-CAR_E_ARG = -1
-P_ = ctypes.c_void_p
 NAMES = tuple(GR.SETS)
 
 
-@functools.lru_cache(maxsize=None)
-def _lib():
-    from cross_attention_renderer_amd import _lib as L
-    return L.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return None if t is None else P_(t.data_ptr())
-
-
-def _stream():
-    return P_(torch.cuda.current_stream().cuda_stream)
-
-
 def _d(t):
-    return t.contiguous().to(_dev())
-
-
-class Guarded:
-    """n elements (float32, or int32 filled with a sentinel) inside a guard-filled buffer."""
-    SENTINEL = -0x5a5a5a5b
-
-    def __init__(self, *shape, dtype=torch.float32):
-        self.shape, self.dtype = shape, dtype
-        self.n = 1
-        for s in shape:
-            self.n *= s
-        self.fill = NAN if dtype == torch.float32 else self.SENTINEL
-        self.full = torch.full((2 * MARGIN + self.n,), self.fill, dtype=dtype, device=_dev())
-
-    @property
-    def ptr(self):
-        return P_(self.full.data_ptr() + 4 * MARGIN)
-
-    def _is_fill(self, t):
-        return torch.isnan(t) if self.dtype == torch.float32 else t == self.fill
-
-    def untouched(self):
-        return bool(self._is_fill(self.full).all())
-
-    def get(self, what=""):
-        f = self.full.cpu()
-        assert bool(self._is_fill(f[:MARGIN]).all()) and bool(self._is_fill(f[MARGIN + self.n:]).all()), f"{what}: wrote outside the buffer"
-        return f[MARGIN:MARGIN + self.n].reshape(self.shape).clone()
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
+    return t.contiguous().to(abi.dev())
 
 
 def _same(got, want, what):
-    d = _bits(got) != _bits(want.reshape(got.shape).to(got.dtype))
+    d = abi.bits(got) != abi.bits(want.reshape(got.shape).to(got.dtype))
     assert not bool(d.any()), f"{what}: {int(d.sum())} of {d.numel()} floats differ from the float32 restatement, first at {d.nonzero()[0].tolist()}"
 
 
 def _judge(test, name, got, yard):
-    """got, yard: {field: ratio}.  Prints ratio / tolerance per field, asserts ratio <= 8 x max(r32, 2^-22)."""
-    parts, bad = [], []
-    for k, rk in got.items():
-        tol = GR.tolerance(yard[k])
-        parts.append(f"{k}={rk / tol:.3f} (kernel {rk:.2e} r32 {yard[k]:.2e})")
-        if not rk <= tol:
-            bad.append((k, rk, tol))
-    print(f"[parity] {test} {name}: " + " ".join(parts))
-    assert not bad, (test, name, bad)
+    """got, yard: {field: ratio}, taken with geometry_reference.ratio on the decided elements."""
+    judge(test, name, {k: (rk, yard[k]) for k, rk in got.items()}, what="r32")
 
 
 # ---- launches ------------------------------------------------------------------------------------------------------------------------------
 def run_poses(c):
-    lib = _lib()
-    out = Guarded(c["b"] * c["V"], GR.POSE_FLOATS)
+    lib = abi.lib()
+    out = Guarded((c["b"] * c["V"], GR.POSE_FLOATS))
     keep = [_d(c[k]) for k in ("c2w_ctx", "c2w_q", "K_ctx", "K_q")]
-    rc = lib.car_pose_setup(*[_ptr(t) for t in keep], c["b"], c["V"], c["H"], out.ptr, _stream())
+    rc = lib.car_pose_setup(*[abi.ptr(t) for t in keep], c["b"], c["V"], c["H"], out.ptr, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return out.get("poses")
 
 
 def run_rays(c, P32, pad_phi=5, coords=True, phi=True):
-    lib = _lib()
+    lib = abi.lib()
     n, R, V = c["b"] * c["V"], c["R"], c["V"]
     ld = 9 * V + pad_phi
-    out = {"rays": Guarded(n, R, 12), "coords9": Guarded(n, R, 9), "phi_x": Guarded(c["b"], R, ld)}
+    out = {"rays": Guarded((n, R, 12)), "coords9": Guarded((n, R, 9)), "phi_x": Guarded((c["b"], R, ld))}
     keep = [_d(P32), _d(c["uv"]), _d(c["steps"])]
-    rc = lib.car_ray_setup(_ptr(keep[0]), _ptr(keep[1]), c["b"], V, R, c["H"], c["W"], c["P"], c["no_sample"], _ptr(keep[2]), out["rays"].ptr,
-                           out["coords9"].ptr if coords else None, out["phi_x"].ptr if phi else None, ld, _stream())
+    rc = lib.car_ray_setup(abi.ptr(keep[0]), abi.ptr(keep[1]), c["b"], V, R, c["H"], c["W"], c["P"], c["no_sample"], abi.ptr(keep[2]), out["rays"].ptr,
+                           out["coords9"].ptr if coords else None, out["phi_x"].ptr if phi else None, ld, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return {k: v.get(k) for k, v in out.items()}
@@ -131,17 +72,17 @@ OPTIONAL = ("pixel_val", "pt", "g", "grid_in", "xenc", "pt_in")
 
 def run_samples(c, P32, R32, col=2, tail=3, skip=()):
     """One launch of car_sample_setup; xenc's window starts at column `col` of rows `col + width + tail` wide.  `skip`: outputs given as NULL."""
-    lib = _lib()
+    lib = abi.lib()
     b, V, R, P = c["b"], c["V"], c["R"], c["P"]
     S = b * V * R * P
     width = 6 if V == 1 else 3
     ld = col + width + tail
-    out = {"pixel_val": Guarded(S, 2), "pt": Guarded(S, 3), "g": Guarded(S, 16), "grid_in": Guarded(S, V, 2),
-           "xenc": Guarded(S if V == 1 else S * V, ld), "pt_in": Guarded(S, V, 3)}
+    out = {"pixel_val": Guarded((S, 2)), "pt": Guarded((S, 3)), "g": Guarded((S, 16)), "grid_in": Guarded((S, V, 2)),
+           "xenc": Guarded((S if V == 1 else S * V, ld)), "pt_in": Guarded((S, V, 3))}
     p = {k: (None if k in skip else v.ptr) for k, v in out.items()}
     keep = [_d(P32), _d(R32), _d(c["steps"])]
-    rc = lib.car_sample_setup(_ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), b, V, R, P, c["H"], c["W"], c["no_sample"], p["pixel_val"], p["pt"], p["g"],
-                              p["grid_in"], p["xenc"], ld, col, p["pt_in"], _stream())
+    rc = lib.car_sample_setup(abi.ptr(keep[0]), abi.ptr(keep[1]), abi.ptr(keep[2]), b, V, R, P, c["H"], c["W"], c["no_sample"], p["pixel_val"], p["pt"], p["g"],
+                              p["grid_in"], p["xenc"], ld, col, p["pt_in"], abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     got = {k: v.get(k) for k, v in out.items()}
@@ -211,11 +152,11 @@ def test_ray_kernel_layout(name):
     assert bool(torch.isnan(phi[..., 9 * V:]).all()), "phi_x: padding written"
     for coords, ph in ((False, True), (True, False), (False, False)):
         o2 = run_rays(c, st["P32"], coords=coords, phi=ph)
-        assert torch.equal(_bits(o2["rays"]), _bits(out["rays"]))
-        assert torch.equal(_bits(o2["coords9"]), _bits(out["coords9"])) if coords else bool(torch.isnan(o2["coords9"]).all())
-        assert torch.equal(_bits(o2["phi_x"]), _bits(out["phi_x"])) if ph else bool(torch.isnan(o2["phi_x"]).all())
+        assert torch.equal(abi.bits(o2["rays"]), abi.bits(out["rays"]))
+        assert torch.equal(abi.bits(o2["coords9"]), abi.bits(out["coords9"])) if coords else bool(torch.isnan(o2["coords9"]).all())
+        assert torch.equal(abi.bits(o2["phi_x"]), abi.bits(out["phi_x"])) if ph else bool(torch.isnan(o2["phi_x"]).all())
     tight = run_rays(c, st["P32"], pad_phi=0)
-    assert torch.equal(_bits(tight["phi_x"]), _bits(phi[..., :9 * V]))
+    assert torch.equal(abi.bits(tight["phi_x"]), abi.bits(phi[..., :9 * V]))
 
 
 # ---- 3. samples ----------------------------------------------------------------------------------------------------------------------------
@@ -266,9 +207,9 @@ def test_sample_kernel_null_outputs(name):
             if k == skip:
                 assert bool(torch.isnan(got[k]).all()), f"{k} written though NULL"
             else:
-                assert torch.equal(_bits(got[k]), _bits(full[k])), f"{k} changed when {skip} is NULL"
+                assert torch.equal(abi.bits(got[k]), abi.bits(full[k])), f"{k} changed when {skip} is NULL"
     tight, _ = run_samples(c, st["P32"], st["R32"], col=0, tail=0)
-    assert torch.equal(_bits(tight["xenc"]), _bits(full["xenc"][:, col:col + width]))
+    assert torch.equal(abi.bits(tight["xenc"]), abi.bits(full["xenc"][:, col:col + width]))
 
 
 # ---- 4. car_project_points, car_exchange_rows ---------------------------------------------------------------------------------------------------
@@ -276,13 +217,13 @@ def test_sample_kernel_null_outputs(name):
 def test_project_points_kernel(view):
     """Two scenes whose two views have different intrinsics (fx != fy, the principal point off centre, H != W): points in front of, on
     (z = -1e-12f: zz exactly 0), and behind the camera plane, +-inf and NaN coordinates."""
-    lib = _lib()
+    lib = abi.lib()
     st = GR.stage("wide")
     c, pts = st["c"], GR.project_inputs()
     npts = pts.shape[1]
-    out = Guarded(2, npts, 2)
+    out = Guarded((2, npts, 2))
     keep = [_d(st["P32"]), _d(pts)]
-    rc = lib.car_project_points(_ptr(keep[0]), _ptr(keep[1]), 2, npts, c["V"], view, c["H"], c["W"], out.ptr, _stream())
+    rc = lib.car_project_points(abi.ptr(keep[0]), abi.ptr(keep[1]), 2, npts, c["V"], view, c["H"], c["W"], out.ptr, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     got = out.get("grid")
@@ -298,15 +239,15 @@ def test_project_points_kernel(view):
 def test_exchange_rows_kernel(V):
     """row_src (the view and its 1 << 30 flag) exactly; row_grid bit for bit and against float64 (component 0: the sample's own pixel_val
     bits); row_pe the point encoding's bits with the fourth float 0 whatever ptenc holds there (NaN here)."""
-    lib = _lib()
+    lib = abi.lib()
     st = GR.stage("v3" if V == 3 else "wide")
     c = st["c"]
     pv, pin, pe = GR.exchange_inputs(V)
     pts = pv.shape[0] // (2 * V)
     rows = 2 * V * pts * V
-    src, grid, rpe = Guarded(rows, dtype=torch.int32), Guarded(rows, 2), Guarded(rows, 4)
+    src, grid, rpe = Guarded((rows,), dtype=torch.int32), Guarded((rows, 2)), Guarded((rows, 4))
     keep = [_d(st["P32"]), _d(pv), _d(pin), _d(pe)]
-    rc = lib.car_exchange_rows(*[_ptr(t) for t in keep], 2, V, pts, c["H"], c["W"], src.ptr, grid.ptr, rpe.ptr, _stream())
+    rc = lib.car_exchange_rows(*[abi.ptr(t) for t in keep], 2, V, pts, c["H"], c["W"], src.ptr, grid.ptr, rpe.ptr, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     f32 = GR.exchange_rows(st["P32"], pv, pin, pe, 2, V, pts, c["H"], c["W"], dtype=F32)
@@ -351,8 +292,8 @@ def test_pose_routes_against_the_float64_chain(name):
 
 # ---- 6. refusals: all return before any launch ---------------------------------------------------------------------------------------------------
 def _refused(fn, args, outs):
-    assert fn(*args, _stream()) == CAR_E_ARG, (fn.__name__, args)
-    assert _lib().car_last_error()
+    assert fn(*args, abi.stream()) == CAR_E_ARG, (fn.__name__, args)
+    assert abi.lib().car_last_error()
     torch.cuda.synchronize()
     assert all(g.untouched() for g in outs)
 
@@ -367,10 +308,10 @@ def _edit(args, field, value):
                          ids=str)
 def test_pose_setup_refusals(field, value):
     c = GR.cameras("square")
-    out = Guarded(4, 96)
+    out = Guarded((4, 96))
     keep = {k: _d(c[k]) for k in ("c2w_ctx", "c2w_q", "K_ctx", "K_q")}
-    args = dict({k: _ptr(t) for k, t in keep.items()}, b=2, V=2, H=16, poses=out.ptr)
-    _refused(_lib().car_pose_setup, _edit(args, field, value), [out])
+    args = dict({k: abi.ptr(t) for k, t in keep.items()}, b=2, V=2, H=16, poses=out.ptr)
+    _refused(abi.lib().car_pose_setup, _edit(args, field, value), [out])
 
 
 @pytest.mark.parametrize("field,value", [(k, None) for k in ("poses", "uv", "rays")] +
@@ -379,13 +320,13 @@ def test_ray_setup_refusals(field, value):
     """Null inputs and records; non-positive sizes, V above 3, H or W of 1; no_sample without depth_steps; phi_x with ld_phi below 9 V."""
     st = GR.stage("square")
     c = st["c"]
-    outs = {"rays": Guarded(4, c["R"], 12), "coords9": Guarded(4, c["R"], 9), "phi_x": Guarded(2, c["R"], 18)}
+    outs = {"rays": Guarded((4, c["R"], 12)), "coords9": Guarded((4, c["R"], 9)), "phi_x": Guarded((2, c["R"], 18))}
     keep = [_d(st["P32"]), _d(c["uv"]), _d(c["steps"])]
-    args = dict(poses=_ptr(keep[0]), uv=_ptr(keep[1]), b=2, V=2, R=c["R"], H=16, W=16, P=c["P"], no_sample=0, steps=_ptr(keep[2]), rays=outs["rays"].ptr,
+    args = dict(poses=abi.ptr(keep[0]), uv=abi.ptr(keep[1]), b=2, V=2, R=c["R"], H=16, W=16, P=c["P"], no_sample=0, steps=abi.ptr(keep[2]), rays=outs["rays"].ptr,
                 coords9=outs["coords9"].ptr, phi_x=outs["phi_x"].ptr, ld_phi=18)
     if field == "no_sample+steps":
         args["no_sample"], field = 1, "steps"
-    _refused(_lib().car_ray_setup, _edit(args, field, value), outs.values())
+    _refused(abi.lib().car_ray_setup, _edit(args, field, value), outs.values())
 
 
 @pytest.mark.parametrize("V,field,value", [(2, k, None) for k in ("poses", "rays", "steps")] +
@@ -397,12 +338,12 @@ def test_sample_setup_refusals(V, field, value):
     st = GR.stage("square" if V == 2 else "v1")
     c = st["c"]
     S = c["b"] * V * c["R"] * c["P"]
-    outs = {"pixel_val": Guarded(S, 2), "pt": Guarded(S, 3), "g": Guarded(S, 16), "grid_in": Guarded(S, V, 2), "xenc": Guarded(S * V, 8), "pt_in": Guarded(S, V, 3)}
+    outs = {"pixel_val": Guarded((S, 2)), "pt": Guarded((S, 3)), "g": Guarded((S, 16)), "grid_in": Guarded((S, V, 2)), "xenc": Guarded((S * V, 8)), "pt_in": Guarded((S, V, 3))}
     keep = [_d(st["P32"]), _d(st["R32"]), _d(c["steps"])]
-    args = dict(poses=_ptr(keep[0]), rays=_ptr(keep[1]), steps=_ptr(keep[2]), b=c["b"], V=V, R=c["R"], P=c["P"], H=16, W=16, no_sample=0,
+    args = dict(poses=abi.ptr(keep[0]), rays=abi.ptr(keep[1]), steps=abi.ptr(keep[2]), b=c["b"], V=V, R=c["R"], P=c["P"], H=16, W=16, no_sample=0,
                 pixel_val=outs["pixel_val"].ptr, pt=outs["pt"].ptr, g=outs["g"].ptr, grid_in=outs["grid_in"].ptr, xenc=outs["xenc"].ptr, ld_xenc=8, col_xenc=2,
                 pt_in=outs["pt_in"].ptr)
-    _refused(_lib().car_sample_setup, _edit(args, field, value), outs.values())
+    _refused(abi.lib().car_sample_setup, _edit(args, field, value), outs.values())
 
 
 @pytest.mark.parametrize("field,value", [(k, None) for k in ("poses", "pts", "grid")] +
@@ -410,10 +351,10 @@ def test_sample_setup_refusals(V, field, value):
 def test_project_points_refusals(field, value):
     st = GR.stage("wide")
     pts = GR.project_inputs()
-    out = Guarded(2, pts.shape[1], 2)
+    out = Guarded((2, pts.shape[1], 2))
     keep = [_d(st["P32"]), _d(pts)]
-    args = dict(poses=_ptr(keep[0]), pts=_ptr(keep[1]), n_scenes=2, npts=pts.shape[1], V=2, view=0, H=12, W=20, grid=out.ptr)
-    _refused(_lib().car_project_points, _edit(args, field, value), [out])
+    args = dict(poses=abi.ptr(keep[0]), pts=abi.ptr(keep[1]), n_scenes=2, npts=pts.shape[1], V=2, view=0, H=12, W=20, grid=out.ptr)
+    _refused(abi.lib().car_project_points, _edit(args, field, value), [out])
 
 
 @pytest.mark.parametrize("field,value", [(k, None) for k in ("poses", "pixel_val", "pt_in", "ptenc", "row_src", "row_grid", "row_pe")] +
@@ -423,8 +364,8 @@ def test_exchange_rows_refusals(field, value):
     pv, pin, pe = GR.exchange_inputs(2)
     pts = pv.shape[0] // 4
     rows = 2 * 2 * pts * 2
-    outs = [Guarded(rows, dtype=torch.int32), Guarded(rows, 2), Guarded(rows, 4)]
+    outs = [Guarded((rows,), dtype=torch.int32), Guarded((rows, 2)), Guarded((rows, 4))]
     keep = [_d(st["P32"]), _d(pv), _d(pin), _d(pe)]
-    args = dict(poses=_ptr(keep[0]), pixel_val=_ptr(keep[1]), pt_in=_ptr(keep[2]), ptenc=_ptr(keep[3]), n_scenes=2, V=2, pts=pts, H=12, W=20,
+    args = dict(poses=abi.ptr(keep[0]), pixel_val=abi.ptr(keep[1]), pt_in=abi.ptr(keep[2]), ptenc=abi.ptr(keep[3]), n_scenes=2, V=2, pts=pts, H=12, W=20,
                 row_src=outs[0].ptr, row_grid=outs[1].ptr, row_pe=outs[2].ptr)
-    _refused(_lib().car_exchange_rows, _edit(args, field, value), outs)
+    _refused(abi.lib().car_exchange_rows, _edit(args, field, value), outs)

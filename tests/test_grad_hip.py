@@ -7,24 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+import abi_harness as abi
 import grad_cases as G
 from golden_util import load_case, rel_err
 from hip_harness import build_module, oracle_cfg, to_device
 
 pytestmark = pytest.mark.gpu
-
-
-def _lib():
-    from cross_attention_renderer_amd import _lib as L
-    return L.load()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @pytest.mark.parametrize("name", G.GRAD_CASES)
@@ -79,7 +67,7 @@ def test_training_forward_equals_the_literal_inference_forward(name):
 
 def test_wgrad_kernel_matches_torch():
     """car_linear_wgrad alone: dW += dY^T X, db += sum dY, ragged sizes, strides, the relu-on-load flag and accumulation."""
-    lib, dev = _lib(), torch.device("cuda:0")
+    lib, dev = abi.lib(), torch.device("cuda:0")
     g = torch.Generator().manual_seed(1)
     # (4099, 288, 576), (8221, 576, 579), (5000, 128, 576), (4100, 200, 100): wide layers over >= 4096 rows -> the bf16 x 3 kernel (ragged
     # tiles in both directions, the bias column at 579 = a tile's last live column); the rest: the fp32-pipe kernels
@@ -98,7 +86,7 @@ def test_wgrad_kernel_matches_torch():
         dw = torch.randn(N, K + 5, generator=g).to(dev)
         db = torch.randn(N, generator=g).to(dev)
         dw0, db0 = dw.clone(), db.clone()
-        rc = lib.car_linear_wgrad(_ptr(dy), ldy, _ptr(x), ldx, M, N, K, 1 if relu else 0, _ptr(dw), K + 5, _ptr(db), _stream())
+        rc = lib.car_linear_wgrad(abi.ptr(dy), ldy, abi.ptr(x), ldx, M, N, K, 1 if relu else 0, abi.ptr(dw), K + 5, abi.ptr(db), abi.stream())
         assert rc == 0, lib.car_last_error()
         torch.cuda.synchronize()
         xs = (x[:, :K].clamp_min(0) if relu else x[:, :K]).double()
@@ -110,7 +98,7 @@ def test_wgrad_kernel_matches_torch():
         assert (db.double() - want_b).abs().max().item() <= 2e-5 * want_b.abs().max().item(), (M, N, K)
         # the same product kept on the fp32 matrix pipe (CAR_WGRAD_FP32 = 16): the two kernels agree to the same bound
         dw2, db2 = dw0.clone(), db0.clone()
-        assert lib.car_linear_wgrad(_ptr(dy), ldy, _ptr(x), ldx, M, N, K, (1 if relu else 0) | 16, _ptr(dw2), K + 5, _ptr(db2), _stream()) == 0
+        assert lib.car_linear_wgrad(abi.ptr(dy), ldy, abi.ptr(x), ldx, M, N, K, (1 if relu else 0) | 16, abi.ptr(dw2), K + 5, abi.ptr(db2), abi.stream()) == 0
         torch.cuda.synchronize()
         assert (dw2[:, :K].double() - want_w).abs().max().item() <= 2e-5 * scale, (M, N, K, "fp32 pipe")
         assert (dw2 - dw).abs().max().item() <= 2e-5 * scale
@@ -119,14 +107,14 @@ def test_wgrad_kernel_matches_torch():
 def test_wgrad_bf16_split_keeps_small_and_large_rows():
     """The bf16 x 3 weight-gradient kernel on operands whose rows span twelve orders of magnitude (bf16 keeps fp32's exponent: no scale is
     chosen anywhere) and on columns that cancel: the error stays rounding-like — 2e-5 of sum |dY||X| per entry against fp64."""
-    lib, dev = _lib(), torch.device("cuda:0")
+    lib, dev = abi.lib(), torch.device("cuda:0")
     g = torch.Generator().manual_seed(7)
     M, N, K = 6000, 288, 576
     dy = (torch.randn(M, N, generator=g) * torch.logspace(-8, 4, M).unsqueeze(1)).to(dev)
     x = (torch.randn(M, K, generator=g) * torch.logspace(3, -6, M).unsqueeze(1)).to(dev)
     x[:, :8] = 1.0                                                      # constant columns: entries that are sums with little cancellation
     dw = torch.zeros(N, K, device=dev)
-    assert lib.car_linear_wgrad(_ptr(dy), N, _ptr(x), K, M, N, K, 0, _ptr(dw), K, None, _stream()) == 0, lib.car_last_error()
+    assert lib.car_linear_wgrad(abi.ptr(dy), N, abi.ptr(x), K, M, N, K, 0, abi.ptr(dw), K, None, abi.stream()) == 0, lib.car_last_error()
     torch.cuda.synchronize()
     want = dy.double().t() @ x.double()
     bound = dy.double().abs().t() @ x.double().abs()
@@ -138,7 +126,7 @@ def test_gather_backward_is_the_adjoint_of_the_gather():
     """<gather(maps), dout> == <maps, gather_backward(dout)> for both padding modes and every placement (the adjoint identity of a
     linear map), with coordinates inside, on the edge of and far outside the maps."""
     from cross_attention_renderer_amd.engine import PLACE_OTHER2, PLACE_OWN, PLACE_PLAIN
-    lib, dev = _lib(), torch.device("cuda:0")
+    lib, dev = abi.lib(), torch.device("cuda:0")
     g = torch.Generator().manual_seed(2)
     n_maps, pts, V = 4, 300, 2
     maps = [torch.randn(n_maps, h, h, cch, generator=g).to(dev) for h, cch in ((5, 8), (9, 12), (17, 4))]
@@ -155,11 +143,11 @@ def test_gather_backward_is_the_adjoint_of_the_gather():
         for place, rows, ld in ((PLACE_PLAIN, n_maps * pts, C + 4), (PLACE_OWN, n_maps * pts * V, C + 8), (PLACE_OTHER2, n_maps * pts * V, C)):
             out = torch.zeros(rows, ld, device=dev)
             ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in maps])
-            assert lib.car_gather_bilinear(ptrs, cs, hs, ws, L, n_maps, _ptr(grid), pts, 1, mode, place, V, _ptr(out), ld, 0, _stream()) == 0
+            assert lib.car_gather_bilinear(ptrs, cs, hs, ws, L, n_maps, abi.ptr(grid), pts, 1, mode, place, V, abi.ptr(out), ld, 0, abi.stream()) == 0
             dout = torch.randn(rows, ld, generator=g).to(dev)
             dmaps = [torch.zeros_like(t) for t in maps]
             dptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in dmaps])
-            rc = lib.car_gather_bilinear_backward(dptrs, cs, hs, ws, L, n_maps, _ptr(grid), pts, mode, place, V, _ptr(dout), ld, 0, _stream())
+            rc = lib.car_gather_bilinear_backward(dptrs, cs, hs, ws, L, n_maps, abi.ptr(grid), pts, mode, place, V, abi.ptr(dout), ld, 0, abi.stream())
             assert rc == 0, lib.car_last_error()
             torch.cuda.synchronize()
             lhs = (out[:, :C].double() * dout[:, :C].double()).sum().item()
@@ -173,7 +161,7 @@ def test_binned_scatter_equals_the_atomic_scatter():
     one dout; coordinates inside, on the edge of and far outside the maps, points piled on one texel; channel counts of 1, 3 and 64 float4s
     per texel; maps the binned form must overwrite (NaN before the call)."""
     from cross_attention_renderer_amd.engine import PLACE_OTHER2, PLACE_OWN, PLACE_PLAIN
-    lib, dev = _lib(), torch.device("cuda:0")
+    lib, dev = abi.lib(), torch.device("cuda:0")
     g = torch.Generator().manual_seed(5)
     for (n_maps, pts, V, shapes) in ((4, 300, 2, ((5, 8), (9, 12), (17, 4))), (2, 5000, 2, ((32, 256), (16, 256), (64, 64))), (3, 77, 1, ((7, 4),))):
         maps = [torch.randn(n_maps, h, h + 1, cch, generator=g).to(dev) for h, cch in shapes]
@@ -199,7 +187,7 @@ def test_binned_scatter_equals_the_atomic_scatter():
             want = [torch.zeros_like(t) for t in maps]
             dptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in want])
             for grid, mode, place in gathers:
-                assert lib.car_gather_bilinear_backward(dptrs, cs, hs, ws, L, n_maps, _ptr(grid), pts, mode, place, V, _ptr(dout), ld, 4, _stream()) == 0
+                assert lib.car_gather_bilinear_backward(dptrs, cs, hs, ws, L, n_maps, abi.ptr(grid), pts, mode, place, V, abi.ptr(dout), ld, 4, abi.stream()) == 0
             got = [torch.full_like(t, float("nan")) for t in maps]
             gptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in got])
             G = len(gathers)
@@ -209,15 +197,15 @@ def test_binned_scatter_equals_the_atomic_scatter():
             nbytes = lib.car_scatter_workspace_bytes(hs, ws, L, n_maps, pts, G)
             assert nbytes > 0
             work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            rc = lib.car_gather_bilinear_backward_binned(gptrs, cs, hs, ws, L, n_maps, gr, mo, pl, G, pts, V, _ptr(dout), ld, 4, _ptr(work), nbytes, _stream())
+            rc = lib.car_gather_bilinear_backward_binned(gptrs, cs, hs, ws, L, n_maps, gr, mo, pl, G, pts, V, abi.ptr(dout), ld, 4, abi.ptr(work), nbytes, abi.stream())
             assert rc == 0, lib.car_last_error()
             torch.cuda.synchronize()
             for a, b_ in zip(got, want):
                 assert torch.isfinite(a).all()
                 assert (a - b_).abs().max().item() <= 2e-5 * max(1.0, b_.abs().max().item()), (n_maps, pts, len(gathers))
             # a workspace one byte short is refused
-            assert lib.car_gather_bilinear_backward_binned(gptrs, cs, hs, ws, L, n_maps, gr, mo, pl, G, pts, V, _ptr(dout), ld, 4, _ptr(work), nbytes - 1,
-                                                           _stream()) != 0
+            assert lib.car_gather_bilinear_backward_binned(gptrs, cs, hs, ws, L, n_maps, gr, mo, pl, G, pts, V, abi.ptr(dout), ld, 4, abi.ptr(work), nbytes - 1,
+                                                           abi.stream()) != 0
 
 
 def test_a_gradient_step_lowers_the_image_loss_by_the_predicted_amount():

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_harness as abi
 import cases as C
 from golden_util import load_case, rel_err
 from hip_harness import argmax_exact_where_decided, build_module, err_stats, oracle_cfg, run_case, to_device
@@ -35,15 +36,6 @@ DEVICE_POSE_MAX = 2e-2
 HIP_CASES = list(C.CASES)
 
 
-def _lib():
-    from cross_attention_renderer_amd import _lib
-    return _lib.load()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 # ----------------------------------------------------------------------------------------------------------
 # the MFMA linear kernel against torch (fp64 reference of the same op)
 # ----------------------------------------------------------------------------------------------------------
@@ -55,7 +47,7 @@ def _ptr(t):
 @pytest.mark.parametrize("no_glds", [0, 8])
 def test_linear_matches_torch(M, K, N, flags, no_glds):
     from cross_attention_renderer_amd.engine import PackedLinear
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(M * 7 + K * 3 + N)
     ldx = (K + 3) // 4 * 4 + 4
@@ -70,11 +62,11 @@ def test_linear_matches_torch(M, K, N, flags, no_glds):
     Xd, Yd = X.to(dev), Y0.clone().to(dev)
     layer = PackedLinear(Wt, bias, dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rc = lib.car_linear(_ptr(Xd), ldx, _ptr(layer.packed), K, N, _ptr(Yd), ldy, M, flags | no_glds, st)
+    rc = lib.car_linear(abi.ptr(Xd), ldx, abi.ptr(layer.packed), K, N, abi.ptr(Yd), ldy, M, flags | no_glds, st)
     assert rc == 0, lib.car_last_error()
     # accumulate variant on top
     Ya = Y0.clone().to(dev)
-    rc = lib.car_linear(_ptr(Xd), ldx, _ptr(layer.packed), K, N, _ptr(Ya), ldy, M, (flags & 1) | 4 | no_glds, st)
+    rc = lib.car_linear(abi.ptr(Xd), ldx, abi.ptr(layer.packed), K, N, abi.ptr(Ya), ldy, M, (flags & 1) | 4 | no_glds, st)
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     got = Yd.cpu()
@@ -92,7 +84,7 @@ def test_split_fp16_linear_matches_torch(M, K, N, flags):
     """car_linear_x3: the stage entries' wide layers on the f16 matrix pipe (fp16 hi / lo halves, three products, fp32 accumulate, a power of
     two per row and per layer) against an fp64 reference — the same bound as the fp32-pipe kernel — with rows of very different magnitudes."""
     from cross_attention_renderer_amd.engine import PackedLinear
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(M * 7 + K * 3 + N)
     ldx = (K + 3) // 4 * 4 + 4
@@ -114,8 +106,8 @@ def test_split_fp16_linear_matches_torch(M, K, N, flags):
     tiles, bdev = layer.x3
     Xd, Yd, Ya = X.to(dev), Y0.clone().to(dev), Y0.clone().to(dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert lib.car_linear_x3(_ptr(Xd), ldx, _ptr(tiles), _ptr(bdev), K, N, _ptr(Yd), ldy, M, flags, st) == 0, lib.car_last_error()
-    assert lib.car_linear_x3(_ptr(Xd), ldx, _ptr(tiles), _ptr(bdev), K, N, _ptr(Ya), ldy, M, (flags & 1) | 4, st) == 0
+    assert lib.car_linear_x3(abi.ptr(Xd), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N, abi.ptr(Yd), ldy, M, flags, st) == 0, lib.car_last_error()
+    assert lib.car_linear_x3(abi.ptr(Xd), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N, abi.ptr(Ya), ldy, M, (flags & 1) | 4, st) == 0
     torch.cuda.synchronize()
     got = Yd.cpu()
     # per row: the error is relative to the row's own scale (|x| |W| summed), whatever the row's magnitude
@@ -125,7 +117,7 @@ def test_split_fp16_linear_matches_torch(M, K, N, flags):
     want_acc = Y0[:, :N].double() + xin @ Wt.double().T + bias.double()
     assert ((Ya.cpu()[:, :N].double() - want_acc).abs() / (bound + Y0[:, :N].double().abs())).max().item() < 4e-6
     # shapes the entry refuses (car_linear serves them)
-    assert lib.car_linear_x3(_ptr(Xd), ldx, _ptr(tiles), _ptr(bdev), K, N - 1, _ptr(Yd), ldy, M, 0, st) != 0
+    assert lib.car_linear_x3(abi.ptr(Xd), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N - 1, abi.ptr(Yd), ldy, M, 0, st) != 0
 
 
 @pytest.mark.parametrize("M,K,N,flags", [(4100, 288, 576, 0), (1000, 128, 128, 4), (333, 576, 64, 0), (777, 64, 32, 2)])
@@ -133,7 +125,7 @@ def test_split_fp16_linear_with_the_relu_mask_applied_as_it_writes(M, K, N, flag
     """car_linear_x3_masked = car_linear_x3 followed by car_relu_mask, bit for bit (the backward's data gradient of a layer behind a ReLU),
     for every tile count of the kernel, with ACCUM and RELU_OUT, a strided activation, and -0.0 / NaN activations (not > 0: zeroed)."""
     from cross_attention_renderer_amd.engine import PackedLinear
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(M + K + N)
     ldx, ldy, lda = (K + 3) // 4 * 4, N + 4, N + 8
@@ -147,16 +139,16 @@ def test_split_fp16_linear_with_the_relu_mask_applied_as_it_writes(M, K, N, flag
     tiles, bdev = layer.x3
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     want, got = Y0.clone(), Y0.clone()
-    assert lib.car_linear_x3(_ptr(X), ldx, _ptr(tiles), _ptr(bdev), K, N, _ptr(want), ldy, M, flags, st) == 0, lib.car_last_error()
-    assert lib.car_relu_mask(_ptr(want), ldy, _ptr(act), lda, M, N, st) == 0
-    assert lib.car_linear_x3_masked(_ptr(X), ldx, _ptr(tiles), _ptr(bdev), K, N, _ptr(got), ldy, M, flags, _ptr(act), lda, st) == 0, lib.car_last_error()
+    assert lib.car_linear_x3(abi.ptr(X), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N, abi.ptr(want), ldy, M, flags, st) == 0, lib.car_last_error()
+    assert lib.car_relu_mask(abi.ptr(want), ldy, abi.ptr(act), lda, M, N, st) == 0
+    assert lib.car_linear_x3_masked(abi.ptr(X), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N, abi.ptr(got), ldy, M, flags, abi.ptr(act), lda, st) == 0, lib.car_last_error()
     torch.cuda.synchronize()
     assert torch.equal(got, want)
     assert (got[:, :N] == 0).float().mean().item() > 0.4                                   # the mask did something
     # refused: no activation, a row stride that does not hold a row or is not a multiple of 4
-    assert lib.car_linear_x3_masked(_ptr(X), ldx, _ptr(tiles), _ptr(bdev), K, N, _ptr(got), ldy, M, flags, None, lda, st) != 0
-    assert lib.car_linear_x3_masked(_ptr(X), ldx, _ptr(tiles), _ptr(bdev), K, N, _ptr(got), ldy, M, flags, _ptr(act), N - 4, st) != 0
-    assert lib.car_linear_x3_masked(_ptr(X), ldx, _ptr(tiles), _ptr(bdev), K, N, _ptr(got), ldy, M, flags, _ptr(act), N + 2, st) != 0
+    assert lib.car_linear_x3_masked(abi.ptr(X), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N, abi.ptr(got), ldy, M, flags, None, lda, st) != 0
+    assert lib.car_linear_x3_masked(abi.ptr(X), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N, abi.ptr(got), ldy, M, flags, abi.ptr(act), N - 4, st) != 0
+    assert lib.car_linear_x3_masked(abi.ptr(X), ldx, abi.ptr(tiles), abi.ptr(bdev), K, N, abi.ptr(got), ldy, M, flags, abi.ptr(act), N + 2, st) != 0
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -179,7 +171,7 @@ def test_gather_matches_grid_sample(chans):
     class Dummy:
         pass
     eng = RenderEngine.__new__(RenderEngine)
-    eng.lib = _lib()
+    eng.lib = abi.lib()
     maps = [t.permute(0, 2, 3, 1).contiguous().to(dev) for t in z]
     Ct = sum(chans)
     ld = Ct + 8
@@ -495,7 +487,7 @@ def test_first_round_partial_sums_equal_the_row_reduction(R, P, b):
         md = m.to(dev)
         out = md(to_device(inp, dev, cameras_on_host=True), z=[t.to(dev) for t in z], debug=True)
     torch.cuda.synchronize()
-    eng, lib = md._engine, _lib()
+    eng, lib = md._engine, abi.lib()
     assert eng.last_calls == 1
     d = eng._dims(b, R, [t.to(dev) for t in z])
     V, n = 2, 2 * b
@@ -516,11 +508,11 @@ def test_first_round_partial_sums_equal_the_row_reduction(R, P, b):
         depth = torch.empty(b, R, device=dev)
         amax = torch.empty(n, R, dtype=torch.int32, device=dev)
         if parts:
-            L.check(lib.car_attend_parts(_ptr(logit), _ptr(part), ts, 576, b, V, R, P, _ptr(w), _ptr(zz), 576, 1, _ptr(pt), _ptr(poses),
-                                         _ptr(depth), _ptr(amax), st), "car_attend_parts")
+            L.check(lib.car_attend_parts(abi.ptr(logit), abi.ptr(part), ts, 576, b, V, R, P, abi.ptr(w), abi.ptr(zz), 576, 1, abi.ptr(pt), abi.ptr(poses),
+                                         abi.ptr(depth), abi.ptr(amax), st), "car_attend_parts")
         else:
-            L.check(lib.car_attend(_ptr(logit), None, 128, _ptr(e), 576, b, V, R, P, None, 0.0, _ptr(w), _ptr(zz), 576, 1, _ptr(pt),
-                                   _ptr(poses), _ptr(depth), _ptr(amax), st), "car_attend")
+            L.check(lib.car_attend(abi.ptr(logit), None, 128, abi.ptr(e), 576, b, V, R, P, None, 0.0, abi.ptr(w), abi.ptr(zz), 576, 1, abi.ptr(pt),
+                                   abi.ptr(poses), abi.ptr(depth), abi.ptr(amax), st), "car_attend")
         torch.cuda.synchronize()
         res.append((w, zz, depth, amax))
     (w0, z0, d0, a0), (w1, z1, d1, a1) = res
@@ -606,7 +598,6 @@ def test_two_phase_entry_on_two_streams_equals_the_one_call():
     one behind an event, each batch in its own workspace — bit-identical to car_render_forward on the whole set of rays."""
     import ctypes
     from cross_attention_renderer_amd import _lib, synthetic as S
-    from cross_attention_renderer_amd.engine import _ptr
     from cross_attention_renderer_amd.models import CrossAttentionRenderer
     dev = torch.device("cuda:0")
     H, P, R, nb = 64, 32, 192, 2
@@ -648,7 +639,7 @@ def test_two_phase_entry_on_two_streams_equals_the_one_call():
         for phase, stream in ((1, sa), (2, sb)):
             if phase == 2:
                 sb.wait_event(ev)
-            _lib.check(lib.car_render_forward_phase(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co), _ptr(work), need, phase,
+            _lib.check(lib.car_render_forward_phase(ctypes.byref(d), abi.ptr(plan), ctypes.byref(ci), ctypes.byref(co), abi.ptr(work), need, phase,
                                                     ctypes.c_void_p(stream.cuda_stream)), "car_render_forward_phase")
             if phase == 1:
                 ev.record(sa)
@@ -658,7 +649,7 @@ def test_two_phase_entry_on_two_streams_equals_the_one_call():
     assert torch.equal(torch.cat([o["rgb"] for o in outs], dim=2), ref["rgb"])
     for k in ("depth_ray", "at_wt", "valid_mask"):
         assert torch.equal(torch.cat([o[k] for o in outs], dim=1), ref[k]), k
-    assert lib.car_render_forward_phase(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co), _ptr(work), need, 4, None) != 0
+    assert lib.car_render_forward_phase(ctypes.byref(d), abi.ptr(plan), ctypes.byref(ci), ctypes.byref(co), abi.ptr(work), need, 4, None) != 0
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -754,14 +745,14 @@ def test_all_zero_layers_and_dead_relu_rows_stay_finite(route):
 # a3 on the device: car_pose_setup (fp64 Gauss-Jordan) against the host pose algebra (torch.inverse, the reference's call)
 # ----------------------------------------------------------------------------------------------------------
 def _device_poses(inp, H):
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     ctx, q = inp["context"], inp["query"]
     b, V = ctx["cam2world"].shape[:2]
     t = [x.float().contiguous().to(dev) for x in (ctx["cam2world"], q["cam2world"][:, 0], ctx["intrinsics"], q["intrinsics"][:, 0])]
     poses = torch.empty(b * V, 96, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rc = lib.car_pose_setup(_ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _ptr(t[3]), b, V, H, _ptr(poses), st)
+    rc = lib.car_pose_setup(abi.ptr(t[0]), abi.ptr(t[1]), abi.ptr(t[2]), abi.ptr(t[3]), b, V, H, abi.ptr(poses), st)
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return poses.cpu()
@@ -818,7 +809,7 @@ def test_merged_lattice_kernel_matches_grid_sample(sizes):
     wide for the tables (840-texel rows: the kernel's table-free form)."""
     import torch.nn.functional as F
     from cross_attention_renderer_amd import _lib as L
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     n_maps, C = (3 if max(w for _, w in sizes) < 200 else 2), 576
     g = torch.Generator().manual_seed(5)
@@ -831,7 +822,7 @@ def test_merged_lattice_kernel_matches_grid_sample(sizes):
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     L.check(lib.car_merge_lattice(ptrs, hs, wsz, nl, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(pad), st), "shape")
     lat = torch.full((n_maps, 2, lh.value, lw.value, C), float("nan"), device=dev)
-    L.check(lib.car_merge_lattice(ptrs, hs, wsz, nl, n_maps, _ptr(lat), None, None, None, st), "car_merge_lattice")
+    L.check(lib.car_merge_lattice(ptrs, hs, wsz, nl, n_maps, abi.ptr(lat), None, None, None, st), "car_merge_lattice")
     torch.cuda.synchronize()
     hm, wm = max(h for h, _ in sizes), max(w for _, w in sizes)
     uy = torch.arange(lh.value, device=dev, dtype=torch.float64) - pad.value
@@ -853,7 +844,7 @@ def test_fused_exchange_layers_equal_the_two_launches(rows, N):
     """car_lattice_encode_linear (the gather-fed instance of csrc/car_linear16.hip) against car_lattice_encode_rows followed by car_linear_x3
     on the same rows: bit-identical — border and zeros rows, points on / beyond the lattice's outer ring, several maps, ragged row counts."""
     from cross_attention_renderer_amd import _lib as L
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(rows + N)
     n_maps, C = 3, 576
@@ -866,7 +857,7 @@ def test_fused_exchange_layers_equal_the_two_launches(rows, N):
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     L.check(lib.car_merge_lattice(ptrs, hs, wsz, 3, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(pad), st), "shape")
     lat = torch.empty(n_maps, 2, lh.value, lw.value, C, device=dev)
-    L.check(lib.car_merge_lattice(ptrs, hs, wsz, 3, n_maps, _ptr(lat), None, None, None, st), "car_merge_lattice")
+    L.check(lib.car_merge_lattice(ptrs, hs, wsz, 3, n_maps, abi.ptr(lat), None, None, None, st), "car_merge_lattice")
     src = (torch.randint(0, n_maps, (rows,), generator=g) | (torch.randint(0, 2, (rows,), generator=g) << 30)).to(torch.int32).to(dev)
     grid = (torch.rand(rows, 2, generator=g) * 2.8 - 1.4)
     grid[0] = torch.tensor([1e10, -1e10]); grid[1] = torch.tensor([-1.0, 1.0]); grid[2] = torch.tensor([1.0, 1.0]); grid[3] = torch.tensor([float("nan"), 0.0])
@@ -876,16 +867,16 @@ def test_fused_exchange_layers_equal_the_two_launches(rows, N):
     W = (torch.randn(N, C, generator=g) / C ** 0.5).to(dev)
     bias = torch.randn(N, generator=g).to(dev)
     tiles = torch.empty(lib.car_linear_x3_packed_floats(C, N), device=dev)
-    L.check(lib.car_linear_x3_pack(_ptr(W), C, C, N, _ptr(tiles), st), "pack")
+    L.check(lib.car_linear_x3_pack(abi.ptr(W), C, C, N, abi.ptr(tiles), st), "pack")
     h1 = torch.empty(rows, C, device=dev)
-    L.check(lib.car_lattice_encode_rows(_ptr(lat), lh.value, lw.value, pad.value, C, _ptr(src), _ptr(grid), _ptr(pe), _ptr(wpt), n_maps, rows, _ptr(h1), C, st),
+    L.check(lib.car_lattice_encode_rows(abi.ptr(lat), lh.value, lw.value, pad.value, C, abi.ptr(src), abi.ptr(grid), abi.ptr(pe), abi.ptr(wpt), n_maps, rows, abi.ptr(h1), C, st),
             "car_lattice_encode_rows")
     for flags in (0, 2):
         want = torch.empty(rows, N, device=dev)
-        L.check(lib.car_linear_x3(_ptr(h1), C, _ptr(tiles), _ptr(bias), C, N, _ptr(want), N, rows, flags, st), "car_linear_x3")
+        L.check(lib.car_linear_x3(abi.ptr(h1), C, abi.ptr(tiles), abi.ptr(bias), C, N, abi.ptr(want), N, rows, flags, st), "car_linear_x3")
         got = torch.full((rows, N), float("nan"), device=dev)
-        L.check(lib.car_lattice_encode_linear(_ptr(lat), lh.value, lw.value, pad.value, _ptr(src), _ptr(grid), _ptr(pe), _ptr(wpt), n_maps, rows, _ptr(tiles),
-                                              _ptr(bias), C, N, _ptr(got), N, flags, st), "car_lattice_encode_linear")
+        L.check(lib.car_lattice_encode_linear(abi.ptr(lat), lh.value, lw.value, pad.value, abi.ptr(src), abi.ptr(grid), abi.ptr(pe), abi.ptr(wpt), n_maps, rows, abi.ptr(tiles),
+                                              abi.ptr(bias), C, N, abi.ptr(got), N, flags, st), "car_lattice_encode_linear")
         torch.cuda.synchronize()
         assert torch.isfinite(want).all()
         assert torch.equal(got, want), (flags, (got - want).abs().max().item())
@@ -897,7 +888,7 @@ def test_fused_rows_kernel_matches_the_two_exchange_layers(R, P, nsets):
     and step counts) against car_lattice_encode_rows + car_linear_x3 on the same rows — the split-fp16 first layer with one power of two per
     launch against the fp32 gather: fp32 class, 5e-5 of the row's scale like the two-view routes' A/B."""
     from cross_attention_renderer_amd import _lib as L
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(R + P)
     n_maps, C, ncomp = 3, 576, 3
@@ -910,7 +901,7 @@ def test_fused_rows_kernel_matches_the_two_exchange_layers(R, P, nsets):
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     L.check(lib.car_merge_lattice(ptrs, hs, wsz, 3, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(pad), st), "shape")
     lat = torch.empty(n_maps, 2, lh.value, lw.value, C, device=dev)
-    L.check(lib.car_merge_lattice(ptrs, hs, wsz, 3, n_maps, _ptr(lat), None, None, None, st), "car_merge_lattice")
+    L.check(lib.car_merge_lattice(ptrs, hs, wsz, 3, n_maps, abi.ptr(lat), None, None, None, st), "car_merge_lattice")
     S = nsets * R * P
     rows = S * ncomp
     # one (map, padding mode) per (set, component), as the exchange's row list has it
@@ -930,20 +921,20 @@ def test_fused_rows_kernel_matches_the_two_exchange_layers(R, P, nsets):
     w1d, b1d, w2d, b2d = [t.to(dev).contiguous() for t in (w1, b1, w2, b2)]
     wpt = torch.cat([w1[:, C:], b1[:, None]], dim=1).contiguous().to(dev)
     tiles = torch.empty(lib.car_linear_x3_packed_floats(C, C // 2), device=dev)
-    L.check(lib.car_linear_x3_pack(_ptr(w2d), C, C, C // 2, _ptr(tiles), st), "pack")
+    L.check(lib.car_linear_x3_pack(abi.ptr(w2d), C, C, C // 2, abi.ptr(tiles), st), "pack")
     h1 = torch.empty(rows, C, device=dev)
-    L.check(lib.car_lattice_encode_rows(_ptr(lat), lh.value, lw.value, pad.value, C, _ptr(src), _ptr(grid), _ptr(pe), _ptr(wpt), n_maps, rows, _ptr(h1), C, st),
+    L.check(lib.car_lattice_encode_rows(abi.ptr(lat), lh.value, lw.value, pad.value, C, abi.ptr(src), abi.ptr(grid), abi.ptr(pe), abi.ptr(wpt), n_maps, rows, abi.ptr(h1), C, st),
             "car_lattice_encode_rows")
     want = torch.empty(rows, C // 2, device=dev)
-    L.check(lib.car_linear_x3(_ptr(h1), C, _ptr(tiles), _ptr(b2d), C, C // 2, _ptr(want), C // 2, rows, 0, st), "car_linear_x3")
+    L.check(lib.car_linear_x3(abi.ptr(h1), C, abi.ptr(tiles), abi.ptr(b2d), C, C // 2, abi.ptr(want), C // 2, rows, 0, st), "car_linear_x3")
     blob = torch.zeros(lib.car_fused_blob_floats(), device=dev)
     fb = torch.empty(lib.car_fused_bias_floats(), device=dev)
     fwpt = torch.empty(C * 4, device=dev)
-    L.check(lib.car_fused_pack_rows(_ptr(w1d), _ptr(b1d), _ptr(w2d), _ptr(b2d), _ptr(blob), _ptr(fb), _ptr(fwpt), st), "car_fused_pack_rows")
+    L.check(lib.car_fused_pack_rows(abi.ptr(w1d), abi.ptr(b1d), abi.ptr(w2d), abi.ptr(b2d), abi.ptr(blob), abi.ptr(fb), abi.ptr(fwpt), st), "car_fused_pack_rows")
     gmeta = lat.abs().max().reshape(1).contiguous()
     got = torch.full((rows, C // 2), float("nan"), device=dev)
-    L.check(lib.car_fused_rows(_ptr(lat), lh.value, lw.value, pad.value, _ptr(gmeta), _ptr(fwpt), _ptr(blob), _ptr(fb), _ptr(src), _ptr(grid), _ptr(pe),
-                               nsets, R, P, ncomp, _ptr(got), st), "car_fused_rows")
+    L.check(lib.car_fused_rows(abi.ptr(lat), lh.value, lw.value, pad.value, abi.ptr(gmeta), abi.ptr(fwpt), abi.ptr(blob), abi.ptr(fb), abi.ptr(src), abi.ptr(grid), abi.ptr(pe),
+                               nsets, R, P, ncomp, abi.ptr(got), st), "car_fused_rows")
     torch.cuda.synchronize()
     assert torch.equal(fwpt.view(C, 4), wpt)
     assert torch.isfinite(got).all() and torch.isfinite(want).all()
@@ -955,7 +946,7 @@ def test_exchange_row_lists_match_their_definition():
     """car_exchange_rows against the row lists written out with torch indexing and car_project_points (the form engine._encode_three_views
     used to build them in, ~40 launches): bit-identical."""
     from cross_attention_renderer_amd import _lib as L
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(3)
     b, V, pts, H = 2, 3, 500, 64
@@ -980,7 +971,7 @@ def test_exchange_row_lists_match_their_definition():
             if o == c:
                 continue
             q = pin[:, o, :, c, :].contiguous()
-            L.check(lib.car_project_points(_ptr(poses), _ptr(q), b, pts, V, o, H, H, _ptr(grid), st), "car_project_points")
+            L.check(lib.car_project_points(abi.ptr(poses), abi.ptr(q), b, pts, V, o, H, H, abi.ptr(grid), st), "car_project_points")
             src[:, c, :, k] = (sc * V + o) | (1 << 30)
             rgrid[:, c, :, k] = grid
             rpe[:, c, :, k, :3] = pe[:, o, :, c, :3]
@@ -988,7 +979,7 @@ def test_exchange_row_lists_match_their_definition():
     s2 = torch.empty_like(src)
     g2 = torch.full_like(rgrid, float("nan"))
     p2 = torch.full_like(rpe, float("nan"))
-    L.check(lib.car_exchange_rows(_ptr(poses), _ptr(pixel_val), _ptr(pt_in), _ptr(ptenc), b, V, pts, H, H, _ptr(s2), _ptr(g2), _ptr(p2), st), "car_exchange_rows")
+    L.check(lib.car_exchange_rows(abi.ptr(poses), abi.ptr(pixel_val), abi.ptr(pt_in), abi.ptr(ptenc), b, V, pts, H, H, abi.ptr(s2), abi.ptr(g2), abi.ptr(p2), st), "car_exchange_rows")
     torch.cuda.synchronize()
     assert torch.equal(s2, src) and torch.equal(p2, rpe)
     assert torch.equal(torch.nan_to_num(g2, nan=7.0), torch.nan_to_num(rgrid, nan=7.0))
@@ -1021,7 +1012,7 @@ def test_key_query_chain_kernel_matches_the_separate_layers(M, Ce):
     fp64 matmuls of the same layers: qry and the logits at the fp32-class bound of the split-fp16 layers, ragged row counts, the widths of
     the one-, two- and three-view routes."""
     from cross_attention_renderer_amd import _lib as L
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     g_ = torch.Generator().manual_seed(M + Ce)
     rnd = lambda *sh: torch.randn(*sh, generator=g_)
@@ -1033,13 +1024,13 @@ def test_key_query_chain_kernel_matches_the_separate_layers(M, Ce):
     q2w, q2b = (rnd(128, 128) / 128 ** 0.5).to(dev), rnd(128).to(dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     tiles = torch.empty(lib.car_linear_x3_packed_floats(Ce, 128), device=dev)
-    L.check(lib.car_linear_x3_pack(_ptr(k1w), Ce, Ce, 128, _ptr(tiles), st), "pack")
+    L.check(lib.car_linear_x3_pack(abi.ptr(k1w), Ce, Ce, 128, abi.ptr(tiles), st), "pack")
     tail = torch.empty(lib.car_kq_tail_floats(), device=dev)
     tb = torch.empty(lib.car_kq_bias_floats(), device=dev)
-    L.check(lib.car_kq_pack(_ptr(k2w), _ptr(k2b), _ptr(q1w), _ptr(q1b), _ptr(q2w), _ptr(q2b), _ptr(tail), _ptr(tb), st), "car_kq_pack")
+    L.check(lib.car_kq_pack(abi.ptr(k2w), abi.ptr(k2b), abi.ptr(q1w), abi.ptr(q1b), abi.ptr(q2w), abi.ptr(q2b), abi.ptr(tail), abi.ptr(tb), st), "car_kq_pack")
     qry = torch.full((M, 128), float("nan"), device=dev)
     logit = torch.full((M,), float("nan"), device=dev)
-    L.check(lib.car_key_query_logits(_ptr(e), Ce, _ptr(tiles), _ptr(k1b), Ce, _ptr(gq), _ptr(tail), _ptr(tb), M, _ptr(qry), _ptr(logit), st),
+    L.check(lib.car_key_query_logits(abi.ptr(e), Ce, abi.ptr(tiles), abi.ptr(k1b), Ce, abi.ptr(gq), abi.ptr(tail), abi.ptr(tb), M, abi.ptr(qry), abi.ptr(logit), st),
             "car_key_query_logits")
     torch.cuda.synchronize()
     d = lambda t: t.double()
@@ -1061,7 +1052,7 @@ def test_second_round_bilinear_form_matches_the_two_layers(b, R, P, wscale):
     fp64 matmuls of the four separate layers (models.py:529, 549-556) and against car_round2_logits fed the fp64-made query rows; ragged sizes,
     weights of very different magnitude."""
     from cross_attention_renderer_amd import _lib as L
-    lib = _lib()
+    lib = abi.lib()
     dev = torch.device("cuda:0")
     V = 2
     S = b * V * R * P
@@ -1075,9 +1066,9 @@ def test_second_round_bilinear_form_matches_the_two_layers(b, R, P, wscale):
     wq2, bq2 = (rnd(128, 128) / 128 ** 0.5 / wscale).to(dev), rnd(128).to(dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     wp, bp = torch.empty(lib.car_round2q_packed_floats(), device=dev), torch.empty(lib.car_round2q_bias_floats(), device=dev)
-    L.check(lib.car_round2q_pack(_ptr(wr1), _ptr(br1), _ptr(wr2), _ptr(br2), _ptr(wq1), _ptr(bq1), _ptr(wq2), _ptr(bq2), _ptr(wp), _ptr(bp), st), "car_round2q_pack")
+    L.check(lib.car_round2q_pack(abi.ptr(wr1), abi.ptr(br1), abi.ptr(wr2), abi.ptr(br2), abi.ptr(wq1), abi.ptr(bq1), abi.ptr(wq2), abi.ptr(bq2), abi.ptr(wp), abi.ptr(bp), st), "car_round2q_pack")
     logit = torch.full((S,), float("nan"), device=dev)
-    L.check(lib.car_round2_logits_from_g(_ptr(gq), _ptr(uh), _ptr(wp), _ptr(bp), b, V, R, P, _ptr(logit), st), "car_round2_logits_from_g")
+    L.check(lib.car_round2_logits_from_g(abi.ptr(gq), abi.ptr(uh), abi.ptr(wp), abi.ptr(bp), b, V, R, P, abi.ptr(logit), st), "car_round2_logits_from_g")
     d = lambda t: t.double()
     ray = (torch.arange(S, device=dev) // P)                               # (scene-view, ray) -> (scene, ray)
     ray = (ray // R // V) * R + ray % R
@@ -1093,10 +1084,10 @@ def test_second_round_bilinear_form_matches_the_two_layers(b, R, P, wscale):
     assert ((d(logit) - want).abs() / bound).max().item() < 4e-6
     # the stored-query kernel on the same inputs (the staged routes' form)
     w0, b0 = torch.empty(lib.car_round2_packed_floats(), device=dev), torch.empty(lib.car_round2_bias_floats(), device=dev)
-    L.check(lib.car_round2_pack(_ptr(wr1), _ptr(br1), _ptr(wr2), _ptr(br2), _ptr(w0), _ptr(b0), st), "car_round2_pack")
+    L.check(lib.car_round2_pack(abi.ptr(wr1), abi.ptr(br1), abi.ptr(wr2), abi.ptr(br2), abi.ptr(w0), abi.ptr(b0), st), "car_round2_pack")
     qrows = qry.float().contiguous()
     logit0 = torch.empty(S, device=dev)
-    L.check(lib.car_round2_logits(_ptr(gq), _ptr(uh), _ptr(qrows), _ptr(w0), _ptr(b0), b, V, R, P, _ptr(logit0), st), "car_round2_logits")
+    L.check(lib.car_round2_logits(abi.ptr(gq), abi.ptr(uh), abi.ptr(qrows), abi.ptr(w0), abi.ptr(b0), b, V, R, P, abi.ptr(logit0), st), "car_round2_logits")
     torch.cuda.synchronize()
     assert ((d(logit) - d(logit0)).abs() / bound).max().item() < 4e-6
 
@@ -1155,10 +1146,10 @@ def test_lattice_beyond_the_fused_kernels_range_takes_the_stage_route():
         z = [torch.empty(2, 256, H // 4, H // 4, device="meta"), torch.empty(2, 256, H // 2, H // 2, device="meta"), torch.empty(2, 64, H, H, device="meta")]
         assert eng._common_lattice(z)
         assert eng._lattice_fits(1, 64, z) == fits, H
-    lib = _lib()
+    lib = abi.lib()
     one = torch.zeros(64, device="cuda:0")
-    rc = lib.car_fused_samples(_ptr(one), _ptr(one), _ptr(one), _ptr(one), 1033, 1033, 5, _ptr(one), _ptr(one), _ptr(one), _ptr(one), 1, 2, 8, 8, 512, 512, 0,
-                               _ptr(one), _ptr(one), _ptr(one), _ptr(one), _ptr(one), _ptr(one), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = lib.car_fused_samples(abi.ptr(one), abi.ptr(one), abi.ptr(one), abi.ptr(one), 1033, 1033, 5, abi.ptr(one), abi.ptr(one), abi.ptr(one), abi.ptr(one), 1, 2, 8, 8, 512, 512, 0,
+                               abi.ptr(one), abi.ptr(one), abi.ptr(one), abi.ptr(one), abi.ptr(one), abi.ptr(one), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc != 0 and b"2 GiB" in lib.car_last_error()
 
 

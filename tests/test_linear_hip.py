@@ -4,7 +4,7 @@ kernels (csrc/car_backward.hip), and the six entries' refusals.  No kernel is th
 
 Tolerance, measured against the reference and never against a kernel: every element must be finite and satisfy |got - ref64| <= tol x
 bound, the bound the float64 sum of magnitudes that goes with the value (linear_reference.py); where the bound is 0 the value must be
-exactly 0.  tol = 8 x max(r, 2^-22) (fused_reference.tolerance), r the worst ratio of the kernel's yardstick on the same inputs: the
+exactly 0.  tol = 8 x max(r, 2^-22) (parity_rule.tolerance), r the worst ratio of the kernel's yardstick on the same inputs: the
 float32 run of the same formula for car_linear and the fp32-pipe weight-gradient kernels; for the split-fp16 entries the float32 run
 decides and the three-product emulation's ratio is printed beside it; for the bf16 weight-gradient kernel the three-product bf16
 emulation decides and the float32 run's ratio is printed beside it.  Integer sets are compared bit for bit.  Every test prints
@@ -13,90 +13,29 @@ ratio_kernel / tolerance as a ``[parity]`` line (profiles/linear_parity.md).
 Every output lies inside a larger NaN-filled buffer; row padding of Y and dW and a guard row behind the last row must come back NaN,
 bit for bit; the row padding of X, dY and e holds NaN and +-inf that must not reach an output.  test_linear_reference.py (CPU) asserts
 that the shapes take the paths and the input sets hold the values they exist for."""
-import ctypes
 import functools
 
 import pytest
 import torch
 
+import abi_harness as abi
 import linear_reference as LR
+from abi_harness import CAR_E_ARG, F32, F64, NAN, P_, Guarded, rows_out, take_rows
+from parity_rule import judge
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-MARGIN = 64
-CAR_E_ARG = -1
-F32, F64 = torch.float32, torch.float64
-P_ = ctypes.c_void_p
 FLAGS8 = list(range(8))
 FLAG_IDS = ["plain", "relu_in", "relu_out", "relu_in+out", "accum", "relu_in+accum", "accum+relu_out", "all"]
 
 
-def _lib():
-    from cross_attention_renderer_amd import _lib as L
-    return L.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return None if t is None else P_(t.data_ptr())
-
-
-def _stream():
-    return P_(torch.cuda.current_stream().cuda_stream)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _up4(n):
-    return (n + 3) & ~3
-
-
-class Guarded:
-    """A contiguous float32 tensor of `shape` filled with `fill`, inside a NaN-filled buffer; `off` floats off the buffer's 256-byte
-    alignment."""
-
-    def __init__(self, shape, fill=NAN, off=0):
-        n = 1
-        for d in shape:
-            n *= d
-        self.n, self.off = n, off
-        self.full = torch.full((MARGIN + off + n + MARGIN,), NAN, dtype=F32, device=_dev())
-        self.view = self.full[MARGIN + off:MARGIN + off + n].view(*shape)
-        self.view.fill_(fill)
-
-    def untouched(self):
-        return bool(torch.isnan(self.full).all())
-
-
-def _rows_out(rows, ld, off=0):
-    """`rows` rows at a stride of ld floats and a guard row behind them, all NaN."""
-    return Guarded((rows + 1, ld), off=off)
-
-
-def _take_rows(out, rows, width, what):
-    """The rows' windows; everything else of the buffer must still be NaN."""
-    got = out.view[:rows, :width].clone()
-    out.view[:rows, :width] = NAN
-    assert out.untouched(), f"{what}: wrote outside the rows' windows (padding columns, the guard row or the margins)"
-    return got.cpu()
-
-
-def _judge(test, case, got, ref, bound, r, what="fp32", extra=""):
-    """Prints the [parity] line and holds the worst ratio to 8 x max(yardstick, 2^-22)."""
-    rk = LR.ratio(got, ref, bound)
-    tol = LR.tolerance(r)
-    print(f"[parity] {test} {case}: {rk / tol:.3f} (kernel {rk:.2e} {what} {r:.2e} tol {tol:.2e}{extra})" + ("  ABOVE HALF THE TOLERANCE" if rk > tol / 2 else ""))
-    assert rk <= tol, (test, case, rk, tol)
+def _judge(test, case, got, ref, bound, r, what="fp32", also=None):
+    """One result held to the yardstick `what` of ratio r; `also`: {name: ratio} of a yardstick that is printed and decides nothing."""
+    judge(test, case, {"": ((got, ref, bound), r)}, what=what, also=also)
 
 
 def _exact(test, case, got, ref):
-    assert torch.equal(_bits(got), _bits(ref.float())), (test, case, "not bit for bit", float((got.double() - ref).abs().max()))
+    assert torch.equal(abi.bits(got), abi.bits(ref.float())), (test, case, "not bit for bit", float((got.double() - ref).abs().max()))
     print(f"[parity] {test} {case}: exact")
 
 
@@ -106,8 +45,8 @@ def _pack(lib, W, b, K, N, ldw=None):
     n = lib.car_linear_packed_floats(K, N)
     assert n == LR.pack_geom(K, N)["floats"]
     packed = Guarded((n,))
-    dW, db = W.to(_dev()).contiguous(), None if b is None else b.to(_dev())
-    rc = lib.car_linear_pack(_ptr(dW), ldw or W.shape[1], _ptr(db), K, N, _ptr(packed.view), _stream())
+    dW, db = W.to(abi.dev()).contiguous(), None if b is None else b.to(abi.dev())
+    rc = lib.car_linear_pack(abi.ptr(dW), ldw or W.shape[1], abi.ptr(db), K, N, abi.ptr(packed.view), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return packed
@@ -118,13 +57,13 @@ def _pack(lib, W, b, K, N, ldw=None):
 def test_linear_pack_is_the_index_formula(K, N, bias):
     """The packed buffer bit for bit against linear_reference.packed_layout, ldw = K + 3 (the columns behind K are NaN and never read),
     with and without a bias; nothing written outside car_linear_packed_floats floats; sizes 0 give 0 floats."""
-    lib = _lib()
+    lib = abi.lib()
     W, b = LR.weights(N, K, 40 + K)
     Wp = LR.padded(W, K + 3)
     packed = _pack(lib, Wp, b if bias else None, K, N, ldw=K + 3)
     want = LR.packed_layout(W, b if bias else None, K, N)
     got = packed.view.clone().cpu()
-    assert torch.equal(_bits(got), _bits(want))
+    assert torch.equal(abi.bits(got), abi.bits(want))
     packed.view.fill_(NAN)
     assert packed.untouched()
     assert lib.car_linear_packed_floats(0, N) == 0 and lib.car_linear_packed_floats(K, 0) == 0
@@ -136,7 +75,7 @@ STORES = {"float4": (4, 0), "odd-ldy": (1, 0), "off-by-4-bytes": (4, 1)}       #
 
 def _ldy(N, store):
     step, _ = STORES[store]
-    return _up4(N) + 4 if step == 4 else (N + 1) | 1
+    return abi.up4(N) + 4 if step == 4 else (N + 1) | 1
 
 
 @functools.lru_cache(maxsize=None)
@@ -151,15 +90,15 @@ def _linear_reference(name, M, K, N, flags, seed=1):
 def _run_linear(lib, X, ldx, W, b, Y0, flags, store):
     M, K, N = X.shape[0], W.shape[1], W.shape[0]
     packed = _pack(lib, W, b, K, N)
-    dX = LR.padded(X, ldx).to(_dev())
+    dX = LR.padded(X, ldx).to(abi.dev())
     ldy = _ldy(N, store)
-    out = _rows_out(M, ldy, off=STORES[store][1])
+    out = rows_out(M, ldy, offset=STORES[store][1])
     if flags & LR.ACCUM:
-        out.view[:M, :N] = Y0.to(_dev())
-    rc = lib.car_linear(_ptr(dX), ldx, _ptr(packed.view), K, N, _ptr(out.view), ldy, M, flags, _stream())
+        out.view[:M, :N] = Y0.to(abi.dev())
+    rc = lib.car_linear(abi.ptr(dX), ldx, abi.ptr(packed.view), K, N, abi.ptr(out.view), ldy, M, flags, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
-    return _take_rows(out, M, N, "Y")
+    return take_rows(out, M, N, "Y")
 
 
 @pytest.mark.parametrize("store", list(STORES))
@@ -170,7 +109,7 @@ def test_linear_shapes_match_fp64(M, K, N, extra, store):
     Flags alternate with the shape so that ACCUM | RELU_OUT meets every instance."""
     flags = (LR.ACCUM | LR.RELU_OUT) if (M + N) % 2 else LR.RELU_IN
     X, W, b, Y0, ref, bound, r32 = _linear_reference("gauss", M, K, N, flags)
-    got = _run_linear(_lib(), X, _up4(K) + extra, W, b, Y0, flags, store)
+    got = _run_linear(abi.lib(), X, abi.up4(K) + extra, W, b, Y0, flags, store)
     _judge("linear", f"gauss M={M} K={K} N={N} {store} flags={flags}", got, ref, bound, r32)
 
 
@@ -180,7 +119,7 @@ def test_linear_shapes_match_fp64(M, K, N, extra, store):
 def test_linear_flags_match_fp64(M, K, N, flags, glds):
     """All eight combinations of RELU_IN, RELU_OUT, ACCUM, each with the weights staged by LDS-DMA and through registers (CAR_LIN_NO_GLDS)."""
     X, W, b, Y0, ref, bound, r32 = _linear_reference("gauss", M, K, N, flags)
-    got = _run_linear(_lib(), X, _up4(K), W, b, Y0, flags | glds, "float4")
+    got = _run_linear(abi.lib(), X, abi.up4(K), W, b, Y0, flags | glds, "float4")
     _judge("linear", f"flags M={M} K={K} N={N} flags={flags | glds}", got, ref, bound, r32)
 
 
@@ -190,7 +129,7 @@ def test_linear_flags_match_fp64(M, K, N, flags, glds):
 def test_linear_value_sets_match_fp64(M, K, N, name, flags):
     """Gaussian rows, rows spanning 1e-6 .. 1e4, the cancelling set (results 2^-10 of their bound) and integers (bit for bit)."""
     X, W, b, Y0, ref, bound, r32 = _linear_reference(name, M, K, N, flags)
-    got = _run_linear(_lib(), X, _up4(K) + 4, W, b, Y0, flags, "float4" if flags else "odd-ldy")
+    got = _run_linear(abi.lib(), X, abi.up4(K) + 4, W, b, Y0, flags, "float4" if flags else "odd-ldy")
     if name == "int":
         _exact("linear", f"{name} M={M} K={K} N={N} flags={flags}", got, ref)
     else:
@@ -199,9 +138,9 @@ def test_linear_value_sets_match_fp64(M, K, N, name, flags):
 
 # ---- car_linear_x3, car_linear_x3_masked ------------------------------------------------------------------------------------------------------------------
 def _pack_x3(lib, W, K, N):
-    tiles = torch.empty(lib.car_linear_x3_packed_floats(K, N), device=_dev())
-    dW = W.to(_dev()).contiguous()
-    rc = lib.car_linear_x3_pack(_ptr(dW), K, K, N, _ptr(tiles), _stream())
+    tiles = torch.empty(lib.car_linear_x3_packed_floats(K, N), device=abi.dev())
+    dW = W.to(abi.dev()).contiguous()
+    rc = lib.car_linear_x3_pack(abi.ptr(dW), K, K, N, abi.ptr(tiles), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     return tiles
@@ -221,24 +160,24 @@ def _x3_reference(name, M, K, N, flags, bias, seed=1):
 def _run_x3(lib, X, ldx, W, b, Y0, flags, act=None, lda=0):
     M, K, N = X.shape[0], W.shape[1], W.shape[0]
     tiles = _pack_x3(lib, W, K, N)
-    dX, db = LR.padded(X, ldx).to(_dev()), None if b is None else b.to(_dev())
+    dX, db = LR.padded(X, ldx).to(abi.dev()), None if b is None else b.to(abi.dev())
     ldy = N + 8
-    out = _rows_out(M, ldy)
+    out = rows_out(M, ldy)
     if flags & LR.ACCUM:
-        out.view[:M, :N] = Y0.to(_dev())
+        out.view[:M, :N] = Y0.to(abi.dev())
     if act is None:
-        rc = lib.car_linear_x3(_ptr(dX), ldx, _ptr(tiles), _ptr(db), K, N, _ptr(out.view), ldy, M, flags, _stream())
+        rc = lib.car_linear_x3(abi.ptr(dX), ldx, abi.ptr(tiles), abi.ptr(db), K, N, abi.ptr(out.view), ldy, M, flags, abi.stream())
     else:
-        dact = LR.padded(act, lda).to(_dev())
-        rc = lib.car_linear_x3_masked(_ptr(dX), ldx, _ptr(tiles), _ptr(db), K, N, _ptr(out.view), ldy, M, flags, _ptr(dact), lda, _stream())
+        dact = LR.padded(act, lda).to(abi.dev())
+        rc = lib.car_linear_x3_masked(abi.ptr(dX), ldx, abi.ptr(tiles), abi.ptr(db), K, N, abi.ptr(out.view), ldy, M, flags, abi.ptr(dact), lda, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
-    return _take_rows(out, M, N, "Y")
+    return take_rows(out, M, N, "Y")
 
 
 def _judge_x3(test, case, got, ref, bound, r32, r3):
     """The float32 yardstick decides; the three-product emulation's ratio and the tolerance it would give are printed beside it."""
-    _judge(test, case, got, ref, bound, r32, extra=f"; x3-emulation {r3:.2e} tol {LR.tolerance(r3):.2e}")
+    _judge(test, case, got, ref, bound, r32, also={"x3-emulation": r3})
 
 
 @pytest.mark.parametrize("bias", [True, False], ids=["bias", "nobias"])
@@ -249,15 +188,15 @@ def test_linear_x3_shapes_match_fp64(M, K, N, extra, bias):
     pad columns) and wider; with a bias and without."""
     flags = (LR.ACCUM | LR.RELU_OUT) if (M + K) % 2 else 0
     X, W, b, Y0, ref, bound, r32, r3 = _x3_reference("gauss", M, K, N, flags, bias)
-    got = _run_x3(_lib(), X, _up4(K) + extra, W, b, Y0, flags)
-    _judge_x3("linear_x3", f"gauss M={M} K={K} N={N} ldx={_up4(K) + extra} bias={bias} flags={flags}", got, ref, bound, r32, r3)
+    got = _run_x3(abi.lib(), X, abi.up4(K) + extra, W, b, Y0, flags)
+    _judge_x3("linear_x3", f"gauss M={M} K={K} N={N} ldx={abi.up4(K) + extra} bias={bias} flags={flags}", got, ref, bound, r32, r3)
 
 
 @pytest.mark.parametrize("flags", FLAGS8, ids=FLAG_IDS)
 def test_linear_x3_flags_match_fp64(flags):
     M, K, N = 17, 33, 128
     X, W, b, Y0, ref, bound, r32, r3 = _x3_reference("gauss", M, K, N, flags, True)
-    got = _run_x3(_lib(), X, _up4(K), W, b, Y0, flags)
+    got = _run_x3(abi.lib(), X, abi.up4(K), W, b, Y0, flags)
     _judge_x3("linear_x3", f"flags M={M} K={K} N={N} flags={flags}", got, ref, bound, r32, r3)
 
 
@@ -268,21 +207,21 @@ def test_linear_x3_value_sets_match_fp64(name):
     one), a row at largest magnitude 2^-40 and one at 2^40 without a bias, and the two integer sets (bit for bit: lo(X) != 0 in one,
     lo(W) != 0 in the other, so that each of the three products carries signal)."""
     M, K, N = LR.X3_SET_SHAPE
-    lib = _lib()
+    lib = abi.lib()
     bias = name != "tiny_huge"
     for flags in (0, LR.ACCUM) if name.startswith("int") else (0,):
         X, W, b, Y0, ref, bound, r32, r3 = _x3_reference(name, M, K, N, flags, bias)
-        got = _run_x3(lib, X, _up4(K), W, b, Y0, flags)
+        got = _run_x3(lib, X, abi.up4(K), W, b, Y0, flags)
         if name.startswith("int"):
             _exact("linear_x3", f"{name} flags={flags}", got, ref)
         else:
             _judge_x3("linear_x3", f"{name} M={M} K={K} N={N}", got, ref, bound, r32, r3)
     if name == "zero_rows":
-        assert torch.equal(_bits(got[0::2]), _bits(b[None, :].expand(len(got[0::2]), N))), "an all-zero row is not the bias bit for bit"
+        assert torch.equal(abi.bits(got[0::2]), abi.bits(b[None, :].expand(len(got[0::2]), N))), "an all-zero row is not the bias bit for bit"
         X, W, _, Y0, ref, bound, r32, r3 = _x3_reference(name, M, K, N, 0, False)
-        got = _run_x3(lib, X, _up4(K), W, None, Y0, 0)
+        got = _run_x3(lib, X, abi.up4(K), W, None, Y0, 0)
         _judge_x3("linear_x3", f"{name} nobias", got, ref, bound, r32, r3)
-        assert bool((_bits(got[0::2]) == 0).all()), "an all-zero row without a bias is not +0.0"
+        assert bool((abi.bits(got[0::2]) == 0).all()), "an all-zero row without a bias is not +0.0"
 
 
 def mask_values(M: int, N: int, seed: int):
@@ -304,9 +243,9 @@ def test_linear_x3_masked_matches_fp64(N, M, flags):
     X, W, b, Y0, ref, bound, r32, r3 = _x3_reference("gauss", M, K, N, flags, True)
     act = mask_values(M, N, 50 + N + M)
     keep = act > 0
-    assert bool(keep.any()) and bool((~keep).any()) and bool(torch.isnan(act).any()) and bool((act == 2.0 ** -126).any()) and bool((_bits(act) == 1).any())
-    got = _run_x3(_lib(), X, _up4(K), W, b, Y0, flags, act=act, lda=N + 4)
-    assert bool((_bits(got)[~keep] == 0).all()), "a masked column is not +0.0"
+    assert bool(keep.any()) and bool((~keep).any()) and bool(torch.isnan(act).any()) and bool((act == 2.0 ** -126).any()) and bool((abi.bits(act) == 1).any())
+    got = _run_x3(abi.lib(), X, abi.up4(K), W, b, Y0, flags, act=act, lda=N + 4)
+    assert bool((abi.bits(got)[~keep] == 0).all()), "a masked column is not +0.0"
     zero = torch.zeros_like(ref)
     _judge_x3("linear_x3_masked", f"M={M} N={N} flags={flags}", got, torch.where(keep, ref, zero), torch.where(keep, bound, zero), r32, r3)
 
@@ -326,18 +265,18 @@ def test_key_query_logits_match_the_unfolded_chain(M, Ce, extra):
     """car_key_query_logits: qry and logit against kq_chain (unfolded, float64) at Ce 96, 100, 288, 576, 864, lde = Ce rounded up to 4 and
     wider (poison behind the row), M 1, 17, 193; row 0 of e is all zero — k1 = relu(bk1) is negative throughout before the ReLU, key must
     be bk2: the logit's bound holds |bk2| alone on the key side — and the last row of g is all zero."""
-    lib = _lib()
+    lib = abi.lib()
     P, e, g, r64, yard = _kq_reference(M, Ce)
-    d = {k: v.to(_dev()).contiguous() for k, v in P.items()}
+    d = {k: v.to(abi.dev()).contiguous() for k, v in P.items()}
     tiles = _pack_x3(lib, P["Wk1"], Ce, 128)
-    tail = torch.empty(lib.car_kq_tail_floats(), device=_dev())
-    tb = torch.empty(lib.car_kq_bias_floats(), device=_dev())
-    rc = lib.car_kq_pack(_ptr(d["Wk2"]), _ptr(d["bk2"]), _ptr(d["Wq1"]), _ptr(d["bq1"]), _ptr(d["Wq2"]), _ptr(d["bq2"]), _ptr(tail), _ptr(tb), _stream())
+    tail = torch.empty(lib.car_kq_tail_floats(), device=abi.dev())
+    tb = torch.empty(lib.car_kq_bias_floats(), device=abi.dev())
+    rc = lib.car_kq_pack(abi.ptr(d["Wk2"]), abi.ptr(d["bk2"]), abi.ptr(d["Wq1"]), abi.ptr(d["bq1"]), abi.ptr(d["Wq2"]), abi.ptr(d["bq2"]), abi.ptr(tail), abi.ptr(tb), abi.stream())
     assert rc == 0, lib.car_last_error()
-    lde = _up4(Ce) + extra
-    de, dg = LR.padded(e, lde).to(_dev()), g.to(_dev()).contiguous()
+    lde = abi.up4(Ce) + extra
+    de, dg = LR.padded(e, lde).to(abi.dev()), g.to(abi.dev()).contiguous()
     qry, logit = Guarded((M, 128)), Guarded((M,))
-    rc = lib.car_key_query_logits(_ptr(de), lde, _ptr(tiles), _ptr(d["bk1"]), Ce, _ptr(dg), _ptr(tail), _ptr(tb), M, _ptr(qry.view), _ptr(logit.view), _stream())
+    rc = lib.car_key_query_logits(abi.ptr(de), lde, abi.ptr(tiles), abi.ptr(d["bk1"]), Ce, abi.ptr(dg), abi.ptr(tail), abi.ptr(tb), M, abi.ptr(qry.view), abi.ptr(logit.view), abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     got = {"qry": qry.view.clone().cpu(), "logit": logit.view.clone().cpu()}
@@ -371,20 +310,20 @@ def _wgrad_reference(name, case, prefill):
 
 def _run_wgrad(lib, case, dY, X, dW0, db0):
     M, N, K, has_db, relu, flags = LR.WGRAD_SHAPES[case]
-    ldy, ldx, lddw = _up4(N) + 4, _up4(K) + (4 if K % 4 == 0 else 0), K + 5
-    ddY, dX = LR.padded(dY, ldy).to(_dev()), LR.padded(X, ldx).to(_dev())
-    out = _rows_out(N, lddw)
-    out.view[:N, :K] = dW0.to(_dev())
+    ldy, ldx, lddw = abi.up4(N) + 4, abi.up4(K) + (4 if K % 4 == 0 else 0), K + 5
+    ddY, dX = LR.padded(dY, ldy).to(abi.dev()), LR.padded(X, ldx).to(abi.dev())
+    out = rows_out(N, lddw)
+    out.view[:N, :K] = dW0.to(abi.dev())
     dbo = Guarded((N,))
     if has_db:
-        dbo.view.copy_(db0.to(_dev()))
-    rc = lib.car_linear_wgrad(_ptr(ddY), ldy, _ptr(dX), ldx, M, N, K, (LR.RELU_IN if relu else 0) | flags, _ptr(out.view), lddw, _ptr(dbo.view) if has_db else None, _stream())
+        dbo.view.copy_(db0.to(abi.dev()))
+    rc = lib.car_linear_wgrad(abi.ptr(ddY), ldy, abi.ptr(dX), ldx, M, N, K, (LR.RELU_IN if relu else 0) | flags, abi.ptr(out.view), lddw, abi.ptr(dbo.view) if has_db else None, abi.stream())
     assert rc == 0, lib.car_last_error()
     torch.cuda.synchronize()
     gb = dbo.view.clone().cpu() if has_db else None
     dbo.view.fill_(NAN)
     assert dbo.untouched(), "db: wrote outside its N floats" if has_db else "db is NULL and was written"
-    return _take_rows(out, N, K, "dW"), gb
+    return take_rows(out, N, K, "dW"), gb
 
 
 def _check_wgrad(lib, name, case, prefill):
@@ -398,10 +337,10 @@ def _check_wgrad(lib, name, case, prefill):
         if has_db:
             _exact("linear_wgrad db", tag, gb, db)
         return
-    r, what, extra = (r16, "bf16-emulation", f"; fp32 {r32:.2e} tol {LR.tolerance(r32):.2e}") if kernel == "bf16" else (r32, "fp32", "")
-    _judge("linear_wgrad dW", tag, gW, dW, BW, r, what, extra)
+    r, what, also = (r16, "bf16-emulation", {"fp32": r32}) if kernel == "bf16" else (r32, "fp32", None)
+    _judge("linear_wgrad dW", tag, gW, dW, BW, r, what, also)
     if has_db:
-        _judge("linear_wgrad db", tag, gb, db, Bb, r, what, extra)
+        _judge("linear_wgrad db", tag, gb, db, Bb, r, what, also)
 
 
 @pytest.mark.parametrize("prefill", [True, False], ids=["accumulate", "zero"])
@@ -414,7 +353,7 @@ def test_linear_wgrad_shapes_match_fp64(case, prefill):
     dW has a row stride of K + 5: the padding and a guard row come back NaN."""
     M, N, K, has_db, relu, flags = LR.WGRAD_SHAPES[case]
     assert case.startswith(LR.wgrad_dispatch(M, N, K, has_db, flags))
-    _check_wgrad(_lib(), "gauss", case, prefill)
+    _check_wgrad(abi.lib(), "gauss", case, prefill)
 
 
 @pytest.mark.parametrize("name", LR.WGRAD_SETS[1:])
@@ -423,22 +362,22 @@ def test_linear_wgrad_value_sets_match_fp64(case, name):
     """Rows spanning twelve orders of magnitude, constant columns (sums without cancellation) and the two integer sets (bit for bit:
     lo(dY) != 0 in one, lo(X) != 0 in the other; zero rows keep every sum below 2^24) on both fp32-pipe tiles and on the bf16 kernel's
     partial-block, four-tile whole-block and one-tile whole-block shapes."""
-    _check_wgrad(_lib(), name, case, name != "int_X")
+    _check_wgrad(abi.lib(), name, case, name != "int_X")
 
 
 # ---- refusals: all return CAR_E_ARG before any launch, leave a message that starts with the entry's name and write nothing ----------------------------------
 @functools.lru_cache(maxsize=None)
 def _refusal_inputs():
     """Small valid arguments of every entry: M = 16 rows, K = 32, N = 32 (car_key_query_logits: Ce = 32)."""
-    lib = _lib()
+    lib = abi.lib()
     M, K, N = 16, 32, 32
-    z = lambda *shape: torch.zeros(*shape, device=_dev())
+    z = lambda *shape: torch.zeros(*shape, device=abi.dev())
     W, b = LR.weights(N, K, 90)
     P = LR.kq_params(K, 91)
-    d = {k: v.to(_dev()).contiguous() for k, v in P.items()}
-    tail, tb = torch.empty(lib.car_kq_tail_floats(), device=_dev()), torch.empty(lib.car_kq_bias_floats(), device=_dev())
-    assert lib.car_kq_pack(_ptr(d["Wk2"]), _ptr(d["bk2"]), _ptr(d["Wq1"]), _ptr(d["bq1"]), _ptr(d["Wq2"]), _ptr(d["bq2"]), _ptr(tail), _ptr(tb), _stream()) == 0
-    t = {"W": W.to(_dev()), "b": torch.cat([b, torch.zeros(4)]).to(_dev()), "X": z(M + 1, K), "dY": z(M + 1, N), "act": z(M + 1, N + 32), "g": z(M + 1, 16),
+    d = {k: v.to(abi.dev()).contiguous() for k, v in P.items()}
+    tail, tb = torch.empty(lib.car_kq_tail_floats(), device=abi.dev()), torch.empty(lib.car_kq_bias_floats(), device=abi.dev())
+    assert lib.car_kq_pack(abi.ptr(d["Wk2"]), abi.ptr(d["bk2"]), abi.ptr(d["Wq1"]), abi.ptr(d["bq1"]), abi.ptr(d["Wq2"]), abi.ptr(d["bq2"]), abi.ptr(tail), abi.ptr(tb), abi.stream()) == 0
+    t = {"W": W.to(abi.dev()), "b": torch.cat([b, torch.zeros(4)]).to(abi.dev()), "X": z(M + 1, K), "dY": z(M + 1, N), "act": z(M + 1, N + 32), "g": z(M + 1, 16),
          "packed": _pack(lib, W, b, K, N).view, "tiles": _pack_x3(lib, W, K, N), "tiles_k1": _pack_x3(lib, P["Wk1"], K, 128), "bk1": torch.cat([d["bk1"], z(4)]),
          "tail": tail, "tb": tb}
     torch.cuda.synchronize()
@@ -447,7 +386,7 @@ def _refusal_inputs():
 
 def _entry(name):
     """(function, ordered argument dict, outputs) of an entry, valid as it stands; the stream is appended by the caller."""
-    lib = _lib()
+    lib = abi.lib()
     M, K, N, t = _refusal_inputs()
     if name == "car_linear_pack":
         out = {"packed": Guarded((lib.car_linear_packed_floats(K, N),))}
@@ -471,9 +410,9 @@ def _entry(name):
 
 def _c(v):
     if isinstance(v, Guarded):
-        return _ptr(v.view)
+        return abi.ptr(v.view)
     if isinstance(v, torch.Tensor):
-        return _ptr(v)
+        return abi.ptr(v)
     return v
 
 
@@ -504,14 +443,14 @@ def test_refusals(entry, field, value, message):
     four bytes on), N no multiple of 32.  Each returns CAR_E_ARG before any launch, leaves a message that starts with the name of the entry
     that was called and writes nothing.  (Not reachable with arguments a test may pass: car_linear_wgrad's slab count and 32-bit block
     offset checks, profiles/linear_parity.md.)"""
-    lib = _lib()
+    lib = abi.lib()
     fn, a, out = _entry(entry)
     if field.endswith("+4"):
         k = field[:-2]
         a[k] = P_((a[k].view if isinstance(a[k], Guarded) else a[k]).data_ptr() + 4)
     else:
         a[field] = value
-    rc = fn(*[_c(v) for v in a.values()], _stream())
+    rc = fn(*[_c(v) for v in a.values()], abi.stream())
     assert rc == CAR_E_ARG, (entry, field, value, rc)
     msg = lib.car_last_error().decode()
     assert message in msg and msg.startswith(entry + ":"), msg

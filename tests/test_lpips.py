@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import abi_harness as abi
 import lpips_restatement as LR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -256,24 +257,16 @@ def test_train_script_says_why_it_has_no_lpips_loss(tmp_path):
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------------------
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _gpu_conv(lib, x_nhwc, w, b):
     """car_conv3x3_pack + car_conv3x3 on a channel-last float32 device tensor; returns [n, H, W, N]."""
     from cross_attention_renderer_amd import _lib
     n, H, W, K = x_nhwc.shape
     N = w.shape[0]
-    wd, bd = w.to(_dev()).contiguous(), b.to(_dev()).contiguous()
-    packed = torch.empty(lib.car_conv3x3_packed_floats(K, N), dtype=torch.float32, device=_dev())
-    _lib.check(lib.car_conv3x3_pack(wd.data_ptr(), bd.data_ptr(), K, N, packed.data_ptr(), _stream()), "car_conv3x3_pack")
-    y = torch.full((n, H, W, N), float("nan"), dtype=torch.float32, device=_dev())
-    _lib.check(lib.car_conv3x3(x_nhwc.data_ptr(), n, H, W, K, N, packed.data_ptr(), y.data_ptr(), _stream()), "car_conv3x3")
+    wd, bd = w.to(abi.dev()).contiguous(), b.to(abi.dev()).contiguous()
+    packed = torch.empty(lib.car_conv3x3_packed_floats(K, N), dtype=torch.float32, device=abi.dev())
+    _lib.check(lib.car_conv3x3_pack(wd.data_ptr(), bd.data_ptr(), K, N, packed.data_ptr(), abi.stream()), "car_conv3x3_pack")
+    y = torch.full((n, H, W, N), float("nan"), dtype=torch.float32, device=abi.dev())
+    _lib.check(lib.car_conv3x3(x_nhwc.data_ptr(), n, H, W, K, N, packed.data_ptr(), y.data_ptr(), abi.stream()), "car_conv3x3")
     torch.cuda.synchronize()
     return y
 
@@ -316,7 +309,7 @@ def test_conv3x3_matches_float64_conv2d(lib, shape):
     want = _ref_conv(x, w, b, K == 3)
     assert 1.0 <= want.abs().max().item() <= 10.0
     assert (want > 0).double().mean().item() > 0.25
-    _assert_parity(_gpu_conv(lib, x.to(_dev()).contiguous(), w, b), want, f"conv {K} -> {N} at {side} x {side}")
+    _assert_parity(_gpu_conv(lib, x.to(abi.dev()).contiguous(), w, b), want, f"conv {K} -> {N} at {side} x {side}")
 
 
 @pytest.mark.gpu
@@ -326,12 +319,12 @@ def test_conv_chain_matches_float64_layer_by_layer(lib, weights, hw):
     conv2d of that same map; the pools must be exact."""
     from cross_attention_renderer_amd import _lib
     conv_w, conv_b, _ = weights
-    cur = _to_pm1(LR.make_image(21, 2, *hw)).to(_dev())
+    cur = _to_pm1(LR.make_image(21, 2, *hw)).to(abi.dev())
     for l in range(13):
         if l in LR.POOL_BEFORE:
             n, H, W, C = cur.shape
-            out = torch.full((n, H // 2, W // 2, C), float("nan"), dtype=torch.float32, device=_dev())
-            _lib.check(lib.car_maxpool2x2(cur.data_ptr(), n, H, W, C, out.data_ptr(), _stream()), "car_maxpool2x2")
+            out = torch.full((n, H // 2, W // 2, C), float("nan"), dtype=torch.float32, device=abi.dev())
+            _lib.check(lib.car_maxpool2x2(cur.data_ptr(), n, H, W, C, out.data_ptr(), abi.stream()), "car_maxpool2x2")
             torch.cuda.synchronize()
             assert torch.equal(out.cpu(), F.max_pool2d(cur.cpu().permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1)), l
             cur = out
@@ -346,14 +339,14 @@ def _gpu_head(lib, f0, f1, lin, per_tap=True):
     """car_lpips_head on lists of five [B, C, h, w] float32 CPU maps."""
     from cross_attention_renderer_amd import _lib
     B, H, W = f0[0].shape[0], f0[0].shape[2], f0[0].shape[3]
-    maps = [torch.cat([a, b]).permute(0, 2, 3, 1).contiguous().to(_dev()) for a, b in zip(f0, f1)]
+    maps = [torch.cat([a, b]).permute(0, 2, 3, 1).contiguous().to(abi.dev()) for a, b in zip(f0, f1)]
     table = (ctypes.c_void_p * 5)(*[m.data_ptr() for m in maps])
-    lin_d = torch.cat([w.float() for w in lin]).to(_dev())
+    lin_d = torch.cat([w.float() for w in lin]).to(abi.dev())
     n = lib.car_lpips_head_scratch_doubles(B, H, W)
-    scratch = torch.empty(n, dtype=torch.float64, device=_dev())
-    out, taps = torch.empty(B, dtype=torch.float64, device=_dev()), torch.empty(B, 5, dtype=torch.float64, device=_dev())
+    scratch = torch.empty(n, dtype=torch.float64, device=abi.dev())
+    out, taps = torch.empty(B, dtype=torch.float64, device=abi.dev()), torch.empty(B, 5, dtype=torch.float64, device=abi.dev())
     _lib.check(lib.car_lpips_head(table, B, H, W, lin_d.data_ptr(), out.data_ptr(), taps.data_ptr() if per_tap else None, scratch.data_ptr(), n,
-                                  _stream()), "car_lpips_head")
+                                  abi.stream()), "car_lpips_head")
     torch.cuda.synchronize()
     return out.cpu(), taps.cpu()
 
@@ -405,7 +398,7 @@ def test_lpips_matches_the_restatement(weights, dev_weights, shape, kind):
     want, want_taps = LR.lpips(x, y, *weights)
     cpu32, cpu32_taps = LR.lpips(x, y, *weights, dtype=torch.float32)
     dev32 = max(_rel(cpu32.double(), want), _rel(cpu32_taps.double(), want_taps))
-    got, got_taps = harness.lpips(img.to(_dev()), ref.to(_dev()), dev_weights, return_taps=True)
+    got, got_taps = harness.lpips(img.to(abi.dev()), ref.to(abi.dev()), dev_weights, return_taps=True)
     assert got.shape == (b,) and got.dtype == torch.float64 and got_taps.shape == (b, 5)
     dev_hip = max(_rel(got.cpu(), want), _rel(got_taps.cpu(), want_taps))
     print(f"lpips {kind} B={b} {h}x{w}: value {want[0].item():.6e}, HIP vs float64 {dev_hip:.3e}, CPU float32 vs float64 {dev32:.3e}")
@@ -421,10 +414,10 @@ def test_lpips_of_identical_images_is_exactly_zero_and_batch_independent(dev_wei
     from cross_attention_renderer_amd import harness
     w = dev_weights
     for b, h, wd, seed in E2E_SHAPES:
-        img = LR.make_image(seed, b, h, wd).to(_dev())
+        img = LR.make_image(seed, b, h, wd).to(abi.dev())
         got, taps = harness.lpips(img, img.clone(), w, return_taps=True)
         assert (got == 0.0).all() and (taps == 0.0).all(), (b, h, wd, got)
-    img, ref = (t.to(_dev()) for t in _pair("noisy", 3, 50, 70, 41))
+    img, ref = (t.to(abi.dev()) for t in _pair("noisy", 3, 50, 70, 41))
     a, c = harness.lpips(img, ref, w), harness.lpips(img, ref, w)
     assert torch.equal(a, c)
     for i in range(3):
@@ -433,7 +426,7 @@ def test_lpips_of_identical_images_is_exactly_zero_and_batch_independent(dev_wei
     # a pair against itself at another place in the batch: image i of x equals image i of y, whatever surrounds it
     mixed = torch.stack([ref[0], img[1], ref[2]])
     assert harness.lpips(img, mixed, w)[1].item() == 0.0
-    for bad in (torch.rand(15, 16, 3, device=_dev()), torch.rand(0, 16, 16, 3, device=_dev())):
+    for bad in (torch.rand(15, 16, 3, device=abi.dev()), torch.rand(0, 16, 16, 3, device=abi.dev())):
         with pytest.raises(ValueError):
             harness.lpips(bad, bad, w)
 
@@ -466,7 +459,7 @@ def test_eval_script_reports_lpips_with_the_reference_protocol(weights, tmp_path
     assert outs[0] == outs[1]
     # the script's images: the chunked render and the un-chunked render of the same frame, both blended over 0.5 grey with the valid mask
     opt = common.add_precision(common.parser("t")).parse_args(base[2:])
-    dev = _dev()
+    dev = abi.dev()
     model = common.build_model(opt, dev, with_encoder=None)
     inp, z = harness.synthetic_pair(H, 2, seed=5)
     inp, z = harness.to_device(inp, dev, opt.cameras), [t.to(dev) for t in z]

@@ -18,6 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import abi_harness as abi
 import lpips_backward_reference as LBR
 import lpips_restatement as LR
 
@@ -241,17 +242,9 @@ def test_train_script_refuses_lpips_without_weights_before_any_device(tmp_path):
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------------------
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _nhwc(t):
     """[n, C, h, w] CPU -> channel-last float32 on the device."""
-    return t.permute(0, 2, 3, 1).contiguous().float().to(_dev())
+    return t.permute(0, 2, 3, 1).contiguous().float().to(abi.dev())
 
 
 def _nchw64(t):
@@ -292,18 +285,18 @@ def _check_data_gradient(lib, shape, use_act, use_add):
         want = want * (act > 0)
         assert 0.3 < (act > 0).double().mean().item() < 0.7
     assert 1.0 <= want.abs().max().item() <= 10.0
-    wd = w.to(_dev()).contiguous()
+    wd = w.to(abi.dev()).contiguous()
     if K == 3:
-        packed = torch.empty(lib.car_conv3x3_packed_floats(3, 64), dtype=torch.float32, device=_dev())
-        bias = torch.zeros(64, device=_dev())
-        _lib.check(lib.car_conv3x3_pack(wd.data_ptr(), bias.data_ptr(), 3, 64, packed.data_ptr(), _stream()), "car_conv3x3_pack")
+        packed = torch.empty(lib.car_conv3x3_packed_floats(3, 64), dtype=torch.float32, device=abi.dev())
+        bias = torch.zeros(64, device=abi.dev())
+        _lib.check(lib.car_conv3x3_pack(wd.data_ptr(), bias.data_ptr(), 3, 64, packed.data_ptr(), abi.stream()), "car_conv3x3_pack")
     else:
-        packed = torch.empty(lib.car_conv3x3_backward_packed_floats(K, N), dtype=torch.float32, device=_dev())
-        _lib.check(lib.car_conv3x3_backward_pack(wd.data_ptr(), K, N, packed.data_ptr(), _stream()), "car_conv3x3_backward_pack")
+        packed = torch.empty(lib.car_conv3x3_backward_packed_floats(K, N), dtype=torch.float32, device=abi.dev())
+        _lib.check(lib.car_conv3x3_backward_pack(wd.data_ptr(), K, N, packed.data_ptr(), abi.stream()), "car_conv3x3_backward_pack")
     dd, ad, gd = _nhwc(d), (_nhwc(act) if use_act else None), (_nhwc(add) if use_add else None)
-    out = torch.full((2, side, side, K), float("nan"), dtype=torch.float32, device=_dev())
+    out = torch.full((2, side, side, K), float("nan"), dtype=torch.float32, device=abi.dev())
     _lib.check(lib.car_conv3x3_backward(dd.data_ptr(), 2, side, side, K, N, packed.data_ptr(), ad.data_ptr() if use_act else None,
-                                        gd.data_ptr() if use_add else None, out.data_ptr(), _stream()), "car_conv3x3_backward")
+                                        gd.data_ptr() if use_add else None, out.data_ptr(), abi.stream()), "car_conv3x3_backward")
     torch.cuda.synchronize()
     what = " with " + " and ".join(n for n, u in (("act", use_act), ("add", use_add)) if u) if use_act or use_add else ""
     _assert_parity(out, want.permute(0, 2, 3, 1).contiguous(), f"data gradient of {K} -> {N} at {side} x {side}{what}")
@@ -344,8 +337,8 @@ def test_pool_backward_is_exact(lib, hw):
     td, ad, gd = _nhwc(t), _nhwc(act), _nhwc(add)
     for use_add in (False, True):
         want = ((routed + add) if use_add else routed) * (act > 0)
-        out = torch.full((3, h, w, 64), float("nan"), dtype=torch.float32, device=_dev())
-        _lib.check(lib.car_maxpool2x2_backward(td.data_ptr(), ad.data_ptr(), gd.data_ptr() if use_add else None, 3, h, w, 64, out.data_ptr(), _stream()),
+        out = torch.full((3, h, w, 64), float("nan"), dtype=torch.float32, device=abi.dev())
+        _lib.check(lib.car_maxpool2x2_backward(td.data_ptr(), ad.data_ptr(), gd.data_ptr() if use_add else None, 3, h, w, 64, out.data_ptr(), abi.stream()),
                    "car_maxpool2x2_backward")
         torch.cuda.synchronize()
         assert torch.equal(out.cpu(), want.permute(0, 2, 3, 1)), (hw, use_add)
@@ -355,16 +348,16 @@ def _gpu_head_backward(lib, f0, f1, lin, g, sides="xy"):
     """car_lpips_head_backward on lists of five [B, C, h, w] float32 CPU maps -> lists of five [B, h, w, C] CPU gradients (or None)."""
     from cross_attention_renderer_amd import _lib
     B, H, W = f0[0].shape[0], f0[0].shape[2], f0[0].shape[3]
-    maps = [torch.cat([a, b]).permute(0, 2, 3, 1).contiguous().to(_dev()) for a, b in zip(f0, f1)]
+    maps = [torch.cat([a, b]).permute(0, 2, 3, 1).contiguous().to(abi.dev()) for a, b in zip(f0, f1)]
     table = (ctypes.c_void_p * 5)(*[m.data_ptr() for m in maps])
-    lin_d = torch.cat([w.float() for w in lin]).to(_dev())
-    gd = g.double().to(_dev())
+    lin_d = torch.cat([w.float() for w in lin]).to(abi.dev())
+    gd = g.double().to(abi.dev())
     outs, tabs = [], []
     for s in "xy":
-        o = [torch.full((B, *m.shape[1:]), float("nan"), dtype=torch.float32, device=_dev()) for m in maps] if s in sides else None
+        o = [torch.full((B, *m.shape[1:]), float("nan"), dtype=torch.float32, device=abi.dev()) for m in maps] if s in sides else None
         outs.append(o)
         tabs.append((ctypes.c_void_p * 5)(*[t.data_ptr() for t in o]) if o else None)
-    _lib.check(lib.car_lpips_head_backward(table, B, H, W, lin_d.data_ptr(), gd.data_ptr(), tabs[0], tabs[1], _stream()), "car_lpips_head_backward")
+    _lib.check(lib.car_lpips_head_backward(table, B, H, W, lin_d.data_ptr(), gd.data_ptr(), tabs[0], tabs[1], abi.stream()), "car_lpips_head_backward")
     torch.cuda.synchronize()
     return [[t.cpu() for t in o] if o else None for o in outs]
 
@@ -408,17 +401,17 @@ def _chain(lib, dev_weights, x, y, g, sides="xy", maps=True):
     """car_lpips_forward_train + car_lpips_backward through the C ABI: (lpips [B], gx, gy, the 13 retained maps [2 B, C, h, w] float32 CPU)."""
     from cross_attention_renderer_amd import _lib
     B, H, W, _ = x.shape
-    xd, yd, gd = x.to(_dev()).contiguous(), y.to(_dev()).contiguous(), g.double().to(_dev())
-    packed, packed_b = dev_weights.packed(_dev()), dev_weights.packed_backward(_dev())
+    xd, yd, gd = x.to(abi.dev()).contiguous(), y.to(abi.dev()).contiguous(), g.double().to(abi.dev())
+    packed, packed_b = dev_weights.packed(abi.dev()), dev_weights.packed_backward(abi.dev())
     n = lib.car_lpips_train_workspace_bytes(B, H, W)
-    work = torch.empty(n, dtype=torch.uint8, device=_dev())
-    out = torch.empty(B, dtype=torch.float64, device=_dev())
-    _lib.check(lib.car_lpips_forward_train(xd.data_ptr(), yd.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), None, work.data_ptr(), n, _stream()),
+    work = torch.empty(n, dtype=torch.uint8, device=abi.dev())
+    out = torch.empty(B, dtype=torch.float64, device=abi.dev())
+    _lib.check(lib.car_lpips_forward_train(xd.data_ptr(), yd.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), None, work.data_ptr(), n, abi.stream()),
                "car_lpips_forward_train")
-    gx = torch.full((B, H, W, 3), float("nan"), dtype=torch.float32, device=_dev()) if "x" in sides else None
-    gy = torch.full((B, H, W, 3), float("nan"), dtype=torch.float32, device=_dev()) if "y" in sides else None
+    gx = torch.full((B, H, W, 3), float("nan"), dtype=torch.float32, device=abi.dev()) if "x" in sides else None
+    gy = torch.full((B, H, W, 3), float("nan"), dtype=torch.float32, device=abi.dev()) if "y" in sides else None
     _lib.check(lib.car_lpips_backward(gd.data_ptr(), gx.data_ptr() if gx is not None else None, gy.data_ptr() if gy is not None else None, B, H, W,
-                                      packed.data_ptr(), packed_b.data_ptr(), work.data_ptr(), n, _stream()), "car_lpips_backward")
+                                      packed.data_ptr(), packed_b.data_ptr(), work.data_ptr(), n, abi.stream()), "car_lpips_backward")
     torch.cuda.synchronize()
     acts = []
     if maps:
@@ -506,7 +499,7 @@ def test_lpips_loss_backward_matches_float64_autograd(lib, weights, dev_weights,
     conv_w, conv_b, lin = weights
     x, y = _pair_pm1(kind, b, h, w, seed)
     g = torch.ones(b, dtype=torch.float64)
-    xd, yd = x.to(_dev()).requires_grad_(True), y.to(_dev()).requires_grad_(True)
+    xd, yd = x.to(abi.dev()).requires_grad_(True), y.to(abi.dev()).requires_grad_(True)
     loss = harness.lpips_loss(xd, yd, dev_weights)
     assert loss.dtype == torch.float64 and loss.shape == (b,)
     loss.sum().backward()
@@ -535,7 +528,7 @@ def test_exact_properties(dev_weights):
     (the rows' powers of two follow the gradient's magnitude).  The value is harness.lpips's, bit for bit."""
     from cross_attention_renderer_amd import harness
     for b, h, w, seed in ((2, 50, 70, 13), (12, 32, 32, 51)):
-        img = ((LR.make_image(seed, b, h, w) - 0.5) * 2).contiguous().to(_dev())
+        img = ((LR.make_image(seed, b, h, w) - 0.5) * 2).contiguous().to(abi.dev())
         a, c = img.clone().requires_grad_(True), img.clone().requires_grad_(True)
         loss = harness.lpips_loss(a, c, dev_weights)
         loss.sum().backward()
@@ -547,7 +540,7 @@ def test_exact_properties(dev_weights):
         (loss * scale).sum().backward()
         return loss.detach(), a.grad, c.grad
     for (b, h, w, seed), kind in (((2, 50, 70, 13), "noisy"), ((12, 32, 32, 51), "unrelated")):
-        x, y = (t.to(_dev()) for t in _pair_pm1(kind, b, h, w, seed))
+        x, y = (t.to(abi.dev()) for t in _pair_pm1(kind, b, h, w, seed))
         v0, gx0, gy0 = run(x, y)
         v1, gx1, gy1 = run(x, y)
         assert torch.equal(v0, v1) and torch.equal(gx0, gx1) and torch.equal(gy0, gy1)
@@ -567,8 +560,8 @@ def test_exact_properties(dev_weights):
 def test_loss_value_is_harness_lpips_bit_for_bit(dev_weights):
     from cross_attention_renderer_amd import harness
     for (b, h, w, seed), kind in (((2, 50, 70, 13), "noisy"), ((12, 32, 32, 51), "unrelated"), ((1, 256, 256, 11), "near")):
-        img = LR.make_image(seed, b, h, w).to(_dev())
-        other = LR.make_image(seed + 7, b, h, w).to(_dev())
+        img = LR.make_image(seed, b, h, w).to(abi.dev())
+        other = LR.make_image(seed + 7, b, h, w).to(abi.dev())
         want = harness.lpips(img, other, dev_weights)
         x, y = ((t.to(torch.float32) - 0.5) * 2 for t in (img, other))          # harness.lpips's own mapping
         got = harness.lpips_loss(x, y, dev_weights)
@@ -608,7 +601,7 @@ def test_a_gradient_step_lowers_the_combined_loss_by_the_predicted_amount(dev_we
     import numpy as np
     from cross_attention_renderer_amd import harness, synthetic as S
     from cross_attention_renderer_amd.models import CrossAttentionRenderer
-    dev = _dev()
+    dev = abi.dev()
     H, P = 64, 32
     torch.manual_seed(0)
     m = CrossAttentionRenderer(model="midas_vit", n_view=2, npoints=P, with_encoder=False).train()

@@ -11,12 +11,13 @@ car_round2_logits_from_g, the softmax over the ray's V * P samples and ebar = su
 
 Shapes: one ray (fewer rays than workgroups), odd ray counts (a last batch of one ray), three 32-sample tiles per view (P = 96), and
 twelve scenes (uh is indexed by scene and ray and shared by the scene's views).  Every output lies in a NaN-filled buffer with margins."""
-import ctypes
-
 import pytest
 import torch
 
+import abi_harness as abi
 import attention_reference as A
+from abi_harness import CAR_E_ARG, Guarded
+from parity_rule import error_ratio as _ratio
 
 pytestmark = pytest.mark.gpu
 
@@ -24,48 +25,7 @@ V = 2
 D = 576
 TOL = 2e-5                                   # tests/test_attention_hip.py: fp32 sums against fp64, times the sum of the terms' magnitudes
 LOGIT_TOL = 4e-6                             # test_second_round_bilinear_form_matches_the_two_layers
-MARGIN = 64
-NAN = float("nan")
-CAR_E_ARG = -1
 SHAPES = [(1, 1, 32, 1.0), (1, 5, 32, 1.0), (2, 33, 64, 30.0), (1, 7, 96, 1e-3), (12, 3, 64, 1.0)]       # (b, R, P, wscale)
-
-
-def _lib():
-    from cross_attention_renderer_amd import _lib as L
-    return L.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class Guarded:
-    """n floats inside a NaN-filled buffer: get() hands back the n and checks that the margins came back untouched."""
-
-    def __init__(self, n):
-        self.n = n
-        self.full = torch.full((MARGIN + n + MARGIN,), NAN, device=_dev())
-        self.view = self.full[MARGIN:MARGIN + n]
-
-    @property
-    def ptr(self):
-        return ctypes.c_void_p(self.view.data_ptr())
-
-    def get(self, what):
-        f = self.full.cpu()
-        assert torch.isnan(f[:MARGIN]).all() and torch.isnan(f[MARGIN + self.n:]).all(), f"{what}: wrote outside the buffer"
-        return f[MARGIN:MARGIN + self.n].clone()
-
-    def untouched(self):
-        return bool(torch.isnan(self.full).all())
 
 
 def _inputs(b, R, P, wscale, g_edit=None, uh_edit=None):
@@ -91,22 +51,22 @@ def _inputs(b, R, P, wscale, g_edit=None, uh_edit=None):
 def _run(x, merged=True, want_logits=True):
     """The merged entry, or the two launches it replaces.  Returns host tensors: logit [b*V, R, P] (None when not asked for), w, z [b, R, D]."""
     from cross_attention_renderer_amd import _lib as L
-    lib = _lib()
-    dev = _dev()
+    lib = abi.lib()
+    dev = abi.dev()
     b, R, P = x["b"], x["R"], x["P"]
     S = b * V * R * P
     d = {k: x[k].contiguous().to(dev) for k in ("g", "uh", "wr1", "br1", "wr2", "br2", "wq1", "bq1", "wq2", "bq2", "e")}
-    st = _stream()
+    st = abi.stream()
     wp, bp = torch.empty(lib.car_round2q_packed_floats(), device=dev), torch.empty(lib.car_round2q_bias_floats(), device=dev)
-    L.check(lib.car_round2q_pack(_ptr(d["wr1"]), _ptr(d["br1"]), _ptr(d["wr2"]), _ptr(d["br2"]), _ptr(d["wq1"]), _ptr(d["bq1"]), _ptr(d["wq2"]),
-                                 _ptr(d["bq2"]), _ptr(wp), _ptr(bp), st), "car_round2q_pack")
-    logit, w, z = Guarded(S), Guarded(S), Guarded(b * R * D)
+    L.check(lib.car_round2q_pack(abi.ptr(d["wr1"]), abi.ptr(d["br1"]), abi.ptr(d["wr2"]), abi.ptr(d["br2"]), abi.ptr(d["wq1"]), abi.ptr(d["bq1"]), abi.ptr(d["wq2"]),
+                                 abi.ptr(d["bq2"]), abi.ptr(wp), abi.ptr(bp), st), "car_round2q_pack")
+    logit, w, z = Guarded((S,)), Guarded((S,)), Guarded((b * R * D,))
     if merged:
-        L.check(lib.car_attend_round2(_ptr(d["g"]), _ptr(d["uh"]), _ptr(wp), _ptr(bp), _ptr(d["e"]), D, b, V, R, P, w.ptr, z.ptr, D,
+        L.check(lib.car_attend_round2(abi.ptr(d["g"]), abi.ptr(d["uh"]), abi.ptr(wp), abi.ptr(bp), abi.ptr(d["e"]), D, b, V, R, P, w.ptr, z.ptr, D,
                                       logit.ptr if want_logits else None, st), "car_attend_round2")
     else:
-        L.check(lib.car_round2_logits_from_g(_ptr(d["g"]), _ptr(d["uh"]), _ptr(wp), _ptr(bp), b, V, R, P, logit.ptr, st), "car_round2_logits_from_g")
-        L.check(lib.car_attend(logit.ptr, None, 128, _ptr(d["e"]), D, b, V, R, P, None, 0.0, w.ptr, z.ptr, D, 1, None, None, None, None, st), "car_attend")
+        L.check(lib.car_round2_logits_from_g(abi.ptr(d["g"]), abi.ptr(d["uh"]), abi.ptr(wp), abi.ptr(bp), b, V, R, P, logit.ptr, st), "car_round2_logits_from_g")
+        L.check(lib.car_attend(logit.ptr, None, 128, abi.ptr(d["e"]), D, b, V, R, P, None, 0.0, w.ptr, z.ptr, D, 1, None, None, None, None, st), "car_attend")
     torch.cuda.synchronize()
     if merged and not want_logits:
         assert logit.untouched()
@@ -124,11 +84,6 @@ def _case(b, R, P, wscale):
         x = _inputs(b, R, P, wscale)
         _cache[key] = (x, _run(x, merged=True), _run(x, merged=False))
     return _cache[key]
-
-
-def _ratio(err, bound):
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
-    return r.max().item()
 
 
 @pytest.mark.parametrize("b,R,P,wscale", SHAPES)
@@ -198,16 +153,16 @@ def test_one_hot_ray_and_constant_ray():
 
 
 def test_refusals_write_nothing():
-    lib = _lib()
-    dev = _dev()
+    lib = abi.lib()
+    dev = abi.dev()
     b, R, P = 1, 3, 32
     S = b * V * R * 64
     g, uh, e = torch.zeros(S * 16, device=dev), torch.zeros(b * R * 128, device=dev), torch.zeros(S * D, device=dev)
     wp, bp = torch.zeros(lib.car_round2q_packed_floats(), device=dev), torch.zeros(lib.car_round2q_bias_floats(), device=dev)
-    logit, w, z = Guarded(S), Guarded(S), Guarded(b * R * D)
-    st = _stream()
+    logit, w, z = Guarded((S,)), Guarded((S,)), Guarded((b * R * D,))
+    st = abi.stream()
     call = lambda g_, uh_, wp_, bp_, e_, D_, P_, w_, z_: lib.car_attend_round2(g_, uh_, wp_, bp_, e_, D_, b, V, R, P_, w_, z_, D, logit.ptr, st)
-    ok = (_ptr(g), _ptr(uh), _ptr(wp), _ptr(bp), _ptr(e))
+    ok = (abi.ptr(g), abi.ptr(uh), abi.ptr(wp), abi.ptr(bp), abi.ptr(e))
     assert call(*ok, D, 8, w.ptr, z.ptr) == CAR_E_ARG and b"P" in lib.car_last_error()
     assert call(*ok, D, 40, w.ptr, z.ptr) == CAR_E_ARG
     assert call(*ok, 512, P, w.ptr, z.ptr) == CAR_E_ARG and b"576" in lib.car_last_error()
@@ -225,7 +180,7 @@ def _forward(precision, merged):
     from cross_attention_renderer_amd.engine import RenderEngine
     from golden_util import load_case
     from hip_harness import build_module, to_device
-    dev = _dev()
+    dev = abi.dev()
     c, inp, z, sd, _ = load_case("t2_c2")
     m = build_module(c, sd, dev)
     m._engine = RenderEngine(m)
