@@ -4,17 +4,16 @@ Every arithmetic step of the reference forward (models.py:206-621) is a HIP kern
 C ABI (``include/car_hip.h``); PyTorch is used for device memory, the stream handle and the (reference-identical) 4x4 pose
 algebra on the host.  There is no CPU or eager-PyTorch fallback: tensors must live on a ROCm device and the library must load.
 
-Two routes:
+Two routes, both dispatched by ``RenderEngine._render``; this module holds what they share (the caches and weight packing, the
+plan and lattice builders, the budgets, the kernel wrappers):
   * the reference's default configuration (n_view = 2, three pyramid levels, 576 channels; epipolar sampling or ``no_sample``'s depth
     sampling, with or without the second attention round) goes through the
     ONE-CALL C ABI — ``car_plan_build`` once per set of weights, ``car_project_maps`` once per stereo pair,
     ``car_render_forward`` per batch of rays (csrc/car_render.hip over csrc/car_pack.hip and csrc/car_lattice.hip: weight packing, the
-    lattice merge and the launch sequence are C++).  This
-    module only sizes the calls: rays (and, if need be, scenes) are chunked so that the per-call workspace fits the free device
-    memory (rays and scenes are independent, so this changes nothing);
-  * the other constructor variants (n_view 1 / 3, no_latent_concat, other widths) are sequenced here stage by stage
-    (``RenderEngine._staged``) — also the A/B partner of the first route in the tests.  The training forward (training.render_train)
-    is the same method with a save dict: the literal stage forms, every activation its backward reads kept.
+    lattice merge and the launch sequence are C++).  ``one_call.render`` only sizes the calls;
+  * the other constructor variants (n_view 1 / 3, no_latent_concat, other widths) are sequenced stage by stage
+    (``staged.forward``) — also the A/B partner of the first route in the tests.  The training forward (training.render_train)
+    is the same function with a ``staged.Saved`` record: the literal stage forms, every activation its backward reads kept.
 
 Stage map:
   a3 poses.pack_poses (host, torch.inverse like the reference)          a11-a13, a15, a17  car_linear (fp32 MFMA)
@@ -40,6 +39,14 @@ PLACE_PLAIN, PLACE_OWN, PLACE_OTHER2 = 0, 1, 2
 
 def _ptr(t: Optional[Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _levels(maps: List[Tensor], rows: Optional[slice] = None):
+    """Channel-last levels [n, H_l, W_l, C_l] as the C ABI takes them: (pointers, channels, heights, widths, number of levels);
+    ``rows``: the pointers lead to that slice of every level's maps."""
+    L = len(maps)
+    return ((ctypes.c_void_p * L)(*[(t if rows is None else t[rows]).data_ptr() for t in maps]), (ctypes.c_int * L)(*[t.shape[3] for t in maps]),
+            (ctypes.c_int * L)(*[t.shape[1] for t in maps]), (ctypes.c_int * L)(*[t.shape[2] for t in maps]), L)
 
 
 def _stream():
@@ -119,7 +126,7 @@ class RenderEngine:
     def __init__(self, module):
         self.m = module
         self.lib = _lib.load()
-        # _weights, _channel_last, _projected_maps, _poses, _plan_for, _plan16_for, _pair_for, _exchange_lattice; _packed_layers by packer
+        # _weights, _channel_last, _projected_maps, _poses, _plan_for, _plan16_for, _pair_for, staged._exchange_lattice; _packed_layers by packer
         self._packed, self._pyramid, self._gmaps, self._pose = _Cached(), _Cached(), _Cached(), _Cached()
         self._plan, self._plan16, self._pairs, self._xlat = _Cached(), _Cached(), _Cached(), _Cached()
         self._layer_packs: Dict[str, _Cached] = collections.defaultdict(_Cached)
@@ -146,6 +153,7 @@ class RenderEngine:
         # attention as two launches (CAR_PHASE_SPLIT_SECOND_ROUND: A/B measurements and tests)
         self.second_round_merged = True
         self.wgrad_fp32 = False        # training: True keeps the wide layers' weight gradients on the fp32 matrix pipe (CAR_WGRAD_FP32) instead of bf16 x 3
+        self.scatter_atomics = False   # training: True scatters the pyramid's gradient with fp32 atomics, one launch per gather (A/B and tests); False = taps binned by texel
         self.fuse_kq = True            # staged route: key / query chains and the first round's logits in one kernel (car_key_query_logits); False = five launches (A/B)
         # three-view exchange, first + second layer: "rows" = the fused per-sample kernel's source pass over the rows (car_fused_rows, default);
         # True = the gather-fed linear kernel (car_lattice_encode_linear); False = two launches (A/B partners)
@@ -315,8 +323,7 @@ class RenderEngine:
             with torch.cuda.stream(side):
                 for dst, t in zip(maps, z):
                     dst.copy_(t.detach().permute(0, 2, 3, 1))
-                ptrs = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in maps])
-                _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), ptrs, _ptr(pair), ctypes.c_void_p(side.cuda_stream)),
+                _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), _levels(maps)[0], _ptr(pair), ctypes.c_void_p(side.cuda_stream)),
                            "car_project_maps")
                 done = torch.cuda.Event()
                 done.record(side)
@@ -374,11 +381,8 @@ class RenderEngine:
 
     def gather_encode(self, gmaps: List[Tensor], wpt: Tensor, pixel_val: Tensor, grid_in: Tensor, ptenc: Tensor,
                       V: int, pts: int, out: Tensor, ld_out: int):
-        L = len(gmaps)
-        ptrs = (ctypes.c_void_p * L)(*[g.data_ptr() for g in gmaps])
-        hs = (ctypes.c_int * L)(*[g.shape[1] for g in gmaps])
-        ws = (ctypes.c_int * L)(*[g.shape[2] for g in gmaps])
-        _lib.check(self.lib.car_gather_encode(ptrs, hs, ws, L, gmaps[0].shape[3], _ptr(pixel_val), _ptr(grid_in),
+        ptrs, cs, hs, ws, L = _levels(gmaps)
+        _lib.check(self.lib.car_gather_encode(ptrs, hs, ws, L, cs[0], _ptr(pixel_val), _ptr(grid_in),
                                               _ptr(ptenc), _ptr(wpt), gmaps[0].shape[0], V, pts, _ptr(out), ld_out,
                                               _stream()), "car_gather_encode")
 
@@ -474,7 +478,7 @@ class RenderEngine:
         return self._packed_layers("car_kq_pack", ("key_map_2", "query_embed", "query_embed_2"),
                                    (self.lib.car_kq_tail_floats(), self.lib.car_kq_bias_floats()), device)
 
-    # ------------------------------------------------------------------ the one-call route (default configuration)
+    # ------------------------------------------------------------------ plans, lattices and budgets (the one-call route; prefetch)
     def _dims(self, b: int, R: int, z: List[Tensor]) -> "_lib.CarDims":
         m = self.m
         d = _lib.CarDims()
@@ -542,14 +546,14 @@ class RenderEngine:
     def _pair_for(self, plan: Tensor, z: List[Tensor], device, s0: int, s1: int, R: int):
         """car_project_maps for scenes [s0, s1): the first point-MLP layer applied per texel of the pyramid and every level summed on the
         common lattice, once per stereo pair (and plan).  Returns (buffer, its car_dims).  One buffer is cached: the whole batch
-        normally; when the lattices of all scenes do not fit the device memory (_render_one_call) the last group's."""
+        normally; when the lattices of all scenes do not fit the device memory (one_call.render) the last group's."""
         maps = self._channel_last(z)
         V = self.m.n_view
         d = self._dims(s1 - s0, R, z)
 
         def build():
             pair = torch.empty(self.lib.car_gmaps_floats(ctypes.byref(d)), device=device, dtype=torch.float32)
-            ptrs = (ctypes.c_void_p * len(maps))(*[t[s0 * V:s1 * V].data_ptr() for t in maps])
+            ptrs = _levels(maps, slice(s0 * V, s1 * V))[0]
             _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), ptrs, _ptr(pair), _stream()), "car_project_maps")
             return pair
         return self._pairs.get([plan, *z], (s0, s1), build), d
@@ -602,135 +606,6 @@ class RenderEngine:
                 # the reference returns pixel_val on the CPU (models.py:570), forcing a device sync on every call; here it stays on the
                 # device unless debug is set
                 "pixel_val": t["pixel_val"].cpu() if debug else t["pixel_val"], "z": z}
-
-    def _render_one_call(self, inp, z, b: int, R: int, debug: bool) -> Dict[str, Tensor]:
-        m, lib = self.m, self.lib
-        V, P = m.n_view, m.npoints
-        poses, uv, steps = self._rays_in(inp, b, R)
-        dev = uv.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        n = b * V
-        d_all = self._dims(b, R, z)
-        plan = self._plan_for(d_all, dev)
-        f16 = self.render_precision == "fp16"
-        plan16 = self._plan16_for(d_all, dev) if f16 else None
-        lh, lw, _ = self._lattice_shape(d_all)
-        lattice_scene = V * 2 * lh * lw * 576                                                    # floats per scene
-
-        phases = 1 | 2 | (0 if self.first_round_parts else 4) | (0 if self.second_round_merged else 8)
-
-        def ws_bytes(nb, nr):
-            return lib.car_workspace_bytes(ctypes.byref(self._dims(nb, nr, z)))
-
-        def pair_bytes(nb):
-            return 4 * lib.car_gmaps_floats(ctypes.byref(self._dims(nb, R, z)))
-
-        # Scenes per lattice buffer: all of them (2.5 GB per scene at 256 x 256, 5.6 GB at 384 x 384) unless that would leave less than
-        # half of the usable device memory for the workspace; then the scenes are rendered in groups, each with its own
-        # car_project_maps (re-done on every forward: the one cached buffer holds the last group — a fallback, not a fast path).
-        self._channel_last(z)
-        pg = b
-        if not self._pairs.holds([plan, *z], (0, b)):
-            # what is live while a group renders: ONE lattice buffer (the previous group's is dropped before the next is allocated, below)
-            # and the workspace.  The cached buffer and workspace of an earlier forward count as available because both are released
-            # before this forward allocates (a stale workspace sized for another split would otherwise sit beside the new pair)
-            self._pairs.drop()
-            if pair_bytes(b) > (self._free_budget(dev)) // 2:
-                self._work = None                                      # grouped fallback: start from everything this engine can free
-            usable = self._free_budget(dev)
-            if self.max_pair_bytes is not None:
-                usable = min(usable, 2 * int(self.max_pair_bytes))
-            while pg > 1 and pair_bytes(pg) > usable // 2:
-                pg = (pg + 1) // 2
-
-        # inside a lattice group — scenes per call: any number (the fused kernel addresses the lattice of ONE view and padding mode with
-        # 32-bit offsets); max_level_bytes lets tests force smaller calls.  Rays per call: the workspace (~0.44 MB per ray at 64 samples)
-        # must fit the free memory.  Rays and scenes are independent, so every split is exact.
-        gs_cap = pg if self.max_level_bytes is None else max(1, min(pg, self.max_level_bytes // (4 * lattice_scene)))
-
-        out = {"rgb": torch.empty(b, 1, R, 3, **f32), "valid_mask": torch.empty(b, R, 1, **f32), "depth_ray": torch.empty(b, R, 1, **f32),
-               "at_wt": torch.empty(n, R, P, **f32), "at_wt_max": torch.empty(n, R, 1, device=dev, dtype=torch.int32),
-               "coords": torch.empty(n, R, 9, **f32), "pixel_val": torch.empty(n, R, P, 2, **f32)}
-        lead = {"rgb": 1, "valid_mask": 1, "depth_ray": 1, "at_wt": V, "at_wt_max": V, "coords": V, "pixel_val": V}   # rows per scene
-        order = ("rgb", "valid_mask", "depth_ray", "at_wt", "at_wt_max", "coords", "pixel_val")
-        st = _stream()
-        calls = 0
-        d_last = None
-        self.last_pair_groups = -(-b // pg)
-        pair = work = None
-        for p0 in range(0, b, pg):
-            p1 = min(b, p0 + pg)
-            if pg < b:
-                # several lattice groups (memory pressure): the previous group's buffer must be gone before the next one is allocated —
-                # _pair_for drops the engine's reference, this drops the loop's — and the workspace is re-sized against what is then free
-                pair = work = None
-                self._work = None
-            pair, d_pair = self._pair_for(plan, z, dev, p0, p1, R)
-            gmeta_ptr = pair.data_ptr() + 4 * lib.car_gmeta_offset(ctypes.byref(d_pair))
-            budget = self._workspace_budget(dev)
-            gs = min(gs_cap, p1 - p0)
-            while gs > 1 and ws_bytes(gs, R) > budget:
-                gs = (gs + 1) // 2
-            rc = R
-            if ws_bytes(gs, R) > budget:
-                per_ray = ws_bytes(gs, 4800) / 4800.0
-                rc = int(budget / per_ray) // 48 * 48            # whole sample tiles of the fused kernel (24 rays each)
-                if rc < 48:
-                    raise RuntimeError(f"forward: {budget / 2**20:.0f} MiB of workspace cannot hold even 48 rays "
-                                       f"({ws_bytes(gs, 48) / 2**20:.0f} MiB needed): free device memory")
-            need = ws_bytes(gs, min(rc, R))
-            if self._work is None or self._work.numel() * 4 < need:
-                self._work = None
-                self._work = torch.empty(need // 4, **f32)
-            work = self._work
-            for s0 in range(p0, p1, gs):
-                s1 = min(p1, s0 + gs)
-                for r0 in range(0, R, rc):
-                    r1 = min(R, r0 + rc)
-                    d = self._dims(s1 - s0, r1 - r0, z)
-                    whole = (r0 == 0 and r1 == R)
-                    if whole:
-                        tgt = {k: out[k][s0 * lead[k]:s1 * lead[k]] for k in order}            # contiguous scene slices: written in place
-                        uv_c = uv[s0:s1]
-                    else:
-                        tgt = {k: torch.empty((s1 - s0) * lead[k], r1 - r0, *out[k].shape[2 if k != "rgb" else 3:],
-                                              device=dev, dtype=out[k].dtype) for k in order}
-                        uv_c = uv[s0:s1, r0:r1].contiguous()
-                    ci = _lib.CarInputs()
-                    ci.poses = poses.data_ptr() + 4 * 96 * s0 * V
-                    ci.uv = uv_c.data_ptr()
-                    ci.lattice = pair.data_ptr() + 4 * (s0 - p0) * lattice_scene
-                    ci.gmeta = gmeta_ptr
-                    ci.steps = steps.data_ptr()
-                    co = _lib.CarOutputs(*[tgt[k].data_ptr() for k in order])
-                    if f16:
-                        _lib.check(lib.car_render_forward_f16(ctypes.byref(d), _ptr(plan), _ptr(plan16), ctypes.byref(ci), ctypes.byref(co),
-                                                              _ptr(work), work.numel() * 4, phases, st), "car_render_forward_f16")
-                    else:                                       # phases == 3 is car_render_forward's own call
-                        _lib.check(lib.car_render_forward_phase(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co),
-                                                                _ptr(work), work.numel() * 4, phases, st), "car_render_forward_phase")
-                    if not whole:
-                        for k in order:
-                            dst = out[k][:, 0] if k == "rgb" else out[k]
-                            dst[s0 * lead[k]:s1 * lead[k], r0:r1] = tgt[k]
-                    calls += 1
-                    d_last = d
-        self.last_calls = calls
-        self.last_precision = "fp16" if f16 else "fp32"
-        res = self._outputs(inp, z, out, debug)
-        if debug:
-            if calls != 1:
-                raise RuntimeError("debug=True needs the forward to fit one car_render_forward call (intermediates live in its workspace)")
-
-            def ws(name, *shape):
-                off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
-                _lib.check(lib.car_workspace_find(ctypes.byref(d_last), name.encode(), ctypes.byref(off), ctypes.byref(cnt)), "car_workspace_find")
-                return work[off.value:off.value + cnt.value].view(*shape).clone()
-            res["stages"] = {"rays": ws("rays", n, R, 12), "pt": ws("pt", n, R, P, 3), "local_coords": None,
-                             "g": ws("g", n, R, P, 16), "interp_val": ws("e", n, R, P, 576),
-                             "z1": ws("z1", b, R, 288),
-                             "at_wt2": ws("at_wt2", n, R, P) if m.repeat_attention else None, "poses": poses}
-        return res
 
     # ------------------------------------------------------------------ stage timing (csrc/car_render.hip)
     def profile(self, on: bool) -> None:
@@ -790,11 +665,7 @@ class RenderEngine:
 
     def gather(self, maps: List[Tensor], grid: Tensor, pts: int, mode: int, place: int, V: int, out: Tensor,
                ld_out: int, col_out: int, run: int = 1):
-        L = len(maps)
-        ptrs = (ctypes.c_void_p * L)(*[m.data_ptr() for m in maps])
-        cs = (ctypes.c_int * L)(*[m.shape[3] for m in maps])
-        hs = (ctypes.c_int * L)(*[m.shape[1] for m in maps])
-        ws = (ctypes.c_int * L)(*[m.shape[2] for m in maps])
+        ptrs, cs, hs, ws, L = _levels(maps)
         _lib.check(self.lib.car_gather_bilinear(ptrs, cs, hs, ws, L, maps[0].shape[0], _ptr(grid), pts, run, mode, place, V,
                                                 _ptr(out), ld_out, col_out, _stream()), "car_gather_bilinear")
 
@@ -819,332 +690,12 @@ class RenderEngine:
             raise ValueError(f"input has {V} context views, module was built with n_view={m.n_view}")
         why = self._one_call_refusal(b, R, z)
         if why is None:
-            return self._render_one_call(inp, z, b, R, debug)
+            return one_call.render(self, inp, z, b, R, debug)
         if self.render_precision == "fp16":
             raise ValueError(f"render_precision='fp16' exists on the one-call route only, and this forward cannot take it: {why}. "
                              "Set render_precision='fp32' for this configuration.")
         self.last_precision = "fp32"
-        return self._staged(inp, z, debug)
+        return staged.forward(self, inp, z, debug)
 
-    def _staged(self, inp, z: List[Tensor], debug: bool = False, save: Optional[dict] = None) -> Dict[str, Tensor]:
-        """The stage-by-stage forward of every configuration the one-call route does not take.
 
-        ``save=None``: inference, with the fused stage kernels the engine's switches select and buffers reused where nothing is kept.
-        ``save`` a dict: the training forward (training.render_train) — the literal forms (gather -> GEMM, five key / query launches, the
-        unfused second round, a copy of the decoder's state per block), every activation its backward reads stored into ``save``."""
-        m, lib = self.m, self.lib
-        keep = save is not None
-        dev = inp["query"]["uv"].device
-        b, V = inp["context"]["rgb"].shape[:2]
-        R = inp["query"]["uv"].shape[2]
-        P, H, W = m.npoints, m.H, m.W
-        n, S, bR = b * V, b * V * R * P, b * R
-        st = _stream()
-        f32 = dict(device=dev, dtype=torch.float32)
-        # a3: pose algebra on the host, exactly the reference's torch calls
-        poses, uv, steps = self._rays_in(inp, b, R)
-        pk = self._weights(dev)
-        maps = self._channel_last(z)
-        C = sum(t.shape[3] for t in maps)
-        mode = _mode(m)
-        Dl, hid = m.latent_dim, m.phi.d_hidden
-        Ce = V * (C // 2) if mode in ("concat2", "concat3") else C
-
-        # a4-a6: rays (constant with respect to every parameter, like the rest of the geometry)
-        rays = torch.empty(n, R, 12, **f32)
-        coords9 = torch.empty(n, R, 9, **f32)
-        ld_phi = _round_up(9 * V, 4)
-        phi_x = torch.zeros(bR, ld_phi, **f32)
-        _lib.check(lib.car_ray_setup(_ptr(poses), _ptr(uv), b, V, R, H, W, P, int(m.no_sample), _ptr(steps),
-                                     _ptr(rays), _ptr(coords9), _ptr(phi_x), ld_phi, st), "car_ray_setup")
-
-        # a6, a8, a9, a13: samples
-        pixel_val = torch.empty(n, R, P, 2, **f32)
-        pt = torch.empty(n, R, P, 3, **f32)
-        g = torch.empty(S, 16, **f32)
-        proj = mode == "concat2" and self.project_maps and not keep     # the first point-MLP layer per texel (car_gather_encode)
-        grid_in = torch.empty(n, R, P, V, 2, **f32) if mode == "concat2" else None
-        pt_in = torch.empty(n, R, P, V, 3, **f32) if mode == "concat3" else None
-        x1, ld1, col = None, 0, 0
-        if proj or mode == "concat3":
-            ld1 = 4                                   # only the 3 point channels: [S*V, 4]; the three-view route assembles its rows below
-            x1 = torch.zeros(S * V, ld1, **f32)
-        elif mode in ("concat2", "single"):
-            col = C                                   # features in [0, C), point channels in [C, C + 3) (two views) or [C, C + 6) (one)
-            ld1 = _round_up(C + (3 if mode == "concat2" else 6), 32)
-            x1 = torch.empty(S * V, ld1, **f32)
-            if keep:
-                x1[:, C + (3 if mode == "concat2" else 6):].zero_()     # the row padding: the backward reads whole rows
-        _lib.check(lib.car_sample_setup(_ptr(poses), _ptr(rays), _ptr(steps), b, V, R, P, H, W, int(m.no_sample),
-                                        _ptr(pixel_val), _ptr(pt), _ptr(g), _ptr(grid_in), _ptr(x1), ld1, col, _ptr(pt_in), st),
-                   "car_sample_setup")
-
-        # a7, a9-a11: per-sample features e
-        h1 = grid_other = cross = None
-        kmajor = False
-        if proj:
-            gmaps, wpt = self._projected_maps(maps, dev)
-            h1 = torch.empty(S * V, C, **f32)
-            self.gather_encode(gmaps, wpt, pixel_val, grid_in, x1, V, R * P, h1, C)
-        elif mode == "concat2":
-            self.gather(maps, pixel_val, R * P, 0, PLACE_OWN, V, x1, ld1, 0, run=P)
-            gi = grid_in.view(b, V, R, P, V, 2)
-            # pixel_val_stack (models.py:316): map (b, s) is sampled where the *other* line's points land in view s
-            grid_other = torch.stack([gi[:, 1, :, :, 0], gi[:, 0, :, :, 1]], dim=1).contiguous()
-            self.gather(maps, grid_other, R * P, 1, PLACE_OTHER2, V, x1, ld1, 0, run=P)
-            h1 = torch.empty(S * V, C, **f32)
-            self.linear(x1, ld1, pk["query_encode_latent"], h1, C, S * V, RELU_OUT)
-        if mode == "concat2":
-            e = torch.empty(S, Ce, **f32)
-            self.linear(h1, C, pk["query_encode_latent_2"], e, C // 2, S * V)
-        elif mode == "concat3":
-            k3 = {} if keep else None
-            e = self._encode_three_views(maps, poses, pixel_val, x1, pt_in, b, R, P, H, W, C, pk, keep=k3)
-            kmajor = self.project_maps and not keep                   # the inference path of _encode_three_views leaves e component-major
-            if keep:
-                x1, h1, ld1, cross = k3["x3"], k3["h1"], k3["ld"], k3["cross"]
-        elif mode == "single":
-            self.gather(maps, pixel_val, R * P, 0, PLACE_PLAIN, V, x1, ld1, 0, run=P)
-            e = torch.empty(S, Ce, **f32)
-            self.linear(x1, ld1, pk["update_val_merge"], e, Ce, S)
-        else:                                                          # no_latent_concat: the gathered features are e
-            e = torch.empty(S, Ce, **f32)
-            self.gather(maps, pixel_val, R * P, 0, PLACE_PLAIN, V, e, Ce, 0, run=P)
-        if keep:
-            save.update(x1=x1, h1=h1, grid_other=grid_other, cross=cross, maps=maps, ld1=ld1, ld_phi=ld_phi, Ce=Ce)
-        x1 = h1 = None
-
-        # a12: keys;  a13: geometric query.  The value projection (latent_value, no nonlinearity before the weighted sum)
-        # commutes with the attention average: sum_s w_s (Wv e_s + bv) = Wv (sum_s w_s e_s) + bv because the softmax
-        # weights of a ray sum to 1, so it is applied once per ray after the reduction instead of once per sample.
-        kmap = pk["key_map.kmajor" if kmajor else "key_map"]
-        q = torch.empty(S, 128, **f32)
-        key = logit1 = None
-        if (not keep and self.fuse_kq and self.linear_x3 and not self.linear_flags and kmap.x3 is not None and kmap.N == 128 and m.hidden_dim == 128
-                and Ce % 4 == 0 and e.data_ptr() % 16 == 0 and S >= self.linear_x3_min_rows):
-            # key_map -> relu -> key_map_2, query_embed -> relu -> query_embed_2 and the first round's logits in one kernel: the 128-wide
-            # k1 / key / q1 rows are never written (csrc/car_linear16.hip, KQ instance)
-            tiles, bias_k1 = kmap.x3
-            tail, tail_bias = self._kq_weights(dev)
-            logit1 = torch.empty(S, **f32)
-            rc = lib.car_key_query_logits(_ptr(e), Ce, _ptr(tiles), _ptr(bias_k1), Ce, _ptr(g), _ptr(tail), _ptr(tail_bias), S, _ptr(q), _ptr(logit1), st)
-            if self._lds_refused(rc, "car_key_query_logits"):
-                self.fuse_kq, logit1 = False, None                     # LDS reservation refused: the five separate launches below
-        if logit1 is None:
-            k1 = torch.empty(S, 128, **f32)
-            self.linear(e, Ce, kmap, k1, 128, S, RELU_OUT)
-            key = torch.empty(S, 128, **f32)
-            self.linear(k1, 128, pk["key_map_2"], key, 128, S)
-            q1 = torch.empty(S, 128, **f32) if keep else k1             # inference: the query's hidden layer in k1's buffer
-            self.linear(g, 16, pk["query_embed"], q1, 128, S, RELU_OUT)
-            self.linear(q1, 128, pk["query_embed_2"], q, 128, S)
-            if keep:
-                save.update(k1=k1, key=key, q1=q1)
-
-        # a14 + a16: attention round 1, depth read-out
-        at_wt = torch.empty(n, R, P, **f32)
-        depth = torch.empty(b, R, 1, **f32)
-        amax = torch.empty(n, R, 1, dtype=torch.int32, device=dev)
-        ebar1 = torch.empty(bR, Ce, **f32)
-        lg, qr = (logit1, None) if logit1 is not None else (key, q)    # the logits of car_key_query_logits, or keys and queries
-        _lib.check(lib.car_attend(_ptr(lg), _ptr(qr), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt), _ptr(ebar1),
-                                  Ce, 1, _ptr(pt), _ptr(poses), _ptr(depth), _ptr(amax), st), "car_attend")
-        lv = pk["latent_value.kmajor" if kmajor else "latent_value"]
-        zrep = torch.empty(bR, V * Dl, **f32)
-        at_wt2 = None
-        if m.repeat_attention:
-            z1 = torch.empty(bR, Dl, **f32)
-            self.linear(ebar1, Ce, lv, z1, Dl, bR)
-            # a15: second round; the z_embed half of query_repeat_embed is per ray, the local_coords half per sample
-            hb = torch.empty(bR, 128, **f32)
-            self.linear(z1, Dl, pk["encode_latent"], hb, 128, bR)
-            uh = torch.empty(bR, 128, **f32)
-            self.linear(hb, 128, pk["query_repeat_embed.h"], uh, 128, bR)
-            at_wt2 = torch.empty(n, R, P, **f32)
-            ebar2 = torch.empty(bR, Ce, **f32) if keep else ebar1      # inference: round 2's average in round 1's buffer
-            if self.fuse_round2 and not keep:
-                # ug = Wr1[:,128:] g + br1, q2 = Wr2 relu(ug + uh) + b and <q2, qry>/16 in one kernel: neither is written
-                r2w, r2b = self._round2_weights(dev)
-                logit2 = torch.empty(S, **f32)
-                _lib.check(lib.car_round2_logits(_ptr(g), _ptr(uh), _ptr(q), _ptr(r2w), _ptr(r2b),
-                                                 b, V, R, P, _ptr(logit2), st), "car_round2_logits")
-                _lib.check(lib.car_attend(_ptr(logit2), None, 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
-                                          _ptr(ebar2), Ce, 1, None, None, None, None, st), "car_attend")
-            else:
-                k1r = torch.empty(S, 128, **f32)
-                self.linear(g, 16, pk["query_repeat_embed.g"], k1r, 128, S)
-                _lib.check(lib.car_add_ray_bias_relu(_ptr(k1r), _ptr(uh), b, V, R, P, 128, st), "car_add_ray_bias_relu")
-                key2 = torch.empty(S, 128, **f32) if keep or key is None else key   # inference: round 2's keys in round 1's buffer
-                self.linear(k1r, 128, pk["query_repeat_embed_2"], key2, 128, S)
-                _lib.check(lib.car_attend(_ptr(key2), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
-                                          _ptr(ebar2), Ce, 1, None, None, None, None, st), "car_attend")
-                if keep:
-                    save.update(k1r=k1r, key2=key2)
-            # z = (Wv ebar2 + bv) + V * z1   (models.py:561-565: "+ z_local" per view, then the view sum)
-            if keep:
-                _lib.check(lib.car_add(_ptr(zrep), V * Dl, _ptr(z1), Dl, float(V), None, 0, 0.0, bR, Dl, st), "car_add")
-                save.update(z1=z1, hb=hb, at_wt2=at_wt2, ebar2=ebar2)
-            else:
-                zrep.view(bR, V, Dl)[:, 0] = z1 * float(V)
-            self.linear(ebar2, Ce, lv, zrep, V * Dl, bR, ACCUM)
-        else:
-            self.linear(ebar1, Ce, lv, zrep, V * Dl, bR)
-        # the per-view replication of models.py:541, 565, 605-606
-        if keep:
-            for v in range(1, V):
-                _lib.check(lib.car_add(_ptr(zrep[:, v * Dl:]), V * Dl, _ptr(zrep), V * Dl, 1.0, None, 0, 0.0, bR, Dl, st), "car_add")
-        elif V > 1:
-            zv = zrep.view(bR, V, Dl)
-            zv[:, 1:] = zv[:, :1]
-
-        # a17: light-field decoder
-        x = torch.empty(bR, hid, **f32)
-        net = None if keep else torch.empty(bR, hid, **f32)
-        self.linear(phi_x, ld_phi, pk["phi.lin_in"], x, hid, bR)
-        xas, nets = [], []
-        for i in range(m.phi.n_blocks):
-            if keep:                                                   # the backward reads every block's input and hidden activation
-                x, net = x.clone(), torch.empty(bR, hid, **f32)
-                xas.append(x)
-                nets.append(net)
-            self.linear(zrep, V * Dl, pk[f"phi.lin_z.{i}"], x, hid, bR, ACCUM)
-            self.linear(x, hid, pk[f"phi.blocks.{i}.fc_0"], net, hid, bR, RELU_IN)
-            if keep:
-                x = x.clone()
-            self.linear(net, hid, pk[f"phi.blocks.{i}.fc_1"], x, hid, bR, RELU_IN | ACCUM)
-        out3 = torch.empty(bR, 4, **f32)
-        self.linear(x, hid, pk["phi.lin_out"], out3, 4, bR, RELU_IN)
-
-        # a18: valid mask, white background
-        rgb = torch.empty(b, 1, R, 3, **f32)
-        valid = torch.empty(b, R, 1, **f32)
-        _lib.check(lib.car_finalize(_ptr(rays), _ptr(out3), 4, b, V, R, _ptr(rgb), _ptr(valid), st), "car_finalize")
-        if keep:
-            save.update(e=e, q=q, at_wt=at_wt, ebar1=ebar1, g=g, pt=pt, poses=poses, rays=rays, phi_x=phi_x, pixel_val=pixel_val,
-                        zrep=zrep, xas=xas, nets=nets, x3=x, valid=valid)
-        out = self._outputs(inp, z, dict(rgb=rgb, valid_mask=valid, depth_ray=depth, at_wt=at_wt, at_wt_max=amax, coords=coords9,
-                                         pixel_val=pixel_val), debug)
-        if debug:
-            out["stages"] = {"rays": rays, "pt": pt.view(n, R, P, 3),
-                             "local_coords": g.view(n, R, P, 16),
-                             # the reference's channel order e[s, 3 ch + k] (models.py:446) when e was kept component-major
-                             "interp_val": (e.view(S, 3, Ce // 3).permute(0, 2, 1).reshape(n, R, P, Ce) if kmajor else e.view(n, R, P, Ce)),
-                             "z_final": zrep[:, :Dl].reshape(b, R, Dl), "at_wt2": at_wt2, "poses": poses}
-        return out
-
-    def _exchange_lattice(self, gmaps, ptrs, hs, ws, n_maps, C, dev):
-        """The projected levels of the three-view exchange summed on their common lattice (car_merge_lattice), cached on those levels;
-        None when the levels have no common lattice, the channel count is not the lattice kernels' 576, or it would not fit."""
-        if C != 576:
-            return None
-
-        def build():
-            L = len(gmaps)
-            lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-            if self.lib.car_merge_lattice(ptrs, hs, ws, L, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad), _stream()) != 0:
-                return None
-            floats = n_maps * 2 * lh.value * lw.value * C
-            if n_maps * 2 * lh.value * lw.value >= 2 ** 31 - 1 or floats * 4 > self._free_budget(dev) // 2:
-                return None
-            lattice = torch.empty(floats, device=dev, dtype=torch.float32)
-            gmax = torch.empty(1, device=dev, dtype=torch.float32)     # largest |lattice value|: taken in the merge's own pass
-            _lib.check(self.lib.car_merge_lattice_max(ptrs, hs, ws, L, n_maps, _ptr(lattice), _ptr(gmax), _stream()), "car_merge_lattice_max")
-            return lattice, lh.value, lw.value, lpad.value, gmax
-        return self._xlat.get(gmaps, (), build)
-
-    def _encode_three_views(self, maps, poses, pixel_val, ptenc, pt_in, b, R, P, H, W, C, pk, keep=None):
-        """Cross-view exchange for three context views (models.py:345-475), restated literally: for the samples of context c
-        the row is the channel-interleaved concatenation of enc(own features, point in frame c) and, for every other view o
-        in ascending order, enc(features of view o where context o's points — moved into frame c, projected with view o's
-        intrinsics — land in image o, those points in frame c).  All arithmetic is in HIP kernels (gather, projection, the two
-        1x1 layers); torch only moves rows into place.  ``keep`` (a dict): the training forward's saves — the 579-wide rows, the first
-        layer's activations and every cross-view gather's grid (training.render_train)."""
-        V, pts = 3, R * P
-        S = b * V * pts
-        dev = pixel_val.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        if keep is None and self.project_maps:
-            # inference: the first layer applied per texel (car_project_maps' arithmetic, as on the two-view route): the 579 -> 576 GEMM over
-            # 3 S rows — two thirds of this variant's FLOPs — becomes one gather over the projected pyramid with an explicit row list
-            gmaps, wpt = self._projected_maps(maps, dev)
-            n = b * V
-            # the row lists (map | padding mode, grid point, point encoding per (sample, component)) in one launch (car_exchange_rows)
-            src = torch.empty(b, V, pts, 3, dtype=torch.int32, device=dev)
-            rgrid = torch.empty(b, V, pts, 3, 2, **f32)
-            rpe = torch.empty(b, V, pts, 3, 4, **f32)
-            _lib.check(self.lib.car_exchange_rows(_ptr(poses), _ptr(pixel_val), _ptr(pt_in), _ptr(ptenc), b, V, pts, H, W, _ptr(src), _ptr(rgrid),
-                                                  _ptr(rpe), _stream()), "car_exchange_rows")
-            L = len(gmaps)
-            ptrs = (ctypes.c_void_p * L)(*[g.data_ptr() for g in gmaps])
-            hs = (ctypes.c_int * L)(*[g.shape[1] for g in gmaps])
-            ws = (ctypes.c_int * L)(*[g.shape[2] for g in gmaps])
-            lat = self._exchange_lattice(gmaps, ptrs, hs, ws, n, C, dev)
-            layer2 = pk["query_encode_latent_2"]
-            if lat is not None and self.fuse_exchange == "rows" and not self.linear_flags and C == 576:
-                # the fused per-sample kernel's source pass over the exchange's rows (car_fused_rows): its gather machinery and W2 in one
-                # launch, e written [S, 3, 288]; the lattice's largest magnitude (the first layer's fp16 scale) is taken once per lattice
-                lattice, lh, lw, lpad, gmax = lat
-                blob, fbias, fwpt = self._exchange_pack(dev)
-                enc = torch.empty(S * 3, C // 2, **f32)
-                rc = self.lib.car_fused_rows(_ptr(lattice), lh, lw, lpad, _ptr(gmax), _ptr(fwpt), _ptr(blob), _ptr(fbias), _ptr(src), _ptr(rgrid), _ptr(rpe),
-                                             n, R, P, 3, _ptr(enc), _stream())
-                if not self._lds_refused(rc, "car_fused_rows"):
-                    return enc.view(S, 3 * (C // 2))
-                self.fuse_exchange = True                          # LDS reservation refused: the gather-fed linear kernel, then two launches
-            if lat is not None and self.fuse_exchange and self.linear_x3 and not self.linear_flags and layer2.x3 is not None:
-                # first AND second exchange layer in one kernel: the lattice rows are gathered 32 channels at a time into the matrix pipe's
-                # operands, the 576-wide rows (2.3 KB x 3 S) are never written (csrc/car_linear16.hip, GATHER instance; bit-identical
-                # to the two launches below)
-                lattice, lh, lw, lpad, _ = lat
-                tiles, bias2 = layer2.x3
-                enc = torch.empty(S * 3, C // 2, **f32)
-                rc = self.lib.car_lattice_encode_linear(_ptr(lattice), lh, lw, lpad, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3,
-                                                        _ptr(tiles), _ptr(bias2), C, C // 2, _ptr(enc), C // 2, 0, _stream())
-                if not self._lds_refused(rc, "car_lattice_encode_linear"):
-                    return enc.view(S, 3 * (C // 2))
-                self.fuse_exchange = False
-            h1 = torch.empty(S * 3, C, **f32)
-            if lat is not None:                                     # four taps of the merged lattice per row (DESIGN.md 4.3) instead of twelve
-                lattice, lh, lw, lpad, _ = lat
-                _lib.check(self.lib.car_lattice_encode_rows(_ptr(lattice), lh, lw, lpad, C, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3,
-                                                            _ptr(h1), C, _stream()), "car_lattice_encode_rows")
-            else:
-                _lib.check(self.lib.car_gather_encode_rows(ptrs, hs, ws, L, C, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3, _ptr(h1), C,
-                                                           _stream()), "car_gather_encode_rows")
-            enc = torch.empty(S * 3, C // 2, **f32)
-            self.linear(h1, C, pk["query_encode_latent_2"], enc, C // 2, S * 3)
-            return enc.view(S, 3 * (C // 2))                          # component-major: the consumers' weights are permuted (_weights)
-        ld = _round_up(C + 3, 32)
-        x3 = torch.empty(S * 3, ld, **f32)
-        x3v = x3.view(b, V, pts, 3, ld)                     # [scene, context c, point, component k, channel]
-        pe = ptenc.view(b, V, pts, V, 4)                    # tanh(nan_to_num(T_s pt)/5): [scene, context, point, frame s]
-        pin = pt_in.view(b, V, pts, V, 3)
-        tmp = torch.empty(S, C, **f32)
-        self.gather(maps, pixel_val, pts, 0, PLACE_PLAIN, V, tmp, C, 0, run=P)
-        x3v[:, :, :, 0, :C] = tmp.view(b, V, pts, C)
-        per_view = [[t.view(b, V, *t.shape[1:])[:, o].contiguous() for t in maps] for o in range(V)]
-        tmp2 = torch.empty(b * pts, C, **f32)
-        grid = torch.empty(b, pts, 2, **f32)
-        for c in range(V):
-            x3v[:, c, :, 0, C:C + 3] = pe[:, c, :, c, :3]
-            k = 1
-            for o in range(V):
-                if o == c:
-                    continue
-                q = pin[:, o, :, c, :].contiguous()         # context o's points expressed in frame c
-                _lib.check(self.lib.car_project_points(_ptr(poses), _ptr(q), b, pts, V, o, H, W, _ptr(grid), _stream()),
-                           "car_project_points")
-                self.gather(per_view[o], grid, pts, 1, PLACE_PLAIN, 1, tmp2, C, 0, run=P)
-                if keep is not None:
-                    keep.setdefault("cross", []).append((c, o, k, grid.clone()))
-                x3v[:, c, :, k, :C] = tmp2.view(b, pts, C)
-                x3v[:, c, :, k, C:C + 3] = pe[:, o, :, c, :3]
-                k += 1
-        h1 = torch.empty(S * 3, C, **f32)
-        self.linear(x3, ld, pk["query_encode_latent"], h1, C, S * 3, RELU_OUT)
-        enc = torch.empty(S * 3, C // 2, **f32)
-        self.linear(h1, C, pk["query_encode_latent_2"], enc, C // 2, S * 3)
-        if keep is not None:
-            keep.update(x3=x3, h1=h1, ld=ld)
-        # channel index = ch*3 + k (torch.cat on dim 2 then flatten(1, 2), models.py:446)
-        return enc.view(S, 3, C // 2).permute(0, 2, 1).contiguous().view(S, 3 * (C // 2))
+from . import one_call, staged  # noqa: E402  (the routes of _render; both import this module's names, so they come last)

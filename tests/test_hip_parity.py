@@ -943,7 +943,7 @@ def test_fused_rows_kernel_matches_the_two_exchange_layers(R, P, nsets):
 
 
 def test_exchange_row_lists_match_their_definition():
-    """car_exchange_rows against the row lists written out with torch indexing and car_project_points (the form engine._encode_three_views
+    """car_exchange_rows against the row lists written out with torch indexing and car_project_points (the form staged._encode_three_views
     used to build them in, ~40 launches): bit-identical."""
     from cross_attention_renderer_amd import _lib as L
     lib = abi.lib()
@@ -1153,7 +1153,7 @@ def test_lattice_beyond_the_fused_kernels_range_takes_the_stage_route():
     assert rc != 0 and b"2 GiB" in lib.car_last_error()
 
 
-def test_pyramid_without_a_common_lattice_takes_the_stage_route():
+def test_pyramid_without_a_common_lattice_takes_the_stage_route(monkeypatch):
     """A pyramid whose coarser levels are no integer refinements of each other (20 x 20 under 32 x 32) has no merged lattice: the
     engine renders it through the stage kernels (per-level gathers), same contract against the oracle."""
     from cross_attention_renderer_amd import synthetic as S
@@ -1173,9 +1173,9 @@ def test_pyramid_without_a_common_lattice_takes_the_stage_route():
     calls = []
     with torch.no_grad():
         m(to_device(inp, dev, cameras_on_host=True), z=[t.to(dev) for t in S.feature_maps(1, 2, H, seed=8)])     # builds the engine
-        eng = m._engine
-        one_call = eng._render_one_call
-        eng._render_one_call = lambda *a, **k: (calls.append(1), one_call(*a, **k))[1]
+        from cross_attention_renderer_amd import one_call
+        render = one_call.render
+        monkeypatch.setattr(one_call, "render", lambda *a, **k: (calls.append(1), render(*a, **k))[1])
         out = m(to_device(inp, dev, cameras_on_host=True), z=[t.to(dev) for t in z])
     torch.cuda.synchronize()
     assert not calls, "this pyramid must not reach the one-call route"

@@ -1,5 +1,5 @@
 """Throughput of the constructor variants on the STAGED route of the engine (stage kernels of the C ABI sequenced
-by engine.py, every layer on the fp32 matrix pipe): rays/s at the C2 shape (256 x 256, 64 samples) in 8192-ray forward calls, so that
+by staged.py, every layer on the fp32 matrix pipe): rays/s at the C2 shape (256 x 256, 64 samples) in 8192-ray forward calls, so that
 what a variant costs next to the fused default route is a number.  Builder-kept figures (the driver benches the default configuration).
 Usage (GPU box): python tools/bench_variants.py [variant ...]     variants: default nview3 nview1 no_sample no_latent_concat no_repeat"""
 import os
