@@ -1,7 +1,8 @@
 """ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h``).
 
 The library is built in-tree by ``__graft_entry__.build()``.  There is no fallback: if it cannot be loaded,
-``load()`` raises, and every wrapper turns a negative return code into ``RuntimeError(car_last_error())``.
+``load()`` raises.  Two handles on the one library: ``api()``, which the package calls — every entry that returns a status checks itself
+and raises ``CarError(car_last_error())`` on a negative code — and ``load()``, the raw one, for tests and tools that assert on the codes.
 ctypes releases the GIL around each call; all work is enqueued on the stream the caller passes.
 """
 from __future__ import annotations
@@ -11,10 +12,15 @@ import os
 from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
 from typing import Optional
 
+# torch comes first: its wheel bundles its own libamdhip64.so, and the process must end up with ONE HIP runtime (the one that owns
+# torch's device context and streams) — loading ours first binds /opt/rocm's copy.
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcar_hip.so")
 
 _P = c_void_p
+CAR_E_ARG, CAR_E_LAUNCH = -1, -2          # include/car_hip.h
 
 
 class CarDims(ctypes.Structure):          # struct car_dims
@@ -171,7 +177,17 @@ SIGNATURES = {
     "car_essential_ransac": (c_int, [_P, _P, c_int, _P, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# the int entries that return a VALUE (the header's words); every other int entry returns a status: 0, or a negative CAR_E_* code
+VALUE_ENTRIES = (
+    "car_version",                # CAR_VERSION
+    "car_device_cu_count",        # "Number of compute units of the current device"
+    "car_fused_tile_steps",       # the step-group size of car_fused_samples_parts' `part`
+    "car_profile_count",          # "stages recorded since enable / the last read"
+    "car_frames_table_slot",      # the slot of (n_src, n_dst); "any other pair has no table and is refused (slot -1)"
+)
+
 _lib: Optional[ctypes.CDLL] = None
+_api: Optional[ctypes.CDLL] = None
 
 
 def source_hash() -> str:
@@ -231,22 +247,52 @@ def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    # torch must be imported first: its wheel bundles its own libamdhip64.so, and the process must end up with ONE
-    # HIP runtime (the one that owns torch's device context and streams) — loading ours first binds /opt/rocm's copy.
-    import torch  # noqa: F401
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (hipcc --offload-arch=gfx950). "
             "The render path has no CPU/PyTorch fallback.")
     if not _stamp_current():                      # a missing stamp counts as stale: the library's sources are unknown
         _rebuild_stale()
+    _lib = _bind(checked=False)
+    return _lib
+
+
+def _bind(checked: bool) -> ctypes.CDLL:
+    """A handle of its own on the library (a second CDLL of one path has its own function objects) with SIGNATURES' prototypes;
+    ``checked``: every status entry raises CarError on a negative code."""
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
+        fn.restype, fn.argtypes = res, args
+        if checked and res is c_int and name not in VALUE_ENTRIES:
+            fn.errcheck = _errcheck
     return lib
+
+
+def api() -> ctypes.CDLL:
+    """The checked handle (once): what the package calls.  A value, a size (0 stays the caller's business) or text comes back as it is."""
+    global _api
+    if _api is None:
+        load()
+        _api = _bind(checked=True)
+    return _api
+
+
+class CarError(RuntimeError):
+    """A negative status ``code`` of ``entry``, with the library's message ``text`` (car_last_error unless given)."""
+
+    def __init__(self, code: int, entry: str, text: Optional[str] = None):
+        if text is None:
+            msg = load().car_last_error()
+            text = msg.decode() if msg else "?"
+        self.code, self.entry, self.text = code, entry, text
+        super().__init__(f"{entry} failed ({code}): {self.text}")
+
+
+def _errcheck(code, fn, args):
+    if code < 0:
+        raise CarError(code, fn.__name__)
+    return code
 
 
 def check_exports() -> None:
@@ -260,6 +306,26 @@ def check_exports() -> None:
 
 
 def check(code: int, what: str = "") -> None:
+    """The same check for a code taken from the raw handle (tests, tools) or made by hand (a size of 0 as CAR_E_ARG)."""
     if code < 0:
-        msg = load().car_last_error()
-        raise RuntimeError(f"{what or 'libcar_hip'} failed ({code}): {msg.decode() if msg else '?'}")
+        raise CarError(code, what or "libcar_hip")
+
+
+def user_call(fn, *args):
+    """``fn(*args)`` for the user-facing wrappers: an argument the library refuses (CAR_E_ARG) is the caller's ValueError, with the
+    library's bare text; anything else stays a CarError."""
+    try:
+        return fn(*args)
+    except CarError as e:
+        if e.code == CAR_E_ARG:
+            raise ValueError(e.text) from None
+        raise
+
+
+def ptr(t):
+    return None if t is None else c_void_p(t.data_ptr())
+
+
+def stream():
+    """The current torch stream as the ``void* stream`` of the C ABI."""
+    return c_void_p(torch.cuda.current_stream().cuda_stream)

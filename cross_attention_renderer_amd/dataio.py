@@ -459,7 +459,7 @@ def frame_tables() -> np.ndarray:
     """The coefficient tables of csrc/car_frames.hip as one int32 array (include/car_hip.h): a slot of {i0, i1, w0, w1} entries for every
     resize the chain can ask for, from ``_linear_coefs``, then the 256 float32 values ``v / 127.5 - 1`` as numpy computes them."""
     from . import _lib
-    lib = _lib.load()
+    lib = _lib.api()
     out = np.zeros(lib.car_frames_table_ints(), dtype=np.int32)
     pairs = [(SIDE - 2 * p, SIDE) for p in range(32)] + [(360, 256), (640, 455)]
     for n_src, n_dst in pairs:
@@ -579,7 +579,7 @@ class TrainLoader:
     def _device_state(self):
         if self._dev is None:
             from . import _lib
-            st = {"lib": _lib.load(), "stream": torch.cuda.Stream(self.device), "slots": [], "next": 0, "scratch": None}
+            st = {"lib": _lib.api(), "stream": torch.cuda.Stream(self.device), "slots": [], "next": 0, "scratch": None}
             with torch.cuda.device(self.device):
                 st["tables"] = torch.from_numpy(frame_tables()).to(self.device)          # uploaded once
             self._dev = st
@@ -606,7 +606,6 @@ class TrainLoader:
     def _prepare(self, st, plans):
         """One batch on the loader's stream: stage, upload, both launches.  Returns ((model_input, gt), event)."""
         from torch.utils.data import default_collate
-        from . import _lib
         lib = st["lib"]
         frames = [f for p in plans for f in p["frames"][:p["num_query"]]] + [f for p in plans for f in p["frames"][p["num_query"]:]]
         records = [r for p in plans for r in p["records"][:p["num_query"]]] + [r for p in plans for r in p["records"][p["num_query"]:]]
@@ -650,10 +649,9 @@ class TrainLoader:
             base, stream = dev.data_ptr(), st["stream"].cuda_stream
             hptr = slot["pinned"].data_ptr()
             if n_a:
-                _lib.check(lib.car_frames_resize_u8(base, upload, hptr + off_a, base + off_a, n_a, st["tables"].data_ptr(), base + upload,
-                                                    n_a * SIDE * SIDE * 3, stream), "car_frames_resize_u8")
-            _lib.check(lib.car_frames_resize_f32(base, total, hptr + off_b, base + off_b, len(frames), hptr + off_idx, base + off_idx, n_idx,
-                                                 st["tables"].data_ptr(), out.data_ptr(), n_out, stream), "car_frames_resize_f32")
+                lib.car_frames_resize_u8(base, upload, hptr + off_a, base + off_a, n_a, st["tables"].data_ptr(), base + upload, n_a * SIDE * SIDE * 3, stream)
+            lib.car_frames_resize_f32(base, total, hptr + off_b, base + off_b, len(frames), hptr + off_idx, base + off_idx, n_idx,
+                                      st["tables"].data_ptr(), out.data_ptr(), n_out, stream)
         b, Q = len(plans), plans[0]["num_query"]
         V = (len(frames) - nq) // b
         if R == SIDE * SIDE or R % 4 == 0:

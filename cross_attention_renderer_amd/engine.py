@@ -37,8 +37,7 @@ RELU_IN, RELU_OUT, ACCUM, NO_GLDS = 1, 2, 4, 8
 PLACE_PLAIN, PLACE_OWN, PLACE_OTHER2 = 0, 1, 2
 
 
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+_ptr, _stream = _lib.ptr, _lib.stream
 
 
 def _levels(maps: List[Tensor], rows: Optional[slice] = None):
@@ -47,10 +46,6 @@ def _levels(maps: List[Tensor], rows: Optional[slice] = None):
     L = len(maps)
     return ((ctypes.c_void_p * L)(*[(t if rows is None else t[rows]).data_ptr() for t in maps]), (ctypes.c_int * L)(*[t.shape[3] for t in maps]),
             (ctypes.c_int * L)(*[t.shape[1] for t in maps]), (ctypes.c_int * L)(*[t.shape[2] for t in maps]), L)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _round_up(x: int, m: int) -> int:
@@ -62,20 +57,19 @@ class PackedLinear:
 
     def __init__(self, weight: Tensor, bias: Optional[Tensor], device, name: str = ""):
         self.name = name
-        lib = _lib.load()
+        lib = _lib.api()
         w = weight.detach().reshape(weight.shape[0], -1).to(device=device, dtype=torch.float32).contiguous()
         self.N, self.K = int(w.shape[0]), int(w.shape[1])
         bdev = None if bias is None else bias.detach().to(device=device, dtype=torch.float32).contiguous()
         n = lib.car_linear_packed_floats(self.K, self.N)
         self.packed = torch.empty(n, device=device, dtype=torch.float32)
-        _lib.check(lib.car_linear_pack(_ptr(w), self.K, _ptr(bdev), self.K, self.N, _ptr(self.packed), _stream()),
-                   "car_linear_pack")
+        lib.car_linear_pack(_ptr(w), self.K, _ptr(bdev), self.K, self.N, _ptr(self.packed), _stream())
         # the same layer for the split-fp16 kernel (car_linear_x3: 5x the fp32 pipe's ceiling): layers wide enough to matter, whose
         # outputs fill whole 32-channel tiles; the narrow ones (point embeddings, the 16-wide query input, rgb) stay on car_linear
         self.x3 = None
         if self.N % 32 == 0 and self.K >= 64:
             tiles = torch.empty(lib.car_linear_x3_packed_floats(self.K, self.N), device=device, dtype=torch.float32)
-            _lib.check(lib.car_linear_x3_pack(_ptr(w), self.K, self.K, self.N, _ptr(tiles), _stream()), "car_linear_x3_pack")
+            lib.car_linear_x3_pack(_ptr(w), self.K, self.K, self.N, _ptr(tiles), _stream())
             self.x3 = (tiles, bdev)
 
 
@@ -125,7 +119,7 @@ class RenderEngine:
 
     def __init__(self, module):
         self.m = module
-        self.lib = _lib.load()
+        self.lib = _lib.api()            # the checked handle: a negative status raises _lib.CarError
         # _weights, _channel_last, _projected_maps, _poses, _plan_for, _plan16_for, _pair_for, staged._exchange_lattice; _packed_layers by packer
         self._packed, self._pyramid, self._gmaps, self._pose = _Cached(), _Cached(), _Cached(), _Cached()
         self._plan, self._plan16, self._pairs, self._xlat = _Cached(), _Cached(), _Cached(), _Cached()
@@ -323,8 +317,7 @@ class RenderEngine:
             with torch.cuda.stream(side):
                 for dst, t in zip(maps, z):
                     dst.copy_(t.detach().permute(0, 2, 3, 1))
-                _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), _levels(maps)[0], _ptr(pair), ctypes.c_void_p(side.cuda_stream)),
-                           "car_project_maps")
+                self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), _levels(maps)[0], _ptr(pair), ctypes.c_void_p(side.cuda_stream))
                 done = torch.cuda.Event()
                 done.record(side)
             # the entry holds everything the side stream reads (z, the plan) and writes until the launch stream has waited for ``done``
@@ -382,9 +375,8 @@ class RenderEngine:
     def gather_encode(self, gmaps: List[Tensor], wpt: Tensor, pixel_val: Tensor, grid_in: Tensor, ptenc: Tensor,
                       V: int, pts: int, out: Tensor, ld_out: int):
         ptrs, cs, hs, ws, L = _levels(gmaps)
-        _lib.check(self.lib.car_gather_encode(ptrs, hs, ws, L, cs[0], _ptr(pixel_val), _ptr(grid_in),
-                                              _ptr(ptenc), _ptr(wpt), gmaps[0].shape[0], V, pts, _ptr(out), ld_out,
-                                              _stream()), "car_gather_encode")
+        self.lib.car_gather_encode(ptrs, hs, ws, L, cs[0], _ptr(pixel_val), _ptr(grid_in), _ptr(ptenc), _ptr(wpt), gmaps[0].shape[0], V, pts,
+                                   _ptr(out), ld_out, _stream())
 
     def _poses(self, inp, H: int, n: int, dev) -> Tensor:
         """Device pose records (``struct CarPose``) for this input (models.py:207-211, 285-286).
@@ -412,8 +404,7 @@ class RenderEngine:
             b, V = ts[0].shape[:2]
             c2w, Kc, c2w_q, Kq = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in ts]
             poses = torch.empty(n, 96, device=dev, dtype=torch.float32)
-            _lib.check(self.lib.car_pose_setup(_ptr(c2w), _ptr(c2w_q), _ptr(Kc), _ptr(Kq), b, V, H, _ptr(poses), _stream()),
-                       "car_pose_setup")
+            self.lib.car_pose_setup(_ptr(c2w), _ptr(c2w_q), _ptr(Kc), _ptr(Kq), b, V, H, _ptr(poses), _stream())
             return poses
 
         def build():
@@ -459,7 +450,7 @@ class RenderEngine:
         def build():
             f = [t.detach().to(device=device, dtype=torch.float32).reshape(t.shape[0], -1).contiguous() for t in ps]
             out = [torch.zeros(n, device=device, dtype=torch.float32) for n in sizes]
-            _lib.check(getattr(self.lib, packer)(*[_ptr(t) for t in f + out], _stream()), packer)
+            getattr(self.lib, packer)(*[_ptr(t) for t in f + out], _stream())
             return out
         return self._layer_packs[packer].get(ps, (str(device),), build)
 
@@ -526,7 +517,7 @@ class RenderEngine:
         if nbytes == 0:
             _lib.check(-1, f"car_{what}_bytes")
         plan = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
-        _lib.check(getattr(self.lib, f"car_{what}_build")(ctypes.byref(d), ctypes.byref(w), _ptr(plan), _stream()), f"car_{what}_build")
+        getattr(self.lib, f"car_{what}_build")(ctypes.byref(d), ctypes.byref(w), _ptr(plan), _stream())
         return plan
 
     def _plan_for(self, d, device) -> Tensor:
@@ -554,7 +545,7 @@ class RenderEngine:
         def build():
             pair = torch.empty(self.lib.car_gmaps_floats(ctypes.byref(d)), device=device, dtype=torch.float32)
             ptrs = _levels(maps, slice(s0 * V, s1 * V))[0]
-            _lib.check(self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), ptrs, _ptr(pair), _stream()), "car_project_maps")
+            self.lib.car_project_maps(ctypes.byref(d), _ptr(plan), ptrs, _ptr(pair), _stream())
             return pair
         return self._pairs.get([plan, *z], (s0, s1), build), d
 
@@ -569,7 +560,7 @@ class RenderEngine:
     def _lattice_shape(self, d) -> tuple:
         """(lat_h, lat_w, lat_pad) of the common lattice of d's pyramid (car_lattice_shape)."""
         lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(self.lib.car_lattice_shape(ctypes.byref(d), ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad)), "car_lattice_shape")
+        self.lib.car_lattice_shape(ctypes.byref(d), ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad))
         return lh.value, lw.value, lpad.value
 
     def _lattice_fits(self, b: int, R: int, z: List[Tensor]) -> bool:
@@ -618,24 +609,27 @@ class RenderEngine:
         rows = []
         for i in range(lib.car_profile_count()):
             name, ms = ctypes.c_char_p(), ctypes.c_float()
-            _lib.check(lib.car_profile_read(i, ctypes.byref(name), ctypes.byref(ms)), "car_profile_read")
+            lib.car_profile_read(i, ctypes.byref(name), ctypes.byref(ms))
             rows.append((name.value.decode(), ms.value))
         lib.car_profile_reset()
         return rows
 
     # ------------------------------------------------------------------ kernels
-    def _lds_refused(self, rc: int, what: str) -> bool:
-        """True when ``rc`` says the device refused the kernel's LDS reservation (CAR_E_LAUNCH with the "cannot reserve" text: a part with less
-        than gfx950's 160 KB per compute unit) — the ONE condition under which a route steps down to the next HIP kernel of the same library.
-        Anything else (an argument error, a sticky fault of an earlier launch) raises: it must not silently change the arithmetic."""
-        if rc == 0:
-            return False
-        msg = (self.lib.car_last_error() or b"").decode()
-        if rc == -2 and "cannot reserve" in msg:
-            import warnings
-            warnings.warn(f"{what}: {msg}: taking the next kernel of the library")
+    @staticmethod
+    def _ran(entry, *args, what: str = "") -> bool:
+        """Calls ``entry`` of the checked handle.  False when the device refused the kernel's LDS reservation (CAR_E_LAUNCH with the "cannot
+        reserve" text: a part with less than gfx950's 160 KB per compute unit) — the ONE condition under which a route steps down to the next
+        HIP kernel of the same library.  Anything else (an argument error, a sticky fault of an earlier launch) raises: it must not silently
+        change the arithmetic."""
+        try:
+            entry(*args)
             return True
-        raise RuntimeError(f"{what} failed ({rc}): {msg}")
+        except _lib.CarError as e:
+            if e.code != _lib.CAR_E_LAUNCH or "cannot reserve" not in e.text:
+                raise
+            import warnings
+            warnings.warn(f"{what or e.entry}: {e.text}: taking the next kernel of the library")
+            return False
 
     def linear(self, x: Tensor, ldx: int, layer: PackedLinear, y: Tensor, ldy: int, M: int, flags: int = 0, mask=None):
         """``mask = (act, lda)``: the result is zeroed where ``act <= 0`` (the backward of a ReLU in front of the layer whose data gradient this
@@ -645,29 +639,25 @@ class RenderEngine:
         if (self.linear_x3 and not self.linear_flags and layer.x3 is not None and ldx % 4 == 0 and ldy % 4 == 0 and x.data_ptr() % 16 == 0
                 and y.data_ptr() % 16 == 0 and M >= self.linear_x3_min_rows):
             tiles, bias = layer.x3
+            args = (_ptr(x), ldx, _ptr(tiles), _ptr(bias), layer.K, layer.N, _ptr(y), ldy, M, flags)
             if mask is not None and mask[1] % 4 == 0 and mask[0].data_ptr() % 16 == 0:
-                rc = self.lib.car_linear_x3_masked(_ptr(x), ldx, _ptr(tiles), _ptr(bias), layer.K, layer.N, _ptr(y), ldy, M, flags, _ptr(mask[0]),
-                                                   mask[1], _stream())
-                mask = None if rc == 0 else mask
-            else:
-                rc = self.lib.car_linear_x3(_ptr(x), ldx, _ptr(tiles), _ptr(bias), layer.K, layer.N, _ptr(y), ldy, M, flags, _stream())
-            if not self._lds_refused(rc, "car_linear_x3"):
+                if self._ran(self.lib.car_linear_x3_masked, *args, _ptr(mask[0]), mask[1], _stream(), what="car_linear_x3"):
+                    return                                 # the mask was applied in the kernel's store
+            elif self._ran(self.lib.car_linear_x3, *args, _stream()):
                 if mask is not None:
-                    _lib.check(self.lib.car_relu_mask(_ptr(y), ldy, _ptr(mask[0]), mask[1], M, layer.N, _stream()), "car_relu_mask")
+                    self.lib.car_relu_mask(_ptr(y), ldy, _ptr(mask[0]), mask[1], M, layer.N, _stream())
                 return
             # the split-fp16 kernel's 72 KB weight double buffer was refused: the same layer on the fp32 matrix pipe from here on — another
             # HIP kernel of the same library, never a host path
             self.linear_x3 = False
-        _lib.check(self.lib.car_linear(_ptr(x), ldx, _ptr(layer.packed), layer.K, layer.N, _ptr(y), ldy, M,
-                                       flags | self.linear_flags, _stream()), "car_linear")
+        self.lib.car_linear(_ptr(x), ldx, _ptr(layer.packed), layer.K, layer.N, _ptr(y), ldy, M, flags | self.linear_flags, _stream())
         if mask is not None:
-            _lib.check(self.lib.car_relu_mask(_ptr(y), ldy, _ptr(mask[0]), mask[1], M, layer.N, _stream()), "car_relu_mask")
+            self.lib.car_relu_mask(_ptr(y), ldy, _ptr(mask[0]), mask[1], M, layer.N, _stream())
 
     def gather(self, maps: List[Tensor], grid: Tensor, pts: int, mode: int, place: int, V: int, out: Tensor,
                ld_out: int, col_out: int, run: int = 1):
         ptrs, cs, hs, ws, L = _levels(maps)
-        _lib.check(self.lib.car_gather_bilinear(ptrs, cs, hs, ws, L, maps[0].shape[0], _ptr(grid), pts, run, mode, place, V,
-                                                _ptr(out), ld_out, col_out, _stream()), "car_gather_bilinear")
+        self.lib.car_gather_bilinear(ptrs, cs, hs, ws, L, maps[0].shape[0], _ptr(grid), pts, run, mode, place, V, _ptr(out), ld_out, col_out, _stream())
 
     # ------------------------------------------------------------------ the forward pass
     @torch.no_grad()

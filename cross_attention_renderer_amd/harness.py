@@ -6,6 +6,7 @@ into chunks, shards them over ranks and puts the tiles back together.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 import zlib
@@ -14,7 +15,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import sharding, synthetic
+from . import _lib, sharding, synthetic
 
 CHUNK_RAYS = 8192          # render_realestate10k_traj.py:96
 
@@ -88,8 +89,6 @@ def ssim(img: torch.Tensor, ref: torch.Tensor, data_range: float = 2.0) -> torch
     for the usual convention for [0, 1] images.
 
     Raises ValueError for CPU tensors (there is no CPU fallback), mismatched shapes and the shapes / ranges car_ssim refuses."""
-    import ctypes
-    from . import _lib
     if not (torch.is_tensor(img) and torch.is_tensor(ref)):
         raise ValueError("ssim: img and ref must be tensors")
     if img.device.type != "cuda" or ref.device != img.device:
@@ -98,16 +97,12 @@ def ssim(img: torch.Tensor, ref: torch.Tensor, data_range: float = 2.0) -> torch
         raise ValueError(f"ssim: need two (H, W, C) or (B, H, W, C) images of one shape, got {tuple(img.shape)} and {tuple(ref.shape)}")
     x, y = (t.to(torch.float32).contiguous() for t in (img, ref))
     B, H, W, C = x.shape if x.dim() == 4 else (1, *x.shape)
-    lib = _lib.load()
+    lib = _lib.api()
     with torch.cuda.device(x.device):
         n = lib.car_ssim_scratch_doubles(B, H, W, C)
         out = torch.empty(B, dtype=torch.float64, device=x.device)
         scratch = torch.empty(max(n, 1), dtype=torch.float64, device=x.device)      # car_ssim refuses the shape when n == 0
-        code = lib.car_ssim(x.data_ptr(), y.data_ptr(), B, H, W, C, ctypes.c_double(data_range), out.data_ptr(), scratch.data_ptr(),
-                            n, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if code == -1:
-        raise ValueError(lib.car_last_error().decode())
-    _lib.check(code, "car_ssim")
+        _lib.user_call(lib.car_ssim, x.data_ptr(), y.data_ptr(), B, H, W, C, ctypes.c_double(data_range), out.data_ptr(), scratch.data_ptr(), n, _lib.stream())
     return out[0] if img.dim() == 3 else out
 
 
@@ -162,20 +157,17 @@ class LpipsWeights:
     def _pack_once(self, cache, device, groups, floats, pack) -> torch.Tensor:
         """``cache[device]``, made on first use: the float32 tensor lists ``groups`` go to the device, entry ``pack`` (one table of
         pointers per group, the output, the stream) writes entry ``floats``'s count of floats.  The one key rule of both packed forms."""
-        import ctypes
-        from . import _lib
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError(f"lpips: the weights are packed on a ROCm device, not on {device}; there is no CPU fallback")
         key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
         if key not in cache:
-            lib = _lib.load()
+            lib = _lib.api()
             with torch.cuda.device(device):
                 dev = [[t.to(device) for t in group] for group in groups]
                 tables = [(ctypes.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in dev]
                 out = torch.empty(getattr(lib, floats)(), dtype=torch.float32, device=device)
-                code = getattr(lib, pack)(*tables, out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-                _lib.check(code, pack)
+                getattr(lib, pack)(*tables, out.data_ptr(), _lib.stream())
                 torch.cuda.current_stream().synchronize()              # the float32 copies in `dev` are released on return
             cache[key] = out
         return cache[key]
@@ -213,8 +205,6 @@ def lpips(img: torch.Tensor, ref: torch.Tensor, weights: LpipsWeights, return_ta
     terms, (5,) or (B, 5)).  Nothing waits for the launches.  Identical images give exactly 0.
 
     Raises ValueError for CPU tensors (there is no CPU fallback), mismatched shapes and the shapes car_lpips refuses."""
-    import ctypes
-    from . import _lib
     if not (torch.is_tensor(img) and torch.is_tensor(ref)):
         raise ValueError("lpips: img and ref must be tensors")
     if img.device.type != "cuda" or ref.device != img.device:
@@ -225,18 +215,14 @@ def lpips(img: torch.Tensor, ref: torch.Tensor, weights: LpipsWeights, return_ta
         raise ValueError("lpips: weights must come from load_lpips_weights")
     x, y = (((t.to(torch.float32) - 0.5) * 2).contiguous() for t in (img, ref))
     B, H, W, _ = x.shape if x.dim() == 4 else (1, *x.shape)
-    lib = _lib.load()
+    lib = _lib.api()
     with torch.cuda.device(x.device):
         packed = weights.packed(x.device)
         n = lib.car_lpips_workspace_bytes(B, H, W)
         work = weights.workspace(x.device, B, H, W, n)
         out = torch.empty(max(B, 1), dtype=torch.float64, device=x.device)
         taps = torch.empty(max(B, 1), 5, dtype=torch.float64, device=x.device)
-        code = lib.car_lpips(x.data_ptr(), y.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), taps.data_ptr(), work.data_ptr(), n,
-                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if code == -1:
-        raise ValueError(lib.car_last_error().decode())
-    _lib.check(code, "car_lpips")
+        _lib.user_call(lib.car_lpips, x.data_ptr(), y.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), taps.data_ptr(), work.data_ptr(), n, _lib.stream())
     out, taps = (out[0], taps[0]) if img.dim() == 3 else (out, taps)
     return (out, taps) if return_taps else out
 
@@ -247,9 +233,7 @@ class _LpipsLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, weights):
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
+        lib = _lib.api()
         xc, yc = x.detach().contiguous(), y.detach().contiguous()
         B, H, W, _ = xc.shape
         with torch.cuda.device(xc.device):
@@ -257,19 +241,13 @@ class _LpipsLoss(torch.autograd.Function):
             n = lib.car_lpips_train_workspace_bytes(B, H, W)
             work = torch.empty(max(n, 16), dtype=torch.uint8, device=xc.device)
             out = torch.empty(max(B, 1), dtype=torch.float64, device=xc.device)
-            code = lib.car_lpips_forward_train(xc.data_ptr(), yc.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), None, work.data_ptr(), n,
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if code == -1:
-            raise ValueError(lib.car_last_error().decode())
-        _lib.check(code, "car_lpips_forward_train")
+            _lib.user_call(lib.car_lpips_forward_train, xc.data_ptr(), yc.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), None, work.data_ptr(), n,
+                           _lib.stream())
         ctx.weights, ctx.work, ctx.shape = weights, work, (B, H, W)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
         B, H, W = ctx.shape
         need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_x or need_y):
@@ -279,10 +257,9 @@ class _LpipsLoss(torch.autograd.Function):
         with torch.cuda.device(dev):
             gx = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if need_x else None
             gy = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if need_y else None
-            code = lib.car_lpips_backward(g.data_ptr(), gx.data_ptr() if need_x else None, gy.data_ptr() if need_y else None, B, H, W,
+            _lib.api().car_lpips_backward(g.data_ptr(), gx.data_ptr() if need_x else None, gy.data_ptr() if need_y else None, B, H, W,
                                           ctx.weights.packed(dev).data_ptr(), ctx.weights.packed_backward(dev).data_ptr(), ctx.work.data_ptr(),
-                                          ctx.work.numel(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(code, "car_lpips_backward")
+                                          ctx.work.numel(), _lib.stream())
         return gx, gy, None
 
 
@@ -379,9 +356,7 @@ def estimate_pose(kpts0, kpts1, K0, K1, thresh, hypotheses: int = 8192, seed: in
     host in float64 (``recover_pose``).  Neither stage is pinned against cv2.
 
     Raises ValueError for shapes the device entry refuses, RuntimeError without a ROCm device (there is no CPU fallback)."""
-    import ctypes
     import numpy as np
-    from . import _lib
     kpts0, kpts1 = np.asarray(kpts0, dtype=np.float64), np.asarray(kpts1, dtype=np.float64)
     if kpts0.ndim != 2 or kpts0.shape[1] != 2 or kpts0.shape != kpts1.shape:
         raise ValueError(f"estimate_pose: need two (N, 2) arrays of matched keypoints, got {kpts0.shape} and {kpts1.shape}")
@@ -396,10 +371,10 @@ def estimate_pose(kpts0, kpts1, K0, K1, thresh, hypotheses: int = 8192, seed: in
         raise RuntimeError("estimate_pose: needs a ROCm device; there is no CPU fallback")
     dev = torch.device(device if device is not None else "cuda")
     N, H = len(x0), int(hypotheses)
-    lib = _lib.load()
+    lib = _lib.api()
     nbytes = lib.car_essential_workspace_bytes(N, H)
-    if nbytes == 0:
-        raise ValueError(lib.car_last_error().decode())
+    if nbytes == 0:                                         # the size entry's refusal: CAR_E_ARG, with its message
+        _lib.user_call(_lib.check, _lib.CAR_E_ARG, "car_essential_workspace_bytes")
     with torch.cuda.device(dev):
         d0, d1 = torch.from_numpy(x0).to(dev), torch.from_numpy(x1).to(dev)
         table = torch.from_numpy(pose_sample_table(N, H, seed)).to(dev)
@@ -407,12 +382,8 @@ def estimate_pose(kpts0, kpts1, K0, K1, thresh, hypotheses: int = 8192, seed: in
         E = torch.empty(9, dtype=torch.float64, device=dev)
         best = torch.empty(3, dtype=torch.int32, device=dev)
         inl = torch.empty(N, dtype=torch.uint8, device=dev)
-        code = lib.car_essential_ransac(d0.data_ptr(), d1.data_ptr(), N, table.data_ptr(), H, ctypes.c_double(norm_thresh), E.data_ptr(),
-                                        best.data_ptr(), inl.data_ptr(), work.data_ptr(), nbytes,
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if code == -1:
-            raise ValueError(lib.car_last_error().decode())
-        _lib.check(code, "car_essential_ransac")
+        _lib.user_call(lib.car_essential_ransac, d0.data_ptr(), d1.data_ptr(), N, table.data_ptr(), H, ctypes.c_double(norm_thresh), E.data_ptr(),
+                       best.data_ptr(), inl.data_ptr(), work.data_ptr(), nbytes, _lib.stream())
         E, best, inl = E.cpu().numpy(), best.cpu().numpy(), inl.cpu().numpy()
     if best[0] < 1:
         return None

@@ -136,11 +136,9 @@ def render(eng, inp, z: List[Tensor], b: int, R: int, debug: bool) -> Dict[str, 
             ci.steps = steps.data_ptr()
             co = _lib.CarOutputs(*[tgt[k].data_ptr() for k in order])
             if f16:
-                _lib.check(lib.car_render_forward_f16(ctypes.byref(d), _ptr(plan), _ptr(plan16), ctypes.byref(ci), ctypes.byref(co),
-                                                      _ptr(work), work.numel() * 4, phases, st), "car_render_forward_f16")
+                lib.car_render_forward_f16(ctypes.byref(d), _ptr(plan), _ptr(plan16), ctypes.byref(ci), ctypes.byref(co), _ptr(work), work.numel() * 4, phases, st)
             else:                                       # phases == 3 is car_render_forward's own call
-                _lib.check(lib.car_render_forward_phase(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co),
-                                                        _ptr(work), work.numel() * 4, phases, st), "car_render_forward_phase")
+                lib.car_render_forward_phase(ctypes.byref(d), _ptr(plan), ctypes.byref(ci), ctypes.byref(co), _ptr(work), work.numel() * 4, phases, st)
             if not whole:
                 for k in order:
                     dst = out[k][:, 0] if k == "rgb" else out[k]
@@ -156,7 +154,7 @@ def render(eng, inp, z: List[Tensor], b: int, R: int, debug: bool) -> Dict[str, 
 
         def ws(name, *shape):
             off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
-            _lib.check(lib.car_workspace_find(ctypes.byref(d_last), name.encode(), ctypes.byref(off), ctypes.byref(cnt)), "car_workspace_find")
+            lib.car_workspace_find(ctypes.byref(d_last), name.encode(), ctypes.byref(off), ctypes.byref(cnt))
             return work[off.value:off.value + cnt.value].view(*shape).clone()
         res["stages"] = {"rays": ws("rays", n, R, 12), "pt": ws("pt", n, R, P, 3), "local_coords": None,
                          "g": ws("g", n, R, P, 16), "interp_val": ws("e", n, R, P, 576),

@@ -119,8 +119,7 @@ def _rays_and_samples(r: _Run, uv: Tensor):
     coords9 = torch.empty(n, R, 9, **r.f32)
     ld_phi = _round_up(9 * V, 4)
     phi_x = torch.zeros(r.bR, ld_phi, **r.f32)
-    _lib.check(lib.car_ray_setup(_ptr(r.poses), _ptr(uv), b, V, R, m.H, m.W, P, int(m.no_sample), _ptr(r.steps),
-                                 _ptr(rays), _ptr(coords9), _ptr(phi_x), ld_phi, r.st), "car_ray_setup")
+    lib.car_ray_setup(_ptr(r.poses), _ptr(uv), b, V, R, m.H, m.W, P, int(m.no_sample), _ptr(r.steps), _ptr(rays), _ptr(coords9), _ptr(phi_x), ld_phi, r.st)
     pixel_val = torch.empty(n, R, P, 2, **r.f32)
     pt = torch.empty(n, R, P, 3, **r.f32)
     g = torch.empty(S, 16, **r.f32)
@@ -136,9 +135,8 @@ def _rays_and_samples(r: _Run, uv: Tensor):
         x1 = torch.empty(S * V, ld1, **r.f32)
         if r.save is not None:
             x1[:, C + (3 if mode == "concat2" else 6):].zero_()     # the row padding: the backward reads whole rows
-    _lib.check(lib.car_sample_setup(_ptr(r.poses), _ptr(rays), _ptr(r.steps), b, V, R, P, m.H, m.W, int(m.no_sample),
-                                    _ptr(pixel_val), _ptr(pt), _ptr(g), _ptr(grid_in), _ptr(x1), ld1, col, _ptr(pt_in), r.st),
-               "car_sample_setup")
+    lib.car_sample_setup(_ptr(r.poses), _ptr(rays), _ptr(r.steps), b, V, R, P, m.H, m.W, int(m.no_sample),
+                         _ptr(pixel_val), _ptr(pt), _ptr(g), _ptr(grid_in), _ptr(x1), ld1, col, _ptr(pt_in), r.st)
     return rays, coords9, phi_x, ld_phi, pixel_val, pt, g, grid_in, pt_in, x1, ld1
 
 
@@ -190,14 +188,15 @@ def _exchange_lattice(eng, gmaps, ptrs, hs, ws, n_maps, C, dev):
     def build():
         L = len(gmaps)
         lh, lw, lpad = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        if eng.lib.car_merge_lattice(ptrs, hs, ws, L, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad), _stream()) != 0:
+        # the shape query on the raw handle: a refusal (no common lattice) is an answer here, not an error
+        if _lib.load().car_merge_lattice(ptrs, hs, ws, L, n_maps, None, ctypes.byref(lh), ctypes.byref(lw), ctypes.byref(lpad), _stream()) != 0:
             return None
         floats = n_maps * 2 * lh.value * lw.value * C
         if n_maps * 2 * lh.value * lw.value >= 2 ** 31 - 1 or floats * 4 > eng._free_budget(dev) // 2:
             return None
         lattice = torch.empty(floats, device=dev, dtype=torch.float32)
         gmax = torch.empty(1, device=dev, dtype=torch.float32)     # largest |lattice value|: taken in the merge's own pass
-        _lib.check(eng.lib.car_merge_lattice_max(ptrs, hs, ws, L, n_maps, _ptr(lattice), _ptr(gmax), _stream()), "car_merge_lattice_max")
+        eng.lib.car_merge_lattice_max(ptrs, hs, ws, L, n_maps, _ptr(lattice), _ptr(gmax), _stream())
         return lattice, lh.value, lw.value, lpad.value, gmax
     return eng._xlat.get(gmaps, (), build)
 
@@ -235,8 +234,7 @@ def _encode_three_views(r: _Run, pixel_val: Tensor, ptenc: Tensor, pt_in: Tensor
             if o == c:
                 continue
             q = pin[:, o, :, c, :].contiguous()         # context o's points expressed in frame c
-            _lib.check(lib.car_project_points(_ptr(poses), _ptr(q), b, pts, V, o, H, W, _ptr(grid), _stream()),
-                       "car_project_points")
+            lib.car_project_points(_ptr(poses), _ptr(q), b, pts, V, o, H, W, _ptr(grid), _stream())
             eng.gather(per_view[o], grid, pts, 1, PLACE_PLAIN, 1, tmp2, C, 0, run=P)
             if sv is not None:
                 cross.append((c, o, k, grid.clone()))
@@ -267,8 +265,7 @@ def _exchange_projected(r: _Run, pixel_val: Tensor, ptenc: Tensor, pt_in: Tensor
     src = torch.empty(b, V, pts, 3, dtype=torch.int32, device=dev)
     rgrid = torch.empty(b, V, pts, 3, 2, **f32)
     rpe = torch.empty(b, V, pts, 3, 4, **f32)
-    _lib.check(lib.car_exchange_rows(_ptr(r.poses), _ptr(pixel_val), _ptr(pt_in), _ptr(ptenc), b, V, pts, eng.m.H, eng.m.W, _ptr(src), _ptr(rgrid),
-                                     _ptr(rpe), _stream()), "car_exchange_rows")
+    lib.car_exchange_rows(_ptr(r.poses), _ptr(pixel_val), _ptr(pt_in), _ptr(ptenc), b, V, pts, eng.m.H, eng.m.W, _ptr(src), _ptr(rgrid), _ptr(rpe), _stream())
     ptrs, _, hs, ws, L = _levels(gmaps)
     lat = _exchange_lattice(eng, gmaps, ptrs, hs, ws, n, C, dev)
     layer2 = r.pk["query_encode_latent_2"]
@@ -278,9 +275,8 @@ def _exchange_projected(r: _Run, pixel_val: Tensor, ptenc: Tensor, pt_in: Tensor
         lattice, lh, lw, lpad, gmax = lat
         blob, fbias, fwpt = eng._exchange_pack(dev)
         enc = torch.empty(S * 3, C // 2, **f32)
-        rc = lib.car_fused_rows(_ptr(lattice), lh, lw, lpad, _ptr(gmax), _ptr(fwpt), _ptr(blob), _ptr(fbias), _ptr(src), _ptr(rgrid), _ptr(rpe),
-                                n, R, P, 3, _ptr(enc), _stream())
-        if not eng._lds_refused(rc, "car_fused_rows"):
+        if eng._ran(lib.car_fused_rows, _ptr(lattice), lh, lw, lpad, _ptr(gmax), _ptr(fwpt), _ptr(blob), _ptr(fbias), _ptr(src), _ptr(rgrid), _ptr(rpe),
+                    n, R, P, 3, _ptr(enc), _stream()):
             return enc.view(S, 3 * (C // 2))
         eng.fuse_exchange = True                           # LDS reservation refused: the gather-fed linear kernel, then two launches
     if lat is not None and eng.fuse_exchange and eng.linear_x3 and not eng.linear_flags and layer2.x3 is not None:
@@ -290,19 +286,16 @@ def _exchange_projected(r: _Run, pixel_val: Tensor, ptenc: Tensor, pt_in: Tensor
         lattice, lh, lw, lpad, _ = lat
         tiles, bias2 = layer2.x3
         enc = torch.empty(S * 3, C // 2, **f32)
-        rc = lib.car_lattice_encode_linear(_ptr(lattice), lh, lw, lpad, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3,
-                                           _ptr(tiles), _ptr(bias2), C, C // 2, _ptr(enc), C // 2, 0, _stream())
-        if not eng._lds_refused(rc, "car_lattice_encode_linear"):
+        if eng._ran(lib.car_lattice_encode_linear, _ptr(lattice), lh, lw, lpad, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3,
+                    _ptr(tiles), _ptr(bias2), C, C // 2, _ptr(enc), C // 2, 0, _stream()):
             return enc.view(S, 3 * (C // 2))
         eng.fuse_exchange = False
     h1 = torch.empty(S * 3, C, **f32)
     if lat is not None:                                     # four taps of the merged lattice per row instead of twelve
         lattice, lh, lw, lpad, _ = lat
-        _lib.check(lib.car_lattice_encode_rows(_ptr(lattice), lh, lw, lpad, C, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3,
-                                               _ptr(h1), C, _stream()), "car_lattice_encode_rows")
+        lib.car_lattice_encode_rows(_ptr(lattice), lh, lw, lpad, C, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3, _ptr(h1), C, _stream())
     else:
-        _lib.check(lib.car_gather_encode_rows(ptrs, hs, ws, L, C, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3, _ptr(h1), C,
-                                              _stream()), "car_gather_encode_rows")
+        lib.car_gather_encode_rows(ptrs, hs, ws, L, C, _ptr(src), _ptr(rgrid), _ptr(rpe), _ptr(wpt), n, S * 3, _ptr(h1), C, _stream())
     enc = torch.empty(S * 3, C // 2, **f32)
     eng.linear(h1, C, layer2, enc, C // 2, S * 3)
     return enc.view(S, 3 * (C // 2))                          # component-major: the consumers' weights are permuted (_weights)
@@ -325,8 +318,8 @@ def _keys_and_queries(r: _Run, e: Tensor, g: Tensor):
         tiles, bias_k1 = kmap.x3
         tail, tail_bias = eng._kq_weights(e.device)
         logit1 = torch.empty(S, **f32)
-        rc = eng.lib.car_key_query_logits(_ptr(e), Ce, _ptr(tiles), _ptr(bias_k1), Ce, _ptr(g), _ptr(tail), _ptr(tail_bias), S, _ptr(q), _ptr(logit1), r.st)
-        if eng._lds_refused(rc, "car_key_query_logits"):
+        if not eng._ran(eng.lib.car_key_query_logits, _ptr(e), Ce, _ptr(tiles), _ptr(bias_k1), Ce, _ptr(g), _ptr(tail), _ptr(tail_bias), S, _ptr(q),
+                        _ptr(logit1), r.st):
             eng.fuse_kq, logit1 = False, None                      # LDS reservation refused: the five separate launches below
     if logit1 is None:
         k1 = torch.empty(S, 128, **f32)
@@ -352,8 +345,8 @@ def _attention_rounds(r: _Run, e: Tensor, g: Tensor, q: Tensor, key: Optional[Te
     amax = torch.empty(n, R, 1, dtype=torch.int32, device=e.device)
     ebar1 = torch.empty(bR, Ce, **f32)
     lg, qr = (logit1, None) if logit1 is not None else (key, q)    # the logits of car_key_query_logits, or keys and queries
-    _lib.check(lib.car_attend(_ptr(lg), _ptr(qr), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt), _ptr(ebar1),
-                              Ce, 1, _ptr(pt), _ptr(r.poses), _ptr(depth), _ptr(amax), st), "car_attend")
+    lib.car_attend(_ptr(lg), _ptr(qr), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt), _ptr(ebar1), Ce, 1, _ptr(pt), _ptr(r.poses), _ptr(depth),
+                   _ptr(amax), st)
     lv = pk["latent_value.kmajor" if r.kmajor else "latent_value"]
     zrep = torch.empty(bR, V * Dl, **f32)
     at_wt2 = None
@@ -371,23 +364,20 @@ def _attention_rounds(r: _Run, e: Tensor, g: Tensor, q: Tensor, key: Optional[Te
             # ug = Wr1[:,128:] g + br1, q2 = Wr2 relu(ug + uh) + b and <q2, qry>/16 in one kernel: neither is written
             r2w, r2b = eng._round2_weights(e.device)
             logit2 = torch.empty(S, **f32)
-            _lib.check(lib.car_round2_logits(_ptr(g), _ptr(uh), _ptr(q), _ptr(r2w), _ptr(r2b),
-                                             b, V, R, P, _ptr(logit2), st), "car_round2_logits")
-            _lib.check(lib.car_attend(_ptr(logit2), None, 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
-                                      _ptr(ebar2), Ce, 1, None, None, None, None, st), "car_attend")
+            lib.car_round2_logits(_ptr(g), _ptr(uh), _ptr(q), _ptr(r2w), _ptr(r2b), b, V, R, P, _ptr(logit2), st)
+            lib.car_attend(_ptr(logit2), None, 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2), _ptr(ebar2), Ce, 1, None, None, None, None, st)
         else:
             k1r = torch.empty(S, 128, **f32)
             eng.linear(g, 16, pk["query_repeat_embed.g"], k1r, 128, S)
-            _lib.check(lib.car_add_ray_bias_relu(_ptr(k1r), _ptr(uh), b, V, R, P, 128, st), "car_add_ray_bias_relu")
+            lib.car_add_ray_bias_relu(_ptr(k1r), _ptr(uh), b, V, R, P, 128, st)
             key2 = torch.empty(S, 128, **f32) if keep or key is None else key   # inference: round 2's keys in round 1's buffer
             eng.linear(k1r, 128, pk["query_repeat_embed_2"], key2, 128, S)
-            _lib.check(lib.car_attend(_ptr(key2), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2),
-                                      _ptr(ebar2), Ce, 1, None, None, None, None, st), "car_attend")
+            lib.car_attend(_ptr(key2), _ptr(q), 128, _ptr(e), Ce, b, V, R, P, None, 0.0, _ptr(at_wt2), _ptr(ebar2), Ce, 1, None, None, None, None, st)
             if keep:
                 sv.k1r, sv.key2 = k1r, key2
         # z = (Wv ebar2 + bv) + V * z1   (models.py:561-565: "+ z_local" per view, then the view sum)
         if keep:
-            _lib.check(lib.car_add(_ptr(zrep), V * Dl, _ptr(z1), Dl, float(V), None, 0, 0.0, bR, Dl, st), "car_add")
+            lib.car_add(_ptr(zrep), V * Dl, _ptr(z1), Dl, float(V), None, 0, 0.0, bR, Dl, st)
             sv.z1, sv.hb, sv.at_wt2, sv.ebar2 = z1, hb, at_wt2, ebar2
         else:
             zrep.view(bR, V, Dl)[:, 0] = z1 * float(V)
@@ -397,7 +387,7 @@ def _attention_rounds(r: _Run, e: Tensor, g: Tensor, q: Tensor, key: Optional[Te
     # the per-view replication of models.py:541, 565, 605-606
     if keep:
         for v in range(1, V):
-            _lib.check(lib.car_add(_ptr(zrep[:, v * Dl:]), V * Dl, _ptr(zrep), V * Dl, 1.0, None, 0, 0.0, bR, Dl, st), "car_add")
+            lib.car_add(_ptr(zrep[:, v * Dl:]), V * Dl, _ptr(zrep), V * Dl, 1.0, None, 0, 0.0, bR, Dl, st)
         sv.at_wt, sv.ebar1, sv.zrep = at_wt, ebar1, zrep
     elif V > 1:
         zv = zrep.view(bR, V, Dl)
@@ -428,7 +418,7 @@ def _decode(r: _Run, phi_x: Tensor, ld_phi: int, zrep: Tensor, rays: Tensor):
     eng.linear(x, hid, pk["phi.lin_out"], out3, 4, bR, RELU_IN)
     rgb = torch.empty(b, 1, R, 3, **f32)
     valid = torch.empty(b, R, 1, **f32)
-    _lib.check(eng.lib.car_finalize(_ptr(rays), _ptr(out3), 4, b, V, R, _ptr(rgb), _ptr(valid), r.st), "car_finalize")
+    eng.lib.car_finalize(_ptr(rays), _ptr(out3), 4, b, V, R, _ptr(rgb), _ptr(valid), r.st)
     if keep:
         sv.phi_x, sv.xas, sv.nets, sv.dec_out, sv.valid = phi_x, xas, nets, x, valid
     return rgb, valid

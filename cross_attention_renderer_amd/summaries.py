@@ -29,10 +29,6 @@ PROBE_RAY = 2065                                   # summaries.py:96: the ray wh
 DEPTH_SCALE = 10.0                                 # summaries.py:36
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _on_device(what: str, *tensors: Tensor) -> torch.device:
     dev = tensors[0].device if torch.is_tensor(tensors[0]) else None
     for t in tensors:
@@ -45,12 +41,6 @@ def _f32(t: Tensor) -> Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
-def _checked(lib, code: int, what: str) -> None:
-    if code == -1:
-        raise ValueError(lib.car_last_error().decode())
-    _lib.check(code, what)
-
-
 # ---- the four kernels -----------------------------------------------------------------------------------------------------------------
 def attention_entropy_sum(at_wt: Tensor, nan_rows_zero: bool) -> Tuple[Tensor, int]:
     """``(sum over the rows of -sum_j w_j log(w_j + 1e-5), rows)`` of ``at_wt`` (..., S): the sum a 0-d float64 device tensor.  A caller
@@ -59,13 +49,12 @@ def attention_entropy_sum(at_wt: Tensor, nan_rows_zero: bool) -> Tuple[Tensor, i
     w = _f32(at_wt)
     S = w.shape[-1]
     rows = w.numel() // max(S, 1)
-    lib = _lib.load()
+    lib = _lib.api()
     with torch.cuda.device(dev):
         n = lib.car_attention_entropy_scratch_doubles(rows, S)
         out = torch.empty((), dtype=torch.float64, device=dev)
         scratch = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        code = lib.car_attention_entropy(w.data_ptr(), rows, S, int(bool(nan_rows_zero)), out.data_ptr(), scratch.data_ptr(), n, _stream())
-    _checked(lib, code, "car_attention_entropy")
+        _lib.user_call(lib.car_attention_entropy, w.data_ptr(), rows, S, int(bool(nan_rows_zero)), out.data_ptr(), scratch.data_ptr(), n, _lib.stream())
     return out, rows
 
 
@@ -87,11 +76,9 @@ def colormap(x: Tensor, scale: float = DEPTH_SCALE, lut: Optional[Tensor] = None
     if tuple(table.shape) != (256, 3):
         raise ValueError(f"colormap: the table must be (256, 3), got {tuple(table.shape)}")
     N, H, W = v.shape
-    lib = _lib.load()
     with torch.cuda.device(dev):
         out = torch.empty(N, H, W, 3, dtype=torch.float32, device=dev)
-        code = lib.car_colormap(v.data_ptr(), N, H, W, ctypes.c_float(scale), table.data_ptr(), out.data_ptr(), _stream())
-    _checked(lib, code, "car_colormap")
+        _lib.user_call(_lib.api().car_colormap, v.data_ptr(), N, H, W, ctypes.c_float(scale), table.data_ptr(), out.data_ptr(), _lib.stream())
     return out
 
 
@@ -113,12 +100,10 @@ def epipolar_overlay(trgt: Tensor, ctxt: Tensor, pixel_val: Tensor, at_wt_max: T
         raise ValueError(f"epipolar_overlay: at_wt_max {tuple(at_wt_max.shape)} and uv {tuple(uv.shape)} do not hold {rays} rays per row")
     t, c, pv, u = _f32(trgt), _f32(ctxt), _f32(pixel_val), _f32(uv)
     best = at_wt_max.detach().to(torch.int64).contiguous()
-    lib = _lib.load()
     with torch.cuda.device(dev):
         panel = torch.empty(B * (1 + n_view), H, W, 3, dtype=torch.float32, device=dev)
-        code = lib.car_epipolar_overlay(t.data_ptr(), c.data_ptr(), pv.data_ptr(), best.data_ptr(), u.data_ptr(), B, n_view, H, W, rays,
-                                        int(probe), S, panel.data_ptr(), _stream())
-    _checked(lib, code, "car_epipolar_overlay")
+        _lib.user_call(_lib.api().car_epipolar_overlay, t.data_ptr(), c.data_ptr(), pv.data_ptr(), best.data_ptr(), u.data_ptr(), B, n_view, H, W,
+                       rays, int(probe), S, panel.data_ptr(), _lib.stream())
     return panel
 
 
@@ -139,15 +124,14 @@ def image_grid(x: Tensor, scale_each: bool = False, clamp: Optional[Tuple[float,
     v = _f32(x)
     N, H, W, _ = v.shape
     lo, hi = clamp if clamp is not None else (0.0, 0.0)
-    lib = _lib.load()
+    lib = _lib.api()
     with torch.cuda.device(dev):
         n = lib.car_image_grid_scratch_floats(N, H, W)
         Hg, Wg = grid_shape(max(N, 1), H, W)
         out = torch.empty(3, Hg, Wg, dtype=torch.float32, device=dev)
         scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-        code = lib.car_image_grid(v.data_ptr(), N, H, W, int(bool(scale_each)), int(clamp is not None), ctypes.c_float(lo), ctypes.c_float(hi),
-                                  out.data_ptr(), scratch.data_ptr(), n, _stream())
-    _checked(lib, code, "car_image_grid")
+        _lib.user_call(lib.car_image_grid, v.data_ptr(), N, H, W, int(bool(scale_each)), int(clamp is not None), ctypes.c_float(lo), ctypes.c_float(hi),
+                       out.data_ptr(), scratch.data_ptr(), n, _lib.stream())
     return out
 
 

@@ -30,7 +30,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _lib, staged
+from . import staged
 from .engine import ACCUM, PLACE_OTHER2, PLACE_OWN, PLACE_PLAIN, RELU_IN, PackedLinear, RenderEngine, _Cached, _levels, _mode, _ptr, _round_up, _stream
 
 Tensor = torch.Tensor
@@ -52,28 +52,28 @@ class _Ops:
         # engine.wgrad_fp32 = True keeps the wide layers' weight gradients on the fp32 matrix pipe (CAR_WGRAD_FP32): the reference's fp32
         # arithmetic term for term, at half the rate of the default bf16 hi / lo x 3 kernel (~2^-17 per term)
         flags = (RELU_IN if relu_x else 0) | (WGRAD_FP32 if self.eng.wgrad_fp32 else 0)
-        _lib.check(self.lib.car_linear_wgrad(_ptr(dy), ldy, _ptr(x), ldx, M, N, K, flags, _ptr(dw), lddw, _ptr(db), _stream()), "car_linear_wgrad")
+        self.lib.car_linear_wgrad(_ptr(dy), ldy, _ptr(x), ldx, M, N, K, flags, _ptr(dw), lddw, _ptr(db), _stream())
 
     def relu_mask(self, grad: Tensor, ldg: int, act: Tensor, lda: int, M: int, N: int):
-        _lib.check(self.lib.car_relu_mask(_ptr(grad), ldg, _ptr(act), lda, M, N, _stream()), "car_relu_mask")
+        self.lib.car_relu_mask(_ptr(grad), ldg, _ptr(act), lda, M, N, _stream())
 
     def scale_rows(self, out: Tensor, ldo: int, x: Tensor, ldx: int, s: Tensor, group: int, scale: float, M: int, N: int, accumulate=False):
-        _lib.check(self.lib.car_scale_rows(_ptr(out), ldo, _ptr(x), ldx, _ptr(s), group, scale, M, N, int(accumulate), _stream()), "car_scale_rows")
+        self.lib.car_scale_rows(_ptr(out), ldo, _ptr(x), ldx, _ptr(s), group, scale, M, N, int(accumulate), _stream())
 
     def add(self, out: Tensor, ldo: int, a: Tensor, lda: int, alpha: float, b: Optional[Tensor], ldb: int, beta: float, M: int, N: int):
-        _lib.check(self.lib.car_add(_ptr(out), ldo, _ptr(a), lda, alpha, _ptr(b), ldb, beta, M, N, _stream()), "car_add")
+        self.lib.car_add(_ptr(out), ldo, _ptr(a), lda, alpha, _ptr(b), ldb, beta, M, N, _stream())
 
     def reduce_samples(self, d: Tensor, b: int, V: int, R: int, P: int, C: int, du: Tensor):
-        _lib.check(self.lib.car_reduce_samples(_ptr(d), b, V, R, P, C, _ptr(du), _stream()), "car_reduce_samples")
+        self.lib.car_reduce_samples(_ptr(d), b, V, R, P, C, _ptr(du), _stream())
 
     def attend_backward(self, w, val, D, b, V, R, P, dz, ld_dz, ddepth, pt, poses, dval, accumulate, dlogit):
-        _lib.check(self.lib.car_attend_backward(_ptr(w), _ptr(val), D, b, V, R, P, _ptr(dz), ld_dz, _ptr(ddepth), _ptr(pt), _ptr(poses), _ptr(dval),
-                                            int(accumulate), _ptr(dlogit), _stream()), "car_attend_backward")
+        self.lib.car_attend_backward(_ptr(w), _ptr(val), D, b, V, R, P, _ptr(dz), ld_dz, _ptr(ddepth), _ptr(pt), _ptr(poses), _ptr(dval),
+                                     int(accumulate), _ptr(dlogit), _stream())
 
     def gather_backward(self, dmaps: List[Tensor], grid: Tensor, pts: int, mode: int, place: int, V: int, dout: Tensor, ld_out: int, col_out: int):
         ptrs, cs, hs, ws, L = _levels(dmaps)
-        _lib.check(self.lib.car_gather_bilinear_backward(ptrs, cs, hs, ws, L, dmaps[0].shape[0], _ptr(grid), pts, mode, place, V, _ptr(dout), ld_out,
-                                                     col_out, _stream()), "car_gather_bilinear_backward")
+        self.lib.car_gather_bilinear_backward(ptrs, cs, hs, ws, L, dmaps[0].shape[0], _ptr(grid), pts, mode, place, V, _ptr(dout), ld_out,
+                                              col_out, _stream())
 
     def gather_backward_binned(self, maps: List[Tensor], gathers, pts: int, V: int, dout: Tensor, ld_out: int, col_out: int) -> List[Tensor]:
         """The gradient of the gathered rows `dout` with respect to `maps` for all `gathers` [(grid, padding mode, placement)] at once, every
@@ -87,8 +87,8 @@ class _Ops:
         n_maps = maps[0].shape[0]
         nbytes = self.lib.car_scatter_workspace_bytes(hs, ws, L, n_maps, pts, G)
         work = torch.empty(nbytes, dtype=torch.uint8, device=dout.device)
-        _lib.check(self.lib.car_gather_bilinear_backward_binned(ptrs, cs, hs, ws, L, n_maps, grids, modes, places, G, pts, V, _ptr(dout), ld_out, col_out,
-                                                            _ptr(work), nbytes, _stream()), "car_gather_bilinear_backward_binned")
+        self.lib.car_gather_bilinear_backward_binned(ptrs, cs, hs, ws, L, n_maps, grids, modes, places, G, pts, V, _ptr(dout), ld_out, col_out,
+                                                     _ptr(work), nbytes, _stream())
         return dmaps
 
 

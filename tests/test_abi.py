@@ -83,6 +83,131 @@ def test_round6_training_entries_validate_their_arguments(lib):
     assert b"act" in lib.car_last_error()
 
 
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
+
+
+def _header_prototypes():
+    """{name: (return type, [parameter, ...])} of include/car_hip.h, comments and preprocessor lines stripped; a parameter is its scalar type's
+    name, or "*" for a pointer of any kind."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "car_hip.h")).read(), flags=re.S)
+    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
+    text = re.sub(r"typedef struct \w+ \{.*?\} \w+;", "", text, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"([\w \*]+?)\s*\b(car_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [p.strip() for p in " ".join(params.split()).split(",")]
+        params = [] if params == ["void"] else ["*" if "*" in p else " ".join(w for w in p.split()[:-1] if w != "const") for p in params]
+        protos[name] = (" ".join(ret.split()).replace(" *", "*"), params)
+    return protos
+
+
+def _abi_disagreements(protos, table):
+    """Where ``table`` (the layout of _lib.SIGNATURES) departs from the header's prototypes: names, return types, arity, every parameter."""
+    out = [f"{n}: on one side only" for n in sorted(set(protos) ^ set(table))]
+    for name in sorted(set(protos) & set(table)):
+        (ret, params), (res, args) = protos[name], table[name]
+        if ret not in _RETURNS or _RETURNS[ret] is not res:
+            out.append(f"{name}: returns {ret}, the table says {res}")
+        if len(params) != len(args):
+            out.append(f"{name}: {len(params)} parameters, the table has {len(args)}")
+            continue
+        for i, (p, a) in enumerate(zip(params, args)):
+            ok = (a in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(a, ctypes._Pointer)) if p == "*" else _SCALARS.get(p) is a
+            if not ok:
+                out.append(f"{name}: parameter {i} is {p}, the table says {a.__name__}")
+    return out
+
+
+def test_signatures_mirror_the_header_type_by_type():
+    """Every prototype of the header against _lib.SIGNATURES: the return type, the arity, and each parameter's scalar kind or pointer-ness (a
+    prototype that changes in the header alone would still link, load and run, with shifted arguments)."""
+    from cross_attention_renderer_amd import _lib
+    protos = _header_prototypes()
+    assert len(protos) == 116 == len(_lib.SIGNATURES)
+    assert _abi_disagreements(protos, _lib.SIGNATURES) == []
+
+
+def test_the_header_comparison_catches_drift():
+    from cross_attention_renderer_amd import _lib
+    protos = _header_prototypes()
+    res, args = _lib.SIGNATURES["car_linear"]
+    assert ctypes.c_long in args
+    narrowed = dict(_lib.SIGNATURES, car_linear=(res, [ctypes.c_int if a is ctypes.c_long else a for a in args]))
+    assert _abi_disagreements(protos, narrowed) == ["car_linear: parameter 7 is long, the table says c_int"]
+    res, args = _lib.SIGNATURES["car_attend"]
+    assert _abi_disagreements(protos, dict(_lib.SIGNATURES, car_attend=(res, args[:-1]))) == ["car_attend: 20 parameters, the table has 19"]
+    assert _abi_disagreements(protos, dict(_lib.SIGNATURES, car_version=(ctypes.c_size_t, []))) == [
+        f"car_version: returns int, the table says {ctypes.c_size_t}"]
+    swapped = dict(_lib.SIGNATURES, car_colormap=(ctypes.c_int, [ctypes.c_int if a is ctypes.c_float else a for a in _lib.SIGNATURES["car_colormap"][1]]))
+    assert len(_abi_disagreements(protos, swapped)) == 1
+
+
+def test_the_checked_handle_raises(lib):
+    from cross_attention_renderer_amd import _lib
+    with pytest.raises(_lib.CarError) as err:
+        _lib.api().car_linear(None, 4, None, 4, 4, None, 4, 1, 0, None)
+    e = err.value
+    assert isinstance(e, RuntimeError) and e.code == -1 and e.entry == "car_linear" and "null pointer" in e.text
+    assert str(e) == f"car_linear failed (-1): {e.text}"
+    with pytest.raises(RuntimeError) as by_hand:
+        _lib.check(-1, "car_linear")
+    assert str(by_hand.value) == str(e)
+    # the raw handle stays raw
+    assert lib is _lib.load() and lib.car_linear(None, 4, None, 4, 4, None, 4, 1, 0, None) == -1
+
+
+def test_value_and_size_entries_do_not_raise(lib):
+    from cross_attention_renderer_amd import _lib
+    api = _lib.api()
+    assert api.car_fused_tile_steps() == 8
+    assert api.car_linear_packed_floats(0, 4) == 0
+    assert api.car_profile_count() == 0
+    assert api.car_frames_table_slot(3, 5) == -1                      # "no table": a value, not a status
+    for name in _lib.VALUE_ENTRIES:
+        assert _lib.SIGNATURES[name][0] is ctypes.c_int, name
+    for name, (res, _) in _lib.SIGNATURES.items():
+        checked = getattr(api, name).errcheck is _lib._errcheck
+        assert checked == (res is ctypes.c_int and name not in _lib.VALUE_ENTRIES), name
+        assert getattr(lib, name).errcheck is not _lib._errcheck, name
+
+
+def test_user_call_turns_a_refused_argument_into_value_error(lib):
+    from cross_attention_renderer_amd import _lib
+    assert lib.car_linear(None, 4, None, 4, 4, None, 4, 1, 0, None) == -1            # leaves the library's message
+    text = lib.car_last_error().decode()
+    with pytest.raises(ValueError) as err:
+        _lib.user_call(_lib.check, -1, "probe")
+    assert str(err.value) == text and "null pointer" in text
+    with pytest.raises(_lib.CarError) as err:
+        _lib.user_call(_lib.check, -2, "probe")
+    assert err.value.code == -2 and err.value.entry == "probe"
+    assert _lib.user_call(lambda a, b: a + b, 1, 2) == 3
+
+
+def test_lds_step_down_rule(lib):
+    """RenderEngine._ran with a stand-in entry: only CAR_E_LAUNCH with the "cannot reserve" text steps down (False, with a warning)."""
+    import warnings
+    from cross_attention_renderer_amd import _lib
+    from cross_attention_renderer_amd.engine import RenderEngine
+
+    def failing(code, text):
+        def car_stand_in(*args):
+            raise _lib.CarError(code, "car_stand_in", text)
+        return car_stand_in
+    with pytest.warns(UserWarning, match="car_stand_in: car_stand_in: cannot reserve 163840 bytes of LDS: taking the next kernel of the library"):
+        assert RenderEngine._ran(failing(-2, "car_stand_in: cannot reserve 163840 bytes of LDS"), 1, 2) is False
+    with pytest.warns(UserWarning, match="^car_other: .*cannot reserve"):
+        assert RenderEngine._ran(failing(-2, "cannot reserve"), what="car_other") is False
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        with pytest.raises(_lib.CarError):
+            RenderEngine._ran(failing(-2, "an illegal memory access was encountered"))
+        with pytest.raises(_lib.CarError):
+            RenderEngine._ran(failing(-1, "cannot reserve"))
+        seen = []
+        assert RenderEngine._ran(lambda *a: seen.append(a) or 0, 3, None) is True and seen == [(3, None)]
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "cross_attention_renderer_amd")
     for dirpath, _, files in os.walk(pkg):
