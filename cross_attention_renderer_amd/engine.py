@@ -34,6 +34,7 @@ from .poses import pack_poses
 Tensor = torch.Tensor
 
 RELU_IN, RELU_OUT, ACCUM, NO_GLDS = 1, 2, 4, 8
+WGRAD_FP32 = 16            # CAR_WGRAD_FP32 (include/car_hip.h)
 PLACE_PLAIN, PLACE_OWN, PLACE_OTHER2 = 0, 1, 2
 
 
@@ -80,6 +81,20 @@ def _mode(m) -> str:
     if m.no_latent_concat:
         return "plain"
     return {1: "single", 2: "concat2", 3: "concat3"}[m.n_view]
+
+
+_Layers = collections.namedtuple("_Layers", "head attention round2 decoder blocks")
+
+
+def _render_layers(m) -> _Layers:
+    """The linear layers a module's render path reads, by part: ``head`` (what makes e, per _mode), ``attention``, ``round2`` (read with
+    repeat_attention), ``decoder`` (its two ends, then block by block) and, again, the decoder's ``blocks`` as [(lin_z, fc_0, fc_1)]."""
+    qel = ["query_encode_latent", "query_encode_latent_2"]
+    blocks = [(f"phi.lin_z.{i}", f"phi.blocks.{i}.fc_0", f"phi.blocks.{i}.fc_1") for i in range(m.phi.n_blocks)]
+    return _Layers(head={"concat2": qel, "concat3": qel, "single": ["update_val_merge"], "plain": []}[_mode(m)],
+                   attention=["latent_value", "key_map", "key_map_2", "query_embed", "query_embed_2"],
+                   round2=["query_repeat_embed", "query_repeat_embed_2", "encode_latent"],
+                   decoder=["phi.lin_in", "phi.lin_out"] + [n for block in blocks for n in block], blocks=blocks)
 
 
 class _Cached:
@@ -226,9 +241,9 @@ class RenderEngine:
     def _weights(self, device) -> Dict[str, PackedLinear]:
         m = self.m
         sd = dict(m.named_parameters())
-        names = [] if m.no_latent_concat else ["query_encode_latent", "query_encode_latent_2"] if m.n_view > 1 else ["update_val_merge"]
-        names += ["latent_value", "key_map", "key_map_2", "query_embed", "query_embed_2", "encode_latent", "query_repeat_embed_2", "phi.lin_in",
-                  "phi.lin_out"] + [f"phi.{n}" for i in range(m.phi.n_blocks) for n in (f"lin_z.{i}", f"blocks.{i}.fc_0", f"blocks.{i}.fc_1")]
+        layers = _render_layers(m)
+        qre, qre_2, encode_latent = layers.round2                    # query_repeat_embed is packed as its two halves below
+        names = layers.head + layers.attention + [encode_latent, qre_2] + layers.decoder
 
         def build():
             pk = {n: PackedLinear(sd[n + ".weight"], sd[n + ".bias"], device, n) for n in names}
@@ -242,7 +257,7 @@ class RenderEngine:
             pk["query_repeat_embed.h"] = PackedLinear(wr[:, :128], None, device, "query_repeat_embed.h")           # z_embed half, per ray
             pk["query_repeat_embed.g"] = PackedLinear(wr[:, 128:], sd["query_repeat_embed.bias"], device, "query_repeat_embed.g")  # local_coords half
             return pk
-        return self._packed.get([sd[n + k] for n in names + ["query_repeat_embed"] for k in (".weight", ".bias")], (str(device),), build)
+        return self._packed.get([sd[n + k] for n in names + [qre] for k in (".weight", ".bias")], (str(device),), build)
 
     # ------------------------------------------------------------------ feature maps
     def _channel_last(self, z: List[Tensor]) -> List[Tensor]:
@@ -497,17 +512,17 @@ class RenderEngine:
         for n in _lib.WEIGHT_FIELDS[0]:
             setattr(w, f"{n.replace('.', '_')}_w", dev(n + ".weight"))
             setattr(w, f"{n.replace('.', '_')}_b", dev(n + ".bias"))
-        for i in range(3):
-            w.phi_lin_z_w[i], w.phi_lin_z_b[i] = dev(f"phi.lin_z.{i}.weight"), dev(f"phi.lin_z.{i}.bias")
-            w.phi_fc_0_w[i], w.phi_fc_0_b[i] = dev(f"phi.blocks.{i}.fc_0.weight"), dev(f"phi.blocks.{i}.fc_0.bias")
-            w.phi_fc_1_w[i], w.phi_fc_1_b[i] = dev(f"phi.blocks.{i}.fc_1.weight"), dev(f"phi.blocks.{i}.fc_1.bias")
+        for i, (lin_z, fc_0, fc_1) in enumerate(_render_layers(self.m).blocks[:3]):
+            w.phi_lin_z_w[i], w.phi_lin_z_b[i] = dev(lin_z + ".weight"), dev(lin_z + ".bias")
+            w.phi_fc_0_w[i], w.phi_fc_0_b[i] = dev(fc_0 + ".weight"), dev(fc_0 + ".bias")
+            w.phi_fc_1_w[i], w.phi_fc_1_b[i] = dev(fc_1 + ".weight"), dev(fc_1 + ".bias")
         w.keep = keep
         return w
 
     def _plan_sources(self, d, device):
         """What a plan is built from: the parameters of every layer it packs, and the device and dims it packs them for."""
         sd = dict(self.m.named_parameters())
-        names = list(_lib.WEIGHT_FIELDS[0]) + [f"phi.{n}" for i in range(3) for n in (f"lin_z.{i}", f"blocks.{i}.fc_0", f"blocks.{i}.fc_1")]
+        names = list(_lib.WEIGHT_FIELDS[0]) + [n for block in _render_layers(self.m).blocks[:3] for n in block]
         return [sd[n + k] for n in names for k in (".weight", ".bias")], (str(device), d.P, tuple(d.level_c[:d.n_levels]))
 
     def _build_plan(self, what: str, d, device, w) -> Tensor:

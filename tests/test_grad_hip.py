@@ -65,6 +65,39 @@ def test_training_forward_equals_the_literal_inference_forward(name):
         assert torch.equal(train[k].detach(), infer[k]), k
 
 
+@pytest.mark.parametrize("name", ("t0_default", "t0_nview1", "t0_nview3", "t0_no_latent_concat"))
+def test_parameter_gradients_are_the_same_whether_or_not_the_pyramid_asks_for_one(name):
+    """One backward with the pyramid detached (no stage takes the gathered rows' gradient, nothing is scattered) and one with it requiring
+    gradients, on every way the staged route makes e: the detached run's levels carry no gradient, its parameter gradients are the
+    reference's (the fixtures' bound) and agree with the other run's up to the order of the atomics they meet in — 2e-5 of
+    max(1, largest entry), the bound of test_binned_scatter_equals_the_atomic_scatter."""
+    from cross_attention_renderer_amd.training import render_train
+    dev = torch.device("cuda:0")
+    c, inp, z, sd, _ = load_case(name)
+    fx = np.load(G.grad_fixture_path(name))
+    m = build_module(c, sd, dev).train()
+    inp = to_device(inp, dev, cameras_on_host=True)
+
+    def run(asks):
+        m.zero_grad(set_to_none=True)
+        zr = [t.to(dev).requires_grad_(asks) for t in z]
+        out = render_train(m, inp, z=zr)
+        c_rgb, c_depth = G.cotangents(out["rgb"].shape, out["depth_ray"].shape)
+        ((out["rgb"] * c_rgb.to(dev)).sum() + (out["depth_ray"] * c_depth.to(dev)).sum()).backward()
+        torch.cuda.synchronize()
+        return {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}, zr
+    detached, z_detached = run(False)
+    attached, z_attached = run(True)
+    assert all(t.grad is None for t in z_detached) and all(t.grad is not None for t in z_attached)
+    assert sorted("param." + k for k in detached) == [k for k in G.keys(fx) if k.startswith("param.")] and detached.keys() == attached.keys()
+    for k, g in detached.items():
+        G.compare(fx, "param." + k, g, tol=1e-3)
+        worst = (g - attached[k]).abs().max().item()
+        bound = 2e-5 * max(1.0, attached[k].abs().max().item())
+        print(f"{name} {k}: {worst:.2e} (bound {bound:.2e})")
+        assert worst <= bound, (k, worst, bound)
+
+
 def test_wgrad_kernel_matches_torch():
     """car_linear_wgrad alone: dW += dY^T X, db += sum dY, ragged sizes, strides, the relu-on-load flag and accumulation."""
     lib, dev = abi.lib(), torch.device("cuda:0")
