@@ -1,5 +1,5 @@
 // car_lds_dma.h — the LDS-DMA instruction sequence and the vector-memory wait of the kernels that stream weights or rows L2 -> LDS
-// (car_linear.hip, car_fused.hip, car_fused_mma.h and its users, car_raychain.hip).  Included INSIDE the including file's anonymous
+// (car_linear.hip, car_fused.hip, car_mma_tile.h and its users — car_fused_mma.h, car_row_sweep.h —, car_raychain.hip).  Included INSIDE the including file's anonymous
 // namespace, like car_split.h.  The callers keep their own address arithmetic, readfirstlane and CAR_BOUNDS_TRAP checks: they know
 // their extents.
 #pragma once

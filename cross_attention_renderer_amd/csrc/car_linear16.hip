@@ -1,27 +1,19 @@
 // car_linear16.hip — one wide linear layer of the stage entries on the f16 matrix pipe (car_linear_x3): Y = act(act_in(X) W^T + b (+ Y)).
 // The staged route (constructor variants, training forward, the backward's data gradients: reference models.py:333-341, 487-491, 529,
 // 548, 553) spends most of its time in 576 -> 576 / 288 / 128 layers over every epipolar sample; car_linear runs them on the fp32 matrix
-// pipe (157 TFLOP/s peak).  This kernel is the fused per-sample kernel's layer machinery (car_fused_mma.h) with the B operands read
-// from the rows of X: fp16 hi / lo halves of both operands, three v_mfma_f32_16x16x32_f16 products per term, fp32 accumulation
-// (fp32-class accuracy, 2500 / 3 TFLOP/s peak); the layer's weights carry a power of two chosen at pack time, every row of X a power of two
-// that follows the largest magnitude seen so far along the row (when a later chunk outgrows it, the row's accumulators are moved to the
-// new power of two — an exact multiplication — so X is read once, not twice), both undone exactly on the accumulators.
-// A workgroup = 12 waves x 16 rows; a wave keeps NT tiles of 16 outputs (NT = 18: 288 columns, 72 accumulator registers; wider layers
-// run as column groups); the weight chunks (K = 32 x the group's columns) stream L2 -> LDS by LDS-DMA, double buffered.
+// pipe (157 TFLOP/s peak).  This kernel is the row sweep of car_row_sweep.h (the fused per-sample kernel's tile machinery, car_mma_tile.h,
+// fed one K step of a row at a time; shared with car_lpips.hip's convolution) with the B operands read from the rows of X, or MADE
+// from the merged lattice (GATHER), and the KQ instance's tail behind it: split-fp16 operands, fp32 accumulation (fp32-class accuracy,
+// 2500 / 3 TFLOP/s peak).  NT = 18: 288 columns, 72 accumulator registers; wider layers run as column groups.
 #include "car_common.h"
 #include "car_geom.h"
 
 namespace {
 
-constexpr int kWaves = 12, kRows = 16, kGroupRows = kWaves * kRows;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kPieces = 3;                         // LDS-DMA pieces of the widest chunk (18 tiles = 36 KB over 12 waves); narrower column groups
-                                                   // take fewer (pieces_of): a piece index past the chunk would copy from beyond it
-constexpr int pieces_of(int nt) { return (2 * nt + kWaves - 1) / kWaves; }
-
+#include "car_row_sweep.h"
 #include "car_fused_mma.h"
 
-// The layer stream of this kernel addresses its chunks itself (chunk_desc below); the chunk table car_fused_mma.h asks for serves the KQ
+// The layer stream of this kernel addresses its chunks itself (chunk_desc, car_row_sweep.h); the chunk table car_fused_mma.h asks for serves the KQ
 // instance's tail (car_key_query_logits): a blob of K2 = chunks 0, 1 (two K steps x 8 tiles each) | Q1 = chunk 2 (8 tiles) | Q2 = chunks 3, 4
 constexpr int kG_K2 = 0, kG_Q1 = 2, kG_Q2 = 3, kTailTiles = 72;
 __device__ __forceinline__ constexpr int chunk_tile_offset(int g) { return g <= 0 ? 0 : g == 1 ? 16 : g == 2 ? 32 : g == 3 ? 40 : 56; }
@@ -52,37 +44,18 @@ struct LinArgs {
 template <int NT, bool GATHER = false, bool KQ = false>
 __global__ void __launch_bounds__(kThreads) linear16_kernel(const LinArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];      // [2][NT][512] (+ GATHER: the [K][4] point / bias table)
-    static_assert(kWaves * pieces_of(NT) <= 3 * 2 * NT, "stream_issue_piece wraps a piece index into the chunk with two subtractions");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int s = lane & 15, q4 = lane >> 4;
-    // the column groups of a block of rows read the same rows of X: they sit on ONE XCD (workgroup b runs on XCD b % 8) in consecutive
-    // slots, so the second reader finds the rows in that XCD's L2 — as neighbours in launch order (rounds 4-6) they were on different
-    // XCDs and a 576-wide layer fetched X twice from the fabric (HBM-bound at 1.3-1.5 ms per 589 824 x 576 x 576 layer)
-    const int groups = a.tiles_total / NT;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const long rblock = (long)(slot / groups) * 8 + xcd;
-    if (rblock * kGroupRows >= a.M) return;                            // the grid is padded to whole rounds of eight row blocks
-    const long row = rblock * kGroupRows + wave * kRows + s;
-    const long lrow = row < a.M ? row : a.M - 1;
+    RowPlace pl;
+    if (!place_rows<NT>(a.tiles_total, a.M, wave, s, pl)) return;
+    const long row = pl.row, lrow = pl.lrow;
     const float* xrow = a.X + lrow * a.ldx;
-    const int tile0 = (slot % groups) * NT;
+    const int tile0 = pl.tile0<NT>();
     const bool relu_in = (a.flags & CAR_LIN_RELU_IN) != 0;
     const int K = a.K;
-
-    auto chunk_desc = [&](int c) {
-        const int ce = c < a.chunks ? c : a.chunks - 1;
-        NextChunk n;
-        n.src = a.Wp + ((long)ce * a.tiles_total + tile0) * kTile;
-        n.dst = lds + (ce & 1) * NT * kTile;
-        n.nkb = 2 * NT;
-#ifdef CAR_BOUNDS
-        n.lim = a.Wp + (long)a.chunks * a.tiles_total * kTile;
-#endif
-        return n;
-    };
-    {
-        const NextChunk n0 = chunk_desc(0);
+    {   // chunk 0 goes out now: what follows runs under the DMA
+        const NextChunk n0 = chunk_desc<NT>(a, tile0, lds, 0);
 #pragma unroll
         for (int p = 0; p < pieces_of(NT); ++p) stream_issue_piece(n0, p, lane, wave);
     }
@@ -158,14 +131,6 @@ __global__ void __launch_bounds__(kThreads) linear16_kernel(const LinArgs a) {
             }
         }
     };
-    // largest magnitude of the row's values in a chunk (the four lanes of a row hold eight each)
-    auto row_max = [&](const float (&x)[8]) {
-        float m = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x[e]));
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        return fmaxf(m, __shfl_xor(m, 32, 64));
-    };
     const float dW = a.down[0];
     float xc[8];
     {
@@ -187,22 +152,22 @@ __global__ void __launch_bounds__(kThreads) linear16_kernel(const LinArgs a) {
     split8(xc, p, bhi, blo);
     stream_sync();                                                     // weight chunk 0 landed
 
+    // the sweep's skeleton (car_row_sweep.h)
 #pragma unroll 1
     for (int c = 0; c < a.chunks; ++c) {
         const float* wl = lds + (c & 1) * NT * kTile + 4 * lane;
-        const NextChunk nx = chunk_desc(c + 1);
+        const NextChunk nx = chunk_desc<NT>(a, tile0, lds, c + 1);
         const int cn = c + 1 < a.chunks ? c + 1 : c;
         float4 rawn[kRaw];
-        issue_x(cn, rawn);                                             // next chunk's rows: in flight under this chunk's MFMAs
+        issue_x(cn, rawn);                                             // next K step's values: in flight under this step's MFMAs
 #pragma unroll
         for (int qs = 0; qs < NT / 2; ++qs) {
             const float* w0 = wl + (2 * qs * 2) * 256;
             mfma_pair(acc[2 * qs], acc[2 * qs + 1], w0, w0 + 512, bhi, blo);
-            // nothing follows the last chunk: re-copying it onto itself would write the buffer this iteration's MFMAs are reading
-            if (qs < pieces_of(NT) && c + 1 < a.chunks) stream_issue_piece(nx, qs, lane, wave);
+            issue_next_piece<NT>(nx, qs, c + 1 < a.chunks, lane, wave);
             __builtin_amdgcn_sched_barrier(0);
         }
-        // the next chunk may outgrow the row's power of two: move the row (accumulators and scale) to the smaller one, exactly
+        // the next K step may outgrow the row's power of two: move the row (accumulators and scale) to the smaller one, exactly
         float xn[8];
         finish_x(cn, rawn, xn);
         const float mn = row_max(xn);
@@ -282,10 +247,7 @@ __global__ void __launch_bounds__(kThreads) linear16_kernel(const LinArgs a) {
         float4 v = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
         if (accum) { const float4 o = *dst; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
         if (relu_out) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
-        if (mrow) {                                                    // car_relu_mask's rule: keep where the activation is > 0
-            const float4 k = *reinterpret_cast<const float4*>(mrow + 16 * t);
-            v = make_float4(k.x > 0.0f ? v.x : 0.0f, k.y > 0.0f ? v.y : 0.0f, k.z > 0.0f ? v.z : 0.0f, k.w > 0.0f ? v.w : 0.0f);
-        }
+        if (mrow) v = keep_where_positive(v, *reinterpret_cast<const float4*>(mrow + 16 * t));
         *dst = v;
     }
 }
@@ -294,7 +256,7 @@ template <int NT, bool GATHER = false, bool KQ = false>
 int launch16(const LinArgs& a, int groups, hipStream_t st) {
     const size_t lds_bytes = KQ ? (size_t)(2 * kChunkTiles * kTile + kTailBias) * sizeof(float)
                                 : (size_t)2 * NT * kTile * sizeof(float) + (GATHER ? (size_t)a.K * 4 * sizeof(float) : 0);
-    CAR_LAUNCH_LDS("car_linear_x3", (linear16_kernel<NT, GATHER, KQ>), dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
+    CAR_LAUNCH_LDS("car_linear_x3", (linear16_kernel<NT, GATHER, KQ>), dim3(sweep_grid(a.M, groups)), dim3(kThreads), lds_bytes, st, a);
     return CAR_OK;
 }
 

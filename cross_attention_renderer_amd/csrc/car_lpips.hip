@@ -6,11 +6,11 @@
 // each, 2x2 max-pool in front of blocks 2-5), and at the five taps relu1_2 .. relu5_3 the channel-normalised squared difference of the two
 // images' features, weighted by a 1x1 layer, averaged over the tap's pixels and summed over the taps.  Weights come from the caller.
 //
-// conv3x3_kernel is car_linear16.hip's layer machinery (car_fused_mma.h: split-fp16 operands, three v_mfma_f32_16x16x32_f16 products per
-// term, fp32 accumulation, weight chunks streamed L2 -> LDS by LDS-DMA) run as an implicit GEMM over 9 K in ONE sweep: a row of the A
-// operand is an output pixel, K step c reads 32 channels of tap c / (K / 32) — the pixel's own address plus one of nine offsets — and a tap
-// outside the image contributes zeros.  The row's power of two follows the largest magnitude seen so far along the 9 K values exactly as
-// in car_linear16.hip.  A row's result depends on its own nine pixels and the weights only, never on its neighbours in the launch: an
+// conv3x3_kernel is the row sweep it shares with car_linear16.hip (car_row_sweep.h: split-fp16 operands, three v_mfma_f32_16x16x32_f16
+// products per term, fp32 accumulation, weight chunks streamed L2 -> LDS by LDS-DMA) run as an implicit GEMM over 9 K in ONE sweep: a row
+// of the A operand is an output pixel, K step c reads 32 channels of tap c / (K / 32) — the pixel's own address plus one of nine offsets —
+// and a tap outside the image contributes zeros.  The row's power of two follows the largest magnitude seen so far along the 9 K values:
+// the sweep's rule.  A row's result depends on its own nine pixels and the weights only, never on its neighbours in the launch: an
 // image gives the same bits wherever it sits in the batch, which is what makes LPIPS of two identical images exactly 0.
 // The first layer (K = 3) is a plain fp32 vector kernel with the scaling layer folded in: the weights carry 1 / scale at pack time and
 // the shift is subtracted from a pixel as it is loaded, so a padded tap stays the exact zero of the scaled image's padding.
@@ -21,16 +21,7 @@
 
 namespace {
 
-constexpr int kWaves = 12, kRows = 16, kGroupRows = kWaves * kRows;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kPieces = 3;                         // LDS-DMA pieces of the widest chunk here (16 tiles = 32 KB over 12 waves)
-constexpr int pieces_of(int nt) { return (2 * nt + kWaves - 1) / kWaves; }
-
-#include "car_fused_mma.h"
-
-// this kernel addresses its weight chunks itself (chunk_desc below); the fused kernel's chunk table that car_fused_mma.h asks for is unused
-__device__ __forceinline__ constexpr int chunk_tile_offset(int) { return 0; }
-__device__ __forceinline__ constexpr int chunk_tiles(int) { return 0; }
+#include "car_row_sweep.h"
 
 // ---- the network ---------------------------------------------------------------------------------------------------------------------
 constexpr int kLayers = 13, kTaps = 5;
@@ -67,18 +58,13 @@ struct ConvArgs {
 template <int NT, bool BWD>
 __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];      // [2][NT][512]
-    static_assert(kWaves * pieces_of(NT) <= 3 * 2 * NT, "stream_issue_piece wraps a piece index into the chunk with two subtractions");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int s = lane & 15, q4 = lane >> 4;
-    // the column groups of a block of pixels read the same pixels: one XCD, consecutive slots (car_linear16.hip)
-    const int groups = a.tiles_total / NT;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const long rblock = (long)(slot / groups) * 8 + xcd;
-    if (rblock * kGroupRows >= a.M) return;                            // the grid is padded to whole rounds of eight row blocks
-    const long row = rblock * kGroupRows + wave * kRows + s;
-    const long lrow = row < a.M ? row : a.M - 1;
-    const int tile0 = (slot % groups) * NT;
+    RowPlace pl;                                                       // one XCD per block of pixels: car_row_sweep.h
+    if (!place_rows<NT>(a.tiles_total, a.M, wave, s, pl)) return;
+    const long row = pl.row, lrow = pl.lrow;
+    const int tile0 = pl.tile0<NT>();
     const int K = a.K;
     // the pixel, and which of its nine taps lie inside its image
     const int pix = (int)(lrow % ((long)a.H * a.W)), py = pix / a.W, px = pix % a.W;
@@ -88,25 +74,14 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         if ((unsigned)(py + t / 3 - 1) < (unsigned)a.H && (unsigned)(px + t % 3 - 1) < (unsigned)a.W) inside |= 1u << t;
     const float* xpix = a.X + lrow * K + 8 * q4;
 
-    auto chunk_desc = [&](int c) {
-        const int ce = c < a.chunks ? c : a.chunks - 1;
-        NextChunk n;
-        n.src = a.Wp + ((long)ce * a.tiles_total + tile0) * kTile;
-        n.dst = lds + (ce & 1) * NT * kTile;
-        n.nkb = 2 * NT;
-#ifdef CAR_BOUNDS
-        n.lim = a.Wp + (long)a.chunks * a.tiles_total * kTile;
-#endif
-        return n;
-    };
-    {
-        const NextChunk n0 = chunk_desc(0);
+    {   // chunk 0 goes out now: what follows runs under the DMA
+        const NextChunk n0 = chunk_desc<NT>(a, tile0, lds, 0);
 #pragma unroll
         for (int p = 0; p < pieces_of(NT); ++p) stream_issue_piece(n0, p, lane, wave);
     }
     // this lane's eight values of K step c: tap t = c >> lgk, channels 32 (c & (K / 32 - 1)) + 8 q4 .. + 7 of pixel (py + t / 3 - 1,
     // px + t % 3 - 1).  issue_x only issues the loads — from the pixel itself when the tap is outside, a valid address whose values are
-    // dropped; finish_x turns them into values when they are consumed (car_linear16.hip)
+    // dropped; finish_x turns them into values when they are consumed (car_row_sweep.h)
     auto tap_of = [&](int c) { return c >> a.lgk; };
     auto issue_x = [&](int c, float4 (&raw)[2]) {
         const int t = tap_of(c), kc = c & ((1 << a.lgk) - 1);
@@ -121,13 +96,6 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         const float e[8] = {raw[0].x, raw[0].y, raw[0].z, raw[0].w, raw[1].x, raw[1].y, raw[1].z, raw[1].w};
 #pragma unroll
         for (int i = 0; i < 8; ++i) x[i] = in ? e[i] : 0.0f;
-    };
-    auto row_max = [&](const float (&x)[8]) {
-        float m = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x[e]));
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        return fmaxf(m, __shfl_xor(m, 32, 64));
     };
     const float dW = a.down[0];
     float xc[8];
@@ -148,10 +116,11 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
     split8(xc, p, bhi, blo);
     stream_sync();                                                     // weight chunk 0 landed
 
+    // the sweep's skeleton (car_row_sweep.h)
 #pragma unroll 1
     for (int c = 0; c < a.chunks; ++c) {
         const float* wl = lds + (c & 1) * NT * kTile + 4 * lane;
-        const NextChunk nx = chunk_desc(c + 1);
+        const NextChunk nx = chunk_desc<NT>(a, tile0, lds, c + 1);
         const int cn = c + 1 < a.chunks ? c + 1 : c;
         float4 rawn[2];
         issue_x(cn, rawn);                                             // next K step's values: in flight under this step's MFMAs
@@ -159,8 +128,7 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
         for (int qs = 0; qs < NT / 2; ++qs) {
             const float* w0 = wl + (2 * qs * 2) * 256;
             mfma_pair(acc[2 * qs], acc[2 * qs + 1], w0, w0 + 512, bhi, blo);
-            // nothing follows the last chunk: re-copying it onto itself would write the buffer this iteration's MFMAs are reading
-            if (qs < pieces_of(NT) && c + 1 < a.chunks) stream_issue_piece(nx, qs, lane, wave);
+            issue_next_piece<NT>(nx, qs, c + 1 < a.chunks, lane, wave);
             __builtin_amdgcn_sched_barrier(0);
         }
         // the next K step may outgrow the row's power of two: move the row (accumulators and scale) to the smaller one, exactly
@@ -193,8 +161,7 @@ __global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
             }
             if (a.act) {
                 CAR_BOUNDS_TRAP(at + 16 * t + 4 <= a.M * a.N);
-                const float4 m = *reinterpret_cast<const float4*>(a.act + at + 16 * t);
-                v.x = m.x > 0.0f ? v.x : 0.0f; v.y = m.y > 0.0f ? v.y : 0.0f; v.z = m.z > 0.0f ? v.z : 0.0f; v.w = m.w > 0.0f ? v.w : 0.0f;
+                v = keep_where_positive(v, *reinterpret_cast<const float4*>(a.act + at + 16 * t));
             }
             *reinterpret_cast<float4*>(yrow + 16 * t) = v;
         }
@@ -212,7 +179,7 @@ int launch_conv(const ConvArgs& a, hipStream_t st) {
     const size_t lds_bytes = (size_t)2 * NT * kTile * sizeof(float);
     const int groups = a.tiles_total / NT;
     CAR_LAUNCH_LDS(BWD ? "car_conv3x3_backward" : "car_conv3x3", (conv3x3_kernel<NT, BWD>),
-                   dim3((unsigned)(car_div_up(car_div_up(a.M, kGroupRows), 8) * 8 * groups)), dim3(kThreads), lds_bytes, st, a);
+                   dim3(sweep_grid(a.M, groups)), dim3(kThreads), lds_bytes, st, a);
     return CAR_OK;
 }
 

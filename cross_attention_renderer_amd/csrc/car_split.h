@@ -1,4 +1,4 @@
-// car_split.h — the split-fp16 operand helpers shared by the matrix kernels (car_fused_mma.h, car_round2.hip,
+// car_split.h — the split-fp16 operand helpers shared by the matrix kernels (car_mma_tile.h, car_round2.hip,
 // car_raychain.hip) and the packers (car_pack.hip).
 // Included INSIDE the including file's anonymous namespace, after its half8 typedef.
 #pragma once

@@ -374,6 +374,35 @@ def case_wgrad(M, N, K, flags, tail=True):
          t, ["dW", "db"])
 
 
+def case_conv(K, N, backward, epilogue, tail=True):
+    """car_conv3x3 / car_conv3x3_backward, K -> N channels of the SWEEP (the backward is called for the N -> K forward layer, so its instance
+    is the forward's of the same case): two images of 5 x 7 pixels — 70 rows, under one 192-row block; every tap class occurs and the second
+    image's first pixel follows the first image's last.  epilogue: the backward's act and add both given, or both null."""
+    lib = L.load()
+    g = torch.Generator().manual_seed(K + N + backward)
+    n, H, Wd = 2, 5, 7
+    rnd = lambda *sh: torch.randn(*sh, generator=g).to(dev)
+    P_ = lambda t: ctypes.c_void_p(t.data_ptr())
+    if not backward:
+        w, b = rnd(N, K, 3, 3) / (9 * K) ** 0.5, rnd(N)
+        packed = torch.empty(lib.car_conv3x3_packed_floats(K, N), device=dev)
+        L.check(lib.car_conv3x3_pack(P_(w), P_(b), K, N, P_(packed), stream()), "car_conv3x3_pack")
+        torch.cuda.synchronize()
+        t = {"X": rnd(n, H, Wd, K), "packed": packed, "Y": torch.zeros(n, H, Wd, N, device=dev)}
+        run_both(lambda p: L.check(lib.car_conv3x3(p("X"), n, H, Wd, K, N, p("packed"), p("Y"), stream()), "car_conv3x3"), t, ["Y"], tail)
+        return
+    w = rnd(K, N, 3, 3) / (9 * K) ** 0.5                             # the forward layer N -> K: weights [K][N][3][3]
+    packed = torch.empty(lib.car_conv3x3_backward_packed_floats(N, K), device=dev)
+    L.check(lib.car_conv3x3_backward_pack(P_(w), N, K, P_(packed), stream()), "car_conv3x3_backward_pack")
+    torch.cuda.synchronize()
+    t = {"D": rnd(n, H, Wd, K), "packed": packed, "out": torch.zeros(n, H, Wd, N, device=dev)}
+    if epilogue:
+        t.update(act=rnd(n, H, Wd, N), add=rnd(n, H, Wd, N))
+    opt = (lambda p, k: p(k)) if epilogue else (lambda p, k: None)
+    run_both(lambda p: L.check(lib.car_conv3x3_backward(p("D"), n, H, Wd, N, K, p("packed"), opt(p, "act"), opt(p, "add"), p("out"), stream()),
+                               "car_conv3x3_backward"), t, ["out"], tail)
+
+
 CASES = {
     "x3_nt18": lambda tail: case_linear_x3(200, 576, 576, 2, tail),
     "x3_nt18_k579": lambda tail: case_linear_x3(4097, 579, 288, 0, tail),
@@ -405,6 +434,10 @@ CASES = {
     "wgrad_fp32": lambda tail: case_wgrad(513, 576, 579, 0, tail),
     "wgrad_small": lambda tail: case_wgrad(777, 3, 128, 1, tail),
 }
+for K_, N_ in ((64, 64), (64, 128), (128, 256)):                       # NT 4, 8, 16
+    CASES[f"conv_{K_}_{N_}"] = lambda tail, K_=K_, N_=N_: case_conv(K_, N_, False, False, tail)
+    CASES[f"conv_bwd_{K_}_{N_}"] = lambda tail, K_=K_, N_=N_: case_conv(K_, N_, True, True, tail)
+    CASES[f"conv_bwd_{K_}_{N_}_bare"] = lambda tail, K_=K_, N_=N_: case_conv(K_, N_, True, False, tail)
 # families of cases (tools/oob_selfcheck.sh runs one family per process)
 FAMILIES = {
     "x3": ["x3_nt18", "x3_nt18_k579", "x3_nt8", "x3_nt4", "x3_nt2", "x3_nt2_long"],
@@ -414,6 +447,7 @@ FAMILIES = {
     "tail": ["tail_37_13", "tail_96_32_b2", "attend_864", "attend_100"],
     "exchange": ["exchange_288", "exchange_ragged", "fused_rows", "kq_864", "kq_ragged"],
     "wgrad": ["wgrad16_579", "wgrad16_ragged", "wgrad_fp32", "wgrad_small"],
+    "conv": [n for n in CASES if n.startswith("conv_")],
 }
 
 if __name__ == "__main__":

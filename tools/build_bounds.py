@@ -2,7 +2,7 @@
 compares the range it is about to read with the extent its launcher passed and TRAPS outside it.  Never part of the product
 (``__graft_entry__.build()`` does not know this file).  Output: tools/_dev/libcar_bounds.so — run the out-of-bounds harness on it with
 CAR_OOB_FULL_LIB=tools/_dev/libcar_bounds.so python tests/oob_runner.py <family>   (tools/oob_selfcheck.sh does all of it).
-``--reintroduce-0d74f26``: also tools/_dev/liboldlin16_bounds.so — today's car_linear16.hip with the bug commit 0d74f26 fixed put back
+``--reintroduce-0d74f26``: also tools/_dev/liboldlin16_bounds.so — today's car_linear16.hip and car_row_sweep.h with the bug commit 0d74f26 fixed put back
 (three LDS-DMA pieces issued whatever the column group's width: a narrow group's third piece copies from behind its chunk)."""
 import os
 import subprocess
@@ -31,12 +31,19 @@ def build(reintroduce: bool = False):
         subprocess.check_call([ge._hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs])
     out = [lib]
     if reintroduce:
-        cur = open(os.path.join(ge.CSRC, "car_linear16.hip")).read()
-        old = cur.replace("p < pieces_of(NT); ++p", "p < kPieces; ++p").replace("if (qs < pieces_of(NT)) stream_issue_piece", "if (qs < kPieces) stream_issue_piece")
-        old = old.replace('static_assert(kWaves * pieces_of(NT) <= 3 * 2 * NT,', 'static_assert(true || kWaves * pieces_of(NT) <= 3 * 2 * NT,')
-        assert old != cur and old.count("kPieces; ++p") >= 1, "car_linear16.hip no longer has the lines commit 0d74f26 changed"
+        # the lines this tool puts back stand in car_linear16.hip (the issue of chunk 0) and in car_row_sweep.h (the static_assert, which
+        # would refuse them): patched copies of both, the header BESIDE the unit (a quoted include resolves beside the including
+        # file first), every other header from csrc/ as usual
+        rep = (("p < pieces_of(NT); ++p", "p < kPieces; ++p"),
+               ('static_assert(kWaves * pieces_of(NT) <= 3 * 2 * NT,', 'static_assert(true || kWaves * pieces_of(NT) <= 3 * 2 * NT,'))
         srcf = os.path.join(DEV, "linear16_with_0d74f26_reverted.hip")
-        open(srcf, "w").write(old)
+        for name, out_path, need in (("car_linear16.hip", srcf, "p < kPieces; ++p"), ("car_row_sweep.h", os.path.join(DEV, "car_row_sweep.h"), "static_assert(true ||")):
+            cur = open(os.path.join(ge.CSRC, name)).read()
+            old = cur
+            for was, becomes in rep:
+                old = old.replace(was, becomes)
+            assert old != cur and old.count(need) == 1, f"{name} no longer has the lines commit 0d74f26 changed"
+            open(out_path, "w").write(old)
         # beside it: car_api.hip (errors, the LDS reservation), car_pack.hip (the kernels car_linear_x3_pack launches) and car_round2.hip (size
         # queries car_pack.hip calls) — a library of its own with no symbol left undefined
         for tag, flags in (("", []), ("_bounds", ["-DCAR_BOUNDS"])):
