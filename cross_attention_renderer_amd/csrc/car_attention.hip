@@ -14,15 +14,6 @@ constexpr int kWideSeg = 14;                     // widest row of the streaming 
 constexpr int kNarrowSeg = 9;                    // the two-view routes' rows: 576 channels.  The segment count is a template argument: the
                                                  // partial sums of all kMaxSeg segments are registers (56 for 14, 36 for 9: a wave of occupancy)
 
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // PARTS (car_attend_parts): `val` holds, per ray and group of `tile_steps` consecutive steps of a view, the partial sum
 // sum_j exp(logit_j - m_g) val_j with m_g the group's largest logit (written by the fused per-sample kernel, csrc/car_fused.hip); the value
 // reduction then runs over the V * ceil(P / tile_steps) groups with the weights exp(m_g - M) / L instead of over the V * P sample rows —
@@ -41,8 +32,7 @@ __global__ void __launch_bounds__(256) attend_kernel(const float* __restrict__ q
     const int sc = blockIdx.x / R, r = blockIdx.x % R;
     const int S = V * P;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // sample s = v*P + p of this ray lives at row ((sc*V+v)*R + r)*P + p
-    auto row_of = [&](int s) -> long { return ((long)(sc * V + s / P) * R + r) * P + (s % P); };
+    auto row_of = [&](int s) -> long { return car_sample_row(sc, r, s, V, R, P); };
 
     const int sub = tid & 15, grp = tid >> 4;            // 16 groups of 16 lanes
     // rows of the value reduction (step 3): the samples, or (PARTS) the step groups.  Their addresses do not depend on the softmax, so the

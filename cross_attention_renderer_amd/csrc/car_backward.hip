@@ -15,11 +15,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // dW[n][k] += sum_m dY[m][n] X[m][k]  (k == K: the bias column, X = 1) on the fp32 matrix pipe: D += A B with A = dY^T (32 outputs x 2
 // rows), B = X (2 rows x 32 inputs), lane l feeding dY[m + l / 32][n + l % 32] and X[m + l / 32][k + l % 32].  A workgroup tile is
@@ -389,7 +384,7 @@ __global__ void __launch_bounds__(256) attend_bwd_kernel(const float* __restrict
     const int S = V * P;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int sub = tid & 15, grp = tid >> 4;
-    auto row_of = [&](int s) -> long { return ((long)(sc * V + s / P) * R + r) * P + (s % P); };
+    auto row_of = [&](int s) -> long { return car_sample_row(sc, r, s, V, R, P); };
     const float* dzr = dz + ((long)sc * R + r) * ld_dz;
     for (int s = tid; s < S; s += 256) s_w[s] = w_in[row_of(s)];
     __syncthreads();

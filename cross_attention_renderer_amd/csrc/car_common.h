@@ -37,6 +37,22 @@ void car_set_error(const char* fmt, ...);
 
 static inline unsigned car_div_up(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
+// ---- device side: what several units' kernels share ----
+// Reduction over the wave's 64 lanes by a fixed xor butterfly (32, 16, .. 1): every lane ends with the same bits, and the order of the
+// additions is part of what the bit-for-bit suites pin.  T: float, double, unsigned (wave_max: float, double)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// sample s = v P + p of ray (sc, r) lives at row ((sc V + v) R + r) P + p of the per-sample arrays (logits, weights, value rows, pt)
+__device__ __forceinline__ long car_sample_row(int sc, int r, int s, int V, int R, int P) { return ((long)(sc * V + s / P) * R + r) * P + (s % P); }
+
 // a C++ function that one unit defines for another: kept out of the library's dynamic symbols
 #define CAR_INTERNAL __attribute__((visibility("hidden")))
 

@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
         }
     }
     if (gmax) {
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        mx = wave_max(mx);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
         __syncthreads();
         if (threadIdx.x == 0) atomicMax(gmax, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));

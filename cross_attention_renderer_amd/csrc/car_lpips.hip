@@ -265,10 +265,6 @@ struct HeadArgs {
     int B;
     double* partial;                               // [B, blk0[5]]
 };
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // a fixed butterfly: every lane ends with the same bits
-    return v;
-}
 __global__ void __launch_bounds__(256) lpips_head_kernel(const HeadArgs a) {
     __shared__ double red[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -453,8 +449,7 @@ __global__ void __launch_bounds__(256) conv_first_backward_kernel(const float* _
             }
         }
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o, 64);
+        for (int c = 0; c < 3; ++c) acc[c] = wave_sum(acc[c]);
         if (n < 3) gx[p * 3 + n] = n == 0 ? acc[0] : n == 1 ? acc[1] : acc[2];
     }
 }

@@ -117,8 +117,7 @@ __global__ __launch_bounds__(64) void ssim_mean_kernel(const double* partial, in
         const double* p = partial + ((size_t)img * C + ch) * tiles;
         double s = 0.0;
         for (int t = lane; t < tiles; t += 64) s += p[t];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        total += s / npix;                                           // crop(S, 5).mean() of the channel
+        total += wave_sum(s) / npix;                                          // crop(S, 5).mean() of the channel
     }
     if (lane == 0) mssim[img] = total / C;                           // mean over the channels (multichannel=True)
 }

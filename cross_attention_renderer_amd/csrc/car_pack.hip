@@ -16,7 +16,7 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 constexpr int kTile16 = kTile;                     // floats per (K step, 16-channel tile) of the fused kernel's blob
 
 __device__ __forceinline__ float block_max(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    v = wave_max(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     float m = 0.0f;
@@ -320,7 +320,7 @@ extern "C" int car_round2_pack(const float* wr1, const float* br1, const float* 
     return copy_bias(bias + kD, br2, kD, st, "car_round2_pack");
 }
 
-// For car_round2_logits_from_g (csrc/car_round2.hip, G instance): query_repeat_embed_2 and query_embed_2 folded into the one layer of the
+// For car_round2_logits_from_g (csrc/car_round2.hip round2g_kernel, car_round2_logit.h): query_repeat_embed_2 and query_embed_2 folded into the one layer of the
 // bilinear form <q2, qry> = y^T (M x + v) + u^T x + c (M = Wr2^T Wq2, v = Wr2^T bq2, u = Wq2^T br2, c = <br2, bq2>; bilinear_fold_kernel) and the
 // two 16 -> 128 layers that make y and x from g.  wpacked [car_round2q_packed_floats()] = M (chained K order) | Wr1[:, 128:] | Wq1, each laid out
 // as car_round2_pack lays out its own; bias [car_round2q_bias_floats()] = br1 | v | bq1 | u | 2^-shift of Wr1g, M, Wq1 | c | scratch (their

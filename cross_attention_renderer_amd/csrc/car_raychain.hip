@@ -5,8 +5,8 @@
 //                                            x += fc_1(relu(fc_0(relu(x)))) } ;  rgb = lin_out(relu(x)) valid + (1 - valid)
 // instead of ~30 launches of car_linear over [rays, <= 576] matrices that are each too small to fill the chip.
 //
-// Mapping: weights are the A operand, rays the B operand, a wave owns 32 rays and keeps a layer's outputs in its accumulators: lane
-// (ray s, half h) register r of tile T = channel 32 T + (r & 3) + 8 (r >> 2) + 4 h.  Those registers ARE the next layer's B operands
+// Mapping: weights are the A operand, rays the B operand, a wave owns 32 rays and keeps a layer's outputs in its accumulators (lane
+// (ray s, half h), register r of tile T: channel mma32_channel(T, r, h), car_mma32.h).  Those registers ARE the next layer's B operands
 // (K step (T, kg) takes registers 8 kg .. 8 kg + 7) when the next layer's weights are packed in that K order ("chained") —
 // activations never leave the register file between layers.  Arithmetic: the f16 matrix pipe with fp16 hi/lo operand halves, three
 // v_mfma_f32_32x32x16_f16 products per term and fp32 accumulation (car_fused_mma.h: fp32-class accuracy, 5x the rate of the fp32
@@ -21,9 +21,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
+#include "car_mma32.h"                             // the chained 32x32x16 tile: f32x16, the channel map, add_bias, mma_chunk
 #include "car_lds_dma.h"
 #include "car_fused_layout.h"
 #include "car_chain_layout.h"                      // tile geometry, the layers with their scale slots, both kernels' sequences and bias tables
@@ -81,40 +79,11 @@ struct Stream {
     __device__ __forceinline__ void sync() const { landed(g + 1); }
 };
 
-#include "car_split.h"
+static_assert(kTileFloats == kMma32Tile && kChunkK == 32 && kTileN == 32, "the packers' tile is the one mma_chunk reads");
 template <int NT>
 __device__ __forceinline__ void scale(f32x16 (&acc)[NT], float f) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] *= f;
-}
-
-// one chunk (32 values of K = two K steps) of a layer: acc[t] += W[tile t][chunk] . x, x8[kg] = this lane's 8 B-operand values of
-// K step kg, already multiplied into the fp16 window by p
-template <int NT>
-__device__ __forceinline__ void mma_chunk(f32x16 (&acc)[NT], const float* wl, const float (&x8)[2][8], float p) {
-    half8 bhi[2], blo[2];
-#pragma unroll
-    for (int kg = 0; kg < 2; ++kg) split8(x8[kg], p, bhi[kg], blo[kg]);
-    // one wave per SIMD: nobody else hides an LDS round trip, so the A operands of step (t, kg) + 1 are read BEFORE the three products of
-    // step (t, kg) are issued (the compiler, left alone, reads them into the same two registers right in front of their first use and
-    // waits: ~100 cycles exposed per 96 cycles of MFMA — the chains ran at a third of their matrix time)
-    auto read = [&](int i, half8& ah, half8& al) {
-        const int t = i >> 1, kg = i & 1;
-        ah = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(wl + t * kTileFloats + ((kg * 2 + 0) * 64) * 4));
-        al = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(wl + t * kTileFloats + ((kg * 2 + 1) * 64) * 4));
-    };
-    half8 ah[2], al[2];
-    read(0, ah[0], al[0]);
-#pragma unroll
-    for (int i = 0; i < 2 * NT; ++i) {
-        const int t = i >> 1, kg = i & 1, cur = i & 1;
-        if (i + 1 < 2 * NT) read(i + 1, ah[cur ^ 1], al[cur ^ 1]);
-        __builtin_amdgcn_sched_barrier(0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bhi[kg], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], blo[kg], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cur], bhi[kg], acc[t], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
 }
 
 // acc += W x for a layer whose input rows come from global memory (standard K order: K step ks takes k = 16 ks + 8 h + e).  The row's
@@ -193,28 +162,14 @@ __device__ __forceinline__ void layer_chained(f32x16 (&acc)[NT], const f32x16 (&
     }
     scale<NT>(acc, dW * pinv);
 }
-template <int NT>
-__device__ __forceinline__ void add_bias(f32x16 (&acc)[NT], const float* b, int h) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] += b[32 * t + (r & 3) + 8 * (r >> 2) + 4 * h];
-}
-template <int NT>
-__device__ __forceinline__ void zero(f32x16 (&acc)[NT]) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-}
-// rows of N channels: lane (s, h) holds channels 32 t + 8 g + 4 h .. + 3 in acc[t][4 g .. 4 g + 3]
+// rows of N channels: lane (s, h) holds channels mma32_channel(t, 4 g, h) .. + 3 in acc[t][4 g .. 4 g + 3]
 template <int NT>
 __device__ __forceinline__ void store_rows(const f32x16 (&acc)[NT], float* row, int N, int h) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int n0 = 32 * t + 8 * g + 4 * h;
+            const int n0 = mma32_channel(t, 4 * g, h);
             if (n0 + 4 <= N) *reinterpret_cast<float4*>(row + n0) = make_float4(acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]);
         }
 }
@@ -269,7 +224,7 @@ __global__ void __launch_bounds__(256, 1) ray_tail_kernel(const ChainArgs a) {
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const float4 v = *reinterpret_cast<const float4*>(a.z1_in + lrow * kE + 32 * t + 8 * g + 4 * h);
+            const float4 v = row4(a.z1_in + lrow * kE, t, g, h);
             z[t][4 * g] = a.zscale * v.x; z[t][4 * g + 1] = a.zscale * v.y; z[t][4 * g + 2] = a.zscale * v.z; z[t][4 * g + 3] = a.zscale * v.w;
         }
     add_bias<9>(z, a.bias, h);

@@ -1,5 +1,5 @@
-// car_round2_attend.hip — the whole second attention round in one kernel: the folded bilinear logits of car_round2.hip's G instance
-// (matrix pipe only) computed UNDER the value stream of car_attention.hip's sample-row instance (HBM only).  The two ran one after the other
+// car_round2_attend.hip — the whole second attention round in one kernel: the folded bilinear logits of car_round2.hip's round2g_kernel
+// (car_round2_logit.h; matrix pipe only) computed UNDER the value stream of car_attention.hip's sample-row instance (HBM only).  The two ran one after the other
 // on an otherwise idle chip, with the logits making a round trip through memory in between.
 //
 // One persistent 12-wave workgroup per compute unit, grid-stride over batches of two rays:
@@ -7,9 +7,8 @@
 //              576-wide row as nine non-temporal float4 loads per lane), softmax and reduction order: w_out and z_out come out bit for bit
 //              as car_attend writes them.  Two rows per lane are in flight at any time, also across the batch boundary.
 //   waves 8-11 "matrix": one per SIMD; they compute the NEXT batch's logits into an LDS double buffer while the current one streams.
-//              Arithmetic and summation order are round2_kernel<true>'s, sample by sample; only the live ranges differ: x is kept as its
-//              fp16 hi / lo operand halves (64 registers), M x and y are produced one 32-channel tile at a time (16 registers each) and
-//              dotted at once, in the order (t, gq, r) — the kernel must share its register budget with the stream waves.
+//              A sample's logit is car_round2_logit.h's sample_logit: round2g_kernel's products and sums in its order (bit for bit its
+//              logits), with short live ranges, because the kernel must share its register budget with the stream waves.
 // One __syncthreads() closes each batch.  A stream wave needs no other barrier: it computes the ray's softmax for itself (each of the four
 // waves evaluates all four waves' partial sums, in the two-kernel form's order), and the four waves' partial value sums meet in an LDS
 // double buffer that is folded after the barrier.  The packs of car_round2q_pack (82 KB) sit in LDS for the workgroup's life.
@@ -17,11 +16,10 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+#include "car_mma32.h"
 #include "car_round2_layout.h"
-#include "car_split.h"
+#include "car_round2_logit.h"
 
 constexpr int kC = 576, kSeg = kC / 64;                             // the value rows: nine 64-channel segments
 constexpr int kMaxSamples = CAR_MAX_VIEWS * 256;                    // car_attention.hip's limit on V * P
@@ -33,15 +31,6 @@ constexpr int kLdsUh = kLdsZ + 2 * 2 * 4 * kC;                      // [4 matrix
 constexpr int kLdsFloats = kLdsUh + kMatrixWaves * kD;
 static_assert(kLdsZ % 4 == 0 && kLdsUh % 4 == 0 && kLdsFloats * sizeof(float) <= 160 * 1024, "LDS layout");
 
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 struct Args {
     const float *g, *uh, *wpacked, *bias, *val;
     int b, V, R, P;
@@ -49,118 +38,6 @@ struct Args {
     int ld_z;
     float* logit_out;
 };
-
-// logit of this lane's sample (lane (s, h): sample s of the wave's 32, channel half h), round2_kernel<true>'s arithmetic.  g0, g1: the
-// lane's half of the sample's g row; ub: br1 + uh of the tile's ray, in LDS (a tile of 32 samples lies inside one ray: P % 32 == 0)
-__device__ __forceinline__ float sample_logit(const float* lds, const float4 g0, const float4 g1, const float* ub, int lane, int h) {
-    const float* lb = lds + kLdsBiasG;
-    const float down1 = lb[4 * kD], down2 = lb[4 * kD + 1], downq = lb[4 * kD + 2];
-    half8 ghi, glo;
-    float gp, ginv;
-    {
-        const float gx[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        float m = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf(gx[k]));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        pow2_scale(fmaxf(m, 1e-30f), gp, ginv);
-        split8(gx, gp, ghi, glo);
-    }
-    // x = relu(Wq1 g + bq1), u^T x, and x's fp16 halves: the B operands of the folded layer (K step (c, kg) takes entries 8 kg .. 8 kg + 7 of tile c)
-    half8 bhi[kChunks][2], blo[kChunks][2];
-    float dot_u = 0.0f, xinv;
-    {
-        f32x16 xq[kNT];
-#pragma unroll
-        for (int t = 0; t < kNT; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) xq[t][r] = 0.0f;
-            const float* w1 = lds + kLdsWq1 + t * 512 + 4 * lane;
-            const half8 ah = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1));
-            const half8 al = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1 + 256));
-            xq[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ghi, xq[t], 0, 0, 0);
-            xq[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, glo, xq[t], 0, 0, 0);
-            xq[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, ghi, xq[t], 0, 0, 0);
-        }
-        const float undoq = downq * ginv;
-        const float* lu = lb + 3 * kD;
-        const float* lq = lb + 2 * kD;
-        float xqm = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kNT; ++t)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 u = *reinterpret_cast<const float4*>(lu + 32 * t + 8 * gq + 4 * h);
-                const float4 b = *reinterpret_cast<const float4*>(lq + 32 * t + 8 * gq + 4 * h);
-                const float uu[4] = {u.x, u.y, u.z, u.w}, bb[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float x = fmaxf(fmaf(xq[t][4 * gq + r], undoq, bb[r]), 0.0f);
-                    xq[t][4 * gq + r] = x;
-                    xqm = fmaxf(xqm, x);
-                    dot_u = fmaf(uu[r], x, dot_u);
-                }
-            }
-        xqm = fmaxf(xqm, __shfl_xor(xqm, 32, 64));
-        float xp;
-        pow2_scale(fmaxf(xqm, 1e-30f), xp, xinv);
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c)
-#pragma unroll
-            for (int kg = 0; kg < 2; ++kg) {
-                float x8[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x8[e] = xq[c][8 * kg + e];
-                split8(x8, xp, bhi[c][kg], blo[c][kg]);
-            }
-    }
-    // per 32-channel tile t: y = relu(Wr1g g + br1 + uh) (K = 16), (M x) of the same channels (K = 128), and their products
-    const float undo1 = down1 * ginv;
-    const float* lv = lb + kD;
-    float dot = 0.0f, dot_v = 0.0f;
-#pragma unroll
-    for (int t = 0; t < kNT; ++t) {
-        f32x16 y, acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { y[r] = 0.0f; acc[r] = 0.0f; }
-        {
-            const float* w1 = lds + kLdsW1 + t * 512 + 4 * lane;
-            const half8 ah = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1));
-            const half8 al = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(w1 + 256));
-            y = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ghi, y, 0, 0, 0);
-            y = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, glo, y, 0, 0, 0);
-            y = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, ghi, y, 0, 0, 0);
-        }
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c)
-#pragma unroll
-            for (int kg = 0; kg < 2; ++kg) {
-                const float* wl = lds + (c * kNT + t) * kTile + 4 * lane;
-                const half8 ah = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(wl + ((kg * 2 + 0) * 64) * 4));
-                const half8 al = __builtin_bit_cast(half8, *reinterpret_cast<const float4*>(wl + ((kg * 2 + 1) * 64) * 4));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bhi[c][kg], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, blo[c][kg], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bhi[c][kg], acc, 0, 0, 0);
-            }
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const float4 u = *reinterpret_cast<const float4*>(ub + 32 * t + 8 * gq + 4 * h);
-            const float4 v4 = *reinterpret_cast<const float4*>(lv + 32 * t + 8 * gq + 4 * h);
-            const float uu[4] = {u.x, u.y, u.z, u.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float yy = fmaxf(fmaf(y[4 * gq + r], undo1, uu[r]), 0.0f);
-                dot = fmaf(yy, acc[4 * gq + r], dot);
-                dot_v = fmaf(yy, vv[r], dot_v);
-            }
-        }
-    }
-    // y^T (M x) in the product's units, y^T v and u^T x in true ones
-    dot = fmaf(dot, down2 * xinv, dot_u + dot_v);
-    dot += __shfl_xor(dot, 32, 64);
-    dot += lb[4 * kD + 3];
-    return dot / 16.0f;
-}
 
 __global__ void __launch_bounds__(kThreads) round2_attend_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -173,10 +50,8 @@ __global__ void __launch_bounds__(kThreads) round2_attend_kernel(const Args a) {
     const int V = a.V, R = a.R, P = a.P, S = V * P;
     const long BR = (long)a.b * R, nbatch = (BR + 1) / 2, rows = BR * S;
     const bool matrix = wave >= kStreamWaves;
-    // sample s = v*P + p of ray (sc, r) lives at row ((sc*V+v)*R + r)*P + p
     auto row_of = [&](int ray, int s) -> long {
-        const int sc = ray / R, r = ray % R;
-        const long row = ((long)(sc * V + s / P) * R + r) * P + (s % P);
+        const long row = car_sample_row(ray / R, ray % R, s, V, R, P);
         CAR_BOUNDS_TRAP(ray >= 0 && ray < BR && s >= 0 && s < S && row >= 0 && row < rows);
         return row;
     };
@@ -228,6 +103,7 @@ __global__ void __launch_bounds__(kThreads) round2_attend_kernel(const Args a) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    // a tile of 32 samples lies inside one ray: P % 32 == 0
                     const float logit = sample_logit(lds, g0, g1, ub, lane, h);
                     if (h == 0) {
                         CAR_BOUNDS_TRAP(si < kMaxSamples);

@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(256) scan_sums_kernel(const unsigned* __restri
     const long b0 = (long)blockIdx.x * kScanBlock;
     unsigned s = 0;
     for (int k = threadIdx.x; k < kScanBlock; k += 256) s += b0 + k < n ? count[b0 + k] : 0u;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) sums[blockIdx.x] = red[0] + red[1] + red[2] + red[3];

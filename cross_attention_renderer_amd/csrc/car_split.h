@@ -1,5 +1,5 @@
-// car_split.h — the split-fp16 operand helpers shared by the matrix kernels (car_mma_tile.h, car_round2.hip,
-// car_raychain.hip) and the packers (car_pack.hip).
+// car_split.h — the split-fp16 operand helpers shared by the matrix kernels (through car_mma_tile.h: car_fused.hip, car_linear16.hip,
+// car_lpips.hip; through car_mma32.h: car_raychain.hip, car_round2.hip, car_round2_attend.hip) and the packers (car_pack.hip).
 // Included INSIDE the including file's anonymous namespace, after its half8 typedef.
 #pragma once
 

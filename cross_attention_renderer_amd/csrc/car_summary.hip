@@ -27,7 +27,7 @@ constexpr int kEntropyMaxBlocks = 1024;
 // function of `rows` alone, so nothing depends on launch timing.
 __global__ __launch_bounds__(kThreads) void entropy_rows_kernel(const float* __restrict__ w, long rows, int S, int nan_rows_zero,
                                                                 double* __restrict__ partial) {
-    __shared__ double wave_sum[kWaves];
+    __shared__ double wave_acc[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long n_waves = (long)gridDim.x * kWaves;
     double acc = 0.0;
@@ -39,16 +39,15 @@ __global__ __launch_bounds__(kThreads) void entropy_rows_kernel(const float* __r
             const float term = wj * logf(wj + 1e-5f);
             s += (double)term;
         }
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        double ent = -s;
+        double ent = -wave_sum(s);
         if (nan_rows_zero && ent != ent) ent = 0.0;                  // training.py:113: ent[torch.isnan(ent)] = 0
         acc += ent;
     }
-    if (lane == 0) wave_sum[wave] = acc;
+    if (lane == 0) wave_acc[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
-        double t = wave_sum[0];
-        for (int i = 1; i < kWaves; ++i) t += wave_sum[i];
+        double t = wave_acc[0];
+        for (int i = 1; i < kWaves; ++i) t += wave_acc[i];
         partial[blockIdx.x] = t;
     }
 }
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(64) void entropy_sum_kernel(const double* __restric
     const int lane = threadIdx.x;
     double s = 0.0;
     for (int i = lane; i < n; i += 64) s += partial[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if (lane == 0) out[0] = s;
 }
 
