@@ -1,4 +1,4 @@
-"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h``).
+"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h`` and, for the matcher, in ``include/car_match.h``, which it includes).
 
 The library is built in-tree by ``__graft_entry__.build()``.  There is no fallback: if it cannot be loaded,
 ``load()`` raises.  Two handles on the one library: ``api()``, which the package calls — every entry that returns a status checks itself
@@ -177,6 +177,30 @@ SIGNATURES = {
     "car_essential_ransac": (c_int, [_P, _P, c_int, _P, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# the matcher's entries (SuperPoint, SuperGlue): mirrors include/car_match.h, the header of their own that car_hip.h includes; bound
+# and checked like SIGNATURES
+MATCH_SIGNATURES = {
+    "car_superpoint_packed_floats": (c_size_t, []),
+    "car_superpoint_pack": (c_int, [_P, _P, _P, _P]),
+    "car_superpoint_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_superpoint_dense": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "car_superpoint_conv1a": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
+    "car_superpoint_nms_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_superpoint_nms": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "car_superpoint_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_superpoint_select": (c_int, [_P, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "car_superpoint_sample": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P]),
+    "car_superglue_packed_floats": (c_size_t, [c_int]),
+    "car_superglue_pack": (c_int, [_P, c_int, c_int, _P, _P]),
+    "car_superglue_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "car_superglue_descriptors": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "car_superglue_attention": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P]),
+    "car_superglue_transport_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "car_superglue_transport": (c_int, [_P, c_int, _P, c_int, c_float, c_int, _P, _P, c_size_t, _P]),
+    "car_superglue_matches_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "car_superglue_matches": (c_int, [_P, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 # the int entries that return a VALUE (the header's words); every other int entry returns a status: 0, or a negative CAR_E_* code
 VALUE_ENTRIES = (
     "car_version",                # CAR_VERSION
@@ -191,13 +215,13 @@ _api: Optional[ctypes.CDLL] = None
 
 
 def source_hash() -> str:
-    """sha256 over the kernel sources and the public header: build() stores it next to the library, load() refuses a library built
+    """sha256 over the kernel sources and the public headers: build() stores it next to the library, load() refuses a library built
     from anything else (a pushed .so can not silently lag behind the tree)."""
     import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    files.append(os.path.join(os.path.dirname(here), "include", "car_hip.h"))
+    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())
@@ -261,7 +285,7 @@ def _bind(checked: bool) -> ctypes.CDLL:
     """A handle of its own on the library (a second CDLL of one path has its own function objects) with SIGNATURES' prototypes;
     ``checked``: every status entry raises CarError on a negative code."""
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
         if checked and res is c_int and name not in VALUE_ENTRIES:
@@ -298,7 +322,7 @@ def _errcheck(code, fn, args):
 def check_exports() -> None:
     """Every symbol the header declares must be exported (used by build() and the CPU test-suite)."""
     lib = load()
-    missing = [n for n in SIGNATURES if not hasattr(lib, n)]
+    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES) if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"libcar_hip.so lacks symbols: {missing}")
     if lib.car_version() < 300:

@@ -676,6 +676,10 @@ int car_essential_select(const double* x0, const double* x1, int N, const double
 int car_essential_ransac(const double* x0, const double* x1, int N, const int* samples, int H, double thresh, double* E, int* best,
                          unsigned char* inliers, void* work, size_t work_bytes, void* stream);
 
+/* ---- matching an unposed pair: SuperPoint's and SuperGlue's forwards (estimate_pose/superpoint.py, superglue.py).
+ * A block of its own size, declared in a header of its own; every host that includes this file has it. */
+#include "car_match.h"
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
