@@ -1,4 +1,4 @@
-"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h`` and, for the matcher, in ``include/car_match.h``, which it includes).
+"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h`` and, for the matcher, in ``include/car_match.h`` and, for the encoder, in ``include/car_encoder.h``, which it includes).
 
 The library is built in-tree by ``__graft_entry__.build()``.  There is no fallback: if it cannot be loaded,
 ``load()`` raises.  Two handles on the one library: ``api()``, which the package calls — every entry that returns a status checks itself
@@ -201,6 +201,20 @@ MATCH_SIGNATURES = {
     "car_superglue_matches": (c_int, [_P, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# the encoder's entries (the transformer stage of get_z): mirrors include/car_encoder.h, the header of their own that car_hip.h includes;
+# bound and checked like SIGNATURES
+ENCODER_SIGNATURES = {
+    "car_layernorm": (c_int, [_P, c_int, _P, _P, c_int, c_double, _P, c_int, c_long, _P]),
+    "car_gelu": (c_int, [_P, c_int, c_long, c_int, _P]),
+    "car_mha_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_mha": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    "car_vit_packed_floats": (c_size_t, [c_int, c_int]),
+    "car_vit_packed_offset": (c_size_t, [c_int, c_int]),
+    "car_vit_pack": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "car_vit_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_vit_blocks": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_size_t, _P]),
+}
+
 # the int entries that return a VALUE (the header's words); every other int entry returns a status: 0, or a negative CAR_E_* code
 VALUE_ENTRIES = (
     "car_version",                # CAR_VERSION
@@ -221,7 +235,7 @@ def source_hash() -> str:
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h")]
+    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())
@@ -285,7 +299,7 @@ def _bind(checked: bool) -> ctypes.CDLL:
     """A handle of its own on the library (a second CDLL of one path has its own function objects) with SIGNATURES' prototypes;
     ``checked``: every status entry raises CarError on a negative code."""
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES, **ENCODER_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
         if checked and res is c_int and name not in VALUE_ENTRIES:
@@ -322,7 +336,7 @@ def _errcheck(code, fn, args):
 def check_exports() -> None:
     """Every symbol the header declares must be exported (used by build() and the CPU test-suite)."""
     lib = load()
-    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES) if not hasattr(lib, n)]
+    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES, *ENCODER_SIGNATURES) if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"libcar_hip.so lacks symbols: {missing}")
     if lib.car_version() < 300:

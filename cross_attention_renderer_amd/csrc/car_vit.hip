@@ -1,0 +1,443 @@
+// car_vit.hip — the transformer stage of get_z's image encoder (include/car_encoder.h; encoder.py MultiViewDPTEncoder.forward, the 12
+// pre-norm blocks over the concatenated tokens of a scene's views): LayerNorm, exact GELU, multi-head attention with head width 64, the
+// pack of a stage's parameters and the stage itself as a sequence of these entries and car_linear_x3.  Inference only.
+//
+// car_mha is the one hot kernel here.  One wave owns 32 query rows of one (scene, head) as the B operand of car_mma32.h's chained
+// 32 x 32 x 16 tile; per tile of 32 keys it forms S^T = K Q^T (the keys are the A "weights", K = 64 head channels = 4 K steps), whose
+// accumulators hold, per lane, 16 of the 32 logits of the lane's query — the other 16 live in lane ^ 32 — and, once exponentiated and split
+// in registers, ARE the B operand of O^T += V^T P (A = the V tile transposed, K = the 32 keys in the chained order).  The running maximum
+// and sum of a query row and the 32 x 64 output accumulators follow the online softmax.  mha_absmax_kernel and mha_pack_kernel lay k and v of the whole
+// call out as hi / lo A-operand tiles first, one power of two per (scene, head), the padding keys zero.
+#include "car_common.h"
+#include <math.h>
+#include <stdint.h>
+
+namespace {
+
+#include "car_mma32.h"
+
+constexpr int kHead = 64;                          // head width
+constexpr int kKeys = 32;                          // keys per tile = query rows per wave
+constexpr int kStep = kMma32TileK16;               // floats of one K step's A operand: [hi | lo][lane][8 halves]
+constexpr int kTileK = 4 * kStep;                  // the K part of a tile record: 4 K steps over the 64 channels
+constexpr int kTileFloats = 2 * kTileK;            // + the V part: [channel tile (2)][kg (2)] K steps over the 32 keys
+constexpr float kPScale = 8192.0f;                 // the numerators' power of two: p in [0, 1] -> [0, 2^13]
+
+inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// ---- LayerNorm: one wave per row, the row in registers, statistics in fp64 ------------------------------------------------------------
+constexpr int kLnMax = 4096, kLnVec = kLnMax / (64 * 4);
+__global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, int C, double eps, float* __restrict__ Y, int ldy, long M) {
+    const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const int lane = threadIdx.x & 63;
+    const float* x = X + m * ldx;
+    float4 v[kLnVec];
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < kLnVec; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        v[i] = c < C ? *reinterpret_cast<const float4*>(x + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        sum += ((double)v[i].x + (double)v[i].y) + ((double)v[i].z + (double)v[i].w);
+    }
+    const double mean = wave_sum(sum) / (double)C;
+    double sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < kLnVec; ++i) {
+        if ((i * 64 + lane) * 4 < C) {
+            const double a = (double)v[i].x - mean, b = (double)v[i].y - mean, c = (double)v[i].z - mean, d = (double)v[i].w - mean;
+            sq += (a * a + b * b) + (c * c + d * d);
+        }
+    }
+    const double rstd = 1.0 / sqrt(wave_sum(sq) / (double)C + eps);
+    float* y = Y + m * ldy;
+#pragma unroll
+    for (int i = 0; i < kLnVec; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < C) {
+            const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c);
+            float4 o;
+            o.x = fmaf((float)(((double)v[i].x - mean) * rstd), g.x, b.x);
+            o.y = fmaf((float)(((double)v[i].y - mean) * rstd), g.y, b.y);
+            o.z = fmaf((float)(((double)v[i].z - mean) * rstd), g.z, b.z);
+            o.w = fmaf((float)(((double)v[i].w - mean) * rstd), g.w, b.w);
+            *reinterpret_cast<float4*>(y + c) = o;
+        }
+    }
+}
+
+// ---- exact GELU, in place --------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float gelu1(float x) { return 0.5f * x * erfcf(-0.70710678118654752440f * x); }
+__global__ void __launch_bounds__(256) gelu_kernel(float* __restrict__ Y, int ldy, long M, int N4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M * N4) return;
+    float4* p = reinterpret_cast<float4*>(Y + (i / N4) * ldy + (i % N4) * 4);
+    float4 v = *p;
+    v.x = gelu1(v.x); v.y = gelu1(v.y); v.z = gelu1(v.z); v.w = gelu1(v.w);
+    *p = v;
+}
+
+// ---- attention: the operand tiles of k and v -------------------------------------------------------------------------------------------
+struct MhaArgs {
+    const float* qkv; int ld; int b, S, heads, tiles;
+    float* out; int ldo;
+    float* maxes;          // [b heads][tiles][2]: largest |k|, |v| of a tile
+    float* scales;         // [b heads][2]: 1 / p_k, 1 / p_v
+    float* packed;         // [b heads][tiles][kTileFloats]
+};
+
+// largest magnitudes of one tile's k and v (rows beyond the scene are not read)
+__global__ void __launch_bounds__(256) mha_absmax_kernel(MhaArgs a) {
+    __shared__ float red[2][4];
+    const int tile = blockIdx.x % a.tiles, bh = blockIdx.x / a.tiles, h = bh % a.heads, sc = bh / a.heads;
+    const int key = tile * kKeys + (threadIdx.x >> 3), c = (threadIdx.x & 7) * 8, dim = a.heads * kHead;
+    float mk = 0.0f, mv = 0.0f;
+    if (key < a.S) {
+        const float* row = a.qkv + ((long)sc * a.S + key) * a.ld + h * kHead + c;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float4 k4 = *reinterpret_cast<const float4*>(row + dim + 4 * j), v4 = *reinterpret_cast<const float4*>(row + 2 * dim + 4 * j);
+            mk = fmaxf(mk, fmaxf(fmaxf(fabsf(k4.x), fabsf(k4.y)), fmaxf(fabsf(k4.z), fabsf(k4.w))));
+            mv = fmaxf(mv, fmaxf(fmaxf(fabsf(v4.x), fabsf(v4.y)), fmaxf(fabsf(v4.z), fabsf(v4.w))));
+        }
+    }
+    mk = wave_max(mk); mv = wave_max(mv);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = mk; red[1][threadIdx.x >> 6] = mv; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const float* r = red[threadIdx.x];
+        a.maxes[(long)blockIdx.x * 2 + threadIdx.x] = fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3]));
+    }
+}
+
+__device__ __forceinline__ void split_nearest(float x, _Float16& hi, _Float16& lo) {
+    hi = (_Float16)x;
+    lo = (_Float16)(x - (float)hi);
+}
+
+// one tile record: thread (step, lane) writes the lane's 8 hi and 8 lo halves of one K step.  K part: step = ks, the lane's row is key
+// lane % 32, its 8 values channels 16 ks + 8 (lane / 32) + e.  V part: step = 2 t + kg, the lane's row is channel 32 t + lane % 32, its 8
+// values the keys 16 kg + mma32_channel(0, e, lane / 32) — the order in which the logits' accumulators hold them.
+__global__ void __launch_bounds__(256) mha_pack_kernel(MhaArgs a) {
+    const int tile = blockIdx.x % a.tiles, bh = blockIdx.x / a.tiles, h = bh % a.heads, sc = bh / a.heads;
+    const int dim = a.heads * kHead, step = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, hh = lane >> 5;
+    float mk = 0.0f, mv = 0.0f;
+    for (int t = 0; t < a.tiles; ++t) {
+        mk = fmaxf(mk, a.maxes[((long)bh * a.tiles + t) * 2]);
+        mv = fmaxf(mv, a.maxes[((long)bh * a.tiles + t) * 2 + 1]);
+    }
+    float pk, ik, pv, iv;
+    pow2_scale(fmaxf(mk, 1e-30f), pk, ik);
+    pow2_scale(fmaxf(mv, 1e-30f), pv, iv);
+    if (tile == 0 && threadIdx.x == 0) { a.scales[bh * 2] = ik; a.scales[bh * 2 + 1] = iv; }
+    const float* base = a.qkv + (long)sc * a.S * a.ld + h * kHead;
+    _Float16* rec = reinterpret_cast<_Float16*>(a.packed + ((long)bh * a.tiles + tile) * kTileFloats);
+    half8 hi, lo;
+    {   // K part
+        const int key = tile * kKeys + i;
+        float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (key < a.S) {
+            const float* src = base + (long)key * a.ld + dim + 16 * step + 8 * hh;
+            const float4 a0 = *reinterpret_cast<const float4*>(src), a1 = *reinterpret_cast<const float4*>(src + 4);
+            x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { _Float16 u, l; split_nearest(x[e] * pk, u, l); hi[e] = u; lo[e] = l; }
+        _Float16* dst = rec + (long)step * (2 * kStep);                           // halves: kStep floats = 2 kStep halves
+        *reinterpret_cast<half8*>(dst + lane * 8) = hi;
+        *reinterpret_cast<half8*>(dst + kStep + lane * 8) = lo;
+    }
+    {   // V part
+        const int t = step >> 1, kg = step & 1, c = 32 * t + i;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int key = tile * kKeys + 16 * kg + mma32_channel(0, e, hh);
+            const float x = key < a.S ? base[(long)key * a.ld + 2 * dim + c] : 0.0f;
+            _Float16 u, l; split_nearest(x * pv, u, l); hi[e] = u; lo[e] = l;
+        }
+        _Float16* dst = rec + 2 * kTileK + (long)step * (2 * kStep);
+        *reinterpret_cast<half8*>(dst + lane * 8) = hi;
+        *reinterpret_cast<half8*>(dst + kStep + lane * 8) = lo;
+    }
+}
+
+// ---- attention: one wave = 32 query rows of one (scene, head) --------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) mha_kernel(MhaArgs a) {
+    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= (long)a.b * a.heads * a.tiles) return;                                  // no barrier below: a wave may leave alone
+    const int qt = (int)(wave % a.tiles), bh = (int)(wave / a.tiles), h = bh % a.heads, sc = bh / a.heads;
+    const int lane = threadIdx.x & 63, s = lane & 31, hh = lane >> 5;
+    const int q = qt * kKeys + s, qrow = q < a.S ? q : a.S - 1;                         // rows beyond the scene: a copy of its last row, never stored
+    const float* qsrc = a.qkv + ((long)sc * a.S + qrow) * a.ld + h * kHead + 8 * hh;
+    float x8[4][8];
+    float m = 0.0f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        const float4 a0 = *reinterpret_cast<const float4*>(qsrc + 16 * ks), a1 = *reinterpret_cast<const float4*>(qsrc + 16 * ks + 4);
+        x8[ks][0] = a0.x; x8[ks][1] = a0.y; x8[ks][2] = a0.z; x8[ks][3] = a0.w;
+        x8[ks][4] = a1.x; x8[ks][5] = a1.y; x8[ks][6] = a1.z; x8[ks][7] = a1.w;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x8[ks][e]));
+    }
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    float pq, iq;
+    pow2_scale(fmaxf(m, 1e-30f), pq, iq);
+    half8 qhi[4], qlo[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) split8(x8[ks], pq, qhi[ks], qlo[ks]);
+    const float ik = a.scales[bh * 2], iv = a.scales[bh * 2 + 1];
+    const float cq = 0.125f * iq;                                                       // 1 / sqrt(64), with the query row's power of two
+
+    f32x16 o[2];
+    zero(o);
+    float mrun = -INFINITY, lrun = 0.0f;
+    const float* tw = a.packed + (long)bh * a.tiles * kTileFloats + 4 * lane;
+    // one wave per SIMD at the eval shape: nobody else hides a load, so the K operands of tile kt + 1 are requested while tile kt's softmax
+    // runs, and the V operands of tile kt before its logits are formed
+    half8 kh[4], kl[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) read_a(tw + ks * kStep, kh[ks], kl[ks]);
+    for (int kt = 0; kt < a.tiles; ++kt, tw += kTileFloats) {
+        half8 vh[4], vl[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) read_a(tw + kTileK + i * kStep, vh[i], vl[i]);
+        f32x16 sacc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[r] = 0.0f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) mma3(sacc, kh[ks], kl[ks], qhi[ks], qlo[ks]);
+        if (kt + 1 < a.tiles) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) read_a(tw + kTileFloats + ks * kStep, kh[ks], kl[ks]);
+        }
+        // the lane's 16 logits: keys kt 32 + mma32_channel(0, r, hh); a key beyond the scene is masked by its index
+        const int left = a.S - kt * kKeys;
+        float p[16], tm = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = mma32_channel(0, r, hh) < left ? (sacc[r] * ik) * cq : -INFINITY;
+            tm = fmaxf(tm, p[r]);
+        }
+        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+        const float mnew = fmaxf(mrun, tm), alpha = expf(mrun - mnew);
+        float psum = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = mma32_channel(0, r, hh) < left ? expf(p[r] - mnew) : 0.0f;
+            psum += p[r];
+        }
+        psum += __shfl_xor(psum, 32, 64);
+        lrun = lrun * alpha + psum;
+        mrun = mnew;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+        half8 phi[2], plo[2];
+#pragma unroll
+        for (int kg = 0; kg < 2; ++kg) {
+            float p8[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) p8[e] = p[8 * kg + e];
+            split8(p8, kPScale, phi[kg], plo[kg]);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int kg = 0; kg < 2; ++kg) mma3(o[t], vh[2 * t + kg], vl[2 * t + kg], phi[kg], plo[kg]);
+    }
+    if (q >= a.S) return;
+    const float c = iv * (1.0f / kPScale);
+    float* dst = a.out + ((long)sc * a.S + q) * a.ldo + h * kHead;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float4 v;
+            v.x = (o[t][4 * g] * c) / lrun; v.y = (o[t][4 * g + 1] * c) / lrun; v.z = (o[t][4 * g + 2] * c) / lrun; v.w = (o[t][4 * g + 3] * c) / lrun;
+            *reinterpret_cast<float4*>(dst + mma32_channel(t, 4 * g, hh)) = v;
+        }
+}
+
+struct MhaLayout { size_t maxes, scales, packed, total; int tiles; };
+MhaLayout mha_layout(int b, int S, int heads) {
+    MhaLayout l;
+    l.tiles = (S + kKeys - 1) / kKeys;
+    const size_t bh = (size_t)b * heads;
+    l.maxes = 0;
+    l.scales = up256(bh * l.tiles * 2 * sizeof(float));
+    l.packed = l.scales + up256(bh * 2 * sizeof(float));
+    l.total = l.packed + bh * l.tiles * kTileFloats * sizeof(float);
+    return l;
+}
+bool mha_shape_ok(int b, int S, int heads, const char* who) {
+    if (b < 1 || b > 4096) { car_set_error("%s: b = %d is outside 1..4096", who, b); return false; }
+    if (S < 1 || S > 1024) { car_set_error("%s: S = %d is outside 1..1024", who, S); return false; }
+    if (heads < 1 || heads > 16) { car_set_error("%s: heads = %d is outside 1..16", who, heads); return false; }
+    return true;
+}
+
+// the layout of one block of car_vit_pack: item i of the 12 parameters at off[i], the block's size at off[12] (floats)
+struct VitLayout { size_t off[13]; };
+bool vit_dim_ok(int dim, const char* who) {
+    if (dim < 64 || dim > 1024 || dim % 64) { car_set_error("%s: dim = %d must be a multiple of 64 in 64..1024", who, dim); return false; }
+    return true;
+}
+VitLayout vit_layout(int dim) {
+    const size_t d = (size_t)dim;
+    const size_t n[12] = {d, d, car_linear_x3_packed_floats(dim, 3 * dim), 3 * d, car_linear_x3_packed_floats(dim, dim), d, d, d,
+                          car_linear_x3_packed_floats(dim, 4 * dim), 4 * d, car_linear_x3_packed_floats(4 * dim, dim), d};
+    VitLayout l;
+    size_t o = 0;
+    for (int i = 0; i < 12; ++i) { l.off[i] = o; o += (n[i] + 3) & ~(size_t)3; }
+    l.off[12] = o;
+    return l;
+}
+struct VitWork { size_t norm, att, wide, mha, total; };
+VitWork vit_work(int b, int S, int dim) {
+    const size_t rows = (size_t)b * S, d = (size_t)dim * sizeof(float);
+    VitWork w;
+    w.norm = 0;
+    w.att = up256(rows * d);
+    w.wide = w.att + up256(rows * d);
+    w.mha = w.wide + up256(rows * 4 * d);
+    w.total = w.mha + mha_layout(b, S, dim / kHead).total;
+    return w;
+}
+
+}  // namespace
+
+extern "C" int car_layernorm(const float* X, int ldx, const float* gamma, const float* beta, int C, double eps, float* Y, int ldy, long M,
+                             void* stream) {
+    CAR_REQUIRE(X && gamma && beta && Y, "car_layernorm: null pointer");
+    CAR_REQUIRE(C >= 4 && C <= kLnMax && C % 4 == 0, "car_layernorm: C = %d must be a multiple of 4 in 4..%d", C, kLnMax);
+    CAR_REQUIRE(M > 0 && M <= (1L << 31) && eps >= 0.0, "car_layernorm: bad sizes (M = %ld, eps = %g)", M, eps);
+    CAR_REQUIRE(ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0, "car_layernorm: the row strides (%d, %d) must hold C = %d and be multiples of 4",
+                ldx, ldy, C);
+    CAR_REQUIRE(aligned16(X) && aligned16(Y) && aligned16(gamma) && aligned16(beta), "car_layernorm: X, Y, gamma and beta must be 16-byte aligned");
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(layernorm_kernel, dim3(car_div_up(M, 4)), dim3(256), 0, (hipStream_t)stream, X, ldx, gamma, beta, C, eps, Y, ldy, M);
+    CAR_CHECK_LAUNCH("car_layernorm");
+    return CAR_OK;
+}
+
+extern "C" int car_gelu(float* Y, int ldy, long M, int N, void* stream) {
+    CAR_REQUIRE(Y, "car_gelu: null pointer");
+    CAR_REQUIRE(M > 0 && N > 0 && N % 4 == 0 && (M * (N / 4)) / 256 < (1L << 31), "car_gelu: bad sizes (M = %ld, N = %d: N must be a multiple of 4)", M, N);
+    CAR_REQUIRE(ldy >= N && ldy % 4 == 0, "car_gelu: the row stride (%d) must hold N = %d and be a multiple of 4", ldy, N);
+    CAR_REQUIRE(aligned16(Y), "car_gelu: Y must be 16-byte aligned");
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(gelu_kernel, dim3(car_div_up(M * (N / 4), 256)), dim3(256), 0, (hipStream_t)stream, Y, ldy, M, N / 4);
+    CAR_CHECK_LAUNCH("car_gelu");
+    return CAR_OK;
+}
+
+extern "C" size_t car_mha_workspace_bytes(int b, int S, int heads) {
+    return mha_shape_ok(b, S, heads, "car_mha_workspace_bytes") ? mha_layout(b, S, heads).total : 0;
+}
+
+extern "C" int car_mha(const float* qkv, int ld, int b, int S, int heads, float* out, int ldo, void* work, size_t work_bytes, void* stream) {
+    CAR_REQUIRE(qkv && out && work, "car_mha: null pointer");
+    if (!mha_shape_ok(b, S, heads, "car_mha")) return CAR_E_ARG;
+    const int dim = heads * kHead;
+    CAR_REQUIRE(ld >= 3 * dim && ld % 4 == 0, "car_mha: the row stride of qkv (%d) must hold 3 x %d columns and be a multiple of 4", ld, dim);
+    CAR_REQUIRE(ldo >= dim && ldo % 4 == 0, "car_mha: the row stride of out (%d) must hold %d columns and be a multiple of 4", ldo, dim);
+    CAR_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(work), "car_mha: qkv, out and work must be 16-byte aligned");
+    const MhaLayout l = mha_layout(b, S, heads);
+    CAR_REQUIRE(work_bytes >= l.total, "car_mha: the workspace is too small (%zu bytes, car_mha_workspace_bytes says %zu)", work_bytes, l.total);
+    char* w = static_cast<char*>(work);
+    MhaArgs a{qkv, ld, b, S, heads, l.tiles, out, ldo, reinterpret_cast<float*>(w + l.maxes), reinterpret_cast<float*>(w + l.scales),
+              reinterpret_cast<float*>(w + l.packed)};
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned tiles_all = (unsigned)(b * heads * l.tiles);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(mha_absmax_kernel, dim3(tiles_all), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mha_pack_kernel, dim3(tiles_all), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mha_kernel, dim3(car_div_up(tiles_all, 4)), dim3(256), 0, st, a);
+    CAR_CHECK_LAUNCH("car_mha");
+    return CAR_OK;
+}
+
+extern "C" size_t car_vit_packed_offset(int dim, int item) {
+    if (!vit_dim_ok(dim, "car_vit_packed_offset")) return 0;
+    if (item < 0 || item > 12) { car_set_error("car_vit_packed_offset: item %d is outside 0..12", item); return 0; }
+    return vit_layout(dim).off[item];
+}
+
+extern "C" size_t car_vit_packed_floats(int dim, int depth) {
+    if (!vit_dim_ok(dim, "car_vit_packed_floats")) return 0;
+    if (depth < 1 || depth > 32) { car_set_error("car_vit_packed_floats: depth = %d is outside 1..32", depth); return 0; }
+    return vit_layout(dim).off[12] * (size_t)depth;
+}
+
+extern "C" int car_vit_pack(const float* const* params, int n_params, int dim, int depth, float* packed, void* stream) {
+    CAR_REQUIRE(params && packed, "car_vit_pack: null pointer");
+    if (!vit_dim_ok(dim, "car_vit_pack")) return CAR_E_ARG;
+    CAR_REQUIRE(depth >= 1 && depth <= 32, "car_vit_pack: depth = %d is outside 1..32", depth);
+    CAR_REQUIRE(n_params == 12 * depth, "car_vit_pack: %d parameter arrays do not fit depth %d (12 per block)", n_params, depth);
+    for (int i = 0; i < n_params; ++i) CAR_REQUIRE(params[i], "car_vit_pack: null pointer (parameter %d)", i);
+    CAR_REQUIRE(aligned16(packed), "car_vit_pack: packed must be 16-byte aligned");
+    const VitLayout l = vit_layout(dim);
+    hipStream_t st = (hipStream_t)stream;
+    const int mk[12] = {0, 0, dim, 0, dim, 0, 0, 0, dim, 0, 4 * dim, 0};                // a matrix's K (0: a vector)
+    const int mn[12] = {dim, dim, 3 * dim, 3 * dim, dim, dim, dim, dim, 4 * dim, 4 * dim, dim, dim};
+    for (int blk = 0; blk < depth; ++blk) {
+        float* base = packed + (size_t)blk * l.off[12];
+        for (int i = 0; i < 12; ++i) {
+            const float* src = params[blk * 12 + i];
+            if (mk[i]) CAR_TRY(car_linear_x3_pack(src, mk[i], mk[i], mn[i], base + l.off[i], stream));
+            else CAR_CHECK_HIP(hipMemcpyAsync(base + l.off[i], src, sizeof(float) * mn[i], hipMemcpyDeviceToDevice, st), "car_vit_pack: copy failed");
+        }
+    }
+    return CAR_OK;
+}
+
+extern "C" size_t car_vit_workspace_bytes(int b, int S, int dim) {
+    if (!vit_dim_ok(dim, "car_vit_workspace_bytes") || !mha_shape_ok(b, S, dim / kHead, "car_vit_workspace_bytes")) return 0;
+    return vit_work(b, S, dim).total;
+}
+
+extern "C" int car_vit_blocks(float* tok, int b, int S, int dim, const float* packed, int depth, const int* taps, int n_taps, float* const* tap_out,
+                              void* work, size_t work_bytes, void* stream) {
+    CAR_REQUIRE(tok && packed && work && (n_taps == 0 || (taps && tap_out)), "car_vit_blocks: null pointer");
+    if (!vit_dim_ok(dim, "car_vit_blocks") || !mha_shape_ok(b, S, dim / kHead, "car_vit_blocks")) return CAR_E_ARG;
+    CAR_REQUIRE(depth >= 1 && depth <= 32, "car_vit_blocks: depth = %d is outside 1..32", depth);
+    CAR_REQUIRE(n_taps >= 0 && n_taps <= depth, "car_vit_blocks: %d taps for %d blocks", n_taps, depth);
+    for (int i = 0; i < n_taps; ++i) {
+        CAR_REQUIRE(taps[i] >= 0 && taps[i] < depth && (i == 0 || taps[i] > taps[i - 1]),
+                    "car_vit_blocks: taps must be strictly increasing block indices below depth = %d (tap %d is %d)", depth, i, taps[i]);
+        CAR_REQUIRE(tap_out[i], "car_vit_blocks: null pointer (tap_out %d)", i);
+        CAR_REQUIRE(aligned16(tap_out[i]), "car_vit_blocks: tap_out %d must be 16-byte aligned", i);
+    }
+    CAR_REQUIRE(aligned16(tok) && aligned16(packed) && aligned16(work), "car_vit_blocks: tok, packed and work must be 16-byte aligned");
+    const VitWork w = vit_work(b, S, dim);
+    CAR_REQUIRE(work_bytes >= w.total, "car_vit_blocks: the workspace is too small (%zu bytes, car_vit_workspace_bytes says %zu)", work_bytes, w.total);
+    const VitLayout l = vit_layout(dim);
+    char* wb = static_cast<char*>(work);
+    float* norm = reinterpret_cast<float*>(wb + w.norm);
+    float* att = reinterpret_cast<float*>(wb + w.att);
+    float* wide = reinterpret_cast<float*>(wb + w.wide);                                // qkv [rows][3 dim], then the hidden rows [rows][4 dim]
+    const size_t mha_bytes = w.total - w.mha;
+    const long rows = (long)b * S;
+    const int heads = dim / kHead;
+    hipStream_t st = (hipStream_t)stream;
+    int next_tap = 0;
+    for (int blk = 0; blk < depth; ++blk) {
+        const float* p = packed + (size_t)blk * l.off[12];
+        CAR_TRY(car_layernorm(tok, dim, p + l.off[0], p + l.off[1], dim, 1e-6, norm, dim, rows, stream));
+        CAR_TRY(car_linear_x3(norm, dim, p + l.off[2], p + l.off[3], dim, 3 * dim, wide, 3 * dim, rows, 0, stream));
+        CAR_TRY(car_mha(wide, 3 * dim, b, S, heads, att, dim, wb + w.mha, mha_bytes, stream));
+        CAR_TRY(car_linear_x3(att, dim, p + l.off[4], p + l.off[5], dim, dim, tok, dim, rows, CAR_LIN_ACCUM, stream));
+        CAR_TRY(car_layernorm(tok, dim, p + l.off[6], p + l.off[7], dim, 1e-6, norm, dim, rows, stream));
+        CAR_TRY(car_linear_x3(norm, dim, p + l.off[8], p + l.off[9], dim, 4 * dim, wide, 4 * dim, rows, 0, stream));
+        CAR_TRY(car_gelu(wide, 4 * dim, rows, 4 * dim, stream));
+        CAR_TRY(car_linear_x3(wide, 4 * dim, p + l.off[10], p + l.off[11], 4 * dim, dim, tok, dim, rows, CAR_LIN_ACCUM, stream));
+        if (next_tap < n_taps && taps[next_tap] == blk) {
+            CAR_CHECK_HIP(hipMemcpyAsync(tap_out[next_tap], tok, sizeof(float) * rows * dim, hipMemcpyDeviceToDevice, st), "car_vit_blocks: copy failed");
+            ++next_tap;
+        }
+    }
+    return CAR_OK;
+}

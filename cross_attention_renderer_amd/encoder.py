@@ -1,8 +1,11 @@
 """The multi-view DPT-hybrid image encoder behind ``CrossAttentionRenderer.get_z``.
 
-Runs once per stereo pair, outside the per-ray hot loop, so it is plain PyTorch-ROCm (MIOpen convolutions, rocBLAS /
-``scaled_dot_product_attention`` for the transformer) — no hand-written kernels here.  What matters is that a reference checkpoint
-loads unchanged (``encoder.*`` keys and shapes are the reference's) and that ``get_z`` produces the reference's feature pyramid.
+Runs once per stereo pair, outside the per-ray hot loop.  By default it is plain PyTorch-ROCm (MIOpen convolutions, rocBLAS /
+``scaled_dot_product_attention`` for the transformer).  The transformer stage alone — the 12 blocks over the concatenated tokens — also
+has a route on the library's own kernels (``MultiViewDPTEncoder.vit_route = "device"``: car_vit_blocks, include/car_encoder.h;
+opt-in, inference only); the trunk, the token assembly, the read-out and the fusion are torch on both routes.  What matters is that a
+reference checkpoint loads unchanged (``encoder.*`` keys and shapes are the reference's) and that ``get_z`` produces the reference's
+feature pyramid.
 
 What it computes (reference call sites):
   * ``DPTDepthModel.forward(rgb, rel_pose16, nviews)`` (midas/dpt_depth.py:67-89, 94-117): hybrid backbone -> four reassembled
@@ -291,11 +294,79 @@ class MultiViewDPTEncoder(nn.Module):
     ``forward(rgb, rel_pose16, nviews) -> [path_2, path_1]``."""
 
     TOKENS_PER_VIEW = 257          # `os = 257` in the reference's forward_flex (midas/vit.py:183): 16 x 16 patches + class token
+    VIT_TAPS = (8, 11)             # the blocks whose outputs are re-assembled (midas/vit.py:65-69)
+    VIT_ROUTES = ("torch", "device")
 
     def __init__(self):
         super().__init__()
         self.pretrained = _Pretrained()
         self.scratch = _Scratch()
+        # where the transformer blocks run: "torch" (the default: the modules above) or the opt-in "device" (car_vit_blocks on the packed
+        # parameters: inference only, float32 CUDA tensors only; it refuses anything else instead of falling back)
+        self.vit_route = "torch"
+        self._vit_packed = None    # engine._Cached of the packed blocks (source: their 144 parameter tensors), made on first use
+        self._vit_work = {}        # (b, S, device) -> the stage's workspace on the device
+
+    @property
+    def vit_route(self) -> str:
+        return self._vit_route
+
+    @vit_route.setter
+    def vit_route(self, value: str) -> None:
+        if value not in self.VIT_ROUTES:
+            raise ValueError(f"vit_route must be 'torch' or 'device' (got {value!r})")
+        self._vit_route = value
+
+    def drop_device_caches(self) -> None:
+        """Forgets the packed blocks and the workspaces: the next device-route forward packs the parameters as they are then.  The cache's
+        key sees an in-place update through the tensors' _version, which torch's fused optimizers do not advance
+        (CrossAttentionRenderer.train calls this on leaving train() mode, as it parks the engine's caches)."""
+        if self._vit_packed is not None:
+            self._vit_packed.drop()
+        self._vit_work = {}
+
+    def _vit_parameters(self) -> List[Tensor]:
+        """The blocks' parameters in car_vit_pack's order (12 per block)."""
+        names = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
+                 "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+        return [blk.get_parameter(n) for blk in self.pretrained.model.blocks for n in names]
+
+    def _blocks_on_device(self, tok: Tensor, x: Tensor, BV: int, T: int) -> dict:
+        """The transformer stage through car_vit_blocks: tok [b, V T, dim] (contiguous, overwritten) -> {tap: [BV, T, dim]}."""
+        import ctypes
+        from . import _lib
+        from .engine import _Cached
+        params = self._vit_parameters()
+        if not tok.is_cuda or not all(p.is_cuda for p in params):
+            raise ValueError("vit_route = 'device' needs the images and the encoder on a CUDA device; CPU tensors run on vit_route = 'torch'")
+        if tok.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+            raise ValueError(f"vit_route = 'device' computes in float32 (got {tok.dtype}); other dtypes run on vit_route = 'torch'")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise ValueError("vit_route = 'device' is inference only (its kernels have no backward): call it under torch.no_grad(), or "
+                             "keep vit_route = 'torch' for a forward that autograd records")
+        lib, dev = _lib.api(), tok.device
+        b, S, dim = tok.shape
+        depth = len(params) // 12
+        if self._vit_packed is None:
+            self._vit_packed = _Cached()
+
+        def build():
+            packed = torch.empty(_lib.user_call(lib.car_vit_packed_floats, dim, depth), device=dev, dtype=torch.float32)
+            src = [p.detach().contiguous() for p in params]
+            _lib.user_call(lib.car_vit_pack, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), dim, depth, _lib.ptr(packed),
+                           _lib.stream())
+            return packed
+        with torch.cuda.device(dev):
+            packed = self._vit_packed.get(params, (str(dev), dim, depth), build)
+            key = (b, S, str(dev))
+            if key not in self._vit_work:
+                self._vit_work = {key: torch.empty(lib.car_vit_workspace_bytes(b, S, dim) // 4, device=dev, dtype=torch.float32)}
+            work = self._vit_work[key]
+            outs = [torch.empty(BV, T, dim, device=dev, dtype=torch.float32) for _ in self.VIT_TAPS]
+            _lib.user_call(lib.car_vit_blocks, _lib.ptr(tok), b, S, dim, _lib.ptr(packed), depth, (ctypes.c_int * len(outs))(*self.VIT_TAPS),
+                           len(outs), (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _lib.ptr(work), work.numel() * 4,
+                           _lib.stream())
+        return dict(zip(self.VIT_TAPS, outs))
 
     def forward(self, x: Tensor, rel_pose16: Tensor, nviews: int) -> List[Tensor]:
         vit = self.pretrained.model
@@ -312,11 +383,14 @@ class MultiViewDPTEncoder(nn.Module):
         tok = tok + vit.resized_pos_embed(gh, gw) + vit.pose_embed(rel_pose16)[:, None, :]
         T = tok.shape[1]
         tok = tok.view(BV // nviews, nviews * T, -1)                           # all views of a scene in one sequence
-        taps = {}
-        for i, blk in enumerate(vit.blocks):
-            tok = blk(tok)
-            if i in (8, 11):
-                taps[i] = tok.reshape(BV, T, -1)                               # back to one row per view (midas/vit.py:65-69)
+        if self.vit_route == "device":
+            taps = self._blocks_on_device(tok.contiguous(), x, BV, T)          # a missing kernel or a refused input raises: no fallback
+        else:
+            taps = {}
+            for i, blk in enumerate(vit.blocks):
+                tok = blk(tok)
+                if i in self.VIT_TAPS:
+                    taps[i] = tok.reshape(BV, T, -1)                           # back to one row per view (midas/vit.py:65-69)
 
         def reassemble(t: Tensor, post: nn.Sequential) -> Tensor:
             t = post[0](t).transpose(1, 2).unflatten(2, (gh, gw))

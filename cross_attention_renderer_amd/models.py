@@ -146,6 +146,24 @@ class CrossAttentionRenderer(nn.Module):
         self.render_precision = "fp32"
 
     @property
+    def encoder_route(self) -> str:
+        """Where get_z's transformer blocks run: "torch" (the default) or the opt-in "device" (car_vit_blocks, include/car_encoder.h:
+        inference only, float32 on a CUDA device — get_z raises on anything else instead of falling back; the rest of the encoder is
+        torch on both routes).  The value lives on the encoder (MultiViewDPTEncoder.vit_route); an encoder without that switch — none
+        built, or a caller's own module — has the "torch" route only."""
+        return getattr(self.encoder, "vit_route", "torch")
+
+    @encoder_route.setter
+    def encoder_route(self, value: str) -> None:
+        if value not in ("torch", "device"):
+            raise ValueError(f"encoder_route must be 'torch' or 'device' (got {value!r})")
+        if hasattr(self.encoder, "vit_route"):
+            self.encoder.vit_route = value
+        elif value != "torch":
+            raise ValueError(f"encoder_route = 'device' needs the built-in MultiViewDPTEncoder (model='midas_vit', with_encoder=True): "
+                             f"{type(self.encoder).__name__} has no vit_route")
+
+    @property
     def render_precision(self) -> str:
         return self._render_precision
 
@@ -159,8 +177,12 @@ class CrossAttentionRenderer(nn.Module):
         """Leaving train() mode for eval() — the validation pass between optimizer steps (summaries.render_full) — sets aside what the
         engine built from the parameters and renders from empty caches: torch's fused optimizers update parameters without advancing
         ``_version``, which the engine's cache keys rely on (engine.RenderEngine.park_parameter_caches).  Returning to train() mode puts
-        the training loop's caches back as they were.  A module that was never in train() mode is not touched."""
+        the training loop's caches back as they were.  A module that was never in train() mode is not touched.  The encoder's packed
+        transformer blocks (encoder_route = "device") have the same problem in the same pass and are dropped in the same transition: the
+        next eval() get_z packs the parameters as they are then."""
         engine = getattr(self, "_engine", None)
+        if self.training and not mode and hasattr(getattr(self, "encoder", None), "drop_device_caches"):
+            self.encoder.drop_device_caches()
         if engine is not None and self.training and not mode:
             self._parked_caches = engine.park_parameter_caches()
         elif engine is not None and not self.training and mode and getattr(self, "_parked_caches", None) is not None:
@@ -170,7 +192,8 @@ class CrossAttentionRenderer(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     def get_z(self, input, val=False) -> List[Tensor]:
-        """Feature pyramid of the context views, NCHW (models.py:148-188).  Stock PyTorch by design."""
+        """Feature pyramid of the context views, NCHW (models.py:148-188).  Stock PyTorch by default; with encoder_route = "device" the
+        encoder's transformer blocks run on the library's kernels (inference only)."""
         rgb = input["context"]["rgb"]
         cam2world = input["context"]["cam2world"]
         rel_cam2world = torch.matmul(torch.inverse(cam2world[:, :1]), cam2world)

@@ -52,6 +52,11 @@ def parser(description: str) -> argparse.ArgumentParser:
                    help="report LPIPS (v0.1, net='vgg') computed on the device with these weight files: a torchvision VGG16 state dict and "
                         "the lpips package's vgg.pth, or one file holding lpips.LPIPS(net='vgg').state_dict().  Without it LPIPS is not reported "
                         "(no weights are shipped)")
+    p.add_argument("--encoder_route", choices=("torch", "device"), default="torch",
+                   help="where get_z's transformer blocks run: torch = stock PyTorch (default); device = the library's own kernels "
+                        "(car_vit_blocks: opt-in, inference only, float32; the rest of the encoder stays torch).  Read only where the encoder "
+                        "is built (a checkpoint or --with_encoder); the train script applies it to its validation pass only, because a forward "
+                        "that autograd records refuses 'device'")
     p.add_argument("--port", type=int, default=1492)          # the reference rendezvous port (eval_realestate10k.py:97)
     return p
 
@@ -94,6 +99,8 @@ def build_model(opt, device, with_encoder=None):
     model.H = model.W = opt.img_sidelength
     model.pose_route = "device" if getattr(opt, "cameras", "host") == "device" else "host"
     model.render_precision = getattr(opt, "precision", "fp32")
+    if with_encoder:                                     # a renderer-only module never calls get_z: the flag has nothing to switch there
+        model.encoder_route = getattr(opt, "encoder_route", "torch")
     return model.to(device)
 
 

@@ -113,12 +113,15 @@ def _validation_batches(opt, model, dev):
 
 def _validate(opt, model, batch, log, step, lpips_w):
     """One validation pass (training.py:146-231): eval(), no_grad, get_z once, the chunked full-image render, the losses with val=True, the
-    val_ scalars and panels, train().  Nothing here waits for the device but the PNG writes."""
+    val_ scalars and panels, train().  Nothing here waits for the device but the PNG writes.  --encoder_route holds for this pass alone:
+    the training forward records get_z under autograd, which the device route refuses, so train() keeps the torch encoder."""
     import torch
     from cross_attention_renderer_amd import harness, summaries
     inp, gt, z = batch
     model.eval()
     try:
+        if z is None:
+            model.encoder_route = getattr(opt, "encoder_route", "torch")
         with torch.no_grad():
             if z is None:
                 z = model.get_z(inp)
@@ -131,6 +134,7 @@ def _validate(opt, model, batch, log, step, lpips_w):
                 log.add_scalar("val_" + name, value, step)
             summaries.img_summaries(model, inp, gt, {}, out, log, step, "val_", img_shape=(model.H, model.W), n_view=opt.views)
     finally:
+        model.encoder_route = "torch"
         model.train()
 
 
@@ -144,6 +148,7 @@ def train(rank, opt):
     H, b, R = opt.img_sidelength, opt.batch_size, opt.query_sparsity
     real = bool(opt.data_root)                                    # the RealEstate10K reader; otherwise synthetic scenes, as before
     model = common.build_model(opt, dev, with_encoder=True if real else None).train()
+    model.encoder_route = "torch"                                 # the training forward's get_z is recorded by autograd; _validate applies --encoder_route
     params = [p for p in model.parameters() if p.requires_grad]
     if opt.gpus > 1:                                              # sync_model (train_realestate10k.py:60-62)
         for p in params:
