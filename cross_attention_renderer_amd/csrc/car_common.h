@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include "../../include/car_hip.h"
+#include "car_workspace.h"
 
 void car_set_error(const char* fmt, ...);
 
@@ -36,6 +37,7 @@ void car_set_error(const char* fmt, ...);
 #endif
 
 static inline unsigned car_div_up(long a, long b) { return (unsigned)((a + b - 1) / b); }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---- device side: what several units' kernels share ----
 // Reduction over the wave's 64 lanes by a fixed xor butterfly (32, 16, .. 1): every lane ends with the same bits, and the order of the

@@ -328,19 +328,20 @@ int head_blocks(int H, int W) {
     for (int k = 0; k < kTaps; ++k) n += ((H >> k) * (W >> k) + kHeadPix - 1) / kHeadPix;
     return n;
 }
-size_t up64(size_t n) { return (n + 63) / 64 * 64; }
 size_t conv_tile_floats(int K, int N) { return (size_t)(9 * K / 32) * (N / 16) * kTile; }
 bool conv_shape_ok(int K, int N) {
     return (K == 3 && N == 64) || ((K == 64 || K == 128 || K == 256 || K == 512) && (N == 64 || N == 128 || N == 256 || N == 512));
 }
 
-// the 13 convolutions and 4 pools over the workspace's buffers: 0..4 the taps, 5 and 6 two scratch maps, -1 the input images
+// the 13 convolutions and 4 pools over the workspace's buffers: 0..4 the taps, 5 and 6 two scratch maps, -1 the input images.  The
+// workspace: those seven maps, each as large as its largest tenant, then the head's partial sums; pieces of whole 64 elements
 struct Step { bool pool; int layer, K, N, h, w, src, dst; };
-struct Plan { Step step[kLayers + 4]; int steps; size_t buf[7]; };
-Plan make_plan(int B, int H, int W) {
+struct Plan { Step step[kLayers + 4]; int steps; float* buf[7]; double* scratch; size_t bytes; };
+Plan make_plan(int B, int H, int W, void* work = nullptr) {
     Plan pl{};
+    size_t floats[7] = {};
     int cur = -1, h = H, w = W, K = 3, tap = 0;
-    auto need = [&](int b, size_t n) { if (pl.buf[b] < n) pl.buf[b] = n; };
+    auto need = [&](int b, size_t n) { if (floats[b] < n) floats[b] = n; };
     for (int l = 0; l < kLayers; ++l) {
         if (pool_in_front(l)) {
             pl.step[pl.steps++] = Step{true, l, K, K, h, w, cur, 6};
@@ -352,7 +353,10 @@ Plan make_plan(int B, int H, int W) {
         need(dst, (size_t)2 * B * h * w * N);
         cur = dst; K = N;
     }
-    for (int b = 0; b < 7; ++b) pl.buf[b] = up64(pl.buf[b]);
+    Carver c(work, 64);
+    for (int b = 0; b < 7; ++b) pl.buf[b] = c.take<float>(floats[b]);
+    pl.scratch = c.take<double>(car_lpips_head_scratch_doubles(B, H, W));
+    pl.bytes = c.bytes();
     return pl;
 }
 size_t layer_offset(int l) {                                          // of layer l inside car_lpips_pack's array (l = 13: the lin weights)
@@ -360,7 +364,6 @@ size_t layer_offset(int l) {                                          // of laye
     for (int i = 0, K = 3; i < l; K = kWidth[i], ++i) off += car_conv3x3_packed_floats(K, kWidth[i]);
     return off;
 }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 HeadArgs head_args(const float* const* feats, int B, int H, int W, const float* lin) {
     HeadArgs a{};
@@ -615,7 +618,8 @@ size_t backward_layer_offset(int l) {                                  // of lay
 struct TrainPlan { size_t act[kLayers]; int h[kLayers], w[kLayers]; size_t pooled, scratch, hg[kTaps], ping[2], floats; };
 TrainPlan make_train_plan(int B, int H, int W) {
     TrainPlan tp{};
-    size_t at = 0, pooled = 0;
+    Carver c(nullptr, 64);
+    size_t pooled = 0;
     int h = H, w = W;
     for (int l = 0; l < kLayers; ++l) {
         if (pool_in_front(l)) {
@@ -623,14 +627,13 @@ TrainPlan make_train_plan(int B, int H, int W) {
             const size_t n = (size_t)2 * B * h * w * kWidth[l - 1];
             pooled = n > pooled ? n : pooled;
         }
-        tp.act[l] = at; tp.h[l] = h; tp.w[l] = w;
-        at += up64((size_t)2 * B * h * w * kWidth[l]);
+        tp.act[l] = c.at<float>((size_t)2 * B * h * w * kWidth[l]); tp.h[l] = h; tp.w[l] = w;
     }
-    tp.pooled = at; at += up64(pooled);
-    tp.scratch = at; at += 2 * up64(car_lpips_head_scratch_doubles(B, H, W));
-    for (int k = 0; k < kTaps; ++k) { tp.hg[k] = at; at += up64((size_t)2 * B * (H >> k) * (W >> k) * kTapWidth[k]); }
-    for (int i = 0; i < 2; ++i) { tp.ping[i] = at; at += up64((size_t)2 * B * H * W * 64); }
-    tp.floats = at;
+    tp.pooled = c.at<float>(pooled);
+    tp.scratch = c.at<double>(car_lpips_head_scratch_doubles(B, H, W)) * (sizeof(double) / sizeof(float));
+    for (int k = 0; k < kTaps; ++k) tp.hg[k] = c.at<float>((size_t)2 * B * (H >> k) * (W >> k) * kTapWidth[k]);
+    for (int i = 0; i < 2; ++i) tp.ping[i] = c.at<float>((size_t)2 * B * H * W * 64);
+    tp.floats = c.bytes() / sizeof(float);
     return tp;
 }
 constexpr int kTapLayer[kTaps] = {1, 3, 6, 9, 12};
@@ -718,10 +721,7 @@ extern "C" int car_lpips_pack(const float* const* conv_w, const float* const* co
 
 extern "C" size_t car_lpips_workspace_bytes(int B, int H, int W) {
     if (!lpips_shape_ok(B, H, W)) return 0;
-    const Plan pl = make_plan(B, H, W);
-    size_t floats = 0;
-    for (int b = 0; b < 7; ++b) floats += pl.buf[b];
-    return floats * sizeof(float) + up64(car_lpips_head_scratch_doubles(B, H, W)) * sizeof(double);
+    return make_plan(B, H, W).bytes;
 }
 
 extern "C" int car_lpips(const float* x, const float* y, int B, int H, int W, const float* packed, double* lpips, double* per_tap, void* work,
@@ -734,11 +734,8 @@ extern "C" int car_lpips(const float* x, const float* y, int B, int H, int W, co
     CAR_REQUIRE(work_bytes >= need, "car_lpips: workspace holds %zu bytes, need %zu (car_lpips_workspace_bytes)", work_bytes, need);
     CAR_REQUIRE(aligned16(packed) && aligned16(work), "car_lpips: packed and the workspace must be 16-byte aligned");
 
-    const Plan pl = make_plan(B, H, W);
-    float* buf[7];
-    float* at = static_cast<float*>(work);
-    for (int b = 0; b < 7; ++b) { buf[b] = at; at += pl.buf[b]; }
-    double* scratch = reinterpret_cast<double*>(at);
+    const Plan pl = make_plan(B, H, W, work);
+    float* const* buf = pl.buf;
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
     for (int i = 0; i < pl.steps; ++i) {
@@ -751,7 +748,7 @@ extern "C" int car_lpips(const float* x, const float* y, int B, int H, int W, co
         } else code = conv(buf[s.src], 2 * B, s.h, s.w, s.K, s.N, packed + layer_offset(s.layer), buf[s.dst], st);
         if (code != CAR_OK) return code;
     }
-    return head(buf, B, H, W, packed + layer_offset(kLayers), lpips, per_tap, scratch, st, "car_lpips");
+    return head(buf, B, H, W, packed + layer_offset(kLayers), lpips, per_tap, pl.scratch, st, "car_lpips");
 }
 
 // ---- the backward's entries (include/car_hip.h) ------------------------------------------------------------------------------------------

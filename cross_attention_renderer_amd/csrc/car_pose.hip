@@ -540,7 +540,12 @@ __global__ __launch_bounds__(kSelectThreads) void essential_select_kernel(const 
 
 bool pose_shape_ok(int N, int H) { return N >= 5 && N <= kMaxN && H >= 1 && H <= kMaxH; }
 
-size_t up16(size_t n) { return (n + 15) / 16 * 16; }
+// car_essential_ransac's workspace: cand [H][10][9] doubles | nsol [H] | counts [H][10] | hyp_best [H] ints, each piece of whole 16 bytes
+struct PoseWork { double* cand; int *nsol, *counts, *hyp_best; size_t bytes; };
+PoseWork pose_work(int H, void* work = nullptr) {
+    Carver c(work, 16 / sizeof(int));
+    return {c.take<double>((size_t)H * kCands * 9, 16 / sizeof(double)), c.take<int>(H), c.take<int>((size_t)H * kCands), c.take<int>(H), c.bytes()};
+}
 
 }  // namespace
 
@@ -549,9 +554,7 @@ extern "C" size_t car_essential_workspace_bytes(int N, int H) {
         car_set_error("car_essential_workspace_bytes: N = %d, H = %d; need 5 <= N <= %d matches and 1 <= H <= %d hypotheses", N, H, kMaxN, kMaxH);
         return 0;
     }
-    // cand [H][10][9] doubles | nsol [H] | counts [H][10] | hyp_best [H] ints
-    return up16((size_t)H * kCands * 9 * sizeof(double)) + up16((size_t)H * sizeof(int)) + up16((size_t)H * kCands * sizeof(int)) +
-           up16((size_t)H * sizeof(int));
+    return pose_work(H).bytes;
 }
 
 #define POSE_REQUIRE_SHAPE(who)                                                                                              \
@@ -598,15 +601,8 @@ extern "C" int car_essential_ransac(const double* x0, const double* x1, int N, c
     const size_t need = car_essential_workspace_bytes(N, H);
     CAR_REQUIRE(work_bytes >= need, "car_essential_ransac: workspace holds %zu bytes, need %zu (car_essential_workspace_bytes)", work_bytes, need);
     CAR_REQUIRE(((size_t)work & 15) == 0, "car_essential_ransac: workspace is not 16-byte aligned");
-    char* w = (char*)work;
-    double* cand = (double*)w;
-    w += up16((size_t)H * kCands * 9 * sizeof(double));
-    int* nsol = (int*)w;
-    w += up16((size_t)H * sizeof(int));
-    int* counts = (int*)w;
-    w += up16((size_t)H * kCands * sizeof(int));
-    int* hyp_best = (int*)w;
-    CAR_TRY(car_essential_solve(x0, x1, N, samples, H, cand, nsol, stream));
-    CAR_TRY(car_essential_score(x0, x1, N, cand, nsol, H, thresh, counts, hyp_best, stream));
-    return car_essential_select(x0, x1, N, cand, nsol, counts, H, thresh, E, best, inliers, stream);
+    const PoseWork w = pose_work(H, work);
+    CAR_TRY(car_essential_solve(x0, x1, N, samples, H, w.cand, w.nsol, stream));
+    CAR_TRY(car_essential_score(x0, x1, N, w.cand, w.nsol, H, thresh, w.counts, w.hyp_best, stream));
+    return car_essential_select(x0, x1, N, w.cand, w.nsol, w.counts, H, thresh, E, best, inliers, stream);
 }

@@ -16,7 +16,7 @@ namespace {
 #include "car_fused_layout.h"
 #include "car_chain_layout.h"
 
-inline size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
+constexpr size_t kRound = 64;                                        // every piece of this unit's buffers is a whole number of 64 floats
 
 // ---- plan layout ---------------------------------------------------------------------------------------------------
 struct Plan {
@@ -28,8 +28,8 @@ struct Plan {
 inline bool level_on_f16_pipe(int c) { return c % 4 == 0 && c >= 32; }
 Plan plan_layout(const car_dims& d) {
     Plan p;
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += up64(n); return at; };
+    Carver c(nullptr, kRound);
+    auto take = [&](size_t n) { return c.at<float>(n); };
     p.steps = take((size_t)d.P);
     p.blob = take(car_fused_blob_floats());
     p.fbias = take(car_fused_bias_floats());
@@ -43,7 +43,7 @@ Plan plan_layout(const car_dims& d) {
     p.chain_scale = take(kScaleFloats);
     p.mid_bias = take(kMidBiasFloats);
     p.tail_bias = take(kTailBiasFloats);
-    p.total = o;
+    p.total = c.bytes() / sizeof(float);
     return p;
 }
 
@@ -78,8 +78,8 @@ const struct { const char* name; Span Work::*buf; } kFindable[] = {
 inline size_t step_groups(const car_dims& d) { const int ts = car_fused_tile_steps(); return (size_t)((d.P + ts - 1) / ts); }
 Work work_layout(const car_dims& d) {
     Work w;
-    size_t o = 0;
-    auto take = [&](size_t n) { const Span s{o, n}; o += up64(n); return s; };
+    Carver c(nullptr, kRound);
+    auto take = [&](size_t n) { return Span{c.at<float>(n), n}; };
     const size_t n = (size_t)d.b * d.V, S = n * d.R * d.P, BR = (size_t)d.b * d.R;
     w.rays = take(n * d.R * CAR_RAY_FLOATS);
     w.phi_x = take(BR * kPhiLd);
@@ -99,7 +99,7 @@ Work work_layout(const car_dims& d) {
     w.uh = take(BR * kD);
     w.valid = take(BR);
     w.part = take(n * d.R * step_groups(d) * kC);
-    w.total = o;
+    w.total = c.bytes() / sizeof(float);
     return w;
 }
 
@@ -167,22 +167,26 @@ extern "C" size_t car_workspace_bytes(const car_dims* dims) {
 }
 
 namespace {
-size_t lattice_floats(const car_dims& d) { const car_lattice L = car_lattice_of(d); return (size_t)d.b * d.V * 2 * L.h * L.w * kC; }
-size_t level_floats(const car_dims& d, int l) { return (size_t)d.b * d.V * d.level_h[l] * d.level_w[l] * kC; }
-// projected levels behind the lattice and gmeta (scratch of car_project_maps: the merge reads them)
-size_t level_offset(const car_dims& d, int level) {
-    size_t n = up64(lattice_floats(d)) + 64;
-    for (int l = 0; l < level && l < d.n_levels; ++l) n += up64(level_floats(d, l));
-    return n;
+// the gmaps buffer (floats): the lattice, gmeta, then the projected levels (scratch of car_project_maps: the merge reads them)
+struct Gmaps { size_t gmeta, level[CAR_MAX_LEVELS], total; };
+Gmaps gmaps_layout(const car_dims& d) {
+    Gmaps g{};
+    Carver c(nullptr, kRound);
+    const car_lattice L = car_lattice_of(d);
+    c.at<float>((size_t)d.b * d.V * 2 * L.h * L.w * kC);
+    g.gmeta = c.at<float>(64);
+    for (int l = 0; l < d.n_levels; ++l) g.level[l] = c.at<float>((size_t)d.b * d.V * d.level_h[l] * d.level_w[l] * kC);
+    g.total = c.bytes() / sizeof(float);
+    return g;
 }
 }  // namespace
 extern "C" size_t car_gmeta_offset(const car_dims* dims) {
     if (check_dims(dims, "car_gmeta_offset") != CAR_OK) return 0;
-    return up64(lattice_floats(*dims));
+    return gmaps_layout(*dims).gmeta;
 }
 extern "C" size_t car_gmaps_floats(const car_dims* dims) {
     if (check_dims(dims, "car_gmaps_floats") != CAR_OK) return 0;
-    return level_offset(*dims, CAR_MAX_LEVELS + 1);
+    return gmaps_layout(*dims).total;
 }
 extern "C" int car_lattice_shape(const car_dims* dims, int* lat_h, int* lat_w, int* lat_pad) {
     CAR_TRY(check_dims(dims, "car_lattice_shape"));
@@ -267,14 +271,8 @@ extern "C" int car_plan_build(const car_dims* dims, const car_weights* w, void* 
 // ---- the fp16 precision's plan (car_plan_f16_*): the fused kernel's compact blob, its bias table and point table ----------
 struct Plan16 { size_t blob, fbias, wpt, total; };                 // offsets in floats
 Plan16 plan16_layout() {
-    Plan16 p;
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += up64(n); return at; };
-    p.blob = take(car_fused_blob16_floats());
-    p.fbias = take(car_fused_bias_floats());
-    p.wpt = take((size_t)kC * 4);
-    p.total = o;
-    return p;
+    Carver c(nullptr, kRound);
+    return {c.at<float>(car_fused_blob16_floats()), c.at<float>(car_fused_bias_floats()), c.at<float>((size_t)kC * 4), c.bytes() / sizeof(float)};
 }
 extern "C" size_t car_plan_f16_bytes(const car_dims* dims) {
     if (check_dims(dims, "car_plan_f16_bytes") != CAR_OK) return 0;
@@ -296,14 +294,15 @@ extern "C" int car_project_maps(const car_dims* dims, const void* plan, const fl
     const Plan p = plan_layout(*dims);
     const float* base = static_cast<const float*>(plan);
     hipStream_t st = (hipStream_t)stream;
-    float* gmeta = gmaps + car_gmeta_offset(dims);
+    const Gmaps gm = gmaps_layout(*dims);
+    float* gmeta = gmaps + gm.gmeta;
     CAR_CHECK_HIP(hipMemsetAsync(gmeta, 0, sizeof(float) * CAR_MAX_LEVELS, st), "car_project_maps: memset failed");
     const car_lattice L = car_lattice_of(*dims);
     const float* lv[CAR_MAX_LEVELS];
     for (int l = 0; l < dims->n_levels; ++l) {
         CAR_REQUIRE(maps[l], "car_project_maps: level %d is null", l);
         const long M = (long)dims->b * dims->V * dims->level_h[l] * dims->level_w[l];
-        float* gl = gmaps + level_offset(*dims, l);
+        float* gl = gmaps + gm.level[l];
         // G_l = W1[:, ch_l] F_l per texel: on the f16 matrix pipe with fp16 hi / lo operand halves (car_linear_x3: fp32-class accuracy at
         // 2.3x the fp32 pipe's rate — the arithmetic of the staged route's engine._projected_maps) where the level's width allows it
         if (level_on_f16_pipe(dims->level_c[l]) && ((uintptr_t)maps[l] & 15) == 0)

@@ -179,18 +179,26 @@ unsigned blocks_for(long total, long cap) {
     return (unsigned)(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
 }
 
+// the binned scatter's workspace: counters (-> cursor) | start | block sums (+ total), then the records from the next 16 bytes on
+struct BinWork { unsigned *counter, *start, *sums; Record* rec; long n, blocks; size_t bytes; };
+BinWork bin_work(const int* level_h, const int* level_w, int n_levels, int n_maps, long pts, int n_gathers, void* workspace = nullptr) {
+    long texels = 0;
+    for (int l = 0; l < n_levels; ++l) texels += (long)level_h[l] * level_w[l];
+    const long n = (long)n_maps * texels + 1, blocks = (n + kScanBlock - 1) / kScanBlock;      // one counter per texel and a closing one
+    Carver c(workspace);
+    BinWork w{c.take<unsigned>(n), c.take<unsigned>(n), c.take<unsigned>(blocks + 4), nullptr, n, blocks, 0};
+    c.align(16);
+    w.rec = c.take<Record>((size_t)n_gathers * n_maps * pts * n_levels * 4);
+    w.bytes = c.bytes();
+    return w;
+}
+
 }  // namespace
 
 // Bytes of workspace car_gather_bilinear_backward_binned needs for n_gathers gathers of n_maps x pts points into the given levels.
 extern "C" size_t car_scatter_workspace_bytes(const int* level_h, const int* level_w, int n_levels, int n_maps, long pts, int n_gathers) {
     if (!level_h || !level_w || n_levels <= 0 || n_levels > CAR_MAX_LEVELS || n_maps <= 0 || pts <= 0 || n_gathers <= 0) return 0;
-    long texels = 0;
-    for (int l = 0; l < n_levels; ++l) texels += (long)level_h[l] * level_w[l];
-    const long n = (long)n_maps * texels + 1;
-    const long blocks = (n + kScanBlock - 1) / kScanBlock;
-    const long recs = (long)n_gathers * n_maps * pts * n_levels * 4;
-    // counters (-> cursor) | start | block sums (+ total) | records
-    return (size_t)(((2 * n + blocks + 4) * sizeof(unsigned) + 15) / 16 * 16 + recs * sizeof(Record));
+    return bin_work(level_h, level_w, n_levels, n_maps, pts, n_gathers).bytes;
 }
 
 // dmaps[l] [n_maps, Hl, Wl, Cl] = sum over the n_gathers gathers of grid_sample's backward (NOT accumulated: every texel is written, the
@@ -231,17 +239,12 @@ extern "C" int car_gather_bilinear_backward_binned(float* const* dmaps, const in
     }
     for (int l = 0; l < n_levels; ++l)
         CAR_REQUIRE((long)n_maps * level_h[l] * level_w[l] < 2147483647L, "car_gather_bilinear_backward_binned: level %d too large for 32-bit texel indices", l);
-    const long n = (long)n_maps * t0 + 1;                                  // one counter per texel and a closing one
+    const auto [counter, start, sums, rec, n, blocks, need] = bin_work(level_h, level_w, n_levels, n_maps, pts, n_gathers, workspace);
     const long recs = (long)n_gathers * n_maps * pts * n_levels * 4;
     CAR_REQUIRE(n < (1l << 31) && recs < (1l << 32) && (long)n_maps * pts * (V > 0 ? V : 1) < (1l << 31),
                 "car_gather_bilinear_backward_binned: too many texels / records for 32-bit counters");
-    CAR_REQUIRE(workspace_bytes >= car_scatter_workspace_bytes(level_h, level_w, n_levels, n_maps, pts, n_gathers) && ((uintptr_t)workspace & 15) == 0,
+    CAR_REQUIRE(workspace_bytes >= need && aligned16(workspace),
                 "car_gather_bilinear_backward_binned: workspace too small (car_scatter_workspace_bytes) or not 16-byte aligned");
-    const long blocks = (n + kScanBlock - 1) / kScanBlock;
-    unsigned* counter = reinterpret_cast<unsigned*>(workspace);
-    unsigned* start = counter + n;
-    unsigned* sums = start + n;
-    Record* rec = reinterpret_cast<Record*>(reinterpret_cast<char*>(workspace) + ((2 * n + blocks + 4) * sizeof(unsigned) + 15) / 16 * 16);
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
     if (hipMemsetAsync(counter, 0, n * sizeof(unsigned), st) != hipSuccess) { car_set_error("car_gather_bilinear_backward_binned: memset failed"); return CAR_E_LAUNCH; }

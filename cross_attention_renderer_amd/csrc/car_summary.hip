@@ -293,6 +293,7 @@ bool grid_shape(int N, int H, int W, int* Hg, int* Wg, int* xm_out) {
     *xm_out = xm;
     return true;
 }
+size_t grid_scratch_floats(int N) { return 2 * (size_t)N; }          // grid_range_kernel leaves every image's low and high
 
 }  // namespace
 
@@ -368,7 +369,7 @@ extern "C" size_t car_image_grid_scratch_floats(int N, int H, int W) {
         car_set_error("car_image_grid_scratch_floats: %d images of %d x %d, need N >= 1, H >= 1, W >= 1 and a grid below 2^31 elements", N, H, W);
         return 0;
     }
-    return 2 * (size_t)N;
+    return grid_scratch_floats(N);
 }
 
 extern "C" int car_image_grid(const float* x, int N, int H, int W, int scale_each, int clamp, float lo, float hi, float* out, float* scratch,
@@ -379,8 +380,8 @@ extern "C" int car_image_grid(const float* x, int N, int H, int W, int scale_eac
                 "car_image_grid: %d images of %d x %d, need N >= 1, H >= 1, W >= 1 and a grid below 2^31 elements", N, H, W);
     CAR_REQUIRE(N <= 65535, "car_image_grid: N = %d images are too many", N);
     CAR_REQUIRE(!clamp || lo <= hi, "car_image_grid: clamp range [%g, %g] is empty or NaN", (double)lo, (double)hi);
-    CAR_REQUIRE(scratch_floats >= 2 * (size_t)N, "car_image_grid: scratch holds %zu floats, need %zu (car_image_grid_scratch_floats)", scratch_floats,
-                2 * (size_t)N);
+    CAR_REQUIRE(scratch_floats >= grid_scratch_floats(N), "car_image_grid: scratch holds %zu floats, need %zu (car_image_grid_scratch_floats)",
+                scratch_floats, grid_scratch_floats(N));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(grid_range_kernel, dim3((unsigned)N), dim3(kRangeThreads), 0, st, x, (size_t)H * W * 3, clamp ? 1 : 0, lo, hi, scratch);
     CAR_CHECK_LAUNCH("car_image_grid");

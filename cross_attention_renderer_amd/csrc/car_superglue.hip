@@ -26,8 +26,6 @@ constexpr int kKenc[6] = {3, 32, 64, 128, 256, 256};
 constexpr int kKencParams = 26, kLayerParams = 16;
 constexpr size_t kScratch = 512 * 512 + 512;                  // the widest folded layer and its bias
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // slots of the packed array: 0..4 the keypoint encoder, then per layer qkv | merge | mlp0 | mlp3, then final_proj, then the scratch
 struct Slot { int K, N; };
 Slot slot_of(int layers, int s) {
@@ -219,7 +217,32 @@ __global__ void __launch_bounds__(256) decide_kernel(const float* __restrict__ m
     }
 }
 
-size_t up64(size_t n) { return (n + 63) / 64 * 64; }
+// car_superglue_descriptors' workspace, per row of both images: the [x | message] buffer (512), q | k | v (768), the attention's output
+// (256), the hidden layer (512), the encoder's input (4)
+struct DescWork { float *cat, *qkv, *att, *hid, *kin; size_t bytes; };
+DescWork desc_work(int N0, int N1, void* work = nullptr) {
+    const size_t R = (size_t)N0 + N1;
+    Carver c(work);
+    return {c.take<float>(R * 512), c.take<float>(R * 768), c.take<float>(R * 256), c.take<float>(R * 512), c.take<float>(R * 4), c.bytes()};
+}
+// car_superglue_transport's: the couplings (fp32), then u and v (fp64, cleared in one go: everything from u on), each of whole 64 elements
+struct TransportWork { float* Zc; double *u, *v; size_t bytes; };
+TransportWork transport_work(int m, int n, void* work = nullptr) {
+    Carver c(work, 64);
+    return {c.take<float>((size_t)(m + 1) * (n + 1)), c.take<double>(m + 1), c.take<double>(n + 1), c.bytes()};
+}
+// car_superglue_matches': max0 [N0] floats, then idx0 [N0] and idx1 [N1] ints, then max1 [N1] floats
+struct MatchWork { float* max0; int *idx0, *idx1; float* max1; size_t bytes; };
+MatchWork match_work(int N0, int N1, void* work = nullptr) {
+    Carver c(work);
+    return {c.take<float>(N0), c.take<int>(N0), c.take<int>(N1), c.take<float>(N1), c.bytes()};
+}
+
+bool pair_ok(int N0, int N1, const char* who) {
+    if (N0 >= 1 && N1 >= 1 && N0 <= kMaxKeypoints && N1 <= kMaxKeypoints) return true;
+    car_set_error("%s: %d and %d keypoints, need 1..%d of each", who, N0, N1, kMaxKeypoints);
+    return false;
+}
 
 }  // namespace
 
@@ -279,14 +302,8 @@ extern "C" int car_superglue_attention(const float* q, int ldq, const float* k, 
     return CAR_OK;
 }
 
-// per row of both images: the [x | message] buffer (512), q | k | v (768), the attention's output (256), the hidden layer (512), the
-// encoder's input (4)
 extern "C" size_t car_superglue_workspace_bytes(int N0, int N1) {
-    if (N0 < 1 || N1 < 1 || N0 > kMaxKeypoints || N1 > kMaxKeypoints) {
-        car_set_error("car_superglue_workspace_bytes: %d and %d keypoints, need 1..%d of each", N0, N1, kMaxKeypoints);
-        return 0;
-    }
-    return (size_t)(N0 + N1) * (512 + 768 + 256 + 512 + 4) * sizeof(float);
+    return pair_ok(N0, N1, "car_superglue_workspace_bytes") ? desc_work(N0, N1).bytes : 0;
 }
 
 extern "C" int car_superglue_descriptors(const float* kpts0, const float* scores0, const float* desc0, int N0, int H0, int W0, const float* kpts1,
@@ -303,11 +320,7 @@ extern "C" int car_superglue_descriptors(const float* kpts0, const float* scores
                 "car_superglue_descriptors: packed, the descriptors, mdesc and the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long R = N0 + N1;
-    float* cat = static_cast<float*>(work);            // [R, 512]: x | message
-    float* qkv = cat + R * 512;                        // [R, 768]
-    float* att = qkv + R * 768;                        // [R, 256]
-    float* hid = att + R * 256;                        // [R, 512]
-    float* kin = hid + R * 512;                        // [R, 4]
+    const auto [cat, qkv, att, hid, kin, work_end] = desc_work(N0, N1, work);      // [R, 512]: x | message, [R, 768], [R, 256], [R, 512], [R, 4]
     (void)hipGetLastError();
     const float s0 = 0.7f * (float)(W0 > H0 ? W0 : H0), s1 = 0.7f * (float)(W1 > H1 ? W1 : H1);
     hipLaunchKernelGGL(rows_kernel, dim3(car_div_up(N0, 4)), dim3(256), 0, st, kpts0, scores0, desc0, N0, W0 / 2.0f, H0 / 2.0f, s0, kin, cat);
@@ -337,13 +350,8 @@ extern "C" int car_superglue_descriptors(const float* kpts0, const float* scores
     return CAR_OK;
 }
 
-// the couplings (fp32), then u and v (fp64)
 extern "C" size_t car_superglue_transport_workspace_bytes(int N0, int N1) {
-    if (N0 < 1 || N1 < 1 || N0 > kMaxKeypoints || N1 > kMaxKeypoints) {
-        car_set_error("car_superglue_transport_workspace_bytes: %d and %d keypoints, need 1..%d of each", N0, N1, kMaxKeypoints);
-        return 0;
-    }
-    return up64((size_t)(N0 + 1) * (N1 + 1)) * sizeof(float) + (up64(N0 + 1) + up64(N1 + 1)) * sizeof(double);
+    return pair_ok(N0, N1, "car_superglue_transport_workspace_bytes") ? transport_work(N0, N1).bytes : 0;
 }
 
 extern "C" int car_superglue_transport(const float* mdesc0, int N0, const float* mdesc1, int N1, float bin_score, int iters, float* Z, void* work,
@@ -358,11 +366,9 @@ extern "C" int car_superglue_transport(const float* mdesc0, int N0, const float*
     CAR_REQUIRE(aligned16(mdesc0) && aligned16(mdesc1) && aligned16(work), "car_superglue_transport: mdesc0, mdesc1 and the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int m = N0, n = N1;
-    float* Zc = static_cast<float*>(work);
-    double* u = reinterpret_cast<double*>(Zc + up64((size_t)(m + 1) * (n + 1)));
-    double* v = u + up64(m + 1);
+    const auto [Zc, u, v, work_end] = transport_work(m, n, work);
     (void)hipGetLastError();
-    CAR_CHECK_HIP(hipMemsetAsync(u, 0, (up64(m + 1) + up64(n + 1)) * sizeof(double), st), "car_superglue_transport: memset failed");
+    CAR_CHECK_HIP(hipMemsetAsync(u, 0, work_end - ((char*)u - (char*)work), st), "car_superglue_transport: memset failed");
     hipLaunchKernelGGL(couplings_kernel, dim3((unsigned)(m + 1)), dim3(256), 0, st, mdesc0, mdesc1, m, n, bin_score, Zc);
     CAR_CHECK_LAUNCH("car_superglue_transport");
     const double norm = -log((double)m + (double)n), lmu_last = log((double)n) + norm, lnu_last = log((double)m) + norm;
@@ -377,13 +383,8 @@ extern "C" int car_superglue_transport(const float* mdesc0, int N0, const float*
     return CAR_OK;
 }
 
-// max0 [N0] floats, then idx0 [N0] and idx1 [N1] ints, then max1 [N1] floats
 extern "C" size_t car_superglue_matches_workspace_bytes(int N0, int N1) {
-    if (N0 < 1 || N1 < 1 || N0 > kMaxKeypoints || N1 > kMaxKeypoints) {
-        car_set_error("car_superglue_matches_workspace_bytes: %d and %d keypoints, need 1..%d of each", N0, N1, kMaxKeypoints);
-        return 0;
-    }
-    return (size_t)2 * (N0 + N1) * 4;
+    return pair_ok(N0, N1, "car_superglue_matches_workspace_bytes") ? match_work(N0, N1).bytes : 0;
 }
 
 extern "C" int car_superglue_matches(const float* Z, int N0, int N1, float match_threshold, int* matches0, int* matches1, float* scores0, float* scores1,
@@ -396,10 +397,7 @@ extern "C" int car_superglue_matches(const float* Z, int N0, int N1, float match
     CAR_REQUIRE(work_bytes >= need, "car_superglue_matches: workspace holds %zu bytes, need %zu (car_superglue_matches_workspace_bytes)", work_bytes, need);
     CAR_REQUIRE(((uintptr_t)work & 3) == 0, "car_superglue_matches: the workspace must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    float* max0 = static_cast<float*>(work);
-    int* idx0 = reinterpret_cast<int*>(max0 + N0);
-    int* idx1 = idx0 + N0;
-    float* max1 = reinterpret_cast<float*>(idx1 + N1);
+    const auto [max0, idx0, idx1, max1, work_end] = match_work(N0, N1, work);
     (void)hipGetLastError();
     hipLaunchKernelGGL(argmax_kernel, dim3(car_div_up(N0, 4)), dim3(256), 0, st, Z, N0, N1, (long)(N1 + 1), 1L, max0, idx0);
     CAR_CHECK_LAUNCH("car_superglue_matches");

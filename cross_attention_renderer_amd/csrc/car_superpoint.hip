@@ -28,7 +28,6 @@ struct Layer { int K, N; };                          // the 3 x 3 layers behind 
 constexpr Layer kLayer[9] = {{64, 64}, {64, 64}, {64, 64}, {64, 128}, {128, 128}, {128, 128}, {128, 128}, {128, 256}, {128, 256}};
 constexpr int kLayerConv[9] = {1, 2, 3, 4, 5, 6, 7, 8, 10};       // their index among the twelve convolutions
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool shape_ok(int n, int H, int W) {
     return n >= 1 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && (double)n * H * W <= (double)kMaxPixels;
 }
@@ -310,6 +309,24 @@ int conv1a(const float* gray, int n, int H, int W, const float* packed, float* Y
     return CAR_OK;
 }
 
+// car_superpoint_dense's workspace: two [n, H, W, 64] maps A and B that the layers alternate between.  The ten moves up to conv4b leave
+// x in A, so the heads' [cells, 256] hidden map and the 1 x 1 layer's rows behind it (kLogitLd = 68 wide, or 256 channels) take B:
+// a range of its own, whose capacity ok says they fit
+struct DenseWork { float *A, *B, *rows; size_t bytes; bool ok; };      // head is B's own start
+DenseWork dense_work(int n, int H, int W, void* work = nullptr) {
+    const size_t map = (size_t)n * H * W * 64, cells = (size_t)n * (H / 8) * (W / 8);
+    Carver c(work);
+    float* A = c.take<float>(map);
+    Carver inB = c.sub(map * sizeof(float));
+    return {A, inB.take<float>(cells * 256), inB.take<float>(cells * 256), c.bytes(), inB.ok()};
+}
+// car_superpoint_nms': the mask, the suppression mask and the suppressed scores
+struct NmsWork { float *mask, *supp, *ss; size_t bytes; };
+NmsWork nms_work(size_t total, void* work = nullptr) {
+    Carver c(work);
+    return {c.take<float>(total), c.take<float>(total), c.take<float>(total), c.bytes()};
+}
+
 }  // namespace
 
 extern "C" size_t car_superpoint_packed_floats(void) { return layer_offset(11); }
@@ -338,13 +355,12 @@ extern "C" int car_superpoint_conv1a(const float* gray, int n, int H, int W, con
     return conv1a(gray, n, H, W, packed, Y, (hipStream_t)stream, "car_superpoint_conv1a");
 }
 
-// two [n, H, W, 64] maps that the layers alternate between; everything behind the first pool fits into a quarter of one
 extern "C" size_t car_superpoint_workspace_bytes(int n, int H, int W) {
     if (!shape_ok(n, H, W)) {
         car_set_error("car_superpoint_workspace_bytes: %d images of %d x %d, need H and W multiples of 8, at least 8, and n H W <= 2^22", n, H, W);
         return 0;
     }
-    return (size_t)2 * n * H * W * 64 * sizeof(float);
+    return dense_work(n, H, W).bytes;
 }
 
 extern "C" int car_superpoint_dense(const float* gray, int n, int H, int W, const float* packed, float* scores, float* desc, void* work,
@@ -355,11 +371,11 @@ extern "C" int car_superpoint_dense(const float* gray, int n, int H, int W, cons
     CAR_REQUIRE(work_bytes >= need, "car_superpoint_dense: workspace holds %zu bytes, need %zu (car_superpoint_workspace_bytes)", work_bytes, need);
     CAR_REQUIRE(aligned16(packed) && aligned16(work) && aligned16(desc), "car_superpoint_dense: packed, desc and the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    float* A = static_cast<float*>(work);
-    float* B = A + (size_t)n * H * W * 64;
+    const DenseWork dw = dense_work(n, H, W, work);
+    CAR_REQUIRE(dw.ok, "car_superpoint_dense: the heads' maps do not fit the second map of the workspace");
     (void)hipGetLastError();
-    CAR_TRY(conv1a(gray, n, H, W, packed, A, st, "car_superpoint_dense"));
-    float *src = A, *dst = B;
+    CAR_TRY(conv1a(gray, n, H, W, packed, dw.A, st, "car_superpoint_dense"));
+    float *src = dw.A, *dst = dw.B;
     int h = H, w = W, l = 0;
     auto conv = [&]() {                              // layer l: src -> dst, then the two change places
         const int rc = car_conv3x3(src, n, h, w, kLayer[l].K, kLayer[l].N, packed + layer_offset(l), dst, stream);
@@ -384,8 +400,7 @@ extern "C" int car_superpoint_dense(const float* gray, int n, int H, int W, cons
     CAR_TRY(conv());                                 // conv4a
     CAR_TRY(conv());                                 // conv4b: x [n, h, w, 128] in src
     const long cells = (long)n * h * w;
-    float* head = dst;                               // [cells, 256], then the 1 x 1 layer's rows behind it
-    float* rows = dst + cells * 256;
+    float *head = dw.B, *rows = dw.rows;             // [cells, 256] and the 1 x 1 layer's rows behind it, in B, which is dst here
     CAR_TRY(car_conv3x3(src, n, h, w, 128, 256, packed + layer_offset(7), head, stream));                    // convPa
     CAR_TRY(car_linear(head, 256, packed + layer_offset(9), 256, 65, rows, kLogitLd, cells, 0, stream));     // convPb
     hipLaunchKernelGGL(score_kernel, dim3(car_div_up(cells, 4)), dim3(256), 0, st, rows, scores, h, w, cells);
@@ -402,7 +417,7 @@ extern "C" size_t car_superpoint_nms_workspace_bytes(int n, int H, int W) {
         car_set_error("car_superpoint_nms_workspace_bytes: %d maps of %d x %d, need at least one pixel and at most 2^22", n, H, W);
         return 0;
     }
-    return (size_t)3 * n * H * W * sizeof(float);     // the mask, the suppression mask and the suppressed scores
+    return nms_work((size_t)n * H * W).bytes;
 }
 
 extern "C" int car_superpoint_nms(const float* scores, int n, int H, int W, int radius, float* out, void* work, size_t work_bytes, void* stream) {
@@ -415,9 +430,7 @@ extern "C" int car_superpoint_nms(const float* scores, int n, int H, int W, int 
     CAR_REQUIRE(((uintptr_t)work & 3) == 0, "car_superpoint_nms: the workspace must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long total = (long)n * H * W;
-    float* mask = static_cast<float*>(work);
-    float* supp = mask + total;
-    float* ss = supp + total;
+    const auto [mask, supp, ss, work_end] = nms_work((size_t)total, work);
     const dim3 grid(car_div_up(total, 256)), block(256);
     (void)hipGetLastError();
     hipLaunchKernelGGL(nms_first_kernel, grid, block, 0, st, scores, mask, H, W, radius, total);

@@ -23,9 +23,6 @@ constexpr int kTileK = 4 * kStep;                  // the K part of a tile recor
 constexpr int kTileFloats = 2 * kTileK;            // + the V part: [channel tile (2)][kg (2)] K steps over the 32 keys
 constexpr float kPScale = 8192.0f;                 // the numerators' power of two: p in [0, 1] -> [0, 2^13]
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // ---- LayerNorm: one wave per row, the row in registers, statistics in fp64 ------------------------------------------------------------
 constexpr int kLnMax = 4096, kLnVec = kLnMax / (64 * 4);
 __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ gamma,
@@ -261,16 +258,13 @@ __global__ void __launch_bounds__(256) mha_kernel(MhaArgs a) {
         }
 }
 
-struct MhaLayout { size_t maxes, scales, packed, total; int tiles; };
-MhaLayout mha_layout(int b, int S, int heads) {
-    MhaLayout l;
-    l.tiles = (S + kKeys - 1) / kKeys;
+// car_mha's workspace: pieces of whole 64 floats, the last one as long as it is
+struct MhaLayout { float *maxes, *scales, *packed; size_t total; int tiles; };
+MhaLayout mha_layout(int b, int S, int heads, void* work = nullptr) {
+    const int tiles = (S + kKeys - 1) / kKeys;
     const size_t bh = (size_t)b * heads;
-    l.maxes = 0;
-    l.scales = up256(bh * l.tiles * 2 * sizeof(float));
-    l.packed = l.scales + up256(bh * 2 * sizeof(float));
-    l.total = l.packed + bh * l.tiles * kTileFloats * sizeof(float);
-    return l;
+    Carver c(work, 64);
+    return {c.take<float>(bh * tiles * 2), c.take<float>(bh * 2), c.take<float>(bh * tiles * kTileFloats, 1), c.bytes(), tiles};
 }
 bool mha_shape_ok(int b, int S, int heads, const char* who) {
     if (b < 1 || b > 4096) { car_set_error("%s: b = %d is outside 1..4096", who, b); return false; }
@@ -290,21 +284,18 @@ VitLayout vit_layout(int dim) {
     const size_t n[12] = {d, d, car_linear_x3_packed_floats(dim, 3 * dim), 3 * d, car_linear_x3_packed_floats(dim, dim), d, d, d,
                           car_linear_x3_packed_floats(dim, 4 * dim), 4 * d, car_linear_x3_packed_floats(4 * dim, dim), d};
     VitLayout l;
-    size_t o = 0;
-    for (int i = 0; i < 12; ++i) { l.off[i] = o; o += (n[i] + 3) & ~(size_t)3; }
-    l.off[12] = o;
+    Carver c(nullptr, 4);
+    for (int i = 0; i < 12; ++i) l.off[i] = c.at<float>(n[i]);
+    l.off[12] = c.bytes() / sizeof(float);
     return l;
 }
-struct VitWork { size_t norm, att, wide, mha, total; };
-VitWork vit_work(int b, int S, int dim) {
-    const size_t rows = (size_t)b * S, d = (size_t)dim * sizeof(float);
-    VitWork w;
-    w.norm = 0;
-    w.att = up256(rows * d);
-    w.wide = w.att + up256(rows * d);
-    w.mha = w.wide + up256(rows * 4 * d);
-    w.total = w.mha + mha_layout(b, S, dim / kHead).total;
-    return w;
+// car_vit_blocks' workspace: three maps of whole 64 floats, then car_mha's own workspace as a range nested in this one
+struct VitWork { float *norm, *att, *wide, *mha; size_t mha_bytes, total; };
+VitWork vit_work(int b, int S, int dim, void* work = nullptr) {
+    const size_t rows = (size_t)b * S, d = (size_t)dim, mha_bytes = mha_layout(b, S, dim / kHead).total;
+    Carver c(work, 64);                                                 // wide: qkv [rows][3 dim], then the hidden rows [rows][4 dim]
+    return {c.take<float>(rows * d), c.take<float>(rows * d), c.take<float>(rows * 4 * d), c.sub(mha_bytes).take<float>(mha_bytes / sizeof(float)),
+            mha_bytes, c.bytes()};
 }
 
 }  // namespace
@@ -345,11 +336,9 @@ extern "C" int car_mha(const float* qkv, int ld, int b, int S, int heads, float*
     CAR_REQUIRE(ld >= 3 * dim && ld % 4 == 0, "car_mha: the row stride of qkv (%d) must hold 3 x %d columns and be a multiple of 4", ld, dim);
     CAR_REQUIRE(ldo >= dim && ldo % 4 == 0, "car_mha: the row stride of out (%d) must hold %d columns and be a multiple of 4", ldo, dim);
     CAR_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(work), "car_mha: qkv, out and work must be 16-byte aligned");
-    const MhaLayout l = mha_layout(b, S, heads);
+    const MhaLayout l = mha_layout(b, S, heads, work);
     CAR_REQUIRE(work_bytes >= l.total, "car_mha: the workspace is too small (%zu bytes, car_mha_workspace_bytes says %zu)", work_bytes, l.total);
-    char* w = static_cast<char*>(work);
-    MhaArgs a{qkv, ld, b, S, heads, l.tiles, out, ldo, reinterpret_cast<float*>(w + l.maxes), reinterpret_cast<float*>(w + l.scales),
-              reinterpret_cast<float*>(w + l.packed)};
+    MhaArgs a{qkv, ld, b, S, heads, l.tiles, out, ldo, l.maxes, l.scales, l.packed};
     hipStream_t st = (hipStream_t)stream;
     const unsigned tiles_all = (unsigned)(b * heads * l.tiles);
     (void)hipGetLastError();
@@ -412,14 +401,10 @@ extern "C" int car_vit_blocks(float* tok, int b, int S, int dim, const float* pa
         CAR_REQUIRE(aligned16(tap_out[i]), "car_vit_blocks: tap_out %d must be 16-byte aligned", i);
     }
     CAR_REQUIRE(aligned16(tok) && aligned16(packed) && aligned16(work), "car_vit_blocks: tok, packed and work must be 16-byte aligned");
-    const VitWork w = vit_work(b, S, dim);
+    const VitWork w = vit_work(b, S, dim, work);
     CAR_REQUIRE(work_bytes >= w.total, "car_vit_blocks: the workspace is too small (%zu bytes, car_vit_workspace_bytes says %zu)", work_bytes, w.total);
     const VitLayout l = vit_layout(dim);
-    char* wb = static_cast<char*>(work);
-    float* norm = reinterpret_cast<float*>(wb + w.norm);
-    float* att = reinterpret_cast<float*>(wb + w.att);
-    float* wide = reinterpret_cast<float*>(wb + w.wide);                                // qkv [rows][3 dim], then the hidden rows [rows][4 dim]
-    const size_t mha_bytes = w.total - w.mha;
+    float *norm = w.norm, *att = w.att, *wide = w.wide;
     const long rows = (long)b * S;
     const int heads = dim / kHead;
     hipStream_t st = (hipStream_t)stream;
@@ -428,7 +413,7 @@ extern "C" int car_vit_blocks(float* tok, int b, int S, int dim, const float* pa
         const float* p = packed + (size_t)blk * l.off[12];
         CAR_TRY(car_layernorm(tok, dim, p + l.off[0], p + l.off[1], dim, 1e-6, norm, dim, rows, stream));
         CAR_TRY(car_linear_x3(norm, dim, p + l.off[2], p + l.off[3], dim, 3 * dim, wide, 3 * dim, rows, 0, stream));
-        CAR_TRY(car_mha(wide, 3 * dim, b, S, heads, att, dim, wb + w.mha, mha_bytes, stream));
+        CAR_TRY(car_mha(wide, 3 * dim, b, S, heads, att, dim, w.mha, w.mha_bytes, stream));
         CAR_TRY(car_linear_x3(att, dim, p + l.off[4], p + l.off[5], dim, dim, tok, dim, rows, CAR_LIN_ACCUM, stream));
         CAR_TRY(car_layernorm(tok, dim, p + l.off[6], p + l.off[7], dim, 1e-6, norm, dim, rows, stream));
         CAR_TRY(car_linear_x3(norm, dim, p + l.off[8], p + l.off[9], dim, 4 * dim, wide, 4 * dim, rows, 0, stream));

@@ -100,6 +100,27 @@ class Guarded:
         return v[:, :self.cols].reshape(self.shape).clone()
 
 
+def exact_then_twice(nbytes, run, what, same=True):
+    """An entry's size entry and its launcher agree: `run(work, work_bytes)` — one call of the entry over the Guarded `work`, returning its
+    outputs as host tensors — over a NaN-filled guarded workspace of exactly `nbytes`, then over one twice as large.  Nothing is written outside either
+    workspace, and the outputs of the two calls are the same bytes (same=False: for an entry whose two runs need not be, `run` judges each
+    call itself).  Returns the first call's outputs."""
+    assert nbytes > 0 and nbytes % 4 == 0, (what, nbytes, lib().car_last_error())
+    outs = []
+    for scale in (1, 2):
+        work = Guarded((scale * nbytes // 4,))
+        assert work.view.data_ptr() % 16 == 0
+        outs.append(tuple(run(work, scale * nbytes)))
+        torch.cuda.synchronize()
+        assert work.margins_untouched(), f"{what}: wrote outside a workspace of {scale} x {nbytes} bytes"
+    assert len(outs[0]) == len(outs[1]) > 0
+    for i, (a, b) in enumerate(zip(*outs) if same else ()):
+        a, b = torch.as_tensor(a), torch.as_tensor(b)
+        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.reshape(-1).clone().view(torch.uint8), b.reshape(-1).clone().view(torch.uint8)), \
+            f"{what}: output {i} differs between the exact workspace and the larger one"
+    return outs[0]
+
+
 def rows_out(rows, ld, offset=0, device=None):
     """`rows` rows at a stride of ld floats and a guard row behind them, all NaN."""
     return Guarded((rows + 1, ld), offset=offset, device=device)

@@ -140,8 +140,8 @@ def run_atomic(lib, s, gathers, dmaps=None):
     return dmaps
 
 
-def run_binned(lib, s, gathers, dmaps=None, misalign=0, short=0):
-    """All gathers in one call into NaN-filled (or the given) maps."""
+def run_binned(lib, s, gathers, dmaps=None, misalign=0, short=0, work=None):
+    """All gathers in one call into NaN-filled (or the given) maps.  work: (pointer, bytes) of the caller's own workspace."""
     shapes, n_maps = s["shapes"], s["n_maps"]
     dout, grids = _device_inputs(s, gathers)
     dmaps = dmaps or [Guarded((n_maps, H, W, C)) for H, W, C in shapes]
@@ -149,11 +149,15 @@ def run_binned(lib, s, gathers, dmaps=None, misalign=0, short=0):
     G = len(gathers)
     nbytes = lib.car_scatter_workspace_bytes(hs, ws, len(shapes), n_maps, s["pts"], G)
     assert nbytes > 0
-    work = torch.empty(nbytes + 16, dtype=torch.uint8, device=abi.dev())
-    assert work.data_ptr() % 16 == 0
+    if work is None:
+        work = torch.empty(nbytes + 16, dtype=torch.uint8, device=abi.dev())
+        assert work.data_ptr() % 16 == 0
+        work_ptr, work_bytes = ctypes.c_void_p(work.data_ptr() + misalign), nbytes - short
+    else:
+        work_ptr, work_bytes = work
     rc = lib.car_gather_bilinear_backward_binned(abi.ptrs([d.view for d in dmaps]), cs, hs, ws, len(shapes), n_maps, abi.ptrs(grids), abi.ints([m for _, m, _ in gathers]),
                                                  abi.ints([p for _, _, p in gathers]), G, s["pts"], s["V"], abi.ptr(dout.view), s["ld"], s["col_out"],
-                                                 ctypes.c_void_p(work.data_ptr() + misalign), nbytes - short, abi.stream())
+                                                 work_ptr, work_bytes, abi.stream())
     torch.cuda.synchronize()
     if misalign or short:
         return rc, dmaps
@@ -262,6 +266,27 @@ def test_binned_scatter_scan_sets(name):
 def test_binned_scatter_bin_stride():
     """Four plain gathers x 2 maps x 530 000 points x four levels = 16.96 M items: bin_kernel's grid-stride loop loops, in both passes."""
     _big_binned_case("bin-stride", GR.bin_stride_set())
+
+
+def test_binned_scatter_fits_its_workspace_exactly():
+    """Two levels of 5 x 3 and 4 x 4 texels, two maps, seven points, two gathers: a workspace of exactly car_scatter_workspace_bytes, NaN
+    all around it, then one twice as large.  Neither call writes outside its workspace.  The order of a texel's additions is the order in
+    which the binning pass's integer atomics landed (csrc/car_scatter.hip), so two runs of this entry need not give the same bits: each
+    call is judged by this suite's rule instead."""
+    n_maps, pts, shapes = 2, 7, ((5, 3, 4), (4, 4, 8))
+    grids = [torch.rand(n_maps, pts, 2, generator=GR.gen(71 + j)) * 3 - 1.5 for j in range(2)]
+    grids[0][:, 0], grids[1][:, 0] = torch.tensor([0.0, 0.0]), torch.tensor([-1.0, 1.0])
+    s = {"shapes": shapes, "n_maps": n_maps, "pts": pts, "V": 1, "ld": 16, "col_out": 4, "grids": grids, "modes": (0, 1), "dout": GR._values((n_maps * pts, 12), 73)}
+    gathers = _gathers_of(s)
+    ref, bound, r32 = GR.scatter_ref_r32(shapes, n_maps, gathers, 1, s["dout"], 0)
+    lib = abi.lib()
+
+    def run(work, work_bytes):
+        dmaps = run_binned(lib, s, gathers, work=(work.ptr, work_bytes))
+        _judge("binned", f"exact workspace, {work_bytes} bytes", [(d.view, r.to(abi.dev()), b.to(abi.dev())) for d, r, b in zip(dmaps, ref, bound)], r32)
+        return [d.get("dmaps") for d in dmaps]
+
+    abi.exact_then_twice(lib.car_scatter_workspace_bytes(*_levels(shapes)[1:], len(shapes), n_maps, pts, 2), run, "car_gather_bilinear_backward_binned", same=False)
 
 
 def test_binned_scatter_refuses_a_bad_workspace():

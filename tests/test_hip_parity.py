@@ -652,6 +652,50 @@ def test_two_phase_entry_on_two_streams_equals_the_one_call():
     assert lib.car_render_forward_phase(ctypes.byref(d), abi.ptr(plan), ctypes.byref(ci), ctypes.byref(co), abi.ptr(work), need, 4, None) != 0
 
 
+def test_one_call_forward_fits_its_workspace_exactly():
+    """car_render_forward at the smallest sizes this file renders (two scenes of 16 rays x 8 samples, H = 64) over a workspace of exactly
+    car_workspace_bytes with NaN all around it, then over one twice as large: nothing is written outside either, every output is the same
+    bytes, and they are the engine's."""
+    from cross_attention_renderer_amd import _lib, synthetic as S
+    from cross_attention_renderer_amd.models import CrossAttentionRenderer
+    dev = torch.device("cuda:0")
+    H, P, R, b = 64, 8, 16, 2
+    m = CrossAttentionRenderer(model="midas_vit", n_view=2, npoints=P, with_encoder=False).eval()
+    S.perturb_parameters(m, seed=4)
+    m.H = m.W = H
+    inp = S.stereo_scene(H, b=b, uv=C.select_rays(H, R), seed=7, alpha=0.35)
+    z = S.feature_maps(b, 2, H, seed=2)
+    md = m.to(dev)
+    dinp, dz = to_device(inp, dev, cameras_on_host=True), [t.to(dev) for t in z]
+    with torch.no_grad():
+        ref = md(dinp, z=dz)
+    eng, lib = md._engine, _lib.load()
+    assert eng.last_calls == 1
+    f32 = dict(device=dev, dtype=torch.float32)
+    d = eng._dims(b, R, dz)
+    plan = eng._plan_for(d, dev)
+    pair, d_pair = eng._pair_for(plan, dz, dev, 0, b, R)
+    poses, steps = eng._poses(dinp, H, 2, dev), eng._linspace(0.0, 1.0, P, dev)
+    uv = dinp["query"]["uv"].reshape(b, R, 2).float().contiguous()
+    ci = _lib.CarInputs()
+    ci.poses, ci.uv, ci.lattice, ci.steps = poses.data_ptr(), uv.data_ptr(), pair.data_ptr(), steps.data_ptr()
+    ci.gmeta = pair.data_ptr() + 4 * lib.car_gmeta_offset(ctypes.byref(d_pair))
+    order = ("rgb", "valid_mask", "depth_ray", "at_wt", "at_wt_max", "coords", "pixel_val")
+
+    def run(work, nbytes):
+        o = {"rgb": torch.full((b, 1, R, 3), abi.NAN, **f32), "valid_mask": torch.full((b, R, 1), abi.NAN, **f32), "depth_ray": torch.full((b, R, 1), abi.NAN, **f32),
+             "at_wt": torch.full((2 * b, R, P), abi.NAN, **f32), "at_wt_max": torch.full((2 * b, R, 1), -7, device=dev, dtype=torch.int32),
+             "coords": torch.full((2 * b, R, 9), abi.NAN, **f32), "pixel_val": torch.full((2 * b, R, P, 2), abi.NAN, **f32)}
+        co = _lib.CarOutputs(*[o[k].data_ptr() for k in order])
+        _lib.check(lib.car_render_forward(ctypes.byref(d), abi.ptr(plan), ctypes.byref(ci), ctypes.byref(co), work.ptr, nbytes, abi.stream()), "car_render_forward")
+        torch.cuda.synchronize()
+        return [o[k].cpu() for k in order]
+
+    got = dict(zip(order, abi.exact_then_twice(lib.car_workspace_bytes(ctypes.byref(d)), run, "car_render_forward")))
+    for k in ("rgb", "depth_ray", "at_wt", "valid_mask"):
+        assert torch.equal(got[k], ref[k].cpu()), k
+
+
 # ----------------------------------------------------------------------------------------------------------
 # dynamic range of the split-fp16 arithmetic (csrc/car_fused_mma.h): fp16 halves keep 11 bits only between 2^-14 and 65504
 # ----------------------------------------------------------------------------------------------------------

@@ -397,14 +397,15 @@ def dev_weights(weights):
     return harness.LpipsWeights(*weights)
 
 
-def _chain(lib, dev_weights, x, y, g, sides="xy", maps=True):
-    """car_lpips_forward_train + car_lpips_backward through the C ABI: (lpips [B], gx, gy, the 13 retained maps [2 B, C, h, w] float32 CPU)."""
+def _chain(lib, dev_weights, x, y, g, sides="xy", maps=True, work=None):
+    """car_lpips_forward_train + car_lpips_backward through the C ABI: (lpips [B], gx, gy, the 13 retained maps [2 B, C, h, w] float32 CPU).
+    work: the caller's own workspace (a device tensor of bytes) in place of a fresh one of car_lpips_train_workspace_bytes."""
     from cross_attention_renderer_amd import _lib
     B, H, W, _ = x.shape
     xd, yd, gd = x.to(abi.dev()).contiguous(), y.to(abi.dev()).contiguous(), g.double().to(abi.dev())
     packed, packed_b = dev_weights.packed(abi.dev()), dev_weights.packed_backward(abi.dev())
-    n = lib.car_lpips_train_workspace_bytes(B, H, W)
-    work = torch.empty(n, dtype=torch.uint8, device=abi.dev())
+    n = lib.car_lpips_train_workspace_bytes(B, H, W) if work is None else work.numel()
+    work = torch.empty(n, dtype=torch.uint8, device=abi.dev()) if work is None else work
     out = torch.empty(B, dtype=torch.float64, device=abi.dev())
     _lib.check(lib.car_lpips_forward_train(xd.data_ptr(), yd.data_ptr(), B, H, W, packed.data_ptr(), out.data_ptr(), None, work.data_ptr(), n, abi.stream()),
                "car_lpips_forward_train")
@@ -449,6 +450,32 @@ def test_chain_matches_the_checker_at_the_devices_own_maps(lib, weights, dev_wei
     _, none_x, only_y, _ = _chain(lib, dev_weights, x, y, g, "y", maps=False)
     assert none_x is None and none_y is None
     assert torch.equal(only_x, gx) and torch.equal(only_y, gy)
+
+
+@pytest.mark.gpu
+def test_the_workspaces_are_exactly_as_large_as_their_size_entries_say(lib, dev_weights):
+    """B = 1, 16 x 16 (the smallest image: the last tap is one pixel): car_lpips, then car_lpips_forward_train + car_lpips_backward, each
+    over a workspace of exactly its size entry's bytes with NaN all around it, then over one twice as large.  Nothing is written outside
+    either, and the values, the gradients and the 13 retained maps are the same bytes."""
+    B, H, W = 1, 16, 16
+    x, y = _pair_pm1("unrelated", B, H, W, 14)
+    g = _cotangent(B, 14)
+    xd, yd, packed = x.to(abi.dev()).contiguous(), y.to(abi.dev()).contiguous(), dev_weights.packed(abi.dev())
+
+    def forward(work, wb):
+        value, taps = abi.Guarded((B,), dtype=torch.float64), abi.Guarded((B, 5), dtype=torch.float64)
+        assert lib.car_lpips(xd.data_ptr(), yd.data_ptr(), B, H, W, packed.data_ptr(), value.ptr, taps.ptr, work.ptr, wb, abi.stream()) == 0, lib.car_last_error()
+        return value.get("lpips"), taps.get("per_tap")
+
+    def chain(work, wb):
+        value, gx, gy, acts = _chain(lib, dev_weights, x, y, g, work=work.view.view(torch.uint8))
+        return (value, gx, gy, *acts)
+
+    value, taps = abi.exact_then_twice(lib.car_lpips_workspace_bytes(B, H, W), forward, "car_lpips")
+    assert bool((value > 0).all()) and bool(torch.isfinite(taps).all())
+    n = lib.car_lpips_train_workspace_bytes(B, H, W)
+    out = abi.exact_then_twice(n, chain, "car_lpips_forward_train + car_lpips_backward")
+    assert bool((out[0] > 0).all()) and bool(torch.isfinite(out[1]).all()) and bool(torch.isfinite(out[2]).all())
 
 
 def _decisions_differ(acts_dev, acts64, conv_w, conv_b, limit=20):

@@ -53,6 +53,14 @@ def work_of(nbytes):
     return torch.empty(nbytes, dtype=torch.uint8, device=A.dev())
 
 
+def work_or(work, nbytes):
+    """(pointer, bytes) of the caller's own workspace, or of a fresh one of `nbytes`; the third item keeps the fresh one alive."""
+    if work is not None:
+        return work[0], work[1], None
+    buf = work_of(nbytes)
+    return A.ptr(buf), nbytes, buf
+
+
 def images(n, H, W, seed=1):
     return torch.rand(n, H, W, generator=PR.gen(seed))
 
@@ -127,13 +135,12 @@ def test_sampled_descriptors(state, shape):
         PR.judge("superpoint_sample", f"{n}x{H}x{W} image {i}", {"": ((out.get("sample"), s64, bound), PR.ratio(s32, s64, bound))}, finite=True)
 
 
-def run_nms(maps, r):
+def run_nms(maps, r, work=None):
     n, H, W = maps.shape
     lib = A.lib()
-    nbytes = lib.car_superpoint_nms_workspace_bytes(n, H, W)
-    work = work_of(nbytes)
+    wp, wb, _keep = work_or(work, lib.car_superpoint_nms_workspace_bytes(n, H, W))
     out = A.Guarded((n, H, W))
-    assert lib.car_superpoint_nms(A.ptr(maps.to(A.dev())), n, H, W, r, out.ptr, A.ptr(work), nbytes, A.stream()) == 0, lib.car_last_error()
+    assert lib.car_superpoint_nms(A.ptr(maps.to(A.dev())), n, H, W, r, out.ptr, wp, wb, A.stream()) == 0, lib.car_last_error()
     return out.get("nms")
 
 
@@ -275,12 +282,11 @@ def test_attention(N, M_):
     PR.judge("superglue_attention", f"{N}x{M_}", {"": ((out.get("attention"), o64, bound), PR.ratio(o32, o64, bound))}, finite=True)
 
 
-def run_transport(a, b, iters):
+def run_transport(a, b, iters, work=None):
     lib, (m, n) = A.lib(), (len(a), len(b))
-    nbytes = lib.car_superglue_transport_workspace_bytes(m, n)
-    work = work_of(nbytes)
+    wp, wb, _keep = work_or(work, lib.car_superglue_transport_workspace_bytes(m, n))
     Z = A.Guarded((m + 1, n + 1))
-    assert lib.car_superglue_transport(A.ptr(a.to(A.dev())), m, A.ptr(b.to(A.dev())), n, ctypes.c_float(C.BIN_SCORE), iters, Z.ptr, A.ptr(work), nbytes,
+    assert lib.car_superglue_transport(A.ptr(a.to(A.dev())), m, A.ptr(b.to(A.dev())), n, ctypes.c_float(C.BIN_SCORE), iters, Z.ptr, wp, wb,
                                        A.stream()) == 0, lib.car_last_error()
     return Z.get("Z")
 
@@ -334,12 +340,11 @@ def test_descriptor_network(state, glue, both, golden, name):
                                              for i in range(2)}, finite=True)
 
 
-def run_matches(Z, thr):
+def run_matches(Z, thr, work=None):
     lib, (m, n) = A.lib(), (Z.shape[0] - 1, Z.shape[1] - 1)
-    nbytes = lib.car_superglue_matches_workspace_bytes(m, n)
-    work = work_of(nbytes)
+    wp, wb, _keep = work_or(work, lib.car_superglue_matches_workspace_bytes(m, n))
     m0, m1, s0, s1 = A.Guarded((m,), dtype=I32), A.Guarded((n,), dtype=I32), A.Guarded((m,)), A.Guarded((n,))
-    assert lib.car_superglue_matches(A.ptr(Z.to(A.dev())), m, n, ctypes.c_float(thr), m0.ptr, m1.ptr, s0.ptr, s1.ptr, A.ptr(work), nbytes, A.stream()) == 0, lib.car_last_error()
+    assert lib.car_superglue_matches(A.ptr(Z.to(A.dev())), m, n, ctypes.c_float(thr), m0.ptr, m1.ptr, s0.ptr, s1.ptr, wp, wb, A.stream()) == 0, lib.car_last_error()
     return m0.get("matches0"), m1.get("matches1"), s0.get("scores0"), s1.get("scores1")
 
 
@@ -389,6 +394,56 @@ def test_match_pair_end_to_end(state, glue, both, golden, name):
         sb = w64[2 + i].double() * bi[torch.arange(len(at)), at]
         entries[f"scores{i}"] = ((got[f"matching_scores{i}"].cpu(), w64[2 + i], sb, d), PR.ratio(w32[2 + i], w64[2 + i], sb, d))
     PR.judge("match_pair", name, entries, finite=True)
+
+
+# ---- every workspace-taking entry over a workspace of exactly its size entry's bytes, NaN all around it, then over one twice as large:
+# nothing is written outside either and the outputs are the same bytes (abi_harness.exact_then_twice).  The smallest shapes that
+# populate every piece of each layout.
+def test_dense_fits_its_workspace_exactly(packed):
+    """One 16 x 16 image: 2 x 2 cells, both maps of the workspace and the heads' two pieces inside the second."""
+    n, H, W = 1, 16, 16
+    lib, im = A.lib(), images(n, H, W, seed=5).to(A.dev())
+
+    def run(work, wb):
+        scores, desc = A.Guarded((n, H, W)), A.Guarded((n, H // 8, W // 8, 256))
+        assert lib.car_superpoint_dense(A.ptr(im), n, H, W, A.ptr(packed), scores.ptr, desc.ptr, work.ptr, wb, A.stream()) == 0, lib.car_last_error()
+        return scores.get("scores"), desc.get("desc")
+
+    scores, desc = A.exact_then_twice(lib.car_superpoint_workspace_bytes(n, H, W), run, "car_superpoint_dense")
+    assert bool(torch.isfinite(scores).all()) and bool(torch.isfinite(desc).all())
+
+
+def test_nms_fits_its_workspace_exactly():
+    maps = torch.rand(2, 8, 8, generator=PR.gen(11))
+    kept, = A.exact_then_twice(A.lib().car_superpoint_nms_workspace_bytes(2, 8, 8), lambda w, wb: (run_nms(maps, 2, work=(w.ptr, wb)),), "car_superpoint_nms")
+    assert torch.equal(A.bits(kept), A.bits(R.nms(maps, 2)))
+
+
+def test_glue_stages_fit_their_workspaces_exactly(glue):
+    """N0 = 3 against N1 = 5 keypoints through the three stages, each over its own exact workspace: the descriptor network with two layers
+    (self, cross), two Sinkhorn iterations, the match rule on the couplings they give."""
+    from cross_attention_renderer_amd import matching as M
+    lib, g, (N0, N1), (H, W) = A.lib(), PR.gen(13), (3, 5), (48, 64)
+    layers = ("self", "cross")
+    packed = M.MatcherWeights(C.superpoint_state(), C.superglue_state(len(layers)), layers).packed_glue(A.dev())
+    k = [(torch.rand(N, 2, generator=g) * torch.tensor([W - 1.0, H - 1.0])).to(A.dev()) for N in (N0, N1)]
+    sc = [torch.rand(N, generator=g).to(A.dev()) for N in (N0, N1)]
+    d = [torch.nn.functional.normalize(torch.randn(N, 256, generator=g), dim=1).to(A.dev()) for N in (N0, N1)]
+
+    def descriptors(work, wb):
+        out = A.Guarded((N0 + N1, 256))
+        assert lib.car_superglue_descriptors(A.ptr(k[0]), A.ptr(sc[0]), A.ptr(d[0]), N0, H, W, A.ptr(k[1]), A.ptr(sc[1]), A.ptr(d[1]), N1, H, W, A.ptr(packed),
+                                             len(layers), A.ints([0, 1]), out.ptr, work.ptr, wb, A.stream()) == 0, lib.car_last_error()
+        return (out.get("mdesc"),)
+
+    mdesc, = A.exact_then_twice(lib.car_superglue_workspace_bytes(N0, N1), descriptors, "car_superglue_descriptors")
+    assert bool(torch.isfinite(mdesc).all())
+    Z, = A.exact_then_twice(lib.car_superglue_transport_workspace_bytes(N0, N1), lambda w, wb: (run_transport(mdesc[:N0], mdesc[N0:], 2, work=(w.ptr, wb)),),
+                            "car_superglue_transport")
+    assert bool(torch.isfinite(Z).all())
+    got = A.exact_then_twice(lib.car_superglue_matches_workspace_bytes(N0, N1), lambda w, wb: run_matches(Z, C.MATCH_THRESHOLD, work=(w.ptr, wb)), "car_superglue_matches")
+    w0, w1, _, _ = R.matches(Z, C.MATCH_THRESHOLD)
+    assert torch.equal(got[0].long(), w0) and torch.equal(got[1].long(), w1)
 
 
 def test_superglue_refusals(both, weights):

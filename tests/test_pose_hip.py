@@ -60,17 +60,20 @@ def dev():
             return dict(cand=cand.cpu().numpy(), nsol=nsol.cpu().numpy(), counts=counts.cpu().numpy(), hyp_best=hyp_best.cpu().numpy(),
                         E=E.cpu().numpy(), best=tuple(int(v) for v in best.cpu().numpy()), inliers=inl.cpu().numpy())
 
-        def ransac(self, x0, x1, samples, thresh):
+        def ransac(self, x0, x1, samples, thresh, work=None):
+            """work: (pointer, bytes) of the caller's own workspace"""
             N, H = len(x0), len(samples)
             d0, d1, ds = self.up(x0, np.float64), self.up(x1, np.float64), self.up(samples, np.int32)
             n = lib.car_essential_workspace_bytes(N, H)
             assert n > 0
-            work = torch.empty(n, dtype=torch.uint8, device="cuda")
+            if work is None:
+                buf = torch.empty(n, dtype=torch.uint8, device="cuda")
+                work = (buf.data_ptr(), n)
             E = torch.full((9,), float("nan"), dtype=torch.float64, device="cuda")
             best = torch.full((3,), -7, dtype=torch.int32, device="cuda")
             inl = torch.full((N,), 7, dtype=torch.uint8, device="cuda")
             assert lib.car_essential_ransac(d0.data_ptr(), d1.data_ptr(), N, ds.data_ptr(), H, ctypes.c_double(thresh), E.data_ptr(), best.data_ptr(),
-                                            inl.data_ptr(), work.data_ptr(), n, self.stream()) == 0, lib.car_last_error()
+                                            inl.data_ptr(), work[0], work[1], self.stream()) == 0, lib.car_last_error()
             torch.cuda.synchronize()
             return dict(E=E.cpu().numpy(), best=tuple(int(v) for v in best.cpu().numpy()), inliers=inl.cpu().numpy())
     return Dev()
@@ -221,6 +224,25 @@ def test_two_runs_give_identical_bytes(dev):
     assert a["best"] == b["best"]
     c, d = dev.ransac(x0, x1, S, nt), dev.ransac(x0, x1, S, nt)
     assert c["E"].tobytes() == d["E"].tobytes() == a["E"].tobytes() and c["best"] == d["best"] and np.array_equal(c["inliers"], d["inliers"])
+
+
+def test_ransac_fits_its_workspace_exactly(dev):
+    """N = 6 matches, H = 3 hypotheses: the three int pieces of the workspace end off a 16-byte boundary.  A workspace of exactly
+    car_essential_workspace_bytes, NaN all around it, then one twice as large: nothing is written outside either, the results are the
+    same bytes, and they are the stage entries' on arrays of their own."""
+    import abi_harness as A
+    from cross_attention_renderer_amd import _lib
+    N, H = 6, 3
+    _, _, x0, x1, nt, _, _ = scene_of(N)
+    S = P.sample_table(N, H, seed=N)
+
+    def run(work, work_bytes):
+        one = dev.ransac(x0, x1, S, nt, work=(work.ptr, work_bytes))
+        return one["E"], np.array(one["best"], dtype=np.int32), one["inliers"]
+
+    E, best, inl = A.exact_then_twice(_lib.load().car_essential_workspace_bytes(N, H), run, "car_essential_ransac")
+    got = dev.stages(x0, x1, S, nt)
+    assert tuple(best) == got["best"] and E.tobytes() == got["E"].tobytes() and np.array_equal(inl, got["inliers"])
 
 
 def test_ties_go_to_the_lower_index(dev):

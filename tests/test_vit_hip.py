@@ -101,14 +101,16 @@ def test_gelu_grid_and_special_values():
 
 
 # ---- car_mha ---------------------------------------------------------------------------------------------------------------------------------
-def run_mha(qkv, b, S, heads, pad=4, what="car_mha"):
-    """qkv rows with NaN in the row padding, in front of row 0 and behind row b S; out guarded; the workspace starts as NaN."""
+def run_mha(qkv, b, S, heads, pad=4, what="car_mha", work=None):
+    """qkv rows with NaN in the row padding, in front of row 0 and behind row b S; out guarded; the workspace starts as NaN.
+    work: (pointer, bytes) of the caller's own workspace."""
     dim = heads * VR.HEAD
     Q = Guarded((b * S, 3 * dim), ld=3 * dim + pad, init=qkv)
     O = Guarded((b * S, dim), ld=dim + pad)
     nbytes = lib().car_mha_workspace_bytes(b, S, heads)
     W = torch.full((nbytes // 4,), NAN, device=AH.dev())
-    assert lib().car_mha(Q.ptr, 3 * dim + pad, b, S, heads, O.ptr, dim + pad, ptr(W), nbytes, stream()) == 0, lib().car_last_error()
+    wp, wb = (ptr(W), nbytes) if work is None else work
+    assert lib().car_mha(Q.ptr, 3 * dim + pad, b, S, heads, O.ptr, dim + pad, wp, wb, stream()) == 0, lib().car_last_error()
     sync()
     return O.get(what)
 
@@ -228,6 +230,27 @@ def test_vit_blocks(dim, depth, taps, b, S):
     for i, t in enumerate(taps):
         entries[f"tap{t}"] = ((tapped[i], ref_taps[i][0], ref_taps[i][1]), _yard(y32_taps[i][0], ref_taps[i][0], ref_taps[i][1]))
     PRU.judge("vit_blocks", f"dim={dim} depth={depth} b={b} S={S}", entries, finite=True)
+
+
+def test_mha_and_blocks_fit_their_workspaces_exactly():
+    """car_mha (b = 2, S = 33, one head: a ragged second key tile) and car_vit_blocks (b = 1, S = 33, dim = 64, one block, whose workspace
+    holds car_mha's nested behind its own three maps), each over a workspace of exactly its size entry's bytes with NaN all around it,
+    then over one twice as large: nothing is written outside either and the outputs are the same bytes."""
+    qkv = VR.mha_input("gauss", 2, 33, 1)
+    AH.exact_then_twice(lib().car_mha_workspace_bytes(2, 33, 1), lambda w, wb: (run_mha(qkv, 2, 33, 1, work=(w.ptr, wb)),), "car_mha")
+    dim, depth, b, S = 64, 1, 1, 33
+    packed, _ = _pack(VR.seeded_stage(dim, depth), dim, depth)
+    tok0 = torch.randn(b * S, dim, generator=PRU.gen(dim + S))
+
+    def blocks(work, wb):
+        T, tap = Guarded((b * S, dim), init=tok0), Guarded((b * S, dim))
+        rc = lib().car_vit_blocks(T.ptr, b, S, dim, packed.ptr, depth, AH.ints((0,)), 1, AH.ptrs([tap.view]), work.ptr, wb, stream())
+        assert rc == 0, lib().car_last_error()
+        sync()
+        return T.get("car_vit_blocks tok"), tap.get("car_vit_blocks tap")
+
+    tok, tap = AH.exact_then_twice(lib().car_vit_workspace_bytes(b, S, dim), blocks, "car_vit_blocks")
+    assert torch.equal(AH.bits(tok), AH.bits(tap)) and bool(torch.isfinite(tok).all()) and packed.margins_untouched()
 
 
 def test_vit_pack_layout():
