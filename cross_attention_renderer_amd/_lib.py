@@ -1,4 +1,4 @@
-"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h`` and, for the matcher, in ``include/car_match.h`` and, for the encoder, in ``include/car_encoder.h``, which it includes).
+"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h`` and, for the matcher, in ``include/car_match.h`` and, for the encoder, in ``include/car_encoder.h`` and ``include/car_trunk.h``, which it includes).
 
 The library is built in-tree by ``__graft_entry__.build()``.  There is no fallback: if it cannot be loaded,
 ``load()`` raises.  Two handles on the one library: ``api()``, which the package calls — every entry that returns a status checks itself
@@ -215,6 +215,29 @@ ENCODER_SIGNATURES = {
     "car_vit_blocks": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_size_t, _P]),
 }
 
+# the encoder's front half (the ResNetV2 trunk and the token assembly of get_z): mirrors include/car_trunk.h, the header of their own that
+# car_hip.h includes; bound and checked like SIGNATURES
+TRUNK_SIGNATURES = {
+    "car_weight_standardize": (c_int, [_P, c_int, c_int, c_double, _P, _P]),
+    "car_stem7x7": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
+    "car_groupnorm_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "car_groupnorm": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_double, _P, c_int, _P, _P, c_size_t, _P]),
+    "car_maxpool3x3s2_same": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_conv3x3_same_packed_floats": (c_size_t, [c_int, c_int]),
+    "car_conv3x3_same_pack": (c_int, [_P, c_int, c_int, _P, _P]),
+    "car_conv3x3_same": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "car_pixels_stride2": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_trunk_packed_floats": (c_size_t, [_P]),
+    "car_trunk_pack": (c_int, [_P, c_int, _P, _P, _P]),
+    "car_trunk_workspace_bytes": (c_size_t, [c_int, c_int, c_int, _P]),
+    "car_trunk_forward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "car_vit_tokens_packed_floats": (c_size_t, [c_int, c_int]),
+    "car_vit_tokens_pack": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, c_int, _P, _P]),
+    "car_vit_tokens_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_vit_tokens": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+}
+CAR_GN_RELU = 1                           # include/car_trunk.h
+
 # the int entries that return a VALUE (the header's words); every other int entry returns a status: 0, or a negative CAR_E_* code
 VALUE_ENTRIES = (
     "car_version",                # CAR_VERSION
@@ -235,7 +258,7 @@ def source_hash() -> str:
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h")]
+    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h", "car_trunk.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())
@@ -299,7 +322,7 @@ def _bind(checked: bool) -> ctypes.CDLL:
     """A handle of its own on the library (a second CDLL of one path has its own function objects) with SIGNATURES' prototypes;
     ``checked``: every status entry raises CarError on a negative code."""
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES, **ENCODER_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES, **ENCODER_SIGNATURES, **TRUNK_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
         if checked and res is c_int and name not in VALUE_ENTRIES:
@@ -336,7 +359,7 @@ def _errcheck(code, fn, args):
 def check_exports() -> None:
     """Every symbol the header declares must be exported (used by build() and the CPU test-suite)."""
     lib = load()
-    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES, *ENCODER_SIGNATURES) if not hasattr(lib, n)]
+    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES, *ENCODER_SIGNATURES, *TRUNK_SIGNATURES) if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"libcar_hip.so lacks symbols: {missing}")
     if lib.car_version() < 300:

@@ -270,7 +270,9 @@ extern "C" int car_linear_x3_pack(const float* W, int ldw, int K, int N, float* 
     float* scale = packed + (size_t)ksteps * tiles * kTile;
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
-    if (hipMemsetAsync(scale + 2, 0, sizeof(float), st) != hipSuccess) { car_set_error("car_linear_x3_pack: memset failed"); return CAR_E_LAUNCH; }
+    // all 64 floats of scale, of which only three are used: what the packer hands back is defined to its last float (a caller's torch.empty
+    // may hold NaN there, and a NaN is not equal to its own copy — tests/oob_runner.py compares the packed array with itself)
+    if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("car_linear_x3_pack: memset failed"); return CAR_E_LAUNCH; }
     // scale[2]: the layer's largest magnitude (many workgroups: a training step re-packs every layer), scale[0] = 2^shift, scale[1] = 2^-shift
     const car_pack_scale s{scale + 2, scale, scale + 1};
     car_pack_absmax(st, (long)N * K < 65536 ? 8 : 64, W, ldw, nullptr, nullptr, N, K, s);

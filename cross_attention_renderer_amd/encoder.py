@@ -3,7 +3,9 @@
 Runs once per stereo pair, outside the per-ray hot loop.  By default it is plain PyTorch-ROCm (MIOpen convolutions, rocBLAS /
 ``scaled_dot_product_attention`` for the transformer).  The transformer stage alone — the 12 blocks over the concatenated tokens — also
 has a route on the library's own kernels (``MultiViewDPTEncoder.vit_route = "device"``: car_vit_blocks, include/car_encoder.h;
-opt-in, inference only); the trunk, the token assembly, the read-out and the fusion are torch on both routes.  What matters is that a
+opt-in, inference only), and so has what stands in front of it, the ResNetV2 trunk and the token assembly
+(``MultiViewDPTEncoder.trunk_route = "device"``: car_trunk_forward and car_vit_tokens, include/car_trunk.h; opt-in, inference only,
+independent of the first switch); the read-out and the fusion are torch on every route.  What matters is that a
 reference checkpoint loads unchanged (``encoder.*`` keys and shapes are the reference's) and that ``get_z`` produces the reference's
 feature pyramid.
 
@@ -296,6 +298,7 @@ class MultiViewDPTEncoder(nn.Module):
     TOKENS_PER_VIEW = 257          # `os = 257` in the reference's forward_flex (midas/vit.py:183): 16 x 16 patches + class token
     VIT_TAPS = (8, 11)             # the blocks whose outputs are re-assembled (midas/vit.py:65-69)
     VIT_ROUTES = ("torch", "device")
+    TRUNK_DEPTHS = (3, 4, 9)       # the stages of ResNetV2Trunk, as car_trunk_pack takes them
 
     def __init__(self):
         super().__init__()
@@ -306,6 +309,12 @@ class MultiViewDPTEncoder(nn.Module):
         self.vit_route = "torch"
         self._vit_packed = None    # engine._Cached of the packed blocks (source: their 144 parameter tensors), made on first use
         self._vit_work = {}        # (b, S, device) -> the stage's workspace on the device
+        # where the ResNetV2 trunk and the token assembly run: "torch" (the default) or the opt-in "device" (car_trunk_forward and
+        # car_vit_tokens on the packed parameters; the same conditions and the same refusals as vit_route, and independent of it)
+        self.trunk_route = "torch"
+        self._trunk_packed = None  # engine._Cached of the packed trunk (source: its parameter tensors in state_dict order)
+        self._tokens_packed = None # engine._Cached of the packed token parameters (projection, class token, position and pose embeddings)
+        self._trunk_work = {}      # (BV, H, W, device) -> (the trunk's workspace, the token assembly's workspace)
 
     @property
     def vit_route(self) -> str:
@@ -317,13 +326,91 @@ class MultiViewDPTEncoder(nn.Module):
             raise ValueError(f"vit_route must be 'torch' or 'device' (got {value!r})")
         self._vit_route = value
 
+    @property
+    def trunk_route(self) -> str:
+        return self._trunk_route
+
+    @trunk_route.setter
+    def trunk_route(self, value: str) -> None:
+        if value not in self.VIT_ROUTES:
+            raise ValueError(f"trunk_route must be 'torch' or 'device' (got {value!r})")
+        self._trunk_route = value
+
     def drop_device_caches(self) -> None:
-        """Forgets the packed blocks and the workspaces: the next device-route forward packs the parameters as they are then.  The cache's
-        key sees an in-place update through the tensors' _version, which torch's fused optimizers do not advance
-        (CrossAttentionRenderer.train calls this on leaving train() mode, as it parks the engine's caches)."""
-        if self._vit_packed is not None:
-            self._vit_packed.drop()
+        """Forgets the packed blocks, the packed trunk and token parameters and the workspaces: the next device-route forward packs the
+        parameters as they are then.  The cache's key sees an in-place update through the tensors' _version, which torch's fused optimizers
+        do not advance (CrossAttentionRenderer.train calls this on leaving train() mode, as it parks the engine's caches)."""
+        for cached in (self._vit_packed, self._trunk_packed, self._tokens_packed):
+            if cached is not None:
+                cached.drop()
         self._vit_work = {}
+        self._trunk_work = {}
+
+    def _trunk_parameters(self) -> List[Tensor]:
+        """The trunk's parameters in car_trunk_pack's order: state_dict order of ResNetV2Trunk."""
+        return [p for _, p in self.pretrained.model.patch_embed.backbone.named_parameters()]
+
+    def _token_parameters(self) -> List[Tensor]:
+        """car_vit_tokens_pack's six arrays: the projection, the class token, the position embedding, the pose embedding."""
+        vit = self.pretrained.model
+        return [vit.patch_embed.proj.weight, vit.patch_embed.proj.bias, vit.cls_token, vit.pos_embed, vit.pose_embed.weight, vit.pose_embed.bias]
+
+    def _front_on_device(self, x: Tensor, rel_pose16: Tensor, gh: int, gw: int):
+        """The trunk and the token assembly through car_trunk_forward and car_vit_tokens: x [BV, 3, H, W] ->
+        (layer_1 [BV, 256, H/4, W/4], layer_2 [BV, 512, H/8, W/8] — NCHW views of the channel-last buffers — and tok [BV, 1 + gh gw, 768])."""
+        import ctypes
+        from . import _lib
+        from .engine import _Cached
+        trunk, toks = self._trunk_parameters(), self._token_parameters()
+        params = trunk + toks
+        if not x.is_cuda or not rel_pose16.is_cuda or not all(p.is_cuda for p in params):
+            raise ValueError("trunk_route = 'device' needs the images and the encoder on a CUDA device; CPU tensors run on trunk_route = 'torch'")
+        if x.dtype != torch.float32 or rel_pose16.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+            raise ValueError(f"trunk_route = 'device' computes in float32 (got {x.dtype}); other dtypes run on trunk_route = 'torch'")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise ValueError("trunk_route = 'device' is inference only (its kernels have no backward): call it under torch.no_grad(), or "
+                             "keep trunk_route = 'torch' for a forward that autograd records")
+        lib, dev = _lib.api(), x.device
+        BV, _, H, W = x.shape
+        depths = (ctypes.c_int * 3)(*self.TRUNK_DEPTHS)
+        grid = int(math.sqrt(toks[3].shape[1] - 1))
+        if self._trunk_packed is None:
+            self._trunk_packed, self._tokens_packed = _Cached(), _Cached()
+
+        def build_trunk():
+            packed = torch.empty(_lib.user_call(lib.car_trunk_packed_floats, depths), device=dev, dtype=torch.float32)
+            src = [p.detach().contiguous() for p in trunk]
+            _lib.user_call(lib.car_trunk_pack, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), depths, _lib.ptr(packed), _lib.stream())
+            return packed
+
+        def build_tokens():
+            packed = torch.empty(_lib.user_call(lib.car_vit_tokens_packed_floats, gh, gw), device=dev, dtype=torch.float32)
+            pw, pb, cls, pos, sw, sb = [p.detach().contiguous() for p in toks]
+            _lib.user_call(lib.car_vit_tokens_pack, _lib.ptr(pw), _lib.ptr(pb), _lib.ptr(cls), _lib.ptr(pos), grid, _lib.ptr(sw), _lib.ptr(sb), gh, gw,
+                           _lib.ptr(packed), _lib.stream())
+            return packed
+        with torch.cuda.device(dev):
+            packed = self._trunk_packed.get(trunk, (str(dev), self.TRUNK_DEPTHS), build_trunk)
+            tpacked = self._tokens_packed.get(toks, (str(dev), gh, gw), build_tokens)
+            key = (BV, H, W, str(dev))
+            if key not in self._trunk_work:
+                self._trunk_work = {key: (torch.empty(_lib.user_call(lib.car_trunk_workspace_bytes, BV, H, W, depths) // 4, device=dev, dtype=torch.float32),
+                                          torch.empty(_lib.user_call(lib.car_vit_tokens_workspace_bytes, BV, gh, gw) // 4, device=dev, dtype=torch.float32))}
+            work, twork = self._trunk_work[key]
+            up = lambda v, k: -(-v // k)
+            h4, w4, h8, w8, h16, w16 = up(H, 4), up(W, 4), up(H, 8), up(W, 8), up(H, 16), up(W, 16)
+            if (h16, w16) != (gh, gw):
+                raise ValueError(f"trunk_route = 'device': a {H}x{W} image gives {h16}x{w16} trunk features, not the {gh}x{gw} token grid")
+            layer_1 = torch.empty(BV, h4, w4, 256, device=dev, dtype=torch.float32)
+            layer_2 = torch.empty(BV, h8, w8, 512, device=dev, dtype=torch.float32)
+            feat = torch.empty(BV, h16 * w16, 1024, device=dev, dtype=torch.float32)
+            tok = torch.empty(BV, 1 + gh * gw, 768, device=dev, dtype=torch.float32)
+            xc, pose = x.contiguous(), rel_pose16.contiguous()
+            _lib.user_call(lib.car_trunk_forward, _lib.ptr(xc), BV, H, W, _lib.ptr(packed), depths, _lib.ptr(layer_1), _lib.ptr(layer_2), _lib.ptr(feat),
+                           _lib.ptr(work), work.numel() * 4, _lib.stream())
+            _lib.user_call(lib.car_vit_tokens, _lib.ptr(feat), BV, gh, gw, _lib.ptr(pose), _lib.ptr(tpacked), _lib.ptr(tok), _lib.ptr(twork),
+                           twork.numel() * 4, _lib.stream())
+        return layer_1.permute(0, 3, 1, 2), layer_2.permute(0, 3, 1, 2), tok      # NCHW views: torch's convolutions take channels_last
 
     def _vit_parameters(self) -> List[Tensor]:
         """The blocks' parameters in car_vit_pack's order (12 per block)."""
@@ -377,10 +464,13 @@ class MultiViewDPTEncoder(nn.Module):
                              f"(midas/vit.py:183, 199): only 256x256 inputs work, got {H}x{W}")
         if BV % nviews:
             raise ValueError("batch of views is not a multiple of nviews")
-        layer_1, layer_2, feat = vit.patch_embed.backbone(x)                   # 256 @ H/4, 512 @ H/8, 1024 @ H/16
-        tok = vit.patch_embed.proj(feat).flatten(2).transpose(1, 2)            # (BV, gh*gw, 768)
-        tok = torch.cat((vit.cls_token.expand(BV, -1, -1), tok), dim=1)
-        tok = tok + vit.resized_pos_embed(gh, gw) + vit.pose_embed(rel_pose16)[:, None, :]
+        if self.trunk_route == "device":
+            layer_1, layer_2, tok = self._front_on_device(x, rel_pose16, gh, gw)   # a missing kernel or a refused input raises: no fallback
+        else:
+            layer_1, layer_2, feat = vit.patch_embed.backbone(x)               # 256 @ H/4, 512 @ H/8, 1024 @ H/16
+            tok = vit.patch_embed.proj(feat).flatten(2).transpose(1, 2)        # (BV, gh*gw, 768)
+            tok = torch.cat((vit.cls_token.expand(BV, -1, -1), tok), dim=1)
+            tok = tok + vit.resized_pos_embed(gh, gw) + vit.pose_embed(rel_pose16)[:, None, :]
         T = tok.shape[1]
         tok = tok.view(BV // nviews, nviews * T, -1)                           # all views of a scene in one sequence
         if self.vit_route == "device":

@@ -145,22 +145,32 @@ class CrossAttentionRenderer(nn.Module):
         # only (two views, midas_vit widths, a common lattice): any other forward raises instead of falling back; training refuses it
         self.render_precision = "fp32"
 
+    ENCODER_ROUTES = {"torch": ("torch", "torch"), "device": ("torch", "device"), "device_trunk": ("device", "device")}   # -> (trunk_route, vit_route)
+
     @property
     def encoder_route(self) -> str:
-        """Where get_z's transformer blocks run: "torch" (the default) or the opt-in "device" (car_vit_blocks, include/car_encoder.h:
-        inference only, float32 on a CUDA device — get_z raises on anything else instead of falling back; the rest of the encoder is
-        torch on both routes).  The value lives on the encoder (MultiViewDPTEncoder.vit_route); an encoder without that switch — none
-        built, or a caller's own module — has the "torch" route only."""
-        return getattr(self.encoder, "vit_route", "torch")
+        """Where get_z's encoder runs: "torch" (the default), the opt-in "device" (the transformer blocks alone: car_vit_blocks,
+        include/car_encoder.h) or the opt-in "device_trunk" (the ResNetV2 trunk and the token assembly as well: car_trunk_forward and
+        car_vit_tokens, include/car_trunk.h).  The device routes are inference only, float32 on a CUDA device — get_z raises on anything
+        else instead of falling back; the read-out, the fusion and conv_map are torch on every route.  The value lives on the encoder
+        (MultiViewDPTEncoder.trunk_route and vit_route; a pair set there that has no name here is returned as that pair, (trunk_route,
+        vit_route)); an encoder without the switches — none built, or a caller's own module — has the "torch" route only."""
+        pair = (getattr(self.encoder, "trunk_route", "torch"), getattr(self.encoder, "vit_route", "torch"))
+        return next((name for name, p in self.ENCODER_ROUTES.items() if p == pair), pair)
 
     @encoder_route.setter
     def encoder_route(self, value: str) -> None:
-        if value not in ("torch", "device"):
-            raise ValueError(f"encoder_route must be 'torch' or 'device' (got {value!r})")
+        if value not in self.ENCODER_ROUTES:
+            raise ValueError(f"encoder_route must be 'torch' or 'device' (the blocks alone), or 'device_trunk' (got {value!r})")
+        trunk, vit = self.ENCODER_ROUTES[value]
         if hasattr(self.encoder, "vit_route"):
-            self.encoder.vit_route = value
+            self.encoder.vit_route = vit
+            if hasattr(self.encoder, "trunk_route"):
+                self.encoder.trunk_route = trunk
+            elif trunk != "torch":
+                raise ValueError(f"encoder_route = {value!r} needs the built-in MultiViewDPTEncoder: {type(self.encoder).__name__} has no trunk_route")
         elif value != "torch":
-            raise ValueError(f"encoder_route = 'device' needs the built-in MultiViewDPTEncoder (model='midas_vit', with_encoder=True): "
+            raise ValueError(f"encoder_route = {value!r} needs the built-in MultiViewDPTEncoder (model='midas_vit', with_encoder=True): "
                              f"{type(self.encoder).__name__} has no vit_route")
 
     @property
@@ -193,7 +203,7 @@ class CrossAttentionRenderer(nn.Module):
     # ------------------------------------------------------------------------------------------
     def get_z(self, input, val=False) -> List[Tensor]:
         """Feature pyramid of the context views, NCHW (models.py:148-188).  Stock PyTorch by default; with encoder_route = "device" the
-        encoder's transformer blocks run on the library's kernels (inference only)."""
+        encoder's transformer blocks run on the library's kernels, with "device_trunk" its trunk and token assembly too (inference only)."""
         rgb = input["context"]["rgb"]
         cam2world = input["context"]["cam2world"]
         rel_cam2world = torch.matmul(torch.inverse(cam2world[:, :1]), cam2world)

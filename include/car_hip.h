@@ -684,6 +684,10 @@ int car_essential_ransac(const double* x0, const double* x1, int N, const int* s
  * A block of its own, declared in a header of its own; every host that includes this file has it. */
 #include "car_encoder.h"
 
+/* ---- the image encoder's front half on the device: the weight-standardised ResNetV2 trunk and the token assembly (encoder.py).
+ * A block of its own, declared in a header of its own; every host that includes this file has it. */
+#include "car_trunk.h"
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
