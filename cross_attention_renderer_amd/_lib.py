@@ -1,4 +1,4 @@
-"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h`` and, for the matcher, in ``include/car_match.h`` and, for the encoder, in ``include/car_encoder.h`` and ``include/car_trunk.h``, which it includes).
+"""ctypes binding of ``libcar_hip.so`` (C ABI declared in ``include/car_hip.h`` and, for the matcher, in ``include/car_match.h`` and, for the encoder, in ``include/car_encoder.h``, ``include/car_trunk.h`` and ``include/car_decoder.h``, which it includes).
 
 The library is built in-tree by ``__graft_entry__.build()``.  There is no fallback: if it cannot be loaded,
 ``load()`` raises.  Two handles on the one library: ``api()``, which the package calls — every entry that returns a status checks itself
@@ -238,6 +238,27 @@ TRUNK_SIGNATURES = {
 }
 CAR_GN_RELU = 1                           # include/car_trunk.h
 
+# the encoder's back half and get_z as one call (the read-out, the fusion, conv_map, the normalisation): mirrors include/car_decoder.h, the
+# header of their own that car_hip.h includes; bound and checked like SIGNATURES
+DECODER_SIGNATURES = {
+    "car_conv3x3_pad1_packed_floats": (c_size_t, [c_int, c_int]),
+    "car_conv3x3_pad1_pack": (c_int, [_P, c_int, c_int, _P, _P]),
+    "car_conv3x3_pad1": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
+    "car_upsample2x_bilinear": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "car_readout_packed_floats": (c_size_t, [c_int]),
+    "car_readout_pack": (c_int, [_P, _P, c_int, _P, _P]),
+    "car_readout_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_readout": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "car_conv7x7_pad3": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "car_normalize_rgb": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "car_decoder_packed_floats": (c_size_t, []),
+    "car_decoder_pack": (c_int, [_P, c_int, _P, _P]),
+    "car_decoder_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_decoder_forward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "car_getz_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int]),
+    "car_getz": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 # the int entries that return a VALUE (the header's words); every other int entry returns a status: 0, or a negative CAR_E_* code
 VALUE_ENTRIES = (
     "car_version",                # CAR_VERSION
@@ -258,7 +279,7 @@ def source_hash() -> str:
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h", "car_trunk.h")]
+    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h", "car_trunk.h", "car_decoder.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())
@@ -322,7 +343,7 @@ def _bind(checked: bool) -> ctypes.CDLL:
     """A handle of its own on the library (a second CDLL of one path has its own function objects) with SIGNATURES' prototypes;
     ``checked``: every status entry raises CarError on a negative code."""
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES, **ENCODER_SIGNATURES, **TRUNK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES, **ENCODER_SIGNATURES, **TRUNK_SIGNATURES, **DECODER_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
         if checked and res is c_int and name not in VALUE_ENTRIES:
@@ -359,7 +380,7 @@ def _errcheck(code, fn, args):
 def check_exports() -> None:
     """Every symbol the header declares must be exported (used by build() and the CPU test-suite)."""
     lib = load()
-    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES, *ENCODER_SIGNATURES, *TRUNK_SIGNATURES) if not hasattr(lib, n)]
+    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES, *ENCODER_SIGNATURES, *TRUNK_SIGNATURES, *DECODER_SIGNATURES) if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"libcar_hip.so lacks symbols: {missing}")
     if lib.car_version() < 300:

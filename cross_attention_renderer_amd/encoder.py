@@ -5,7 +5,10 @@ Runs once per stereo pair, outside the per-ray hot loop.  By default it is plain
 has a route on the library's own kernels (``MultiViewDPTEncoder.vit_route = "device"``: car_vit_blocks, include/car_encoder.h;
 opt-in, inference only), and so has what stands in front of it, the ResNetV2 trunk and the token assembly
 (``MultiViewDPTEncoder.trunk_route = "device"``: car_trunk_forward and car_vit_tokens, include/car_trunk.h; opt-in, inference only,
-independent of the first switch); the read-out and the fusion are torch on every route.  What matters is that a
+independent of the first switch), and so has what stands behind it, the read-out, the re-assembly and the RefineNet fusion
+(``MultiViewDPTEncoder.decoder_route = "device"``: car_decoder_forward, include/car_decoder.h; opt-in, inference only, independent of the
+other two).  With all three on the device no torch operator is left between the normalised images and ``[path_2, path_1]``
+(``CrossAttentionRenderer.encoder_route = "device_full"``, which also normalises the images and runs ``conv_map`` there).  What matters is that a
 reference checkpoint loads unchanged (``encoder.*`` keys and shapes are the reference's) and that ``get_z`` produces the reference's
 feature pyramid.
 
@@ -315,6 +318,11 @@ class MultiViewDPTEncoder(nn.Module):
         self._trunk_packed = None  # engine._Cached of the packed trunk (source: its parameter tensors in state_dict order)
         self._tokens_packed = None # engine._Cached of the packed token parameters (projection, class token, position and pose embeddings)
         self._trunk_work = {}      # (BV, H, W, device) -> (the trunk's workspace, the token assembly's workspace)
+        # where the read-out, the re-assembly and the fusion run: "torch" (the default) or the opt-in "device" (car_decoder_forward on the
+        # packed parameters; the same conditions and the same refusals as the other two switches, and independent of them)
+        self.decoder_route = "torch"
+        self._decoder_packed = None  # engine._Cached of the packed decoder (source: the 50 parameter tensors it evaluates)
+        self._decoder_work = {}      # (BV, gh, gw, device) -> the decoder's workspace
 
     @property
     def vit_route(self) -> str:
@@ -336,15 +344,26 @@ class MultiViewDPTEncoder(nn.Module):
             raise ValueError(f"trunk_route must be 'torch' or 'device' (got {value!r})")
         self._trunk_route = value
 
+    @property
+    def decoder_route(self) -> str:
+        return self._decoder_route
+
+    @decoder_route.setter
+    def decoder_route(self, value: str) -> None:
+        if value not in self.VIT_ROUTES:
+            raise ValueError(f"decoder_route must be 'torch' or 'device' (got {value!r})")
+        self._decoder_route = value
+
     def drop_device_caches(self) -> None:
-        """Forgets the packed blocks, the packed trunk and token parameters and the workspaces: the next device-route forward packs the
+        """Forgets the packed blocks, the packed trunk and token parameters, the packed decoder and the workspaces: the next device-route forward packs the
         parameters as they are then.  The cache's key sees an in-place update through the tensors' _version, which torch's fused optimizers
         do not advance (CrossAttentionRenderer.train calls this on leaving train() mode, as it parks the engine's caches)."""
-        for cached in (self._vit_packed, self._trunk_packed, self._tokens_packed):
+        for cached in (self._vit_packed, self._trunk_packed, self._tokens_packed, self._decoder_packed):
             if cached is not None:
                 cached.drop()
         self._vit_work = {}
         self._trunk_work = {}
+        self._decoder_work = {}
 
     def _trunk_parameters(self) -> List[Tensor]:
         """The trunk's parameters in car_trunk_pack's order: state_dict order of ResNetV2Trunk."""
@@ -455,6 +474,60 @@ class MultiViewDPTEncoder(nn.Module):
                            _lib.stream())
         return dict(zip(self.VIT_TAPS, outs))
 
+    def _decoder_parameters(self) -> List[Tensor]:
+        """The 50 parameters the decoder evaluates, in car_decoder_pack's order: state_dict order without refinenet4.resConfUnit1 and
+        scratch.output_conv, which get_z never evaluates."""
+        pre, s = self.pretrained, self.scratch
+        mods = [pre.act_postprocess3[0].project[0], pre.act_postprocess3[3], pre.act_postprocess4[0].project[0], pre.act_postprocess4[3], pre.act_postprocess4[4]]
+        params = [p for m in mods for p in (m.weight, m.bias)] + [getattr(s, f"layer{i}_rn").weight for i in range(1, 5)]
+        for i in range(1, 5):
+            r = getattr(s, f"refinenet{i}")
+            convs = [r.out_conv] + ([r.resConfUnit1.conv1, r.resConfUnit1.conv2] if i < 4 else []) + [r.resConfUnit2.conv1, r.resConfUnit2.conv2]
+            params += [p for m in convs for p in (m.weight, m.bias)]
+        return params
+
+    def _back_on_device(self, tap3: Tensor, tap4: Tensor, layer_1: Tensor, layer_2: Tensor, x: Tensor, gh: int, gw: int) -> List[Tensor]:
+        """The read-out, the re-assembly and the fusion through car_decoder_forward: the two tapped states [BV, 1 + gh gw, 768] and the trunk's
+        first two stage ends (NCHW) -> [path_2 [BV, 256, 4gh, 4gw], path_1 [BV, 256, 8gh, 8gw]], NCHW views of the channel-last buffers."""
+        import ctypes
+        from . import _lib
+        from .engine import _Cached
+        params = self._decoder_parameters()
+        acts = (tap3, tap4, layer_1, layer_2)
+        if not all(t.is_cuda for t in acts) or not all(p.is_cuda for p in params):
+            raise ValueError("decoder_route = 'device' needs the images and the encoder on a CUDA device; CPU tensors run on decoder_route = 'torch'")
+        if any(t.dtype != torch.float32 for t in acts) or any(p.dtype != torch.float32 for p in params):
+            raise ValueError(f"decoder_route = 'device' computes in float32 (got {tap3.dtype}); other dtypes run on decoder_route = 'torch'")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise ValueError("decoder_route = 'device' is inference only (its kernels have no backward): call it under torch.no_grad(), or "
+                             "keep decoder_route = 'torch' for a forward that autograd records")
+        lib, dev = _lib.api(), tap3.device
+        BV = tap3.shape[0]
+        if self._decoder_packed is None:
+            self._decoder_packed = _Cached()
+
+        def build():
+            packed = torch.empty(_lib.user_call(lib.car_decoder_packed_floats), device=dev, dtype=torch.float32)
+            src = [p.detach().contiguous() for p in params]
+            _lib.user_call(lib.car_decoder_pack, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), _lib.ptr(packed), _lib.stream())
+            return packed
+        with torch.cuda.device(dev):
+            packed = self._decoder_packed.get(params, (str(dev),), build)
+            key = (BV, gh, gw, str(dev))
+            if key not in self._decoder_work:
+                self._decoder_work = {key: torch.empty(_lib.user_call(lib.car_decoder_workspace_bytes, BV, gh, gw) // 4, device=dev, dtype=torch.float32)}
+            work = self._decoder_work[key]
+            if tuple(layer_1.shape[-2:]) != (4 * gh, 4 * gw) or tuple(layer_2.shape[-2:]) != (2 * gh, 2 * gw):
+                raise ValueError(f"decoder_route = 'device': stage ends of {tuple(layer_1.shape[-2:])} and {tuple(layer_2.shape[-2:])} are not 4 and 2 times "
+                                 f"the {gh}x{gw} token grid")
+            l1, l2 = layer_1.permute(0, 2, 3, 1).contiguous(), layer_2.permute(0, 2, 3, 1).contiguous()     # no copy behind trunk_route = 'device'
+            t3, t4 = tap3.contiguous(), tap4.contiguous()
+            path_2 = torch.empty(BV, 4 * gh, 4 * gw, 256, device=dev, dtype=torch.float32)
+            path_1 = torch.empty(BV, 8 * gh, 8 * gw, 256, device=dev, dtype=torch.float32)
+            _lib.user_call(lib.car_decoder_forward, _lib.ptr(t3), _lib.ptr(t4), _lib.ptr(l1), _lib.ptr(l2), BV, gh, gw, _lib.ptr(packed), _lib.ptr(path_2),
+                           _lib.ptr(path_1), _lib.ptr(work), work.numel() * 4, _lib.stream())
+        return [path_2.permute(0, 3, 1, 2), path_1.permute(0, 3, 1, 2)]          # NCHW views: the engine takes channels_last without a copy
+
     def forward(self, x: Tensor, rel_pose16: Tensor, nviews: int) -> List[Tensor]:
         vit = self.pretrained.model
         BV, _, H, W = x.shape
@@ -481,6 +554,8 @@ class MultiViewDPTEncoder(nn.Module):
                 tok = blk(tok)
                 if i in self.VIT_TAPS:
                     taps[i] = tok.reshape(BV, T, -1)                           # back to one row per view (midas/vit.py:65-69)
+        if self.decoder_route == "device":
+            return self._back_on_device(taps[8], taps[11], layer_1, layer_2, x, gh, gw)   # a missing kernel or a refused input raises: no fallback
 
         def reassemble(t: Tensor, post: nn.Sequential) -> Tensor:
             t = post[0](t).transpose(1, 2).unflatten(2, (gh, gw))

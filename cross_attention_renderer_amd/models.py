@@ -145,30 +145,37 @@ class CrossAttentionRenderer(nn.Module):
         # only (two views, midas_vit widths, a common lattice): any other forward raises instead of falling back; training refuses it
         self.render_precision = "fp32"
 
-    ENCODER_ROUTES = {"torch": ("torch", "torch"), "device": ("torch", "device"), "device_trunk": ("device", "device")}   # -> (trunk_route, vit_route)
+    # -> (trunk_route, vit_route, decoder_route)
+    ENCODER_ROUTES = {"torch": ("torch", "torch", "torch"), "device": ("torch", "device", "torch"), "device_trunk": ("device", "device", "torch"),
+                      "device_full": ("device", "device", "device")}
 
     @property
     def encoder_route(self) -> str:
         """Where get_z's encoder runs: "torch" (the default), the opt-in "device" (the transformer blocks alone: car_vit_blocks,
-        include/car_encoder.h) or the opt-in "device_trunk" (the ResNetV2 trunk and the token assembly as well: car_trunk_forward and
-        car_vit_tokens, include/car_trunk.h).  The device routes are inference only, float32 on a CUDA device — get_z raises on anything
-        else instead of falling back; the read-out, the fusion and conv_map are torch on every route.  The value lives on the encoder
-        (MultiViewDPTEncoder.trunk_route and vit_route; a pair set there that has no name here is returned as that pair, (trunk_route,
-        vit_route)); an encoder without the switches — none built, or a caller's own module — has the "torch" route only."""
-        pair = (getattr(self.encoder, "trunk_route", "torch"), getattr(self.encoder, "vit_route", "torch"))
-        return next((name for name, p in self.ENCODER_ROUTES.items() if p == pair), pair)
+        include/car_encoder.h), the opt-in "device_trunk" (the ResNetV2 trunk and the token assembly as well: car_trunk_forward and
+        car_vit_tokens, include/car_trunk.h) or the opt-in "device_full" (the read-out, the re-assembly and the fusion too:
+        car_decoder_forward, include/car_decoder.h — and get_z then also normalises the images and runs conv_map through car_normalize_rgb
+        and car_conv7x7_pad3, so that only the 4x4 algebra of the relative pose is left to torch).  The device routes are inference only,
+        float32 on a CUDA device — get_z raises on anything else instead of falling back; the read-out, the fusion and conv_map are torch on
+        every route but "device_full".  The value lives on the encoder (MultiViewDPTEncoder.trunk_route, vit_route and decoder_route; a
+        combination set there that has no name here is returned as the pair (trunk_route, vit_route) while the decoder is on torch, as the
+        triple (trunk_route, vit_route, decoder_route) otherwise); an encoder without the switches — none built, or a caller's own module —
+        has the "torch" route only."""
+        triple = tuple(getattr(self.encoder, a, "torch") for a in ("trunk_route", "vit_route", "decoder_route"))
+        return next((name for name, p in self.ENCODER_ROUTES.items() if p == triple), triple[:2] if triple[2] == "torch" else triple)
 
     @encoder_route.setter
     def encoder_route(self, value: str) -> None:
         if value not in self.ENCODER_ROUTES:
-            raise ValueError(f"encoder_route must be 'torch' or 'device' (the blocks alone), or 'device_trunk' (got {value!r})")
-        trunk, vit = self.ENCODER_ROUTES[value]
+            raise ValueError(f"encoder_route must be 'torch' or 'device' (the blocks alone), 'device_trunk' or 'device_full' (got {value!r})")
+        trunk, vit, decoder = self.ENCODER_ROUTES[value]
         if hasattr(self.encoder, "vit_route"):
             self.encoder.vit_route = vit
-            if hasattr(self.encoder, "trunk_route"):
-                self.encoder.trunk_route = trunk
-            elif trunk != "torch":
-                raise ValueError(f"encoder_route = {value!r} needs the built-in MultiViewDPTEncoder: {type(self.encoder).__name__} has no trunk_route")
+            for attr, route in (("trunk_route", trunk), ("decoder_route", decoder)):
+                if hasattr(self.encoder, attr):
+                    setattr(self.encoder, attr, route)
+                elif route != "torch":
+                    raise ValueError(f"encoder_route = {value!r} needs the built-in MultiViewDPTEncoder: {type(self.encoder).__name__} has no {attr}")
         elif value != "torch":
             raise ValueError(f"encoder_route = {value!r} needs the built-in MultiViewDPTEncoder (model='midas_vit', with_encoder=True): "
                              f"{type(self.encoder).__name__} has no vit_route")
@@ -203,10 +210,21 @@ class CrossAttentionRenderer(nn.Module):
     # ------------------------------------------------------------------------------------------
     def get_z(self, input, val=False) -> List[Tensor]:
         """Feature pyramid of the context views, NCHW (models.py:148-188).  Stock PyTorch by default; with encoder_route = "device" the
-        encoder's transformer blocks run on the library's kernels, with "device_trunk" its trunk and token assembly too (inference only)."""
+        encoder's transformer blocks run on the library's kernels, with "device_trunk" its trunk and token assembly too, with "device_full"
+        everything but the relative pose's 4x4 algebra (inference only)."""
         rgb = input["context"]["rgb"]
         cam2world = input["context"]["cam2world"]
         rel_cam2world = torch.matmul(torch.inverse(cam2world[:, :1]), cam2world)
+        on_device = self.model == "midas_vit" and self.encoder_route == "device_full"
+        if on_device:
+            rgb_cl = torch.flatten(rgb, 0, 1)                           # [BV, H, W, 3]: the layout car_normalize_rgb reads
+            self.H, self.W = rgb_cl.shape[1], rgb_cl.shape[2]
+            self._refuse_off_device(rgb_cl, [*self.encoder.parameters(), *self.conv_map.parameters()])
+            rgb = self._normalize_on_device(rgb_cl)
+            pose16 = rel_cam2world.reshape(-1, 16).to(rgb.device)
+            if self.no_multiview:
+                pose16 = torch.zeros_like(pose16)
+            return list(self.encoder.forward(rgb, pose16, self.n_view)) + [self._conv_map_on_device(rgb)]
         rgb = torch.flatten(rgb, 0, 1).permute(0, -1, 1, 2)
         self.H, self.W = rgb.shape[-2], rgb.shape[-1]
         if self.model in ("resnet", "midas", "midas_vit"):
@@ -224,6 +242,40 @@ class CrossAttentionRenderer(nn.Module):
                 z_conv = torch.zeros_like(z_conv)
             z = z + [z_conv]
         return z
+
+    def _refuse_off_device(self, t: Tensor, params) -> None:
+        """encoder_route = "device_full" makes the refusals of the encoder's own switches for get_z's two lines around the encoder."""
+        if not t.is_cuda or not all(p.is_cuda for p in params):
+            raise ValueError("encoder_route = 'device_full' needs the images and the model on a CUDA device; CPU tensors run on encoder_route = 'torch'")
+        if t.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+            raise ValueError(f"encoder_route = 'device_full' computes in float32 (got {t.dtype}); other dtypes run on encoder_route = 'torch'")
+        if torch.is_grad_enabled() and (t.requires_grad or any(p.requires_grad for p in params)):
+            raise ValueError("encoder_route = 'device_full' is inference only (its kernels have no backward): call get_z under torch.no_grad(), or "
+                             "keep encoder_route = 'torch' for a forward that autograd records")
+
+    def _normalize_on_device(self, rgb_cl: Tensor) -> Tensor:
+        """get_z's normalisation through car_normalize_rgb: [BV, H, W, 3] in [-1, 1] -> [BV, 3, H, W]."""
+        from . import _lib
+        self._refuse_off_device(rgb_cl, ())
+        lib, (n, H, W, _) = _lib.api(), rgb_cl.shape
+        with torch.cuda.device(rgb_cl.device):
+            src, out = rgb_cl.contiguous(), torch.empty(n, 3, H, W, device=rgb_cl.device, dtype=torch.float32)
+            _lib.user_call(lib.car_normalize_rgb, _lib.ptr(src), n, H, W, _lib.ptr(out), _lib.stream())
+        return out
+
+    def _conv_map_on_device(self, x: Tensor) -> Tensor:
+        """conv_map through car_conv7x7_pad3: x [BV, 3, H, W] -> an NCHW view of the channel-last [BV, H, W, 64] (zeros under no_high_freq)."""
+        from . import _lib
+        w, b = self.conv_map.weight, self.conv_map.bias
+        self._refuse_off_device(x, (w, b))
+        lib, (n, _, H, W) = _lib.api(), x.shape
+        if self.no_high_freq:
+            return torch.zeros(n, H, W, 64, device=x.device, dtype=torch.float32).permute(0, 3, 1, 2)
+        with torch.cuda.device(x.device):
+            out = torch.empty(n, H, W, 64, device=x.device, dtype=torch.float32)
+            _lib.user_call(lib.car_conv7x7_pad3, _lib.ptr(x), n, H, W, _lib.ptr(w.detach().contiguous()), _lib.ptr(b.detach().contiguous()), _lib.ptr(out),
+                           _lib.stream())
+        return out.permute(0, 3, 1, 2)
 
     # ------------------------------------------------------------------------------------------
     def forward(self, input, z=None, val=False, debug=False) -> Dict[str, Tensor]:

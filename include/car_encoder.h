@@ -7,8 +7,10 @@
  * What is here: the 12 pre-norm blocks over the concatenated tokens of a scene's views (encoder.py MultiViewDPTEncoder.forward; reference
  * midas/vit.py:183-202, vit_models.py:10-97 with timm 0.5.4's Block / Attention / Mlp).  What stands in front of them — the ResNetV2 trunk
  * and the token assembly (projection, class token, position and pose embeddings) — is on the device too, in car_trunk.h, which car_hip.h
- * includes behind this file.  What is NOT on the device, and what a host without PyTorch therefore still lacks for get_z: the read-out and
- * re-assembly, the RefineNet fusion and conv_map.  Inference only: no entry here has a backward.
+ * includes behind this file.  What stands behind them — the read-out and re-assembly, the RefineNet fusion, conv_map and the image
+ * normalisation — is on the device as well, in car_decoder.h, behind car_trunk.h; its car_getz is the whole of get_z in one call, so a host
+ * without PyTorch has a route from two images to z (the relative pose and the checkpoint stay its own).  Inference only: no entry here has
+ * a backward.
  *
  * Everything is channel-last fp32 rows.  Every status entry returns CAR_OK, CAR_E_ARG (nothing launched) or CAR_E_LAUNCH with a message in
  * car_last_error; a size entry returns 0, with a message, for a refused shape.

@@ -688,6 +688,11 @@ int car_essential_ransac(const double* x0, const double* x1, int N, const int* s
  * A block of its own, declared in a header of its own; every host that includes this file has it. */
 #include "car_trunk.h"
 
+/* ---- the image encoder's back half on the device and get_z as one call: the read-out, the re-assembly, the RefineNet fusion, conv_map and the
+ * image normalisation (encoder.py, models.py get_z).  A block of its own, declared in a header of its own; every host that
+ * includes this file has it. */
+#include "car_decoder.h"
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);

@@ -7,8 +7,9 @@
  * What is here: everything in front of car_vit_blocks (encoder.py ResNetV2Trunk — timm 0.5.4's resnetv2 Bottleneck, StdConv2dSame,
  * GroupNormAct, MaxPool2dSame as restated there — and the token lines of MultiViewDPTEncoder.forward: the 1x1 projection, the class token,
  * the resized position embedding, the pose embedding).  With car_encoder.h the path from an image to the tapped states of the blocks is one
- * run of C-ABI calls.  What is NOT here, and what a host without PyTorch therefore still lacks for get_z: the read-out and re-assembly,
- * the RefineNet fusion and conv_map.  Inference only: no entry here has a backward.
+ * run of C-ABI calls.  What is NOT here — the read-out and re-assembly, the RefineNet fusion, conv_map and the image normalisation — is in
+ * car_decoder.h, which car_hip.h includes behind this file and whose car_getz strings the whole of get_z together.  Inference only: no
+ * entry here has a backward.
  *
  * Activations are channel-last fp32 rows [n][H W][C].  Every status entry returns CAR_OK, CAR_E_ARG (nothing launched) or CAR_E_LAUNCH with
  * a message in car_last_error; a size entry returns 0, with a message, for a refused shape.  Every reduction has a fixed order and uses no

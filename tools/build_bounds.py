@@ -16,7 +16,7 @@ DEV = os.path.join(ROOT, "tools", "_dev")
 def build(reintroduce: bool = False):
     import __graft_entry__ as ge
     os.makedirs(os.path.join(DEV, "bounds_obj"), exist_ok=True)
-    headers = [os.path.join(ge.CSRC, f) for f in os.listdir(ge.CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h", "car_trunk.h")]
+    headers = [os.path.join(ge.CSRC, f) for f in os.listdir(ge.CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h", "car_trunk.h", "car_decoder.h")]
     objs, procs = [], []
     for unit, extra in ge.UNITS.items():
         src, obj = os.path.join(ge.CSRC, unit), os.path.join(DEV, "bounds_obj", unit.replace(".hip", ".o"))
