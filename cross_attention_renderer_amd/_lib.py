@@ -215,6 +215,26 @@ ENCODER_SIGNATURES = {
     "car_vit_blocks": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_size_t, _P]),
 }
 
+# training through the encoder's transformer stage (the recorded forward and the backward of the blocks): mirrors
+# include/car_encoder_train.h, the header of their own that car_hip.h includes; bound and checked like SIGNATURES
+ENCODER_TRAIN_SIGNATURES = {
+    "car_mha_stats_floats": (c_size_t, [c_int, c_int, c_int]),
+    "car_mha_stats": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_size_t, _P]),
+    "car_mha_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_mha_backward": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    "car_layernorm_backward_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "car_layernorm_backward": (c_int, [_P, c_int, _P, c_int, c_double, _P, c_int, _P, c_int, c_long, c_int, _P, _P, _P, c_size_t, _P]),
+    "car_gelu_backward": (c_int, [_P, c_int, _P, c_int, c_long, c_int, _P]),
+    "car_vit_packed_train_floats": (c_size_t, [c_int, c_int]),
+    "car_vit_packed_train_offset": (c_size_t, [c_int, c_int, c_int]),
+    "car_vit_pack_train": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "car_vit_saved_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "car_vit_blocks_train": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "car_vit_grad_offset": (c_size_t, [c_int, c_int]),
+    "car_vit_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "car_vit_blocks_backward": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_size_t, _P, c_int, _P, c_size_t, _P]),
+}
+
 # the encoder's front half (the ResNetV2 trunk and the token assembly of get_z): mirrors include/car_trunk.h, the header of their own that
 # car_hip.h includes; bound and checked like SIGNATURES
 TRUNK_SIGNATURES = {
@@ -279,7 +299,7 @@ def source_hash() -> str:
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h", "car_trunk.h", "car_decoder.h")]
+    files += [os.path.join(os.path.dirname(here), "include", f) for f in ("car_hip.h", "car_match.h", "car_encoder.h", "car_trunk.h", "car_decoder.h", "car_encoder_train.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())
@@ -343,7 +363,8 @@ def _bind(checked: bool) -> ctypes.CDLL:
     """A handle of its own on the library (a second CDLL of one path has its own function objects) with SIGNATURES' prototypes;
     ``checked``: every status entry raises CarError on a negative code."""
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES, **ENCODER_SIGNATURES, **TRUNK_SIGNATURES, **DECODER_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **MATCH_SIGNATURES, **ENCODER_SIGNATURES, **TRUNK_SIGNATURES, **DECODER_SIGNATURES,
+                               **ENCODER_TRAIN_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
         if checked and res is c_int and name not in VALUE_ENTRIES:
@@ -380,7 +401,8 @@ def _errcheck(code, fn, args):
 def check_exports() -> None:
     """Every symbol the header declares must be exported (used by build() and the CPU test-suite)."""
     lib = load()
-    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES, *ENCODER_SIGNATURES, *TRUNK_SIGNATURES, *DECODER_SIGNATURES) if not hasattr(lib, n)]
+    missing = [n for n in (*SIGNATURES, *MATCH_SIGNATURES, *ENCODER_SIGNATURES, *TRUNK_SIGNATURES, *DECODER_SIGNATURES,
+                             *ENCODER_TRAIN_SIGNATURES) if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"libcar_hip.so lacks symbols: {missing}")
     if lib.car_version() < 300:

@@ -1,6 +1,7 @@
 // car_vit.hip — the transformer stage of get_z's image encoder (include/car_encoder.h; encoder.py MultiViewDPTEncoder.forward, the 12
 // pre-norm blocks over the concatenated tokens of a scene's views): LayerNorm, exact GELU, multi-head attention with head width 64, the
-// pack of a stage's parameters and the stage itself as a sequence of these entries and car_linear_x3.  Inference only.
+// pack of a stage's parameters and the stage itself as a sequence of these entries and car_linear_x3; car_mha_stats and car_vit_blocks_train are the same kernels
+// with what the backward (car_vit_backward.hip, include/car_encoder_train.h) needs written down.
 //
 // car_mha is the one hot kernel here.  One wave owns 32 query rows of one (scene, head) as the B operand of car_mma32.h's chained
 // 32 x 32 x 16 tile; per tile of 32 keys it forms S^T = K Q^T (the keys are the A "weights", K = 64 head channels = 4 K steps), whose
@@ -15,9 +16,8 @@
 namespace {
 
 #include "car_mma32.h"
+#include "car_vit_layout.h"
 
-constexpr int kHead = 64;                          // head width
-constexpr int kKeys = 32;                          // keys per tile = query rows per wave
 constexpr int kStep = kMma32TileK16;               // floats of one K step's A operand: [hi | lo][lane][8 halves]
 constexpr int kTileK = 4 * kStep;                  // the K part of a tile record: 4 K steps over the 64 channels
 constexpr int kTileFloats = 2 * kTileK;            // + the V part: [channel tile (2)][kg (2)] K steps over the 32 keys
@@ -83,6 +83,7 @@ struct MhaArgs {
     float* maxes;          // [b heads][tiles][2]: largest |k|, |v| of a tile
     float* scales;         // [b heads][2]: 1 / p_k, 1 / p_v
     float* packed;         // [b heads][tiles][kTileFloats]
+    float* stats;          // null, or [b heads][S][2]: the running maximum and sum a query row ends with (car_mha_stats)
 };
 
 // largest magnitudes of one tile's k and v (rows beyond the scene are not read)
@@ -246,6 +247,7 @@ __global__ void __launch_bounds__(256) mha_kernel(MhaArgs a) {
             for (int kg = 0; kg < 2; ++kg) mma3(o[t], vh[2 * t + kg], vl[2 * t + kg], phi[kg], plo[kg]);
     }
     if (q >= a.S) return;
+    if (a.stats && hh == 0) *reinterpret_cast<float2*>(a.stats + ((long)bh * a.S + q) * 2) = make_float2(mrun, lrun);
     const float c = iv * (1.0f / kPScale);
     float* dst = a.out + ((long)sc * a.S + q) * a.ldo + h * kHead;
 #pragma unroll
@@ -265,29 +267,6 @@ MhaLayout mha_layout(int b, int S, int heads, void* work = nullptr) {
     const size_t bh = (size_t)b * heads;
     Carver c(work, 64);
     return {c.take<float>(bh * tiles * 2), c.take<float>(bh * 2), c.take<float>(bh * tiles * kTileFloats, 1), c.bytes(), tiles};
-}
-bool mha_shape_ok(int b, int S, int heads, const char* who) {
-    if (b < 1 || b > 4096) { car_set_error("%s: b = %d is outside 1..4096", who, b); return false; }
-    if (S < 1 || S > 1024) { car_set_error("%s: S = %d is outside 1..1024", who, S); return false; }
-    if (heads < 1 || heads > 16) { car_set_error("%s: heads = %d is outside 1..16", who, heads); return false; }
-    return true;
-}
-
-// the layout of one block of car_vit_pack: item i of the 12 parameters at off[i], the block's size at off[12] (floats)
-struct VitLayout { size_t off[13]; };
-bool vit_dim_ok(int dim, const char* who) {
-    if (dim < 64 || dim > 1024 || dim % 64) { car_set_error("%s: dim = %d must be a multiple of 64 in 64..1024", who, dim); return false; }
-    return true;
-}
-VitLayout vit_layout(int dim) {
-    const size_t d = (size_t)dim;
-    const size_t n[12] = {d, d, car_linear_x3_packed_floats(dim, 3 * dim), 3 * d, car_linear_x3_packed_floats(dim, dim), d, d, d,
-                          car_linear_x3_packed_floats(dim, 4 * dim), 4 * d, car_linear_x3_packed_floats(4 * dim, dim), d};
-    VitLayout l;
-    Carver c(nullptr, 4);
-    for (int i = 0; i < 12; ++i) l.off[i] = c.at<float>(n[i]);
-    l.off[12] = c.bytes() / sizeof(float);
-    return l;
 }
 // car_vit_blocks' workspace: three maps of whole 64 floats, then car_mha's own workspace as a range nested in this one
 struct VitWork { float *norm, *att, *wide, *mha; size_t mha_bytes, total; };
@@ -329,24 +308,42 @@ extern "C" size_t car_mha_workspace_bytes(int b, int S, int heads) {
     return mha_shape_ok(b, S, heads, "car_mha_workspace_bytes") ? mha_layout(b, S, heads).total : 0;
 }
 
-extern "C" int car_mha(const float* qkv, int ld, int b, int S, int heads, float* out, int ldo, void* work, size_t work_bytes, void* stream) {
-    CAR_REQUIRE(qkv && out && work, "car_mha: null pointer");
-    if (!mha_shape_ok(b, S, heads, "car_mha")) return CAR_E_ARG;
+namespace {
+// car_mha and car_mha_stats: the same checks, the same three launches; stats (or null) is the only difference
+int mha_run(const char* who, const float* qkv, int ld, int b, int S, int heads, float* out, int ldo, float* stats, void* work, size_t work_bytes,
+            void* stream) {
+    CAR_REQUIRE(qkv && out && work, "%s: null pointer", who);
+    if (!mha_shape_ok(b, S, heads, who)) return CAR_E_ARG;
     const int dim = heads * kHead;
-    CAR_REQUIRE(ld >= 3 * dim && ld % 4 == 0, "car_mha: the row stride of qkv (%d) must hold 3 x %d columns and be a multiple of 4", ld, dim);
-    CAR_REQUIRE(ldo >= dim && ldo % 4 == 0, "car_mha: the row stride of out (%d) must hold %d columns and be a multiple of 4", ldo, dim);
-    CAR_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(work), "car_mha: qkv, out and work must be 16-byte aligned");
+    CAR_REQUIRE(ld >= 3 * dim && ld % 4 == 0, "%s: the row stride of qkv (%d) must hold 3 x %d columns and be a multiple of 4", who, ld, dim);
+    CAR_REQUIRE(ldo >= dim && ldo % 4 == 0, "%s: the row stride of out (%d) must hold %d columns and be a multiple of 4", who, ldo, dim);
+    CAR_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(work) && aligned16(stats), "%s: qkv, out, stats and work must be 16-byte aligned", who);
     const MhaLayout l = mha_layout(b, S, heads, work);
-    CAR_REQUIRE(work_bytes >= l.total, "car_mha: the workspace is too small (%zu bytes, car_mha_workspace_bytes says %zu)", work_bytes, l.total);
-    MhaArgs a{qkv, ld, b, S, heads, l.tiles, out, ldo, l.maxes, l.scales, l.packed};
+    CAR_REQUIRE(work_bytes >= l.total, "%s: the workspace is too small (%zu bytes, car_mha_workspace_bytes says %zu)", who, work_bytes, l.total);
+    MhaArgs a{qkv, ld, b, S, heads, l.tiles, out, ldo, l.maxes, l.scales, l.packed, stats};
     hipStream_t st = (hipStream_t)stream;
     const unsigned tiles_all = (unsigned)(b * heads * l.tiles);
     (void)hipGetLastError();
     hipLaunchKernelGGL(mha_absmax_kernel, dim3(tiles_all), dim3(256), 0, st, a);
     hipLaunchKernelGGL(mha_pack_kernel, dim3(tiles_all), dim3(256), 0, st, a);
     hipLaunchKernelGGL(mha_kernel, dim3(car_div_up(tiles_all, 4)), dim3(256), 0, st, a);
-    CAR_CHECK_LAUNCH("car_mha");
+    CAR_CHECK_LAUNCH(who);
     return CAR_OK;
+}
+}  // namespace
+
+extern "C" int car_mha(const float* qkv, int ld, int b, int S, int heads, float* out, int ldo, void* work, size_t work_bytes, void* stream) {
+    return mha_run("car_mha", qkv, ld, b, S, heads, out, ldo, nullptr, work, work_bytes, stream);
+}
+
+extern "C" size_t car_mha_stats_floats(int b, int S, int heads) {
+    return mha_shape_ok(b, S, heads, "car_mha_stats_floats") ? (size_t)b * heads * S * 2 : 0;
+}
+
+extern "C" int car_mha_stats(const float* qkv, int ld, int b, int S, int heads, float* out, int ldo, float* stats, void* work, size_t work_bytes,
+                             void* stream) {
+    CAR_REQUIRE(stats, "car_mha_stats: null pointer");
+    return mha_run("car_mha_stats", qkv, ld, b, S, heads, out, ldo, stats, work, work_bytes, stream);
 }
 
 extern "C" size_t car_vit_packed_offset(int dim, int item) {
@@ -388,41 +385,74 @@ extern "C" size_t car_vit_workspace_bytes(int b, int S, int dim) {
     return vit_work(b, S, dim).total;
 }
 
-extern "C" int car_vit_blocks(float* tok, int b, int S, int dim, const float* packed, int depth, const int* taps, int n_taps, float* const* tap_out,
-                              void* work, size_t work_bytes, void* stream) {
-    CAR_REQUIRE(tok && packed && work && (n_taps == 0 || (taps && tap_out)), "car_vit_blocks: null pointer");
-    if (!vit_dim_ok(dim, "car_vit_blocks") || !mha_shape_ok(b, S, dim / kHead, "car_vit_blocks")) return CAR_E_ARG;
-    CAR_REQUIRE(depth >= 1 && depth <= 32, "car_vit_blocks: depth = %d is outside 1..32", depth);
-    CAR_REQUIRE(n_taps >= 0 && n_taps <= depth, "car_vit_blocks: %d taps for %d blocks", n_taps, depth);
+namespace {
+// car_vit_blocks and car_vit_blocks_train: the same checks and the same sequence of entries on the same strides; with `saved` the
+// intermediates the backward reads are written where it will find them (vit_saved) instead of into the workspace's maps
+int vit_run(const char* who, float* tok, int b, int S, int dim, const float* packed, int depth, const int* taps, int n_taps, float* const* tap_out,
+            void* saved, size_t saved_bytes, bool train, void* work, size_t work_bytes, void* stream) {
+    CAR_REQUIRE(tok && packed && work && (n_taps == 0 || (taps && tap_out)) && (!train || saved), "%s: null pointer", who);
+    if (!vit_dim_ok(dim, who) || !mha_shape_ok(b, S, dim / kHead, who) || !vit_depth_ok(depth, who)) return CAR_E_ARG;
+    CAR_REQUIRE(n_taps >= 0 && n_taps <= depth, "%s: %d taps for %d blocks", who, n_taps, depth);
     for (int i = 0; i < n_taps; ++i) {
         CAR_REQUIRE(taps[i] >= 0 && taps[i] < depth && (i == 0 || taps[i] > taps[i - 1]),
-                    "car_vit_blocks: taps must be strictly increasing block indices below depth = %d (tap %d is %d)", depth, i, taps[i]);
-        CAR_REQUIRE(tap_out[i], "car_vit_blocks: null pointer (tap_out %d)", i);
-        CAR_REQUIRE(aligned16(tap_out[i]), "car_vit_blocks: tap_out %d must be 16-byte aligned", i);
+                    "%s: taps must be strictly increasing block indices below depth = %d (tap %d is %d)", who, depth, i, taps[i]);
+        CAR_REQUIRE(tap_out[i], "%s: null pointer (tap_out %d)", who, i);
+        CAR_REQUIRE(aligned16(tap_out[i]), "%s: tap_out %d must be 16-byte aligned", who, i);
     }
-    CAR_REQUIRE(aligned16(tok) && aligned16(packed) && aligned16(work), "car_vit_blocks: tok, packed and work must be 16-byte aligned");
+    CAR_REQUIRE(aligned16(tok) && aligned16(packed) && aligned16(work) && aligned16(saved), "%s: tok, packed, saved and work must be 16-byte aligned", who);
     const VitWork w = vit_work(b, S, dim, work);
-    CAR_REQUIRE(work_bytes >= w.total, "car_vit_blocks: the workspace is too small (%zu bytes, car_vit_workspace_bytes says %zu)", work_bytes, w.total);
+    CAR_REQUIRE(work_bytes >= w.total, "%s: the workspace is too small (%zu bytes, car_vit_workspace_bytes says %zu)", who, work_bytes, w.total);
+    if (train) {
+        const size_t need = vit_saved(b, S, dim, depth).total;
+        CAR_REQUIRE(saved_bytes >= need, "%s: the saved buffer is too small (%zu bytes, car_vit_saved_bytes says %zu)", who, saved_bytes, need);
+    }
     const VitLayout l = vit_layout(dim);
-    float *norm = w.norm, *att = w.att, *wide = w.wide;
     const long rows = (long)b * S;
+    const size_t map = sizeof(float) * rows * dim;
     const int heads = dim / kHead;
     hipStream_t st = (hipStream_t)stream;
     int next_tap = 0;
     for (int blk = 0; blk < depth; ++blk) {
         const float* p = packed + (size_t)blk * l.off[12];
+        const VitSaved sv = train ? vit_saved(b, S, dim, depth, blk, saved) : VitSaved{};
+        float *norm = w.norm, *att = train ? sv.att : w.att, *qkv = train ? sv.qkv : w.wide, *wide = w.wide;
+        if (train) CAR_CHECK_HIP(hipMemcpyAsync(sv.x0, tok, map, hipMemcpyDeviceToDevice, st), "%s: copy failed", who);
         CAR_TRY(car_layernorm(tok, dim, p + l.off[0], p + l.off[1], dim, 1e-6, norm, dim, rows, stream));
-        CAR_TRY(car_linear_x3(norm, dim, p + l.off[2], p + l.off[3], dim, 3 * dim, wide, 3 * dim, rows, 0, stream));
-        CAR_TRY(car_mha(wide, 3 * dim, b, S, heads, att, dim, w.mha, w.mha_bytes, stream));
+        CAR_TRY(car_linear_x3(norm, dim, p + l.off[2], p + l.off[3], dim, 3 * dim, qkv, 3 * dim, rows, 0, stream));
+        if (train) CAR_TRY(car_mha_stats(qkv, 3 * dim, b, S, heads, att, dim, sv.stats, w.mha, w.mha_bytes, stream));
+        else CAR_TRY(car_mha(qkv, 3 * dim, b, S, heads, att, dim, w.mha, w.mha_bytes, stream));
         CAR_TRY(car_linear_x3(att, dim, p + l.off[4], p + l.off[5], dim, dim, tok, dim, rows, CAR_LIN_ACCUM, stream));
+        if (train) CAR_CHECK_HIP(hipMemcpyAsync(sv.x1, tok, map, hipMemcpyDeviceToDevice, st), "%s: copy failed", who);
         CAR_TRY(car_layernorm(tok, dim, p + l.off[6], p + l.off[7], dim, 1e-6, norm, dim, rows, stream));
-        CAR_TRY(car_linear_x3(norm, dim, p + l.off[8], p + l.off[9], dim, 4 * dim, wide, 4 * dim, rows, 0, stream));
+        if (train) {                                                    // the pre-activation stays; GELU runs on a copy
+            CAR_TRY(car_linear_x3(norm, dim, p + l.off[8], p + l.off[9], dim, 4 * dim, sv.u, 4 * dim, rows, 0, stream));
+            CAR_CHECK_HIP(hipMemcpyAsync(wide, sv.u, 4 * map, hipMemcpyDeviceToDevice, st), "%s: copy failed", who);
+        } else {
+            CAR_TRY(car_linear_x3(norm, dim, p + l.off[8], p + l.off[9], dim, 4 * dim, wide, 4 * dim, rows, 0, stream));
+        }
         CAR_TRY(car_gelu(wide, 4 * dim, rows, 4 * dim, stream));
         CAR_TRY(car_linear_x3(wide, 4 * dim, p + l.off[10], p + l.off[11], 4 * dim, dim, tok, dim, rows, CAR_LIN_ACCUM, stream));
         if (next_tap < n_taps && taps[next_tap] == blk) {
-            CAR_CHECK_HIP(hipMemcpyAsync(tap_out[next_tap], tok, sizeof(float) * rows * dim, hipMemcpyDeviceToDevice, st), "car_vit_blocks: copy failed");
+            CAR_CHECK_HIP(hipMemcpyAsync(tap_out[next_tap], tok, map, hipMemcpyDeviceToDevice, st), "%s: copy failed", who);
             ++next_tap;
         }
     }
     return CAR_OK;
+}
+}  // namespace
+
+extern "C" int car_vit_blocks(float* tok, int b, int S, int dim, const float* packed, int depth, const int* taps, int n_taps, float* const* tap_out,
+                              void* work, size_t work_bytes, void* stream) {
+    return vit_run("car_vit_blocks", tok, b, S, dim, packed, depth, taps, n_taps, tap_out, nullptr, 0, false, work, work_bytes, stream);
+}
+
+extern "C" size_t car_vit_saved_bytes(int b, int S, int dim, int depth) {
+    const char* who = "car_vit_saved_bytes";
+    if (!vit_dim_ok(dim, who) || !mha_shape_ok(b, S, dim / kHead, who) || !vit_depth_ok(depth, who)) return 0;
+    return vit_saved(b, S, dim, depth).total;
+}
+
+extern "C" int car_vit_blocks_train(float* tok, int b, int S, int dim, const float* packed, int depth, const int* taps, int n_taps,
+                                    float* const* tap_out, void* saved, size_t saved_bytes, void* work, size_t work_bytes, void* stream) {
+    return vit_run("car_vit_blocks_train", tok, b, S, dim, packed, depth, taps, n_taps, tap_out, saved, saved_bytes, true, work, work_bytes, stream);
 }

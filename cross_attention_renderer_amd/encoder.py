@@ -294,6 +294,70 @@ class _Scratch(nn.Module):
                                          nn.Identity(), nn.Conv2d(32, 1, 1), nn.Identity(), nn.Identity())
 
 
+class _VitBlocksTrain(torch.autograd.Function):
+    """The 12 blocks as one autograd node over (tok, the 144 block parameters): car_vit_blocks_train forward, car_vit_blocks_backward
+    backward (include/car_encoder_train.h).  Once differentiable: a double backward raises.
+
+    The parameters are packed afresh on every forward (car_vit_pack_train: the forward's layout and the transposed matrices of
+    dX = dY W): the packed cache of the inference route keys on the tensors' _version, which torch's fused optimizers do not advance, so
+    between two training steps it would hand back the old weights.  The parameter gradients come back as views of ONE flat buffer
+    (car_vit_grad_offset's layout), as training.render_train's do; autograd's accumulation into .grad is the usual one, so two backwards
+    without zero_grad add up.  The LayerNorm gradients and the gradient of tok are bit-reproducible; the matrices' and their biases' go
+    through car_linear_wgrad's fp32 atomics and are reproducible to rounding."""
+
+    @staticmethod
+    def forward(ctx, enc, BV, T, tok, *params):
+        import ctypes
+        from . import _lib
+        lib, dev = _lib.api(), tok.device
+        b, S, dim = tok.shape
+        depth, taps = len(params) // 12, enc.VIT_TAPS
+        f32 = dict(device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            packed = torch.empty(_lib.user_call(lib.car_vit_packed_train_floats, dim, depth), **f32)
+            src = [p.detach().contiguous() for p in params]
+            _lib.user_call(lib.car_vit_pack_train, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), dim, depth, _lib.ptr(packed),
+                           _lib.stream())
+            saved = torch.empty(_lib.user_call(lib.car_vit_saved_bytes, b, S, dim, depth) // 4, **f32)
+            work = enc._vit_workspace(lib, b, S, dim, dev)
+            x = tok.detach().clone(memory_format=torch.contiguous_format)     # the stage runs in place
+            outs = [torch.empty(BV, T, dim, **f32) for _ in taps]
+            _lib.user_call(lib.car_vit_blocks_train, _lib.ptr(x), b, S, dim, _lib.ptr(packed), depth, (ctypes.c_int * len(taps))(*taps), len(taps),
+                           (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _lib.ptr(saved), saved.numel() * 4, _lib.ptr(work),
+                           work.numel() * 4, _lib.stream())
+        ctx.packed, ctx.saved, ctx.shape, ctx.taps, ctx.params = packed, saved, (b, S, dim, depth), taps, params
+        # the record lives in plain buffers autograd does not track: an in-place parameter update between forward and backward is
+        # checked by hand, as training.render_train does
+        ctx.param_versions = [p._version for p in params]
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *dtaps):
+        import ctypes
+        from . import _lib
+        stale = [i for i, (p, v) in enumerate(zip(ctx.params, ctx.param_versions)) if p._version != v]
+        if stale:
+            raise RuntimeError(f"vit_route = 'device_train': block parameters were modified in place between forward and backward (blocks "
+                               f"{sorted({i // 12 for i in stale})[:3]} ...): the saved activations no longer belong to them")
+        lib, dev = _lib.api(), ctx.saved.device
+        b, S, dim, depth = ctx.shape
+        f32 = dict(device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            off = [lib.car_vit_grad_offset(dim, i) for i in range(13)]
+            flat = torch.zeros(depth * off[12], **f32)                         # the entry adds the matrices' gradients: zeroed here
+            dtok = torch.zeros(b, S, dim, **f32)                               # the stage's own output is not an output of this node
+            work = torch.empty(_lib.user_call(lib.car_vit_backward_workspace_bytes, b, S, dim) // 4, **f32)
+            d = [None if t is None else t.to(torch.float32).contiguous() for t in dtaps]
+            _lib.user_call(lib.car_vit_blocks_backward, _lib.ptr(dtok), b, S, dim, _lib.ptr(ctx.packed), depth, (ctypes.c_int * len(d))(*ctx.taps), len(d),
+                           (ctypes.c_void_p * len(d))(*[None if t is None else t.data_ptr() for t in d]), _lib.ptr(ctx.saved), ctx.saved.numel() * 4,
+                           _lib.ptr(flat), 0, _lib.ptr(work), work.numel() * 4, _lib.stream())
+        grads = [flat[(i // 12) * off[12] + off[i % 12]:][:p.numel()].view_as(p) if ctx.needs_input_grad[4 + i] else None
+                 for i, p in enumerate(ctx.params)]
+        ctx.packed = ctx.saved = None
+        return (None, None, None, dtok if ctx.needs_input_grad[3] else None, *grads)
+
+
 class MultiViewDPTEncoder(nn.Module):
     """Drop-in for the reference's ``self.encoder`` when ``model == "midas_vit"`` (models.py:82-94): same parameter names, same
     ``forward(rgb, rel_pose16, nviews) -> [path_2, path_1]``."""
@@ -301,6 +365,7 @@ class MultiViewDPTEncoder(nn.Module):
     TOKENS_PER_VIEW = 257          # `os = 257` in the reference's forward_flex (midas/vit.py:183): 16 x 16 patches + class token
     VIT_TAPS = (8, 11)             # the blocks whose outputs are re-assembled (midas/vit.py:65-69)
     VIT_ROUTES = ("torch", "device")
+    VIT_BLOCK_ROUTES = ("torch", "device", "device_train")   # vit_route's own values: the blocks also have a recorded forward and a backward
     TRUNK_DEPTHS = (3, 4, 9)       # the stages of ResNetV2Trunk, as car_trunk_pack takes them
 
     def __init__(self):
@@ -308,7 +373,9 @@ class MultiViewDPTEncoder(nn.Module):
         self.pretrained = _Pretrained()
         self.scratch = _Scratch()
         # where the transformer blocks run: "torch" (the default: the modules above) or the opt-in "device" (car_vit_blocks on the packed
-        # parameters: inference only, float32 CUDA tensors only; it refuses anything else instead of falling back)
+        # parameters: inference only, float32 CUDA tensors only; it refuses anything else instead of falling back) or the opt-in
+        # "device_train" (under no_grad the "device" route, call for call; where autograd records, car_vit_blocks_train with
+        # car_vit_blocks_backward as its backward: _VitBlocksTrain below)
         self.vit_route = "torch"
         self._vit_packed = None    # engine._Cached of the packed blocks (source: their 144 parameter tensors), made on first use
         self._vit_work = {}        # (b, S, device) -> the stage's workspace on the device
@@ -330,8 +397,8 @@ class MultiViewDPTEncoder(nn.Module):
 
     @vit_route.setter
     def vit_route(self, value: str) -> None:
-        if value not in self.VIT_ROUTES:
-            raise ValueError(f"vit_route must be 'torch' or 'device' (got {value!r})")
+        if value not in self.VIT_BLOCK_ROUTES:
+            raise ValueError(f"vit_route must be 'torch', 'device' or 'device_train' (got {value!r})")
         self._vit_route = value
 
     @property
@@ -437,17 +504,40 @@ class MultiViewDPTEncoder(nn.Module):
                  "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
         return [blk.get_parameter(n) for blk in self.pretrained.model.blocks for n in names]
 
+    def _refuse_off_device(self, tok: Tensor, params: List[Tensor]) -> None:
+        """What both device routes of the blocks refuse instead of falling back: CPU tensors, other dtypes."""
+        if not tok.is_cuda or not all(p.is_cuda for p in params):
+            raise ValueError(f"vit_route = {self.vit_route!r} needs the images and the encoder on a CUDA device; CPU tensors run on vit_route = 'torch'")
+        if tok.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+            raise ValueError(f"vit_route = {self.vit_route!r} computes in float32 (got {tok.dtype}); other dtypes run on vit_route = 'torch'")
+
+    def _vit_workspace(self, lib, b: int, S: int, dim: int, dev) -> Tensor:
+        key = (b, S, str(dev))
+        if key not in self._vit_work:
+            self._vit_work = {key: torch.empty(lib.car_vit_workspace_bytes(b, S, dim) // 4, device=dev, dtype=torch.float32)}
+        return self._vit_work[key]
+
+    def _blocks_recorded_on_device(self, tok: Tensor, BV: int, T: int) -> dict:
+        """The transformer stage where autograd records (vit_route = "device_train"): car_vit_blocks_train, with car_vit_blocks_backward
+        as its backward.  tok [b, V T, dim] -> {tap: [BV, T, dim]}, each carrying the gradient back to tok and to the 144 block parameters."""
+        params = self._vit_parameters()
+        self._refuse_off_device(tok, params)
+        outs = _VitBlocksTrain.apply(self, BV, T, tok, *params)
+        return dict(zip(self.VIT_TAPS, outs))
+
     def _blocks_on_device(self, tok: Tensor, x: Tensor, BV: int, T: int) -> dict:
         """The transformer stage through car_vit_blocks: tok [b, V T, dim] (contiguous, overwritten) -> {tap: [BV, T, dim]}."""
+        return self._blocks_inference(tok, x, BV, T, False)
+
+    def _blocks_inference(self, tok: Tensor, x: Tensor, BV: int, T: int, recorded_elsewhere: bool) -> dict:
+        """_blocks_on_device's body.  recorded_elsewhere (vit_route = "device_train" only): grad mode may be on, but neither tok nor a block
+        parameter asks for a gradient, so nothing would flow through the blocks — the inference call is the whole of it."""
         import ctypes
         from . import _lib
         from .engine import _Cached
         params = self._vit_parameters()
-        if not tok.is_cuda or not all(p.is_cuda for p in params):
-            raise ValueError("vit_route = 'device' needs the images and the encoder on a CUDA device; CPU tensors run on vit_route = 'torch'")
-        if tok.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
-            raise ValueError(f"vit_route = 'device' computes in float32 (got {tok.dtype}); other dtypes run on vit_route = 'torch'")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        self._refuse_off_device(tok, params)
+        if not recorded_elsewhere and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise ValueError("vit_route = 'device' is inference only (its kernels have no backward): call it under torch.no_grad(), or "
                              "keep vit_route = 'torch' for a forward that autograd records")
         lib, dev = _lib.api(), tok.device
@@ -464,10 +554,7 @@ class MultiViewDPTEncoder(nn.Module):
             return packed
         with torch.cuda.device(dev):
             packed = self._vit_packed.get(params, (str(dev), dim, depth), build)
-            key = (b, S, str(dev))
-            if key not in self._vit_work:
-                self._vit_work = {key: torch.empty(lib.car_vit_workspace_bytes(b, S, dim) // 4, device=dev, dtype=torch.float32)}
-            work = self._vit_work[key]
+            work = self._vit_workspace(lib, b, S, dim, dev)
             outs = [torch.empty(BV, T, dim, device=dev, dtype=torch.float32) for _ in self.VIT_TAPS]
             _lib.user_call(lib.car_vit_blocks, _lib.ptr(tok), b, S, dim, _lib.ptr(packed), depth, (ctypes.c_int * len(outs))(*self.VIT_TAPS),
                            len(outs), (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _lib.ptr(work), work.numel() * 4,
@@ -546,7 +633,12 @@ class MultiViewDPTEncoder(nn.Module):
             tok = tok + vit.resized_pos_embed(gh, gw) + vit.pose_embed(rel_pose16)[:, None, :]
         T = tok.shape[1]
         tok = tok.view(BV // nviews, nviews * T, -1)                           # all views of a scene in one sequence
-        if self.vit_route == "device":
+        records = self.vit_route == "device_train" and torch.is_grad_enabled() and (tok.requires_grad or any(p.requires_grad for p in self._vit_parameters()))
+        if records:
+            taps = self._blocks_recorded_on_device(tok, BV, T)                 # a missing kernel or a refused input raises: no fallback
+        elif self.vit_route == "device_train":
+            taps = self._blocks_inference(tok.contiguous(), x, BV, T, True)    # nothing to record: the "device" route's own call
+        elif self.vit_route == "device":
             taps = self._blocks_on_device(tok.contiguous(), x, BV, T)          # a missing kernel or a refused input raises: no fallback
         else:
             taps = {}

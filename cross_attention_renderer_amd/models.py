@@ -147,7 +147,7 @@ class CrossAttentionRenderer(nn.Module):
 
     # -> (trunk_route, vit_route, decoder_route)
     ENCODER_ROUTES = {"torch": ("torch", "torch", "torch"), "device": ("torch", "device", "torch"), "device_trunk": ("device", "device", "torch"),
-                      "device_full": ("device", "device", "device")}
+                      "device_full": ("device", "device", "device"), "device_train": ("torch", "device_train", "torch")}
 
     @property
     def encoder_route(self) -> str:
@@ -155,7 +155,9 @@ class CrossAttentionRenderer(nn.Module):
         include/car_encoder.h), the opt-in "device_trunk" (the ResNetV2 trunk and the token assembly as well: car_trunk_forward and
         car_vit_tokens, include/car_trunk.h) or the opt-in "device_full" (the read-out, the re-assembly and the fusion too:
         car_decoder_forward, include/car_decoder.h — and get_z then also normalises the images and runs conv_map through car_normalize_rgb
-        and car_conv7x7_pad3, so that only the 4x4 algebra of the relative pose is left to torch).  The device routes are inference only,
+        and car_conv7x7_pad3, so that only the 4x4 algebra of the relative pose is left to torch), or the opt-in "device_train" (the
+        blocks alone, as "device" — and the same call under no_grad — but a forward that autograd records runs car_vit_blocks_train and
+        trains through car_vit_blocks_backward, include/car_encoder_train.h; the trunk and the decoder stay torch autograd).  The other device routes are inference only,
         float32 on a CUDA device — get_z raises on anything else instead of falling back; the read-out, the fusion and conv_map are torch on
         every route but "device_full".  The value lives on the encoder (MultiViewDPTEncoder.trunk_route, vit_route and decoder_route; a
         combination set there that has no name here is returned as the pair (trunk_route, vit_route) while the decoder is on torch, as the
@@ -167,7 +169,8 @@ class CrossAttentionRenderer(nn.Module):
     @encoder_route.setter
     def encoder_route(self, value: str) -> None:
         if value not in self.ENCODER_ROUTES:
-            raise ValueError(f"encoder_route must be 'torch' or 'device' (the blocks alone), 'device_trunk' or 'device_full' (got {value!r})")
+            raise ValueError("encoder_route must be 'torch' or 'device' (the blocks alone), 'device_train' (the blocks, with a backward), "
+                             f"'device_trunk' or 'device_full' (got {value!r})")
         trunk, vit, decoder = self.ENCODER_ROUTES[value]
         if hasattr(self.encoder, "vit_route"):
             self.encoder.vit_route = vit

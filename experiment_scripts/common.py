@@ -52,14 +52,15 @@ def parser(description: str) -> argparse.ArgumentParser:
                    help="report LPIPS (v0.1, net='vgg') computed on the device with these weight files: a torchvision VGG16 state dict and "
                         "the lpips package's vgg.pth, or one file holding lpips.LPIPS(net='vgg').state_dict().  Without it LPIPS is not reported "
                         "(no weights are shipped)")
-    p.add_argument("--encoder_route", choices=("torch", "device", "device_trunk", "device_full"), default="torch",
+    p.add_argument("--encoder_route", choices=("torch", "device", "device_train", "device_trunk", "device_full"), default="torch",
                    help="where get_z's encoder runs: torch = stock PyTorch (default); device = the transformer blocks on the library's own kernels "
                         "(car_vit_blocks: opt-in, inference only, float32; the rest of the encoder stays torch); device_trunk = the ResNetV2 trunk "
                         "and the token assembly as well (car_trunk_forward, car_vit_tokens; the read-out and the fusion stay torch); device_full = the read-out, the fusion, the image "
                         "normalisation and conv_map as well (car_decoder_forward, car_normalize_rgb, car_conv7x7_pad3: no torch operator is left in get_z but "
                         "the relative pose's 4x4 algebra).  Read only where the encoder "
-                        "is built (a checkpoint or --with_encoder); the train script applies it to its validation pass only, because a forward "
-                        "that autograd records refuses the device routes")
+                        "is built (a checkpoint or --with_encoder); the train script applies these to its validation pass only, because a forward "
+                        "that autograd records refuses them; device_train = the transformer blocks with a backward (car_vit_blocks_train, "
+                        "car_vit_blocks_backward): the one value the train script applies to its training forward; under no_grad it is device")
     p.add_argument("--port", type=int, default=1492)          # the reference rendezvous port (eval_realestate10k.py:97)
     return p
 

@@ -111,10 +111,17 @@ def _validation_batches(opt, model, dev):
         yield inp, gt, z
 
 
+def _train_route(opt):
+    """The encoder route of the training forward: --encoder_route device_train trains through the blocks' device backward; every other
+    device value is inference only and holds for the validation pass alone."""
+    return "device_train" if getattr(opt, "encoder_route", "torch") == "device_train" else "torch"
+
+
 def _validate(opt, model, batch, log, step, lpips_w):
     """One validation pass (training.py:146-231): eval(), no_grad, get_z once, the chunked full-image render, the losses with val=True, the
-    val_ scalars and panels, train().  Nothing here waits for the device but the PNG writes.  --encoder_route holds for this pass alone:
-    the training forward records get_z under autograd, which the device route refuses, so train() keeps the torch encoder."""
+    val_ scalars and panels, train().  Nothing here waits for the device but the PNG writes.  --encoder_route holds for this pass alone
+    (device_train excepted, which the training forward runs too): the training forward records get_z under autograd, which the other
+    device routes refuse, so train() keeps the torch encoder for them."""
     import torch
     from cross_attention_renderer_amd import harness, summaries
     inp, gt, z = batch
@@ -134,7 +141,7 @@ def _validate(opt, model, batch, log, step, lpips_w):
                 log.add_scalar("val_" + name, value, step)
             summaries.img_summaries(model, inp, gt, {}, out, log, step, "val_", img_shape=(model.H, model.W), n_view=opt.views)
     finally:
-        model.encoder_route = "torch"
+        model.encoder_route = _train_route(opt)
         model.train()
 
 
@@ -148,7 +155,8 @@ def train(rank, opt):
     H, b, R = opt.img_sidelength, opt.batch_size, opt.query_sparsity
     real = bool(opt.data_root)                                    # the RealEstate10K reader; otherwise synthetic scenes, as before
     model = common.build_model(opt, dev, with_encoder=True if real else None).train()
-    model.encoder_route = "torch"                                 # the training forward's get_z is recorded by autograd; _validate applies --encoder_route
+    if model.encoder.__class__.__name__ != "EncoderNotBuilt":     # the training forward's get_z is recorded by autograd: torch, or the blocks'
+        model.encoder_route = _train_route(opt)                   # recorded device route; _validate applies the other values of --encoder_route
     params = [p for p in model.parameters() if p.requires_grad]
     if opt.gpus > 1:                                              # sync_model (train_realestate10k.py:60-62)
         for p in params:

@@ -9,8 +9,8 @@
  * and the token assembly (projection, class token, position and pose embeddings) — is on the device too, in car_trunk.h, which car_hip.h
  * includes behind this file.  What stands behind them — the read-out and re-assembly, the RefineNet fusion, conv_map and the image
  * normalisation — is on the device as well, in car_decoder.h, behind car_trunk.h; its car_getz is the whole of get_z in one call, so a host
- * without PyTorch has a route from two images to z (the relative pose and the checkpoint stay its own).  Inference only: no entry here has
- * a backward.
+ * without PyTorch has a route from two images to z (the relative pose and the checkpoint stay its own).  The entries of this file are forwards;
+ * the recorded forward of the blocks and their backward (LayerNorm, GELU, attention, the stage) are in car_encoder_train.h, behind car_decoder.h.
  *
  * Everything is channel-last fp32 rows.  Every status entry returns CAR_OK, CAR_E_ARG (nothing launched) or CAR_E_LAUNCH with a message in
  * car_last_error; a size entry returns 0, with a message, for a refused shape.

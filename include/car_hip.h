@@ -693,6 +693,10 @@ int car_essential_ransac(const double* x0, const double* x1, int N, const int* s
  * includes this file has it. */
 #include "car_decoder.h"
 
+/* ---- training through the encoder's transformer stage: the recorded forward and the backward of the 12 blocks (encoder.py vit_route =
+ * "device_train").  A block of its own, declared in a header of its own; every host that includes this file has it. */
+#include "car_encoder_train.h"
+
 /* host helper: linspace(a, b, n) the way torch's scalar CPU kernel computes it (models.py:261): step = (b-a)/(n-1), first half
  * a + step*i, second half b - step*(n-1-i); `out` is a HOST array.  Equal to torch.linspace for n < 16, within 1 ulp otherwise. */
 void car_linspace(float a, float b, int n, float* out);
