@@ -66,13 +66,25 @@ def attention_entropy(at_wt: Tensor, nan_rows_zero: bool = True) -> Tensor:
     return total / rows
 
 
+_jet_tables = {}
+
+
+def _jet_on(dev: torch.device) -> Tensor:
+    """The default table on ``dev``, uploaded once: an upload from pageable host memory makes torch wait for the stream, and img_summaries
+    promises that nothing of it waits for the device."""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _jet_tables:
+        _jet_tables[key] = _f32(harness.jet_lut()).to(dev)
+    return _jet_tables[key]
+
+
 def colormap(x: Tensor, scale: float = DEPTH_SCALE, lut: Optional[Tensor] = None) -> Tensor:
     """``x`` (N, H, W) -> (N, H, W, 3): matplotlib's colour-map call on ``x / scale`` with the 256-entry table ``lut`` (default: jet)."""
     dev = _on_device("colormap", x)
     if x.dim() != 3:
         raise ValueError(f"colormap: need an (N, H, W) map, got {tuple(x.shape)}")
     v = _f32(x)
-    table = _f32(harness.jet_lut() if lut is None else lut).to(dev)
+    table = _jet_on(dev) if lut is None else _f32(lut).to(dev)
     if tuple(table.shape) != (256, 3):
         raise ValueError(f"colormap: the table must be (256, 3), got {tuple(table.shape)}")
     N, H, W = v.shape
