@@ -106,6 +106,22 @@ CAR_INTERNAL void car_pack_absmax(hipStream_t st, int blocks, const float* W, in
 CAR_INTERNAL void car_pack_rows16(hipStream_t st, int blocks, const float* W, int ldw, const float* bias, int N, int K, int n_tiles, int ksteps,
                                   int chained, int kbase, car_pack_scale s, _Float16* out, bool hi_only = false);
 CAR_INTERNAL void car_pack_conv16(hipStream_t st, int blocks, const float* w, int K, int N, bool flip, car_pack_scale s, _Float16* out);
+// car_conv.hip: a packed 3x3 layer is car_conv3x3_tile_floats(K, N) floats of tiles — 9 K / 32 x N / 16 tiles of 512 floats, [K step][tile]
+// [hi | lo][lane][8 halves] with k = tap * K + channel — then 64 floats of scale (2^shift, 2^-shift, the largest magnitude, zeros) and, where
+// `bias` is given, its N floats behind them.  flip: the data gradient's weights, transposed and with the taps reversed.  K, N: the packed
+// matrix's inputs per tap and outputs.  who: the entry named in an error
+CAR_INTERNAL size_t car_conv3x3_tile_floats(int K, int N);
+CAR_INTERNAL int car_conv3x3_pack_tiles(const char* who, const float* w, const float* bias, int K, int N, bool flip, float* packed, hipStream_t st);
+// car_conv.hip: the launchers of the 3x3 sweep's three forms and of the 7x7 first layer; the callers have checked shapes and alignment.
+// car_conv3x3_lpips: M = n H W pixels, K -> N the SWEEP's widths (the data gradient's are the forward layer's exchanged; it has no bias and
+// takes act and add).  car_conv3x3_general and car_conv7x7: pt, pl the padding in front, Ho x Wo the output's extents; who names the
+// launch; epilogue chooses between the general form's two instances (false: no bias, residual or flag is read)
+CAR_INTERNAL int car_conv3x3_lpips(const float* X, const float* packed, const float* act, const float* add, float* Y, int H, int W, int K, int N, long M,
+                                   bool backward, hipStream_t st);
+CAR_INTERNAL int car_conv3x3_general(const char* who, bool epilogue, const float* X, int n, int H, int W, int K, int N, int stride, int pt, int pl, int Ho, int Wo,
+                                     const float* packed, const float* bias, const float* add, int flags, float* Y, hipStream_t st);
+CAR_INTERNAL int car_conv7x7(const char* who, const float* x, int n, int H, int W, int stride, int pt, int pl, int Ho, int Wo, const float* w,
+                             const float* bias, float* Y, hipStream_t st);
 CAR_INTERNAL void car_pack_tiles32(hipStream_t st, int blocks, const float* W, int ldw, const float* W2, int N, int K, int tiles, int chunks, int kgs,
                                    int chained, car_pack_scale s, _Float16* out);
 // car_lattice.hip: the common lattice of a pyramid's levels (only n_levels, level_h, level_w of d are read), and the merge onto it

@@ -5,20 +5,14 @@
 // sequence of these entries and car_linear_x3, and car_getz as the sequence normalise -> trunk -> tokens -> blocks -> decoder -> conv_map.
 // Inference only.  Activations are channel-last fp32 rows [n][H W][C].
 //
-// conv3x3_pad1_kernel is the one hot kernel here: the row sweep of car_row_sweep.h as an implicit GEMM over 9 K, with the K loop's skeleton
-// in its own frame as that file prescribes.  It is built the way car_trunk.hip's conv3x3_same_kernel is and differs from it in four places:
-// the padding in front is always 1, so the window's centre (stride oy, stride ox) is always inside the image; K = 768 is 24 K steps per tap,
-// no power of two, so the tap and the step within it are carried along instead of being shifted out of the step's number; the input may go
-// through a ReLU on load (the padding stays zeros: a tap outside the image is dropped by index behind the activation); and the epilogue
-// adds the bias and a residual and applies the output ReLU and the accumulation.  Compiled with the flags of the other units that include
-// the sweep (none).
+// The two dense convolutions are car_conv.hip's: the 3x3 one is conv3x3_kernel in its general form (car_conv3x3_general), the form the
+// trunk runs, here with a padding of 1 in front — so the window's centre (stride oy, stride ox) is always inside the image — and the bias,
+// residual, ReLU and accumulation of its epilogue; conv_map is conv7x7_kernel at stride 1 with a padding of 3 and a bias (car_conv7x7).
 #include "car_common.h"
 #include <math.h>
 #include <stdint.h>
 
 namespace {
-
-#include "car_row_sweep.h"
 
 constexpr long kMaxPixels = 1L << 27;              // n H W of the largest map of a call: keeps every row count, grid and per-image offset inside 32 bits
 constexpr int kMaxImages = 4096, kMaxGrid = 64;
@@ -35,146 +29,9 @@ bool image_shape_ok(int n, int H, int W, const char* who) {
     return true;
 }
 
-// ---- 3x3 convolution, stride 1 or 2, zero padding 1 --------------------------------------------------------------------------------------
-struct PadArgs {
-    const float* X;                        // [n, H, W, K]
-    const float* Wp; int tiles_total;      // [K step][tiles_total][512]: k = tap * K + channel
-    const float* down;                     // 2^-shift of the packed layer
-    const float* bias;                     // [N] or null
-    const float* add;                      // [n, Ho, Wo, N] or null
-    float* Y;                              // [n, Ho, Wo, N]
-    int H, W, Ho, Wo, stride;
-    int K, N, ksteps, chunks, flags;       // ksteps = K / 32 K steps per tap, chunks = 9 ksteps
-    long M, Min;                           // n Ho Wo output pixels, n H W input pixels
-};
-// One instance: column groups of four tiles (64 outputs), as car_trunk.hip's kernel has and for its reason.  The decoder's layers run
-// from 128 pixels (layer4_rn and act_postprocess4's strided layer at one pair) to 8192 (refinenet1's at one pair): a 256-wide layer is
-// four workgroups per block of 192 pixels, so the 8192-pixel layers are 172 workgroups and everything below under-fills 256 CUs whatever
-// the width of the group; a wider group would only leave more of the device idle.  No wider instance is built.
-constexpr int kPadTiles = 4;
-__global__ void __launch_bounds__(kThreads) conv3x3_pad1_kernel(const PadArgs a) {
-    constexpr int NT = kPadTiles;
-    extern __shared__ __attribute__((aligned(16))) float lds[];      // [2][NT][512]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int s = lane & 15, q4 = lane >> 4;
-    RowPlace pl;                                                       // one XCD per block of pixels: car_row_sweep.h
-    if (!place_rows<NT>(a.tiles_total, a.M, wave, s, pl)) return;
-    const long row = pl.row, lrow = pl.lrow;
-    const int tile0 = pl.tile0<NT>();
-    const int K = a.K;
-    const bool relu_in = (a.flags & CAR_LIN_RELU_IN) != 0;
-    // the output pixel, the input pixel under the window's centre (stride oy, stride ox: inside its image at padding 1), and which of the
-    // nine taps are inside
-    const int pix = (int)(lrow % ((long)a.Ho * a.Wo)), oy = pix / a.Wo, ox = pix % a.Wo;
-    const long img = lrow / ((long)a.Ho * a.Wo);
-    const int cy = oy * a.stride, cx = ox * a.stride;
-    unsigned inside = 0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-        if ((unsigned)(cy + t / 3 - 1) < (unsigned)a.H && (unsigned)(cx + t % 3 - 1) < (unsigned)a.W) inside |= 1u << t;
-    const float* xpix = a.X + ((img * a.H + cy) * a.W + cx) * K + 8 * q4;
-
-    {   // chunk 0 goes out now: what follows runs under the DMA
-        const NextChunk n0 = chunk_desc<NT>(a, tile0, lds, 0);
-#pragma unroll
-        for (int p = 0; p < pieces_of(NT); ++p) stream_issue_piece(n0, p, lane, wave);
-    }
-    // this lane's eight values of step kc of tap t: channels 32 kc + 8 q4 .. + 7 of input pixel (cy + t / 3 - 1, cx + t % 3 - 1).  issue_x only
-    // issues the loads — from the centre pixel when the tap is outside, a valid address whose values are dropped; finish_x turns them into
-    // values when they are consumed (car_row_sweep.h): the ReLU first, then the tap's index, so the padding is zeros whatever was loaded
-    auto issue_x = [&](int t, int kc, float4 (&raw)[2]) {
-        const long off = ((long)(t / 3 - 1) * a.W + (t % 3 - 1)) * K;              // W K may pass 2^31 in a wide image
-        const float* src = xpix + (((inside >> t) & 1u) ? off : 0) + 32 * kc;
-        CAR_BOUNDS_TRAP(src >= a.X && src + 8 <= a.X + a.Min * K);
-        raw[0] = *reinterpret_cast<const float4*>(src);
-        raw[1] = *reinterpret_cast<const float4*>(src + 4);
-    };
-    auto finish_x = [&](int t, const float4 (&raw)[2], float (&x)[8]) {
-        const bool in = ((inside >> t) & 1u) != 0;
-        const float e[8] = {raw[0].x, raw[0].y, raw[0].z, raw[0].w, raw[1].x, raw[1].y, raw[1].z, raw[1].w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = in ? (relu_in ? fmaxf(e[i], 0.0f) : e[i]) : 0.0f;
-    };
-    const float dW = a.down[0];
-    float xc[8];
-    {
-        float4 raw[2];
-        issue_x(0, 0, raw);
-        finish_x(0, raw, xc);
-    }
-    float mrun = fmaxf(row_max(xc), 1e-30f), p, pinv;
-    pow2_scale<kPow2Lo>(mrun, p, pinv);
-
-    f32x4 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    half8 bhi, blo;
-    split8(xc, p, bhi, blo);
-    stream_sync();                                                     // weight chunk 0 landed
-
-    // the sweep's skeleton (car_row_sweep.h); (tap, kc) = the tap and the step within it of the K step whose values are in bhi / blo
-    int tap = 0, kc = 0;
-#pragma unroll 1
-    for (int c = 0; c < a.chunks; ++c) {
-        const float* wl = lds + (c & 1) * NT * kTile + 4 * lane;
-        const NextChunk nx = chunk_desc<NT>(a, tile0, lds, c + 1);
-        if (c + 1 < a.chunks && ++kc == a.ksteps) { kc = 0; ++tap; }   // the next K step (the last one once more behind the end)
-        float4 rawn[2];
-        issue_x(tap, kc, rawn);                                        // its values: in flight under this step's MFMAs
-#pragma unroll
-        for (int qs = 0; qs < NT / 2; ++qs) {
-            const float* w0 = wl + (2 * qs * 2) * 256;
-            mfma_pair(acc[2 * qs], acc[2 * qs + 1], w0, w0 + 512, bhi, blo);
-            issue_next_piece<NT>(nx, qs, c + 1 < a.chunks, lane, wave);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // the next K step may outgrow the row's power of two: move the row (accumulators and scale) to the smaller one, exactly
-        float xn[8];
-        finish_x(tap, rawn, xn);
-        const float mn = row_max(xn);
-        if (__builtin_amdgcn_ballot_w64(mn > mrun) != 0) {
-            float pn, pninv;
-            mrun = fmaxf(mrun, mn);
-            pow2_scale<kPow2Lo>(mrun, pn, pninv);
-            scale_acc<NT>(acc, pn * pinv);
-            p = pn; pinv = pninv;
-        }
-        split8(xn, p, bhi, blo);
-        stream_sync();
-    }
-    if (row >= a.M) return;
-    // the epilogue: ((sum + bias) + add), the ReLU (a NaN stays a NaN, as F.relu leaves it), then + Y
-    const bool relu_out = (a.flags & CAR_LIN_RELU_OUT) != 0, accum = (a.flags & CAR_LIN_ACCUM) != 0;
-    const long at = row * a.N + 16 * tile0 + 4 * q4;
-    scale_acc<NT>(acc, dW * pinv);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        float4 v = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
-        if (a.bias) {
-            CAR_BOUNDS_TRAP(16 * (tile0 + t) + 4 * q4 + 4 <= a.N);
-            const float4 b = *reinterpret_cast<const float4*>(a.bias + 16 * (tile0 + t) + 4 * q4);
-            v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-        }
-        CAR_BOUNDS_TRAP(at + 16 * t + 4 <= a.M * a.N);
-        if (a.add) {
-            const float4 d = *reinterpret_cast<const float4*>(a.add + at + 16 * t);
-            v.x += d.x; v.y += d.y; v.z += d.z; v.w += d.w;
-        }
-        if (relu_out) { v.x = v.x < 0.0f ? 0.0f : v.x; v.y = v.y < 0.0f ? 0.0f : v.y; v.z = v.z < 0.0f ? 0.0f : v.z; v.w = v.w < 0.0f ? 0.0f : v.w; }
-        float4* dst = reinterpret_cast<float4*>(a.Y + at + 16 * t);
-        if (accum) { const float4 o = *dst; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-        *dst = v;
-    }
-}
-int launch_pad1(const PadArgs& a, hipStream_t st) {
-    const size_t lds_bytes = (size_t)2 * kPadTiles * kTile * sizeof(float);
-    CAR_LAUNCH_LDS("car_conv3x3_pad1", conv3x3_pad1_kernel, dim3(sweep_grid(a.M, a.tiles_total / kPadTiles)), dim3(kThreads), lds_bytes, st, a);
-    return CAR_OK;
-}
+// ---- the 3x3 convolution with zero padding 1 (car_conv.hip) ---------------------------------------------------------------------------------
 bool pad1_widths_ok(int K, int N) { return (K == 256 || K == 512 || K == 768) && (N == 256 || N == 768); }
-size_t pad1_tile_floats(int K, int N) { return (size_t)(9 * K / 32) * (N / 16) * kTile; }
-size_t pad1_floats(int K, int N) { return pad1_tile_floats(K, N) + 64; }
+size_t pad1_floats(int K, int N) { return car_conv3x3_tile_floats(K, N) + 64; }
 
 // ---- bilinear 2x upsampling, align_corners = True -------------------------------------------------------------------------------------------
 // output o of an extent E reads source coordinate o (E - 1) / (2 E - 1), taken exactly: i0 = o (E - 1) div (2 E - 1), the fraction
@@ -239,45 +96,6 @@ bool readout_shape_ok(int BV, int P, int dim, const char* who) {
     if (BV < 1 || BV > kMaxImages || P < 1 || P > kMaxGrid * kMaxGrid) { car_set_error("%s: %d views of %d patches, need 1..%d views of 1..%d patches", who, BV, P, kMaxImages, kMaxGrid * kMaxGrid); return false; }
     if (!readout_dim_ok(dim)) { car_set_error("%s: dim = %d must be a multiple of 32 in 64..1024", who, dim); return false; }
     return true;
-}
-
-// ---- conv_map: 3 -> 64, 7x7, stride 1, zero padding 3, fp32 on the vector pipe ---------------------------------------------------------------
-// car_stem7x7's frame: a wave = the 64 output channels of one pixel at a time (the pixel is wave-uniform: its inputs are scalar loads), 8
-// pixels per wave; lane n keeps channel n's 147 weights.  The accumulator starts at the bias; the terms are added in the order (channel,
-// row, column) of the window by fmaf; a tap in the padding adds nothing.
-constexpr int kMapPix = 8, kMapTerms = 147;
-__global__ void __launch_bounds__(256) conv7x7_kernel(const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ bias,
-                                                      float* __restrict__ Y, int H, int W, long M) {
-    const int n = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float w[kMapTerms];
-#pragma unroll
-    for (int k = 0; k < kMapTerms; ++k) w[k] = Wt[n * kMapTerms + k];
-    const float b = bias[n];
-    const long p0 = ((long)blockIdx.x * 4 + wave) * kMapPix;
-    for (int i = 0; i < kMapPix; ++i) {
-        const long p = p0 + i;
-        if (p >= M) return;
-        const int pix = (int)(p % ((long)H * W)), oy = pix / W, ox = pix % W;
-        const float* img = X + (p / ((long)H * W)) * 3 * H * W;
-        float acc = b;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int ky = 0; ky < 7; ++ky) {
-                const int iy = oy + ky - 3;
-                if ((unsigned)iy >= (unsigned)H) continue;
-#pragma unroll
-                for (int kx = 0; kx < 7; ++kx) {
-                    const int ix = ox + kx - 3;
-                    if ((unsigned)ix < (unsigned)W) {
-                        CAR_BOUNDS_TRAP(img + ((long)c * H + iy) * W + ix < X + M * 3);
-                        acc = fmaf(img[((long)c * H + iy) * W + ix], w[(c * 7 + ky) * 7 + kx], acc);
-                    }
-                }
-            }
-        Y[p * 64 + n] = acc;
-    }
 }
 
 // ---- the image normalisation of get_z: ((v + 1) / 2 - mean_c) / std_c, its operations in its order, nothing contracted -------------------------
@@ -397,15 +215,7 @@ extern "C" int car_conv3x3_pad1_pack(const float* w, int K, int N, float* packed
     CAR_REQUIRE(w && packed, "car_conv3x3_pad1_pack: null pointer");
     CAR_REQUIRE(pad1_widths_ok(K, N), "car_conv3x3_pad1_pack: %d -> %d channels, need K among 256, 512, 768 and N among 256, 768", K, N);
     CAR_REQUIRE(aligned16(w) && aligned16(packed), "car_conv3x3_pad1_pack: w and packed must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    float* scale = packed + pad1_tile_floats(K, N);
-    (void)hipGetLastError();
-    CAR_CHECK_HIP(hipMemsetAsync(scale, 0, 64 * sizeof(float), st), "car_conv3x3_pad1_pack: memset failed");
-    const car_pack_scale s{scale + 2, scale, scale + 1};
-    car_pack_absmax(st, 64, w, 9 * K * N, nullptr, nullptr, 1, 9 * K * N, s);
-    car_pack_conv16(st, 512, w, K, N, false, s, reinterpret_cast<_Float16*>(packed));
-    CAR_CHECK_LAUNCH("car_conv3x3_pad1_pack");
-    return CAR_OK;
+    return car_conv3x3_pack_tiles("car_conv3x3_pad1_pack", w, nullptr, K, N, false, packed, (hipStream_t)stream);
 }
 
 extern "C" int car_conv3x3_pad1(const float* X, int n, int H, int W, int K, int N, int stride, const float* packed, const float* bias, const float* add,
@@ -417,12 +227,8 @@ extern "C" int car_conv3x3_pad1(const float* X, int n, int H, int W, int K, int 
     if (!image_shape_ok(n, H, W, "car_conv3x3_pad1")) return CAR_E_ARG;
     CAR_REQUIRE(aligned16(X) && aligned16(packed) && aligned16(bias) && aligned16(add) && aligned16(Y),
                 "car_conv3x3_pad1: X, packed, bias, add and Y must be 16-byte aligned");
-    PadArgs a;
-    a.X = X; a.Wp = packed; a.tiles_total = N / 16; a.down = packed + pad1_tile_floats(K, N) + 1; a.bias = bias; a.add = add; a.Y = Y;
-    a.H = H; a.W = W; a.Ho = pad1_out(H, stride); a.Wo = pad1_out(W, stride); a.stride = stride;
-    a.K = K; a.N = N; a.ksteps = K / 32; a.chunks = 9 * a.ksteps; a.flags = flags;
-    a.M = (long)n * a.Ho * a.Wo; a.Min = (long)n * H * W;
-    return launch_pad1(a, (hipStream_t)stream);
+    return car_conv3x3_general("car_conv3x3_pad1", true, X, n, H, W, K, N, stride, 1, 1, pad1_out(H, stride), pad1_out(W, stride), packed, bias, add, flags, Y,
+                               (hipStream_t)stream);
 }
 
 extern "C" int car_upsample2x_bilinear(const float* X, int n, int H, int W, int C, float* Y, void* stream) {
@@ -481,11 +287,7 @@ extern "C" int car_conv7x7_pad3(const float* x, int n, int H, int W, const float
     CAR_REQUIRE(x && w && bias && Y, "car_conv7x7_pad3: null pointer");
     if (!image_shape_ok(n, H, W, "car_conv7x7_pad3")) return CAR_E_ARG;
     CAR_REQUIRE(aligned16(x) && aligned16(w) && aligned16(bias) && aligned16(Y), "car_conv7x7_pad3: x, w, bias and Y must be 16-byte aligned");
-    const long M = (long)n * H * W;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(conv7x7_kernel, dim3(car_div_up(M, 4 * kMapPix)), dim3(256), 0, (hipStream_t)stream, x, w, bias, Y, H, W, M);
-    CAR_CHECK_LAUNCH("car_conv7x7_pad3");
-    return CAR_OK;
+    return car_conv7x7("car_conv7x7_pad3", x, n, H, W, 1, 3, 3, H, W, w, bias, Y, (hipStream_t)stream);
 }
 
 extern "C" int car_normalize_rgb(const float* rgb, int n, int H, int W, float* x, void* stream) {

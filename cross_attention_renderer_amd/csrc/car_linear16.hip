@@ -2,7 +2,7 @@
 // The staged route (constructor variants, training forward, the backward's data gradients: reference models.py:333-341, 487-491, 529,
 // 548, 553) spends most of its time in 576 -> 576 / 288 / 128 layers over every epipolar sample; car_linear runs them on the fp32 matrix
 // pipe (157 TFLOP/s peak).  This kernel is the row sweep of car_row_sweep.h (the fused per-sample kernel's tile machinery, car_mma_tile.h,
-// fed one K step of a row at a time; shared with car_lpips.hip's convolution) with the B operands read from the rows of X, or MADE
+// fed one K step of a row at a time; shared with car_conv.hip's convolution) with the B operands read from the rows of X, or MADE
 // from the merged lattice (GATHER), and the KQ instance's tail behind it: split-fp16 operands, fp32 accumulation (fp32-class accuracy,
 // 2500 / 3 TFLOP/s peak).  NT = 18: 288 columns, 72 accumulator registers; wider layers run as column groups.
 #include "car_common.h"

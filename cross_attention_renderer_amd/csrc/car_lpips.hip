@@ -6,12 +6,8 @@
 // each, 2x2 max-pool in front of blocks 2-5), and at the five taps relu1_2 .. relu5_3 the channel-normalised squared difference of the two
 // images' features, weighted by a 1x1 layer, averaged over the tap's pixels and summed over the taps.  Weights come from the caller.
 //
-// conv3x3_kernel is the row sweep it shares with car_linear16.hip (car_row_sweep.h: split-fp16 operands, three v_mfma_f32_16x16x32_f16
-// products per term, fp32 accumulation, weight chunks streamed L2 -> LDS by LDS-DMA) run as an implicit GEMM over 9 K in ONE sweep: a row
-// of the A operand is an output pixel, K step c reads 32 channels of tap c / (K / 32) — the pixel's own address plus one of nine offsets —
-// and a tap outside the image contributes zeros.  The row's power of two follows the largest magnitude seen so far along the 9 K values:
-// the sweep's rule.  A row's result depends on its own nine pixels and the weights only, never on its neighbours in the launch: an
-// image gives the same bits wherever it sits in the batch, which is what makes LPIPS of two identical images exactly 0.
+// The 12 convolutions with K >= 64 and their data gradients are car_conv.hip's conv3x3_kernel in its two LPIPS forms (the row sweep of
+// car_row_sweep.h as an implicit GEMM over 9 K), packed by its packer: this unit calls car_conv3x3_lpips and car_conv3x3_pack_tiles.
 // The first layer (K = 3) is a plain fp32 vector kernel with the scaling layer folded in: the weights carry 1 / scale at pack time and
 // the shift is subtracted from a pixel as it is loaded, so a padded tap stays the exact zero of the scaled image's padding.
 // The max-pool is a kernel of its own (profiles/lpips.md).  The head runs in fp64 with every sum in a fixed order.
@@ -20,8 +16,6 @@
 #include <stdint.h>
 
 namespace {
-
-#include "car_row_sweep.h"
 
 // ---- the network ---------------------------------------------------------------------------------------------------------------------
 constexpr int kLayers = 13, kTaps = 5;
@@ -34,154 +28,6 @@ constexpr int kFirstFloats = 27 * 64 + 64;         // first layer: [tap * 3 + ch
 #define CAR_LPIPS_SHIFT {-0.030f, -0.088f, -0.188f}       // the scaling layer: (v - shift) / scale per channel
 #define CAR_LPIPS_SCALE {0.458, 0.448, 0.450}
 constexpr long kMaxPixels = 1L << 27;              // 2 B H W: keeps every row count, grid and per-image offset far inside 32 bits
-
-// ---- 3x3 convolution, K >= 64 ------------------------------------------------------------------------------------------------------
-struct ConvArgs {
-    const float* X;                        // [n, H, W, K]
-    const float* Wp; int tiles_total;      // [K step][tiles_total][512]: k = tap * K + channel
-    const float* bias;                     // N floats (forward only)
-    const float* down;                     // 2^-shift of the packed layer
-    float* Y;                              // [n, H, W, N]
-    const float* act;                      // data gradient only: [n, H, W, N] forward activation whose sign masks Y, or nullptr
-    const float* add;                      // data gradient only: [n, H, W, N] added in front of the mask, or nullptr
-    int H, W, K, N, lgk, chunks;           // lgk = log2(K / 32)
-    long M;                                // n H W output pixels
-};
-
-// A gradient row's power of two: pow2_scale with the exponent clamped far lower (car_split.h kPow2LoWide).
-// When a later K step raises the row's maximum, the accumulators move by pn * pinv, a power of two as small as 2^-190: what was summed so
-// far may then lose low bits or flush to 0.  It is below 2^-150 of the row's new scale, so the accuracy bound is untouched, but "a
-// cotangent scaled by 2^k scales every entry exactly" holds only while no row's magnitude crosses the clamp span inside one sweep.
-// BWD: the data gradient of the same convolution.  The same sweep over weights packed transposed and flipped
-// (car_pack.hip ConvSource), no bias, a row's power of two from pow2_scale<kPow2LoWide>, and the epilogue Y = (sum + add) * (act > 0) in the place of
-// bias + ReLU.  The forward instance's arithmetic is untouched by the parameter.
-template <int NT, bool BWD>
-__global__ void __launch_bounds__(kThreads) conv3x3_kernel(const ConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];      // [2][NT][512]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int s = lane & 15, q4 = lane >> 4;
-    RowPlace pl;                                                       // one XCD per block of pixels: car_row_sweep.h
-    if (!place_rows<NT>(a.tiles_total, a.M, wave, s, pl)) return;
-    const long row = pl.row, lrow = pl.lrow;
-    const int tile0 = pl.tile0<NT>();
-    const int K = a.K;
-    // the pixel, and which of its nine taps lie inside its image
-    const int pix = (int)(lrow % ((long)a.H * a.W)), py = pix / a.W, px = pix % a.W;
-    unsigned inside = 0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-        if ((unsigned)(py + t / 3 - 1) < (unsigned)a.H && (unsigned)(px + t % 3 - 1) < (unsigned)a.W) inside |= 1u << t;
-    const float* xpix = a.X + lrow * K + 8 * q4;
-
-    {   // chunk 0 goes out now: what follows runs under the DMA
-        const NextChunk n0 = chunk_desc<NT>(a, tile0, lds, 0);
-#pragma unroll
-        for (int p = 0; p < pieces_of(NT); ++p) stream_issue_piece(n0, p, lane, wave);
-    }
-    // this lane's eight values of K step c: tap t = c >> lgk, channels 32 (c & (K / 32 - 1)) + 8 q4 .. + 7 of pixel (py + t / 3 - 1,
-    // px + t % 3 - 1).  issue_x only issues the loads — from the pixel itself when the tap is outside, a valid address whose values are
-    // dropped; finish_x turns them into values when they are consumed (car_row_sweep.h)
-    auto tap_of = [&](int c) { return c >> a.lgk; };
-    auto issue_x = [&](int c, float4 (&raw)[2]) {
-        const int t = tap_of(c), kc = c & ((1 << a.lgk) - 1);
-        const int off = ((t / 3 - 1) * a.W + (t % 3 - 1)) * K;
-        const float* src = xpix + (((inside >> t) & 1u) ? off : 0) + 32 * kc;
-        CAR_BOUNDS_TRAP(src >= a.X && src + 8 <= a.X + a.M * K);
-        raw[0] = *reinterpret_cast<const float4*>(src);
-        raw[1] = *reinterpret_cast<const float4*>(src + 4);
-    };
-    auto finish_x = [&](int c, const float4 (&raw)[2], float (&x)[8]) {
-        const bool in = ((inside >> tap_of(c)) & 1u) != 0;
-        const float e[8] = {raw[0].x, raw[0].y, raw[0].z, raw[0].w, raw[1].x, raw[1].y, raw[1].z, raw[1].w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = in ? e[i] : 0.0f;
-    };
-    const float dW = a.down[0];
-    float xc[8];
-    {
-        float4 raw[2];
-        issue_x(0, raw);
-        finish_x(0, raw, xc);
-    }
-    float mrun = fmaxf(row_max(xc), 1e-30f), p, pinv;
-    pow2_scale<BWD ? kPow2LoWide : kPow2Lo>(mrun, p, pinv);
-
-    f32x4 acc[NT];
-    if constexpr (BWD) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    } else init_bias<NT>(acc, a.bias + 16 * tile0, q4, p / dW);
-    half8 bhi, blo;
-    split8(xc, p, bhi, blo);
-    stream_sync();                                                     // weight chunk 0 landed
-
-    // the sweep's skeleton (car_row_sweep.h)
-#pragma unroll 1
-    for (int c = 0; c < a.chunks; ++c) {
-        const float* wl = lds + (c & 1) * NT * kTile + 4 * lane;
-        const NextChunk nx = chunk_desc<NT>(a, tile0, lds, c + 1);
-        const int cn = c + 1 < a.chunks ? c + 1 : c;
-        float4 rawn[2];
-        issue_x(cn, rawn);                                             // next K step's values: in flight under this step's MFMAs
-#pragma unroll
-        for (int qs = 0; qs < NT / 2; ++qs) {
-            const float* w0 = wl + (2 * qs * 2) * 256;
-            mfma_pair(acc[2 * qs], acc[2 * qs + 1], w0, w0 + 512, bhi, blo);
-            issue_next_piece<NT>(nx, qs, c + 1 < a.chunks, lane, wave);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // the next K step may outgrow the row's power of two: move the row (accumulators and scale) to the smaller one, exactly
-        float xn[8];
-        finish_x(cn, rawn, xn);
-        const float mn = row_max(xn);
-        if (__builtin_amdgcn_ballot_w64(mn > mrun) != 0) {
-            float pn, pninv;
-            mrun = fmaxf(mrun, mn);
-            pow2_scale<BWD ? kPow2LoWide : kPow2Lo>(mrun, pn, pninv);
-            scale_acc<NT>(acc, pn * pinv);
-            p = pn; pinv = pninv;
-        }
-        split8(xn, p, bhi, blo);
-        stream_sync();
-    }
-    if (row >= a.M) return;
-    float* yrow = a.Y + row * a.N + 16 * tile0 + 4 * q4;
-    if constexpr (BWD) {
-        scale_acc<NT>(acc, dW);                                        // two steps: dW * pinv may lie below fp32's normal range
-        scale_acc<NT>(acc, pinv);
-        const long at = row * a.N + 16 * tile0 + 4 * q4;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            float4 v = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
-            if (a.add) {
-                CAR_BOUNDS_TRAP(at + 16 * t + 4 <= a.M * a.N);
-                const float4 d = *reinterpret_cast<const float4*>(a.add + at + 16 * t);
-                v.x += d.x; v.y += d.y; v.z += d.z; v.w += d.w;
-            }
-            if (a.act) {
-                CAR_BOUNDS_TRAP(at + 16 * t + 4 <= a.M * a.N);
-                v = keep_where_positive(v, *reinterpret_cast<const float4*>(a.act + at + 16 * t));
-            }
-            *reinterpret_cast<float4*>(yrow + 16 * t) = v;
-        }
-    } else {
-        scale_acc<NT>(acc, dW * pinv);
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-            *reinterpret_cast<float4*>(yrow + 16 * t) =
-                make_float4(fmaxf(acc[t][0], 0.0f), fmaxf(acc[t][1], 0.0f), fmaxf(acc[t][2], 0.0f), fmaxf(acc[t][3], 0.0f));
-    }
-}
-
-template <int NT, bool BWD = false>
-int launch_conv(const ConvArgs& a, hipStream_t st) {
-    const size_t lds_bytes = (size_t)2 * NT * kTile * sizeof(float);
-    const int groups = a.tiles_total / NT;
-    CAR_LAUNCH_LDS(BWD ? "car_conv3x3_backward" : "car_conv3x3", (conv3x3_kernel<NT, BWD>),
-                   dim3(sweep_grid(a.M, groups)), dim3(kThreads), lds_bytes, st, a);
-    return CAR_OK;
-}
 
 // ---- first layer: 3 -> 64, fp32, scaling layer folded in ---------------------------------------------------------------------------
 // a wave = 64 output channels of one pixel at a time (the pixel is wave-uniform: its 27 inputs are scalar loads), 16 pixels per wave
@@ -230,23 +76,7 @@ __global__ void __launch_bounds__(256) maxpool_kernel(const float* __restrict__ 
     }
 }
 
-// ---- packing -------------------------------------------------------------------------------------------------------------------------
-// A layer's tiles, 64 floats of scale (2^shift, 2^-shift, the largest magnitude, zeros) and, forward only, its bias: car_linear16.hip's
-// tiles [K step][tile][hi | lo][lane][8 halves] with k = tap * K + channel, written by car_pack.hip's 16-wide writer (ConvSource).
-// flip: the data gradient's weights, transposed and with the taps reversed.  K, N: the packed matrix's inputs per tap and outputs.
-int pack_conv(const float* w, const float* bias, int K, int N, bool flip, float* packed, hipStream_t st, const char* who) {
-    float* scale = packed + (size_t)9 * K * N;
-    if (hipMemsetAsync(scale, 0, 64 * sizeof(float), st) != hipSuccess) { car_set_error("%s: memset failed", who); return CAR_E_LAUNCH; }
-    const car_pack_scale s{scale + 2, scale, scale + 1};
-    car_pack_absmax(st, 64, w, 9 * K * N, nullptr, nullptr, 1, 9 * K * N, s);
-    car_pack_conv16(st, 512, w, K, N, flip, s, reinterpret_cast<_Float16*>(packed));
-    if (bias && hipMemcpyAsync(scale + 64, bias, sizeof(float) * N, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        car_set_error("%s: bias copy failed", who);
-        return CAR_E_LAUNCH;
-    }
-    CAR_CHECK_LAUNCH(who);
-    return CAR_OK;
-}
+// ---- packing the first layer (the other layers: car_conv3x3_pack_tiles) -------------------------------------------------------------
 __global__ void first_pack_kernel(const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ out) {
     constexpr double kScale[3] = CAR_LPIPS_SCALE;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -328,7 +158,6 @@ int head_blocks(int H, int W) {
     for (int k = 0; k < kTaps; ++k) n += ((H >> k) * (W >> k) + kHeadPix - 1) / kHeadPix;
     return n;
 }
-size_t conv_tile_floats(int K, int N) { return (size_t)(9 * K / 32) * (N / 16) * kTile; }
 bool conv_shape_ok(int K, int N) {
     return (K == 3 && N == 64) || ((K == 64 || K == 128 || K == 256 || K == 512) && (N == 64 || N == 128 || N == 256 || N == 512));
 }
@@ -399,15 +228,7 @@ int conv(const float* X, int n, int H, int W, int K, int N, const float* packed,
         CAR_CHECK_LAUNCH("car_conv3x3");
         return CAR_OK;
     }
-    ConvArgs a;
-    a.X = X; a.Wp = packed; a.tiles_total = N / 16;
-    a.down = packed + conv_tile_floats(K, N) + 1;
-    a.bias = packed + conv_tile_floats(K, N) + 64;
-    a.Y = Y; a.H = H; a.W = W; a.K = K; a.N = N; a.chunks = 9 * K / 32; a.M = M;
-    a.lgk = K == 64 ? 1 : K == 128 ? 2 : K == 256 ? 3 : 4;
-    if (N == 64) return launch_conv<4>(a, st);
-    if (N == 128) return launch_conv<8>(a, st);
-    return launch_conv<16>(a, st);
+    return car_conv3x3_lpips(X, packed, nullptr, nullptr, Y, H, W, K, N, M, false, st);
 }
 
 int pool(const float* X, int n, int H, int W, int C, float* Y, hipStream_t st) {
@@ -588,16 +409,7 @@ int conv_backward(const float* D, int n, int H, int W, int K, int N, const float
         CAR_CHECK_LAUNCH("car_conv3x3_backward");
         return CAR_OK;
     }
-    ConvArgs a;
-    a.X = D; a.Wp = packed; a.tiles_total = K / 16;
-    a.down = packed + conv_tile_floats(N, K) + 1;
-    a.bias = nullptr;
-    a.Y = out; a.act = act; a.add = add;
-    a.H = H; a.W = W; a.K = N; a.N = K; a.chunks = 9 * N / 32; a.M = M;
-    a.lgk = N == 64 ? 1 : N == 128 ? 2 : N == 256 ? 3 : 4;
-    if (K == 64) return launch_conv<4, true>(a, st);
-    if (K == 128) return launch_conv<8, true>(a, st);
-    return launch_conv<16, true>(a, st);
+    return car_conv3x3_lpips(D, packed, act, add, out, H, W, N, K, M, true, st);      // the sweep runs N -> K
 }
 int pool_backward(const float* T, const float* act, const float* add, int n, int H, int W, int C, float* out, hipStream_t st) {
     const long total = (long)n * H * W * (C / 4);
@@ -644,7 +456,7 @@ constexpr int kTapLayer[kTaps] = {1, 3, 6, 9, 12};
 // otherwise 9 K / 32 x N / 16 tiles of 512 floats, 64 floats of scale, the bias.  0 for a shape car_conv3x3 refuses.
 extern "C" size_t car_conv3x3_packed_floats(int K, int N) {
     if (!conv_shape_ok(K, N)) return 0;
-    return K == 3 ? (size_t)kFirstFloats : conv_tile_floats(K, N) + 64 + (size_t)N;
+    return K == 3 ? (size_t)kFirstFloats : car_conv3x3_tile_floats(K, N) + 64 + (size_t)N;
 }
 
 extern "C" int car_conv3x3_pack(const float* w, const float* bias, int K, int N, float* packed, void* stream) {
@@ -658,7 +470,7 @@ extern "C" int car_conv3x3_pack(const float* w, const float* bias, int K, int N,
         CAR_CHECK_LAUNCH("car_conv3x3_pack");
         return CAR_OK;
     }
-    return pack_conv(w, bias, K, N, false, packed, st, "car_conv3x3_pack");
+    return car_conv3x3_pack_tiles("car_conv3x3_pack", w, bias, K, N, false, packed, st);
 }
 
 extern "C" int car_conv3x3(const float* X, int n, int H, int W, int K, int N, const float* packed, float* Y, void* stream) {
@@ -755,16 +567,14 @@ extern "C" int car_lpips(const float* x, const float* y, int B, int H, int W, co
 // K, N are the FORWARD layer's channel counts throughout.  The data gradient's weights: 9 N / 32 x K / 16 tiles and 64 floats of scale;
 // 0 for a refused shape and for the first layer, whose data gradient reads car_conv3x3_pack's array.
 extern "C" size_t car_conv3x3_backward_packed_floats(int K, int N) {
-    return conv_backward_shape_ok(K, N) ? conv_tile_floats(N, K) + 64 : 0;
+    return conv_backward_shape_ok(K, N) ? car_conv3x3_tile_floats(N, K) + 64 : 0;
 }
 
 extern "C" int car_conv3x3_backward_pack(const float* w, int K, int N, float* packed, void* stream) {
     CAR_REQUIRE(w && packed, "car_conv3x3_backward_pack: null pointer");
     CAR_REQUIRE(conv_backward_shape_ok(K, N), "car_conv3x3_backward_pack: %d -> %d channels, need K and N among 64, 128, 256, 512", K, N);
     CAR_REQUIRE(aligned16(packed), "car_conv3x3_backward_pack: packed must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    (void)hipGetLastError();
-    return pack_conv(w, nullptr, N, K, true, packed, st, "car_conv3x3_backward_pack");
+    return car_conv3x3_pack_tiles("car_conv3x3_backward_pack", w, nullptr, N, K, true, packed, (hipStream_t)stream);
 }
 
 extern "C" int car_conv3x3_backward(const float* D, int n, int H, int W, int K, int N, const float* packed, const float* act, const float* add,

@@ -1,7 +1,7 @@
 // car_mma_tile.h — the v_mfma_f32_16x16x32_f16 tile pieces that need no chunk table: the vector types, one LDS-DMA piece of a weight
 // chunk and the chunk barrier, the split-fp16 / fp16 B operands, the MFMA pair and the accumulator helpers.  The fused per-sample kernel
 // takes them through car_fused_mma.h (which adds its chunk table and the chained layers), the row sweep of car_linear16.hip and
-// car_lpips.hip through car_row_sweep.h.
+// car_conv.hip through car_row_sweep.h.
 // Included INSIDE the kernel file's anonymous namespace, after it has defined kWaves (waves per workgroup = DMA participants).
 //
 // Split-fp16 arithmetic: x = hi + lo with fp16 halves, three products per term (hi*hi + hi*lo + lo*hi, fp32 accumulate; the

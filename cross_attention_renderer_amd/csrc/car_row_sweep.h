@@ -1,6 +1,7 @@
-// car_row_sweep.h — the row-streamed split-fp16 sweep of linear16_kernel (car_linear16.hip) and conv3x3_kernel (car_lpips.hip):
-// Y = X W^T over rows that arrive one 32-wide K step at a time.  Both operands as fp16 hi / lo halves, three v_mfma_f32_16x16x32_f16
-// products per term, fp32 accumulation (car_mma_tile.h); the layer's weights carry a power of two chosen at pack time, every row a power
+// car_row_sweep.h — the row-streamed split-fp16 sweep of linear16_kernel (car_linear16.hip) and conv3x3_kernel (car_conv.hip: the 3x3
+// convolutions of LPIPS, of the encoder's trunk and of its decoder): Y = X W^T over rows that arrive one 32-wide K step at a time.
+// Both operands as fp16 hi / lo halves, three v_mfma_f32_16x16x32_f16 products per term, fp32 accumulation (car_mma_tile.h); the
+// layer's weights carry a power of two chosen at pack time, every row a power
 // of two that follows the largest magnitude seen so far along the row (when a later K step outgrows it, the row's accumulators are
 // moved to the new power of two — an exact multiplication — so a row is read once, not twice), both undone exactly by the caller.
 // A workgroup = 12 waves x 16 rows; a wave keeps NT tiles of 16 outputs (wider layers run as column groups of NT tiles); the weight
@@ -9,9 +10,10 @@
 // may fall.  What is stated here are the sweep's PIECES; the K loop's dozen lines that call them stand in each kernel's own frame (the
 // skeleton at the end of this file).  A loop that lived in a function of its own here was optimised before it was inlined and came out
 // scheduled differently, 1 - 2 % slower in some instances (profiles/row_sweep.md); with the skeleton in the kernel the convolution's six
-// instances and linear16_kernel's four plain ones compile to the very instructions they had when each unit carried the whole text.
-// This arithmetic is shared between exactly these two units and relies on their being compiled with the same flags (no extra flags in
-// __graft_entry__.UNITS): a unit that contracted or vectorised differently would no longer give the other's bits.
+// LPIPS instances and linear16_kernel's four plain ones compile to the very instructions they had when each unit carried the whole text
+// (profiles/conv_once.md: the convolution's skeleton stands once, what its callers differ in comes from a compile-time form).
+// This arithmetic is shared between exactly these two units — the only includers — and relies on their being compiled with the same flags
+// (no extra flags in __graft_entry__.UNITS): a unit that contracted or vectorised differently would no longer give the other's bits.
 // Included INSIDE the unit's anonymous namespace, like car_fused_mma.h.
 #pragma once
 
@@ -85,7 +87,8 @@ __device__ __forceinline__ float4 keep_where_positive(const float4& v, const flo
     return make_float4(act.x > 0.0f ? v.x : 0.0f, act.y > 0.0f ? v.y : 0.0f, act.z > 0.0f ? v.z : 0.0f, act.w > 0.0f ? v.w : 0.0f);
 }
 
-// ---- the sweep's skeleton, as both kernels write it ----------------------------------------------------------------------------------
+// ---- the sweep's skeleton, as both kernels write it (conv3x3_kernel: issue_x, finish_x, the start, the clamp and the epilogue take what
+// differs between its callers from its Form) ---------------------------------------------------------------------------------------------
 //     chunk 0 = chunk_desc<NT>(a, tile0, lds, 0): its pieces_of(NT) pieces go out at once, so what the kernel sets up next (the GATHER
 //         instance's taps) runs under the DMA
 //     issue_x(0, raw); finish_x(0, raw, xc);            the kernel's row source.  issue only issues the loads of this lane's eight values

@@ -1,5 +1,5 @@
 // car_split.h — the split-fp16 operand helpers shared by the matrix kernels (through car_mma_tile.h: car_fused.hip, car_linear16.hip,
-// car_lpips.hip; through car_mma32.h: car_raychain.hip, car_round2.hip, car_round2_attend.hip) and the packers (car_pack.hip).
+// car_conv.hip; through car_mma32.h: car_raychain.hip, car_round2.hip, car_round2_attend.hip) and the packers (car_pack.hip).
 // Included INSIDE the including file's anonymous namespace, after its half8 typedef.
 #pragma once
 
@@ -37,7 +37,7 @@ __device__ __forceinline__ void split8(const float (&x)[8], float p, half8& hi, 
 // power of two p with m p in [2^13, 2^14) for m > 0, and inv = 1 / p; the biased exponent of m is clamped to [LO, 230].
 // kPow2Lo: p in [2^-90, 2^43] — an all-zero vector or matrix (callers pass max(m, 1e-30)) must not push p_x * p_W, or a folded
 // bias * 2^43 * 2^shift, past fp32.
-// kPow2LoWide (car_lpips.hip's data gradient): p in [2^-90, 2^100] — a gradient row's largest magnitude is 1e-5 .. 1e-8 per unit of
+// kPow2LoWide (the LPIPS data gradient, car_conv.hip): p in [2^-90, 2^100] — a gradient row's largest magnitude is 1e-5 .. 1e-8 per unit of
 // cotangent, and the row's power of two has to follow it down so that a cotangent scaled by a power of two scales every result
 // exactly; p and the weights' 2^shift are never multiplied into one float there (the data gradient undoes them in two steps).
 constexpr int kPow2Lo = 97, kPow2LoWide = 40, kPow2Hi = 230;

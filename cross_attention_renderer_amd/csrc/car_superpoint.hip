@@ -2,7 +2,7 @@
 //
 // Stages, each an entry of include/car_match.h:
 //   dense    conv1a (1 -> 64, the fp32 vector kernel below), then the nine 64 / 128 / 256 layers and three pools through car_conv3x3 /
-//            car_maxpool2x2 (csrc/car_lpips.hip: split fp16 on the matrix pipe, ReLU in the store), the two 1 x 1 heads through
+//            car_maxpool2x2 (csrc/car_lpips.hip, csrc/car_conv.hip: split fp16 on the matrix pipe, ReLU in the store), the two 1 x 1 heads through
 //            car_linear (fp32 matrix pipe, bias folded into the pack, no ReLU); softmax over the 65 channels of a cell with the dustbin
 //            dropped and the other 64 laid out as the cell's 8 x 8 pixels; descriptors x / max(|x|, 1e-12).
 //   nms      simple_nms: the (2r+1)^2 maximum with the window clipped at the edges (-inf padding), two suppress-and-recover passes.

@@ -4,10 +4,9 @@
 // pixel copy of a stride-2 1x1 convolution, the trunk as a sequence of these entries and car_linear_x3, and the assembly of the token rows
 // car_vit_blocks reads.  Inference only.  Activations are channel-last fp32 rows [n][H W][C].
 //
-// conv3x3_same_kernel is the one hot kernel here: the row sweep of car_row_sweep.h as an implicit GEMM over 9 K, with the K loop's skeleton in
-// its own frame as that file prescribes.  It differs from car_lpips.hip's conv3x3_kernel only in where a K step's eight values come from —
-// input pixel (oy s + dy - pad_top, ox s + dx - pad_left) of an image whose extents differ from the output's — and in its epilogue (no bias,
-// no activation).  Compiled with the flags of the other two units that include the sweep (none).
+// The two dense convolutions are car_conv.hip's: the 3x3 one is conv3x3_kernel in its general form (car_conv3x3_general) with the padding
+// of TF "SAME" and no bias, residual or activation, the stem conv7x7_kernel at stride 2 (car_conv7x7); this unit works out the padding
+// and the output's extents.
 // GroupNorm's statistics are two passes in fp64 (the mean, then the squared distances from it), each split over slabs of pixels whose partial
 // sums are combined in one fixed order by every reader: no atomics, an image's result does not depend on the other images of the call.
 #include "car_common.h"
@@ -15,8 +14,6 @@
 #include <stdint.h>
 
 namespace {
-
-#include "car_row_sweep.h"
 
 constexpr long kMaxPixels = 1L << 27;              // n H W: keeps every row count, grid and per-image offset far inside 32 bits
 constexpr int kMaxImages = 65535;
@@ -46,41 +43,6 @@ __global__ void __launch_bounds__(256) weight_std_kernel(const float* __restrict
     for (int i = threadIdx.x; i < fan_in; i += 256) { const double d = (double)row[i] - mean; q += d * d; }
     const double rstd = 1.0 / sqrt(block_sum256(q, red) / (double)fan_in + eps);
     for (int i = threadIdx.x; i < fan_in; i += 256) out[(long)blockIdx.x * fan_in + i] = (float)(((double)row[i] - mean) * rstd);
-}
-
-// ---- the stem: 3 -> 64, 7x7, stride 2, SAME, fp32 on the vector pipe ------------------------------------------------------------------
-// a wave = the 64 output channels of one pixel at a time (the pixel is wave-uniform: its inputs are scalar loads), 8 pixels per wave;
-// lane n keeps channel n's 147 weights.  Terms are summed in the order (channel, row, column) of the window by fmaf; a tap in the padding
-// adds nothing.
-constexpr int kStemPix = 8, kStemTerms = 147;
-__global__ void __launch_bounds__(256) stem7x7_kernel(const float* __restrict__ X, const float* __restrict__ Wt, float* __restrict__ Y, int H, int W,
-                                                      int Ho, int Wo, int pt, int pl, long M) {
-    const int n = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float w[kStemTerms];
-#pragma unroll
-    for (int k = 0; k < kStemTerms; ++k) w[k] = Wt[n * kStemTerms + k];
-    const long p0 = ((long)blockIdx.x * 4 + wave) * kStemPix;
-    for (int i = 0; i < kStemPix; ++i) {
-        const long p = p0 + i;
-        if (p >= M) return;
-        const int pix = (int)(p % ((long)Ho * Wo)), oy = pix / Wo, ox = pix % Wo;
-        const float* img = X + (p / ((long)Ho * Wo)) * 3 * H * W;
-        float acc = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int ky = 0; ky < 7; ++ky) {
-                const int iy = 2 * oy + ky - pt;
-                if ((unsigned)iy >= (unsigned)H) continue;
-#pragma unroll
-                for (int kx = 0; kx < 7; ++kx) {
-                    const int ix = 2 * ox + kx - pl;
-                    if ((unsigned)ix < (unsigned)W) acc = fmaf(img[((long)c * H + iy) * W + ix], w[(c * 7 + ky) * 7 + kx], acc);
-                }
-            }
-        Y[p * 64 + n] = acc;
-    }
 }
 
 // ---- GroupNorm ------------------------------------------------------------------------------------------------------------------------
@@ -243,124 +205,9 @@ __global__ void __launch_bounds__(256) pixels_stride2_kernel(const float* __rest
     }
 }
 
-// ---- 3x3 convolution, stride 1 or 2, SAME -----------------------------------------------------------------------------------------------
-struct SameArgs {
-    const float* X;                        // [n, H, W, K]
-    const float* Wp; int tiles_total;      // [K step][tiles_total][512]: k = tap * K + channel
-    const float* down;                     // 2^-shift of the packed layer
-    float* Y;                              // [n, Ho, Wo, N]
-    int H, W, Ho, Wo, stride, pt, pl;      // pt, pl: the padding in front (top, left)
-    int K, N, lgk, chunks;                 // lgk = log2(K / 32)
-    long M, Min;                           // n Ho Wo output pixels, n H W input pixels
-};
-// One instance: column groups of four tiles (64 outputs), so a 256-wide layer is four workgroups per block of 192 pixels.  The trunk's
-// layers are small — 512 pixels at stage 3 of one pair, 8192 at stage 1 — and a wider group only leaves more of the device idle there
-// (stage 3 as one group of 16 tiles is three working workgroups, as four groups twelve).  No shape of the trunk has the 25 000 pixels at
-// which a wider group would still fill 256 CUs, so no wider instance is built.
-constexpr int kSameTiles = 4;
-__global__ void __launch_bounds__(kThreads) conv3x3_same_kernel(const SameArgs a) {
-    constexpr int NT = kSameTiles;
-    extern __shared__ __attribute__((aligned(16))) float lds[];      // [2][NT][512]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int s = lane & 15, q4 = lane >> 4;
-    RowPlace pl;                                                       // one XCD per block of pixels: car_row_sweep.h
-    if (!place_rows<NT>(a.tiles_total, a.M, wave, s, pl)) return;
-    const long row = pl.row, lrow = pl.lrow;
-    const int tile0 = pl.tile0<NT>();
-    const int K = a.K;
-    // the output pixel, the input pixel under the window's centre (always inside its image), and which of the nine taps are inside
-    const int pix = (int)(lrow % ((long)a.Ho * a.Wo)), oy = pix / a.Wo, ox = pix % a.Wo;
-    const long img = lrow / ((long)a.Ho * a.Wo);
-    const int cy = oy * a.stride + 1 - a.pt, cx = ox * a.stride + 1 - a.pl;
-    unsigned inside = 0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-        if ((unsigned)(cy + t / 3 - 1) < (unsigned)a.H && (unsigned)(cx + t % 3 - 1) < (unsigned)a.W) inside |= 1u << t;
-    const float* xpix = a.X + ((img * a.H + cy) * a.W + cx) * K + 8 * q4;
-
-    {   // chunk 0 goes out now: what follows runs under the DMA
-        const NextChunk n0 = chunk_desc<NT>(a, tile0, lds, 0);
-#pragma unroll
-        for (int p = 0; p < pieces_of(NT); ++p) stream_issue_piece(n0, p, lane, wave);
-    }
-    // this lane's eight values of K step c: tap t = c >> lgk, channels 32 (c & (K / 32 - 1)) + 8 q4 .. + 7 of input pixel (cy + t / 3 - 1,
-    // cx + t % 3 - 1).  issue_x only issues the loads — from the centre pixel when the tap is outside, a valid address whose values are
-    // dropped; finish_x turns them into values when they are consumed (car_row_sweep.h)
-    auto tap_of = [&](int c) { return c >> a.lgk; };
-    auto issue_x = [&](int c, float4 (&raw)[2]) {
-        const int t = tap_of(c), kc = c & ((1 << a.lgk) - 1);
-        const long off = ((long)(t / 3 - 1) * a.W + (t % 3 - 1)) * K;              // W K may pass 2^31 in a wide image
-        const float* src = xpix + (((inside >> t) & 1u) ? off : 0) + 32 * kc;
-        CAR_BOUNDS_TRAP(src >= a.X && src + 8 <= a.X + a.Min * K);
-        raw[0] = *reinterpret_cast<const float4*>(src);
-        raw[1] = *reinterpret_cast<const float4*>(src + 4);
-    };
-    auto finish_x = [&](int c, const float4 (&raw)[2], float (&x)[8]) {
-        const bool in = ((inside >> tap_of(c)) & 1u) != 0;
-        const float e[8] = {raw[0].x, raw[0].y, raw[0].z, raw[0].w, raw[1].x, raw[1].y, raw[1].z, raw[1].w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = in ? e[i] : 0.0f;
-    };
-    const float dW = a.down[0];
-    float xc[8];
-    {
-        float4 raw[2];
-        issue_x(0, raw);
-        finish_x(0, raw, xc);
-    }
-    float mrun = fmaxf(row_max(xc), 1e-30f), p, pinv;
-    pow2_scale<kPow2Lo>(mrun, p, pinv);
-
-    f32x4 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    half8 bhi, blo;
-    split8(xc, p, bhi, blo);
-    stream_sync();                                                     // weight chunk 0 landed
-
-    // the sweep's skeleton (car_row_sweep.h)
-#pragma unroll 1
-    for (int c = 0; c < a.chunks; ++c) {
-        const float* wl = lds + (c & 1) * NT * kTile + 4 * lane;
-        const NextChunk nx = chunk_desc<NT>(a, tile0, lds, c + 1);
-        const int cn = c + 1 < a.chunks ? c + 1 : c;
-        float4 rawn[2];
-        issue_x(cn, rawn);                                             // next K step's values: in flight under this step's MFMAs
-#pragma unroll
-        for (int qs = 0; qs < NT / 2; ++qs) {
-            const float* w0 = wl + (2 * qs * 2) * 256;
-            mfma_pair(acc[2 * qs], acc[2 * qs + 1], w0, w0 + 512, bhi, blo);
-            issue_next_piece<NT>(nx, qs, c + 1 < a.chunks, lane, wave);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // the next K step may outgrow the row's power of two: move the row (accumulators and scale) to the smaller one, exactly
-        float xn[8];
-        finish_x(cn, rawn, xn);
-        const float mn = row_max(xn);
-        if (__builtin_amdgcn_ballot_w64(mn > mrun) != 0) {
-            float pn, pninv;
-            mrun = fmaxf(mrun, mn);
-            pow2_scale<kPow2Lo>(mrun, pn, pninv);
-            scale_acc<NT>(acc, pn * pinv);
-            p = pn; pinv = pninv;
-        }
-        split8(xn, p, bhi, blo);
-        stream_sync();
-    }
-    if (row >= a.M) return;
-    float* yrow = a.Y + row * a.N + 16 * tile0 + 4 * q4;
-    scale_acc<NT>(acc, dW * pinv);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) *reinterpret_cast<float4*>(yrow + 16 * t) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
-}
-int launch_same(const SameArgs& a, hipStream_t st) {
-    const size_t lds_bytes = (size_t)2 * kSameTiles * kTile * sizeof(float);
-    CAR_LAUNCH_LDS("car_conv3x3_same", conv3x3_same_kernel, dim3(sweep_grid(a.M, a.tiles_total / kSameTiles)), dim3(kThreads), lds_bytes, st, a);
-    return CAR_OK;
-}
+// ---- the convolutions (car_conv.hip) -----------------------------------------------------------------------------------------------------
+constexpr int kStemTerms = 147;                    // the stem's 3 x 7 x 7 weights per output channel
 bool same_width_ok(int c) { return c == 64 || c == 128 || c == 256; }
-size_t same_tile_floats(int K, int N) { return (size_t)(9 * K / 32) * (N / 16) * kTile; }
 
 // ---- the trunk's layout ----------------------------------------------------------------------------------------------------------------
 constexpr int kStages = 3, kMaxDepth = 16, kGroups = 32;
@@ -393,7 +240,7 @@ TrunkPack trunk_pack_layout(const int* depths) {
                 b.down_w = c.at<float>(car_linear_x3_packed_floats(b.cin, b.cout)); b.down_g = c.at<float>(b.cout); b.down_b = c.at<float>(b.cout);
             }
             b.w1 = c.at<float>(car_linear_x3_packed_floats(b.cin, b.mid)); b.g1 = c.at<float>(b.mid); b.b1 = c.at<float>(b.mid);
-            b.w2 = c.at<float>(same_tile_floats(b.mid, b.mid) + 64); b.g2 = c.at<float>(b.mid); b.b2 = c.at<float>(b.mid);
+            b.w2 = c.at<float>(car_conv3x3_tile_floats(b.mid, b.mid) + 64); b.g2 = c.at<float>(b.mid); b.b2 = c.at<float>(b.mid);
             b.w3 = c.at<float>(car_linear_x3_packed_floats(b.mid, b.cout)); b.g3 = c.at<float>(b.cout); b.b3 = c.at<float>(b.cout);
             cin = b.cout;
         }
@@ -517,13 +364,8 @@ extern "C" int car_stem7x7(const float* x, int n, int H, int W, const float* w_s
     CAR_REQUIRE(x && w_std && Y, "car_stem7x7: null pointer");
     if (!trunk_shape_ok(n, H, W, "car_stem7x7")) return CAR_E_ARG;
     CAR_REQUIRE(aligned16(x) && aligned16(w_std) && aligned16(Y), "car_stem7x7: x, w_std and Y must be 16-byte aligned");
-    const int Ho = same_out(H, 2), Wo = same_out(W, 2);
-    const long M = (long)n * Ho * Wo;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(stem7x7_kernel, dim3(car_div_up(M, 4 * kStemPix)), dim3(256), 0, (hipStream_t)stream, x, w_std, Y, H, W, Ho, Wo,
-                       same_pad_front(H, 7, 2), same_pad_front(W, 7, 2), M);
-    CAR_CHECK_LAUNCH("car_stem7x7");
-    return CAR_OK;
+    return car_conv7x7("car_stem7x7", x, n, H, W, 2, same_pad_front(H, 7, 2), same_pad_front(W, 7, 2), same_out(H, 2), same_out(W, 2), w_std, nullptr, Y,
+                       (hipStream_t)stream);
 }
 
 extern "C" size_t car_groupnorm_workspace_bytes(int n, int HW, int C, int groups) {
@@ -581,22 +423,14 @@ extern "C" int car_pixels_stride2(const float* X, int n, int H, int W, int C, fl
 // k = tap * K + channel — then 64 floats of scale (2^shift, 2^-shift, the largest magnitude, zeros).  No bias.
 extern "C" size_t car_conv3x3_same_packed_floats(int K, int N) {
     if (!same_width_ok(K) || !same_width_ok(N)) { car_set_error("car_conv3x3_same_packed_floats: %d -> %d channels, need K and N among 64, 128, 256", K, N); return 0; }
-    return same_tile_floats(K, N) + 64;
+    return car_conv3x3_tile_floats(K, N) + 64;
 }
 
 extern "C" int car_conv3x3_same_pack(const float* w_std, int K, int N, float* packed, void* stream) {
     CAR_REQUIRE(w_std && packed, "car_conv3x3_same_pack: null pointer");
     CAR_REQUIRE(same_width_ok(K) && same_width_ok(N), "car_conv3x3_same_pack: %d -> %d channels, need K and N among 64, 128, 256", K, N);
     CAR_REQUIRE(aligned16(w_std) && aligned16(packed), "car_conv3x3_same_pack: w_std and packed must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    float* scale = packed + same_tile_floats(K, N);
-    (void)hipGetLastError();
-    CAR_CHECK_HIP(hipMemsetAsync(scale, 0, 64 * sizeof(float), st), "car_conv3x3_same_pack: memset failed");
-    const car_pack_scale s{scale + 2, scale, scale + 1};
-    car_pack_absmax(st, 64, w_std, 9 * K * N, nullptr, nullptr, 1, 9 * K * N, s);
-    car_pack_conv16(st, 512, w_std, K, N, false, s, reinterpret_cast<_Float16*>(packed));
-    CAR_CHECK_LAUNCH("car_conv3x3_same_pack");
-    return CAR_OK;
+    return car_conv3x3_pack_tiles("car_conv3x3_same_pack", w_std, nullptr, K, N, false, packed, (hipStream_t)stream);
 }
 
 extern "C" int car_conv3x3_same(const float* X, int n, int H, int W, int K, int N, int stride, const float* packed, float* Y, void* stream) {
@@ -605,13 +439,8 @@ extern "C" int car_conv3x3_same(const float* X, int n, int H, int W, int K, int 
     CAR_REQUIRE(stride == 1 || stride == 2, "car_conv3x3_same: stride = %d, need 1 or 2", stride);
     if (!trunk_shape_ok(n, H, W, "car_conv3x3_same")) return CAR_E_ARG;
     CAR_REQUIRE(aligned16(X) && aligned16(packed) && aligned16(Y), "car_conv3x3_same: X, packed and Y must be 16-byte aligned");
-    SameArgs a;
-    a.X = X; a.Wp = packed; a.tiles_total = N / 16; a.down = packed + same_tile_floats(K, N) + 1; a.Y = Y;
-    a.H = H; a.W = W; a.Ho = same_out(H, stride); a.Wo = same_out(W, stride); a.stride = stride;
-    a.pt = same_pad_front(H, 3, stride); a.pl = same_pad_front(W, 3, stride);
-    a.K = K; a.N = N; a.lgk = K == 64 ? 1 : K == 128 ? 2 : 3; a.chunks = 9 * K / 32;
-    a.M = (long)n * a.Ho * a.Wo; a.Min = (long)n * H * W;
-    return launch_same(a, (hipStream_t)stream);
+    return car_conv3x3_general("car_conv3x3_same", false, X, n, H, W, K, N, stride, same_pad_front(H, 3, stride), same_pad_front(W, 3, stride), same_out(H, stride),
+                               same_out(W, stride), packed, nullptr, nullptr, 0, Y, (hipStream_t)stream);
 }
 
 extern "C" size_t car_trunk_packed_floats(const int* depths) {

@@ -171,6 +171,33 @@ def test_conv3x3_pad1_equals_car_conv3x3_where_both_apply():
     assert torch.equal(got, Y.get("car_conv3x3"))
 
 
+def test_conv3x3_same_and_pad1_are_one_convolution():
+    """K = N = 256, the one width pair both entries accept, at odd extents, where SAME's padding in front is 1 at either stride and the two
+    geometries coincide: car_conv3x3_same and car_conv3x3_pad1 (no bias, no residual, flags 0) give the same BYTES, and so do their packers.
+    8 images of 5 x 5 at stride 1 are 200 rows, across the 192-row block; 2 images at stride 2.  The pixels' magnitudes span ten orders, so
+    rows move their power of two during the sweep."""
+    K = N = 256
+    w, _, packed = conv_layer(K, N)
+    L = lib()
+    floats = L.car_conv3x3_same_packed_floats(K, N)
+    assert floats == packed.view.numel() > 0, L.car_last_error()
+    own, Wt = Guarded((floats,), fill=0.0), dev_t(w)
+    ok(L.car_conv3x3_same_pack(ptr(Wt), K, N, own.ptr, stream()))
+    sync()
+    assert own.margins_untouched()
+    assert torch.equal(AH.bits(own.view.cpu()), AH.bits(packed.view.cpu())) and bool((own.view != 0).any())
+    for n, stride in ((8, 1), (2, 2)):
+        x = wide_input(n, 25, K, PRU.gen(40 + stride))
+        Ho = DR.pad1_out(5, stride)
+        assert Ho == TR.same_out(5, stride) and TR.same_pad(5, 3, stride)[0] == 1
+        pad1 = run_conv(x, n, 5, 5, K, N, stride, packed)
+        X, Y = Guarded((n, 25, K), init=x), Guarded((n, Ho * Ho, N))
+        ok(L.car_conv3x3_same(X.ptr, n, 5, 5, K, N, stride, own.ptr, Y.ptr, stream()))
+        sync()
+        same = Y.get("car_conv3x3_same")
+        assert torch.equal(AH.bits(same), AH.bits(pad1)) and bool((same != 0).any()), (n, stride)
+
+
 # ---- car_upsample2x_bilinear ----------------------------------------------------------------------------------------------------------------------
 def run_up(x, H, W):
     n, _, C = x.shape
