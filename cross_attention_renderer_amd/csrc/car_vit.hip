@@ -8,7 +8,8 @@
 // accumulators hold, per lane, 16 of the 32 logits of the lane's query — the other 16 live in lane ^ 32 — and, once exponentiated and split
 // in registers, ARE the B operand of O^T += V^T P (A = the V tile transposed, K = the 32 keys in the chained order).  The running maximum
 // and sum of a query row and the 32 x 64 output accumulators follow the online softmax.  mha_absmax_kernel and mha_pack_kernel lay k and v of the whole
-// call out as hi / lo A-operand tiles first, one power of two per (scene, head), the padding keys zero.
+// call out as hi / lo A-operand tiles first, one power of two per (scene, head), the padding keys zero.  The two operand forms, the
+// wave's rows as B operands and the epilogue are car_mha_tile.h's, which the backward shares; LayerNorm's row pass is car_vit_layout.h's.
 #include "car_common.h"
 #include <math.h>
 #include <stdint.h>
@@ -17,49 +18,31 @@ namespace {
 
 #include "car_mma32.h"
 #include "car_vit_layout.h"
+#include "car_mha_tile.h"
 
-constexpr int kStep = kMma32TileK16;               // floats of one K step's A operand: [hi | lo][lane][8 halves]
 constexpr int kTileK = 4 * kStep;                  // the K part of a tile record: 4 K steps over the 64 channels
 constexpr int kTileFloats = 2 * kTileK;            // + the V part: [channel tile (2)][kg (2)] K steps over the 32 keys
 constexpr float kPScale = 8192.0f;                 // the numerators' power of two: p in [0, 1] -> [0, 2^13]
 
 // ---- LayerNorm: one wave per row, the row in registers, statistics in fp64 ------------------------------------------------------------
-constexpr int kLnMax = 4096, kLnVec = kLnMax / (64 * 4);
 __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, int C, double eps, float* __restrict__ Y, int ldy, long M) {
     const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
     const int lane = threadIdx.x & 63;
-    const float* x = X + m * ldx;
-    float4 v[kLnVec];
-    double sum = 0.0;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        v[i] = c < C ? *reinterpret_cast<const float4*>(x + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        sum += ((double)v[i].x + (double)v[i].y) + ((double)v[i].z + (double)v[i].w);
-    }
-    const double mean = wave_sum(sum) / (double)C;
-    double sq = 0.0;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        if ((i * 64 + lane) * 4 < C) {
-            const double a = (double)v[i].x - mean, b = (double)v[i].y - mean, c = (double)v[i].z - mean, d = (double)v[i].w - mean;
-            sq += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-    const double rstd = 1.0 / sqrt(wave_sum(sq) / (double)C + eps);
+    LnRow r;
+    r.load(X + m * ldx, C, eps, lane);
     float* y = Y + m * ldy;
 #pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
+    for (int i = 0; i < LnRow::kVec; ++i) {
         const int c = (i * 64 + lane) * 4;
         if (c < C) {
-            const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c);
+            const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c), v = r.v[i];
             float4 o;
-            o.x = fmaf((float)(((double)v[i].x - mean) * rstd), g.x, b.x);
-            o.y = fmaf((float)(((double)v[i].y - mean) * rstd), g.y, b.y);
-            o.z = fmaf((float)(((double)v[i].z - mean) * rstd), g.z, b.z);
-            o.w = fmaf((float)(((double)v[i].w - mean) * rstd), g.w, b.w);
+            o.x = fmaf((float)(((double)v.x - r.mean) * r.rstd), g.x, b.x);
+            o.y = fmaf((float)(((double)v.y - r.mean) * r.rstd), g.y, b.y);
+            o.z = fmaf((float)(((double)v.z - r.mean) * r.rstd), g.z, b.z);
+            o.w = fmaf((float)(((double)v.w - r.mean) * r.rstd), g.w, b.w);
             *reinterpret_cast<float4*>(y + c) = o;
         }
     }
@@ -88,39 +71,15 @@ struct MhaArgs {
 
 // largest magnitudes of one tile's k and v (rows beyond the scene are not read)
 __global__ void __launch_bounds__(256) mha_absmax_kernel(MhaArgs a) {
-    __shared__ float red[2][4];
     const int tile = blockIdx.x % a.tiles, bh = blockIdx.x / a.tiles, h = bh % a.heads, sc = bh / a.heads;
-    const int key = tile * kKeys + (threadIdx.x >> 3), c = (threadIdx.x & 7) * 8, dim = a.heads * kHead;
-    float mk = 0.0f, mv = 0.0f;
-    if (key < a.S) {
-        const float* row = a.qkv + ((long)sc * a.S + key) * a.ld + h * kHead + c;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float4 k4 = *reinterpret_cast<const float4*>(row + dim + 4 * j), v4 = *reinterpret_cast<const float4*>(row + 2 * dim + 4 * j);
-            mk = fmaxf(mk, fmaxf(fmaxf(fabsf(k4.x), fabsf(k4.y)), fmaxf(fabsf(k4.z), fabsf(k4.w))));
-            mv = fmaxf(mv, fmaxf(fmaxf(fabsf(v4.x), fabsf(v4.y)), fmaxf(fabsf(v4.z), fabsf(v4.w))));
-        }
-    }
-    mk = wave_max(mk); mv = wave_max(mv);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = mk; red[1][threadIdx.x >> 6] = mv; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const float* r = red[threadIdx.x];
-        a.maxes[(long)blockIdx.x * 2 + threadIdx.x] = fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3]));
-    }
+    const int key = tile * kKeys + (threadIdx.x >> 3), dim = a.heads * kHead;
+    tile_absmax<2>(key, a.S, [&](int t) { return a.qkv + ((long)sc * a.S + key) * a.ld + h * kHead + (t + 1) * dim; }, a.maxes);
 }
 
-__device__ __forceinline__ void split_nearest(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
-// one tile record: thread (step, lane) writes the lane's 8 hi and 8 lo halves of one K step.  K part: step = ks, the lane's row is key
-// lane % 32, its 8 values channels 16 ks + 8 (lane / 32) + e.  V part: step = 2 t + kg, the lane's row is channel 32 t + lane % 32, its 8
-// values the keys 16 kg + mma32_channel(0, e, lane / 32) — the order in which the logits' accumulators hold them.
+// one tile record: the K part is k in car_mha_tile.h's rows x channels form, the V part v in its channels x rows form
 __global__ void __launch_bounds__(256) mha_pack_kernel(MhaArgs a) {
     const int tile = blockIdx.x % a.tiles, bh = blockIdx.x / a.tiles, h = bh % a.heads, sc = bh / a.heads;
-    const int dim = a.heads * kHead, step = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, hh = lane >> 5;
+    const int dim = a.heads * kHead, step = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float mk = 0.0f, mv = 0.0f;
     for (int t = 0; t < a.tiles; ++t) {
         mk = fmaxf(mk, a.maxes[((long)bh * a.tiles + t) * 2]);
@@ -132,59 +91,18 @@ __global__ void __launch_bounds__(256) mha_pack_kernel(MhaArgs a) {
     if (tile == 0 && threadIdx.x == 0) { a.scales[bh * 2] = ik; a.scales[bh * 2 + 1] = iv; }
     const float* base = a.qkv + (long)sc * a.S * a.ld + h * kHead;
     _Float16* rec = reinterpret_cast<_Float16*>(a.packed + ((long)bh * a.tiles + tile) * kTileFloats);
-    half8 hi, lo;
-    {   // K part
-        const int key = tile * kKeys + i;
-        float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (key < a.S) {
-            const float* src = base + (long)key * a.ld + dim + 16 * step + 8 * hh;
-            const float4 a0 = *reinterpret_cast<const float4*>(src), a1 = *reinterpret_cast<const float4*>(src + 4);
-            x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { _Float16 u, l; split_nearest(x[e] * pk, u, l); hi[e] = u; lo[e] = l; }
-        _Float16* dst = rec + (long)step * (2 * kStep);                           // halves: kStep floats = 2 kStep halves
-        *reinterpret_cast<half8*>(dst + lane * 8) = hi;
-        *reinterpret_cast<half8*>(dst + kStep + lane * 8) = lo;
-    }
-    {   // V part
-        const int t = step >> 1, kg = step & 1, c = 32 * t + i;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int key = tile * kKeys + 16 * kg + mma32_channel(0, e, hh);
-            const float x = key < a.S ? base[(long)key * a.ld + 2 * dim + c] : 0.0f;
-            _Float16 u, l; split_nearest(x * pv, u, l); hi[e] = u; lo[e] = l;
-        }
-        _Float16* dst = rec + 2 * kTileK + (long)step * (2 * kStep);
-        *reinterpret_cast<half8*>(dst + lane * 8) = hi;
-        *reinterpret_cast<half8*>(dst + kStep + lane * 8) = lo;
-    }
+    const int key = tile * kKeys + (lane & 31);
+    write_rc(rec, step, lane, key < a.S ? base + (long)key * a.ld + dim : nullptr, pk);
+    write_cr(rec + 2 * kTileK, step, lane, [=](int r, int c) { return tile * kKeys + r < a.S ? base[(long)(tile * kKeys + r) * a.ld + 2 * dim + c] : 0.0f; }, pv);
 }
 
 // ---- attention: one wave = 32 query rows of one (scene, head) --------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) mha_kernel(MhaArgs a) {
-    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wave >= (long)a.b * a.heads * a.tiles) return;                                  // no barrier below: a wave may leave alone
-    const int qt = (int)(wave % a.tiles), bh = (int)(wave / a.tiles), h = bh % a.heads, sc = bh / a.heads;
-    const int lane = threadIdx.x & 63, s = lane & 31, hh = lane >> 5;
-    const int q = qt * kKeys + s, qrow = q < a.S ? q : a.S - 1;                         // rows beyond the scene: a copy of its last row, never stored
-    const float* qsrc = a.qkv + ((long)sc * a.S + qrow) * a.ld + h * kHead + 8 * hh;
-    float x8[4][8];
-    float m = 0.0f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const float4 a0 = *reinterpret_cast<const float4*>(qsrc + 16 * ks), a1 = *reinterpret_cast<const float4*>(qsrc + 16 * ks + 4);
-        x8[ks][0] = a0.x; x8[ks][1] = a0.y; x8[ks][2] = a0.z; x8[ks][3] = a0.w;
-        x8[ks][4] = a1.x; x8[ks][5] = a1.y; x8[ks][6] = a1.z; x8[ks][7] = a1.w;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x8[ks][e]));
-    }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float pq, iq;
-    pow2_scale(fmaxf(m, 1e-30f), pq, iq);
+    if (WaveRows::wave() >= (long)a.b * a.heads * a.tiles) return;
+    const WaveRows w(a.S, a.heads, a.tiles);
+    const int bh = w.bh, lane = w.lane, hh = w.hh;
     half8 qhi[4], qlo[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) split8(x8[ks], pq, qhi[ks], qlo[ks]);
+    const float iq = load_rows_b<kPow2Lo>(a.qkv + ((long)w.sc * a.S + w.row) * a.ld + w.h * kHead + 8 * hh, qhi, qlo);
     const float ik = a.scales[bh * 2], iv = a.scales[bh * 2 + 1];
     const float cq = 0.125f * iq;                                                       // 1 / sqrt(64), with the query row's power of two
 
@@ -202,8 +120,7 @@ __global__ void __launch_bounds__(256) mha_kernel(MhaArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) read_a(tw + kTileK + i * kStep, vh[i], vl[i]);
         f32x16 sacc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sacc[r] = 0.0f;
+        zero1(sacc);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) mma3(sacc, kh[ks], kl[ks], qhi[ks], qlo[ks]);
         if (kt + 1 < a.tiles) {
@@ -246,18 +163,10 @@ __global__ void __launch_bounds__(256) mha_kernel(MhaArgs a) {
 #pragma unroll
             for (int kg = 0; kg < 2; ++kg) mma3(o[t], vh[2 * t + kg], vl[2 * t + kg], phi[kg], plo[kg]);
     }
-    if (q >= a.S) return;
-    if (a.stats && hh == 0) *reinterpret_cast<float2*>(a.stats + ((long)bh * a.S + q) * 2) = make_float2(mrun, lrun);
+    if (w.at >= a.S) return;
+    if (a.stats && hh == 0) *reinterpret_cast<float2*>(a.stats + ((long)bh * a.S + w.at) * 2) = make_float2(mrun, lrun);
     const float c = iv * (1.0f / kPScale);
-    float* dst = a.out + ((long)sc * a.S + q) * a.ldo + h * kHead;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 v;
-            v.x = (o[t][4 * g] * c) / lrun; v.y = (o[t][4 * g + 1] * c) / lrun; v.z = (o[t][4 * g + 2] * c) / lrun; v.w = (o[t][4 * g + 3] * c) / lrun;
-            *reinterpret_cast<float4*>(dst + mma32_channel(t, 4 * g, hh)) = v;
-        }
+    store_rows(a.out + ((long)w.sc * a.S + w.at) * a.ldo + w.h * kHead, o, hh, [&](float x) { return (x * c) / lrun; });
 }
 
 // car_mha's workspace: pieces of whole 64 floats, the last one as long as it is
@@ -282,7 +191,7 @@ VitWork vit_work(int b, int S, int dim, void* work = nullptr) {
 extern "C" int car_layernorm(const float* X, int ldx, const float* gamma, const float* beta, int C, double eps, float* Y, int ldy, long M,
                              void* stream) {
     CAR_REQUIRE(X && gamma && beta && Y, "car_layernorm: null pointer");
-    CAR_REQUIRE(C >= 4 && C <= kLnMax && C % 4 == 0, "car_layernorm: C = %d must be a multiple of 4 in 4..%d", C, kLnMax);
+    if (!ln_shape_ok(C, "car_layernorm")) return CAR_E_ARG;
     CAR_REQUIRE(M > 0 && M <= (1L << 31) && eps >= 0.0, "car_layernorm: bad sizes (M = %ld, eps = %g)", M, eps);
     CAR_REQUIRE(ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0, "car_layernorm: the row strides (%d, %d) must hold C = %d and be multiples of 4",
                 ldx, ldy, C);

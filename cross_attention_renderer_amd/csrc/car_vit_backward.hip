@@ -2,10 +2,10 @@
 // GELU and multi-head attention backwards, the pack with the transposed matrices, and the stage's backward as a sequence of these entries,
 // car_linear_x3 (dX = dY W on the transposed matrix) and car_linear_wgrad.  The recorded forward is car_vit.hip's.
 //
-// car_mha_backward is the one hot kernel pair.  Both are car_mha's loop: a wave owns 32 rows of one (scene, head) as the B operand of
-// car_mma32.h's chained 32 x 32 x 16 tile and streams tiles of 32 rows as A operands; the two logit-shaped products (s and dp) leave, per
-// lane, 16 values of the lane's own row, which — multiplied out to p and ds, scaled and split in registers — ARE the B operand of the two
-// value-shaped products.  mha_bwd_dq_kernel: the wave's rows are queries, the stream is the keys (s^T = K Q^T as the forward forms it,
+// car_mha_backward is the one hot kernel pair.  Both stand on what car_mha stands on (car_mha_tile.h: the operand forms, the wave's rows as
+// B operands, the epilogue): a wave owns 32 rows of one (scene, head) and streams tiles of 32 rows as A operands; the two logit-shaped
+// products (s and dp) leave, per lane, 16 values of the lane's own row, which — multiplied out to p and ds, scaled and split in
+// registers — ARE the B operand of the two value-shaped products.  mha_bwd_dq_kernel: the wave's rows are queries, the stream is the keys (s^T = K Q^T as the forward forms it,
 // dp^T = V dO^T, dq^T += K^T ds^T).  mha_bwd_dkv_kernel: the wave's rows are keys, the stream is the queries (s = Q K^T, dp = dO V^T,
 // dv^T += dO^T p, dk^T += Q^T ds).  Nothing is summed across waves: no atomics, every reduction in a fixed order.
 // mha_bwd_absmax_kernel, mha_bwd_rows_kernel and mha_bwd_pack_kernel lay the seven A-operand forms of a tile out first.
@@ -17,13 +17,11 @@ namespace {
 
 #include "car_mma32.h"
 #include "car_vit_layout.h"
+#include "car_mha_tile.h"
 
-constexpr int kStep = kMma32TileK16;               // floats of one K step's A operand: [hi | lo][lane][8 halves]
 constexpr int kForm = 4 * kStep;                   // one operand form of a tile: 4 K steps
-// the forms of a tile record.  RC: rows x channels (the lane's row is row lane % 32 of the tile, K runs over the 64 channels) — the A
-// operand of a logit-shaped product.  CR: channels x rows (the lane's row is a channel, K runs over the tile's 32 rows in the chained
-// order) — the A operand of a value-shaped product.  Powers of two: one per (scene, head) and tensor, except Q_RC, whose rows carry
-// the forward's own per-row power (so that the logits are the forward's).
+// the forms of a tile record, RC (rows x channels) and CR (channels x rows) as car_mha_tile.h writes them.  Powers of two: one per
+// (scene, head) and tensor, except Q_RC, whose rows carry the forward's own per-row power (so that the logits are the forward's).
 enum { F_K_RC, F_V_RC, F_K_CR, F_Q_RC, F_D_RC, F_Q_CR, F_D_CR, kForms };
 constexpr int kTileBwd = kForms * kForm;
 enum { T_Q, T_K, T_V, T_D, kTensors };
@@ -48,31 +46,9 @@ __device__ __forceinline__ const float* tensor_row(const BwdArgs& a, int t, int 
 
 // largest magnitudes of one tile's q, k, v and dout (rows beyond the scene are not read)
 __global__ void __launch_bounds__(256) mha_bwd_absmax_kernel(BwdArgs a) {
-    __shared__ float red[kTensors][4];
     const int tile = blockIdx.x % a.tiles, bh = blockIdx.x / a.tiles, h = bh % a.heads, sc = bh / a.heads;
-    const int row = tile * kKeys + (threadIdx.x >> 3), c = (threadIdx.x & 7) * 8;
-    float m[kTensors] = {0.f, 0.f, 0.f, 0.f};
-    if (row < a.S) {
-#pragma unroll
-        for (int t = 0; t < kTensors; ++t) {
-            const float* src = tensor_row(a, t, sc, h, row) + c;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float4 v = *reinterpret_cast<const float4*>(src + 4 * j);
-                m[t] = fmaxf(m[t], fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < kTensors; ++t) {
-        m[t] = wave_max(m[t]);
-        if ((threadIdx.x & 63) == 0) red[t][threadIdx.x >> 6] = m[t];
-    }
-    __syncthreads();
-    if (threadIdx.x < kTensors) {
-        const float* r = red[threadIdx.x];
-        a.maxes[(long)blockIdx.x * kTensors + threadIdx.x] = fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3]));
-    }
+    const int row = tile * kKeys + (threadIdx.x >> 3);
+    tile_absmax<kTensors>(row, a.S, [&](int t) { return tensor_row(a, t, sc, h, row); }, a.maxes);
 }
 
 // one thread per (scene, head, row): the row's own power of two of q (as car_mha's wave takes it), the saved statistics, D
@@ -94,26 +70,11 @@ __global__ void __launch_bounds__(256) mha_bwd_rows_kernel(BwdArgs a) {
     a.rows[i] = make_float4(iq, a.stats[i * 2], a.stats[i * 2 + 1], D);
 }
 
-__device__ __forceinline__ void split_nearest(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-__device__ __forceinline__ void store_step(_Float16* form, int step, int lane, const float (&x)[8]) {
-    half8 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { _Float16 u, l; split_nearest(x[e], u, l); hi[e] = u; lo[e] = l; }
-    _Float16* dst = form + (long)step * (2 * kStep);                               // halves: kStep floats = 2 kStep halves
-    *reinterpret_cast<half8*>(dst + lane * 8) = hi;
-    *reinterpret_cast<half8*>(dst + kStep + lane * 8) = lo;
-}
-
-// one tile record: thread (step, lane) writes the lane's 8 hi and 8 lo halves of K step `step` of every form.  RC: the lane's row is
-// row lane % 32, its 8 values channels 16 step + 8 (lane / 32) + e.  CR: step = 2 t + kg, the lane's row is channel 32 t + lane % 32,
-// its 8 values the rows 16 kg + mma32_channel(0, e, lane / 32) — the order in which a logit-shaped product's accumulators hold them.
-// Rows beyond the scene are zeros and are not read.
+// one tile record: thread (step, lane) writes the lane's halves of K step `step` of every form.  Rows beyond the scene are zeros and
+// are not read.
 __global__ void __launch_bounds__(256) mha_bwd_pack_kernel(BwdArgs a) {
     const int tile = blockIdx.x % a.tiles, bh = blockIdx.x / a.tiles, h = bh % a.heads, sc = bh / a.heads;
-    const int step = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, hh = lane >> 5;
+    const int step = threadIdx.x >> 6, lane = threadIdx.x & 63, row = tile * kKeys + (lane & 31);
     float p[kTensors];
 #pragma unroll
     for (int t = 0; t < kTensors; ++t) {
@@ -127,50 +88,15 @@ __global__ void __launch_bounds__(256) mha_bwd_pack_kernel(BwdArgs a) {
     const int rc_form[4] = {F_Q_RC, F_K_RC, F_V_RC, F_D_RC}, cr_form[4] = {F_Q_CR, F_K_CR, -1, F_D_CR};
 #pragma unroll
     for (int t = 0; t < kTensors; ++t) {
-        {   // rows x channels
-            const int row = tile * kKeys + i;
-            float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (row < a.S) {
-                const float* src = tensor_row(a, t, sc, h, row) + 16 * step + 8 * hh;
-                const float s = t == T_Q ? 1.0f / a.rows[(long)bh * a.S + row].x : p[t];       // a power of two: the reciprocal is exact
-                const float4 a0 = *reinterpret_cast<const float4*>(src), a1 = *reinterpret_cast<const float4*>(src + 4);
-                x[0] = a0.x * s; x[1] = a0.y * s; x[2] = a0.z * s; x[3] = a0.w * s; x[4] = a1.x * s; x[5] = a1.y * s; x[6] = a1.z * s; x[7] = a1.w * s;
-            }
-            store_step(rec + (long)rc_form[t] * (2 * kForm), step, lane, x);
-        }
-        if (cr_form[t] >= 0) {   // channels x rows
-            const int ct = step >> 1, kg = step & 1, c = 32 * ct + i;
-            float x[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int row = tile * kKeys + 16 * kg + mma32_channel(0, e, hh);
-                x[e] = row < a.S ? tensor_row(a, t, sc, h, row)[c] * p[t] : 0.0f;
-            }
-            store_step(rec + (long)cr_form[t] * (2 * kForm), step, lane, x);
-        }
+        const float* src = row < a.S ? tensor_row(a, t, sc, h, row) : nullptr;
+        const float s = t == T_Q && src ? 1.0f / a.rows[(long)bh * a.S + row].x : p[t];       // a power of two: the reciprocal is exact
+        write_rc(rec + (long)rc_form[t] * (2 * kForm), step, lane, src, s);
+        // the power of two inside the reader's row test, as this kernel always had it: multiplied in by write_cr, a step's eight loads are
+        // in flight together and the kernel holds 70 registers in the place of 54, a wave per SIMD less
+        if (cr_form[t] >= 0)
+            write_cr(rec + (long)cr_form[t] * (2 * kForm), step, lane,
+                     [=](int r, int c) { return tile * kKeys + r < a.S ? tensor_row(a, t, sc, h, tile * kKeys + r)[c] * p[t] : 0.0f; }, 1.0f);
     }
-}
-
-// the wave's own 32 rows of one tensor as B operands: the row's 64 channels, one power of two per row (rows beyond the scene: a copy of
-// its last row, never stored).  -> inv = 1 / p
-template <int LO>
-__device__ __forceinline__ float load_rows_b(const float* src, half8 (&hi)[4], half8 (&lo)[4]) {
-    float x8[4][8];
-    float m = 0.0f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const float4 a0 = *reinterpret_cast<const float4*>(src + 16 * ks), a1 = *reinterpret_cast<const float4*>(src + 16 * ks + 4);
-        x8[ks][0] = a0.x; x8[ks][1] = a0.y; x8[ks][2] = a0.z; x8[ks][3] = a0.w;
-        x8[ks][4] = a1.x; x8[ks][5] = a1.y; x8[ks][6] = a1.z; x8[ks][7] = a1.w;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x8[ks][e]));
-    }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float p, inv;
-    pow2_scale<LO>(fmaxf(m, 1e-30f), p, inv);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) split8(x8[ks], p, hi[ks], lo[ks]);
-    return inv;
 }
 
 // the lane's 16 values of p or ds as the B operand of a value-shaped product: one power of two per row and tile, taken from the largest
@@ -214,22 +140,16 @@ __device__ __forceinline__ void mma_rc(f32x16& acc, const float* form, const hal
         mma3(acc, ah, al, bhi[ks], blo[ks]);
     }
 }
-__device__ __forceinline__ void zero1(f32x16& acc) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-}
 
 // ---- dq: one wave = 32 query rows of one (scene, head), streaming the key tiles ---------------------------------------------------------
 __global__ void __launch_bounds__(256) mha_bwd_dq_kernel(BwdArgs a) {
-    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wave >= (long)a.b * a.heads * a.tiles) return;                                  // no barrier below: a wave may leave alone
-    const int qt = (int)(wave % a.tiles), bh = (int)(wave / a.tiles), h = bh % a.heads, sc = bh / a.heads;
-    const int lane = threadIdx.x & 63, s = lane & 31, hh = lane >> 5;
-    const int q = qt * kKeys + s, qrow = q < a.S ? q : a.S - 1;
+    if (WaveRows::wave() >= (long)a.b * a.heads * a.tiles) return;
+    const WaveRows w(a.S, a.heads, a.tiles);
+    const int bh = w.bh, lane = w.lane, hh = w.hh;
     half8 qhi[4], qlo[4], dhi[4], dlo[4];
-    const float iq = load_rows_b<kPow2Lo>(tensor_row(a, T_Q, sc, h, qrow) + 8 * hh, qhi, qlo);       // the forward's own split of q
-    const float id = load_rows_b<kPow2LoWide>(tensor_row(a, T_D, sc, h, qrow) + 8 * hh, dhi, dlo);
-    const float4 st = a.rows[(long)bh * a.S + qrow];
+    const float iq = load_rows_b<kPow2Lo>(tensor_row(a, T_Q, w.sc, w.h, w.row) + 8 * hh, qhi, qlo);  // mha_kernel's call: the forward's split of q
+    const float id = load_rows_b<kPow2LoWide>(tensor_row(a, T_D, w.sc, w.h, w.row) + 8 * hh, dhi, dlo);
+    const float4 st = a.rows[(long)bh * a.S + w.row];
     const float ik = a.scales[bh * kTensors + T_K], iv = a.scales[bh * kTensors + T_V];
     const float cq = 0.125f * iq;
     f32x16 dq[2];
@@ -257,29 +177,18 @@ __global__ void __launch_bounds__(256) mha_bwd_dq_kernel(BwdArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) dq[t][r] = fmaf(part[t][r], is, dq[t][r]);
     }
-    if (q >= a.S) return;
-    float* dst = a.dqkv + ((long)sc * a.S + q) * a.lddq + h * kHead;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 v;
-            v.x = (dq[t][4 * g] * ik) * 0.125f; v.y = (dq[t][4 * g + 1] * ik) * 0.125f;
-            v.z = (dq[t][4 * g + 2] * ik) * 0.125f; v.w = (dq[t][4 * g + 3] * ik) * 0.125f;
-            *reinterpret_cast<float4*>(dst + mma32_channel(t, 4 * g, hh)) = v;
-        }
+    if (w.at >= a.S) return;
+    store_rows(a.dqkv + ((long)w.sc * a.S + w.at) * a.lddq + w.h * kHead, dq, hh, [&](float x) { return (x * ik) * 0.125f; });
 }
 
 // ---- dk, dv: one wave = 32 keys of one (scene, head), streaming the query tiles -----------------------------------------------------------
 __global__ void __launch_bounds__(256) mha_bwd_dkv_kernel(BwdArgs a) {
-    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wave >= (long)a.b * a.heads * a.tiles) return;
-    const int jt = (int)(wave % a.tiles), bh = (int)(wave / a.tiles), h = bh % a.heads, sc = bh / a.heads;
-    const int lane = threadIdx.x & 63, s = lane & 31, hh = lane >> 5;
-    const int key = jt * kKeys + s, krow = key < a.S ? key : a.S - 1;
+    if (WaveRows::wave() >= (long)a.b * a.heads * a.tiles) return;
+    const WaveRows w(a.S, a.heads, a.tiles);
+    const int bh = w.bh, lane = w.lane, hh = w.hh;
     half8 khi[4], klo[4], vhi[4], vlo[4];
-    const float ik = load_rows_b<kPow2Lo>(tensor_row(a, T_K, sc, h, krow) + 8 * hh, khi, klo);
-    const float iv = load_rows_b<kPow2Lo>(tensor_row(a, T_V, sc, h, krow) + 8 * hh, vhi, vlo);
+    const float ik = load_rows_b<kPow2Lo>(tensor_row(a, T_K, w.sc, w.h, w.row) + 8 * hh, khi, klo);
+    const float iv = load_rows_b<kPow2Lo>(tensor_row(a, T_V, w.sc, w.h, w.row) + 8 * hh, vhi, vlo);
     const float iqs = a.scales[bh * kTensors + T_Q], idd = a.scales[bh * kTensors + T_D];
     const float ck = 0.125f * ik;
     f32x16 dk[2], dv[2];
@@ -317,20 +226,11 @@ __global__ void __launch_bounds__(256) mha_bwd_dkv_kernel(BwdArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) dk[t][r] = fmaf(part[t][r], is, dk[t][r]);
     }
-    if (key >= a.S) return;
+    if (w.at >= a.S) return;
     const int dim = a.heads * kHead;
-    float* dst = a.dqkv + ((long)sc * a.S + key) * a.lddq + h * kHead;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 k4, v4;
-            k4.x = (dk[t][4 * g] * iqs) * 0.125f; k4.y = (dk[t][4 * g + 1] * iqs) * 0.125f;
-            k4.z = (dk[t][4 * g + 2] * iqs) * 0.125f; k4.w = (dk[t][4 * g + 3] * iqs) * 0.125f;
-            v4.x = dv[t][4 * g] * idd; v4.y = dv[t][4 * g + 1] * idd; v4.z = dv[t][4 * g + 2] * idd; v4.w = dv[t][4 * g + 3] * idd;
-            *reinterpret_cast<float4*>(dst + dim + mma32_channel(t, 4 * g, hh)) = k4;
-            *reinterpret_cast<float4*>(dst + 2 * dim + mma32_channel(t, 4 * g, hh)) = v4;
-        }
+    float* dst = a.dqkv + ((long)w.sc * a.S + w.at) * a.lddq + w.h * kHead;
+    store_rows(dst + dim, dk, hh, [&](float x) { return (x * iqs) * 0.125f; });
+    store_rows(dst + 2 * dim, dv, hh, [&](float x) { return x * idd; });
 }
 
 // car_mha_backward's workspace: pieces of whole 64 floats, the last one as long as it is
@@ -343,39 +243,24 @@ MhaBwdLayout mha_bwd_layout(int b, int S, int heads, void* work = nullptr) {
             c.bytes(), tiles};
 }
 
-// ---- LayerNorm backward: one wave per row, the row in registers, statistics in fp64 as the forward takes them -------------------------
-constexpr int kLnMax = 4096, kLnVec = kLnMax / (64 * 4), kLnSlab = 64;
+// ---- LayerNorm backward: one wave per row, the row and its fp64 statistics from the forward's LnRow -----------------------------------
+constexpr int kLnSlab = 64;
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ gamma, int C, double eps,
                                                       const float* dY, int lddy, float* dX, int lddx, long M, int accum, double* __restrict__ rowstat) {
     const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
     const int lane = threadIdx.x & 63;
-    const float* x = X + m * ldx;
-    float4 v[kLnVec];
-    double sum = 0.0;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        v[i] = c < C ? *reinterpret_cast<const float4*>(x + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        sum += ((double)v[i].x + (double)v[i].y) + ((double)v[i].z + (double)v[i].w);
-    }
-    const double mean = wave_sum(sum) / (double)C;
-    double sq = 0.0;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        if ((i * 64 + lane) * 4 < C) {
-            const double a = (double)v[i].x - mean, b = (double)v[i].y - mean, c = (double)v[i].z - mean, d = (double)v[i].w - mean;
-            sq += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-    const double rstd = 1.0 / sqrt(wave_sum(sq) / (double)C + eps);
+    LnRow r;
+    r.load(X + m * ldx, C, eps, lane);
+    const float4 (&v)[LnRow::kVec] = r.v;
+    const double mean = r.mean, rstd = r.rstd;
     if (rowstat && lane == 0) { rowstat[2 * m] = mean; rowstat[2 * m + 1] = rstd; }
     // a = gamma dy; s1 = sum a, s2 = sum a xhat
     const float* dy = dY + m * lddy;
-    float4 a4[kLnVec];
+    float4 a4[LnRow::kVec];
     double s1 = 0.0, s2 = 0.0;
 #pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
+    for (int i = 0; i < LnRow::kVec; ++i) {
         const int c = (i * 64 + lane) * 4;
         a4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c < C) {
@@ -389,7 +274,7 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ X
     const double m1 = wave_sum(s1) / (double)C, m2 = wave_sum(s2) / (double)C;
     float* dx = dX + m * lddx;
 #pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
+    for (int i = 0; i < LnRow::kVec; ++i) {
         const int c = (i * 64 + lane) * 4;
         if (c < C) {
             float4 o;
@@ -477,7 +362,7 @@ VitBwdWork vit_bwd_work(int b, int S, int dim, void* work = nullptr) {
 }  // namespace
 
 extern "C" size_t car_layernorm_backward_workspace_bytes(long M, int C) {
-    if (M < 1 || M > (1L << 31) || C < 4 || C > kLnMax || C % 4) {
+    if (M < 1 || M > (1L << 31) || !ln_shape_ok(C, "car_layernorm_backward_workspace_bytes")) {      // this entry's text names M too
         car_set_error("car_layernorm_backward_workspace_bytes: M = %ld, C = %d: C must be a multiple of 4 in 4..%d", M, C, kLnMax);
         return 0;
     }
@@ -488,7 +373,7 @@ extern "C" int car_layernorm_backward(const float* X, int ldx, const float* gamm
                                       long M, int flags, float* dgamma, float* dbeta, void* work, size_t work_bytes, void* stream) {
     const char* who = "car_layernorm_backward";
     CAR_REQUIRE(X && gamma && dY && dX && (!dgamma == !dbeta) && (!dgamma || work), "%s: null pointer", who);
-    CAR_REQUIRE(C >= 4 && C <= kLnMax && C % 4 == 0, "%s: C = %d must be a multiple of 4 in 4..%d", who, C, kLnMax);
+    if (!ln_shape_ok(C, who)) return CAR_E_ARG;
     CAR_REQUIRE(M > 0 && M <= (1L << 31) && eps >= 0.0, "%s: bad sizes (M = %ld, eps = %g)", who, M, eps);
     CAR_REQUIRE((flags & ~CAR_LIN_ACCUM) == 0, "%s: flags = %d: CAR_LIN_ACCUM is the only one", who, flags);
     CAR_REQUIRE(ldx >= C && lddy >= C && lddx >= C && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0,

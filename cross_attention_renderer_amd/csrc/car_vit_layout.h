@@ -1,5 +1,5 @@
 // car_vit_layout.h — the shapes and layouts the forward (car_vit.hip) and the backward (car_vit_backward.hip) of the encoder's transformer
-// stage share: the accepted ranges, one block of car_vit_pack, the transposed matrices car_vit_pack_train lays out behind it, and the
+// stage share: the accepted ranges, LayerNorm's row pass (LnRow), one block of car_vit_pack, the transposed matrices car_vit_pack_train lays out behind it, and the
 // record car_vit_blocks_train saves per block (profiles/workspace_layout.md, "the transformer stage's backward").  Each layout is ONE
 // function over a Carver: its total is what the size entry returns, its pieces are what the launchers use.
 // Included INSIDE the including file's anonymous namespace, after car_common.h.
@@ -14,6 +14,38 @@ bool mha_shape_ok(int b, int S, int heads, const char* who) {
     if (heads < 1 || heads > 16) { car_set_error("%s: heads = %d is outside 1..16", who, heads); return false; }
     return true;
 }
+// LayerNorm, forward and backward: a row of at most kLnMax floats lives in one wave's registers, kLnVec float4 per lane
+constexpr int kLnMax = 4096, kLnVec = kLnMax / (64 * 4);
+bool ln_shape_ok(int C, const char* who) {
+    if (C < 4 || C > kLnMax || C % 4) { car_set_error("%s: C = %d must be a multiple of 4 in 4..%d", who, C, kLnMax); return false; }
+    return true;
+}
+// one row in its wave's registers with its statistics in fp64: the mean first, then the variance from the squared distances to it.
+// layernorm_kernel and ln_bwd_kernel both start here, so the backward's mean and rstd ARE the forward's
+struct LnRow {
+    static constexpr int kVec = kLnVec;
+    float4 v[kVec];
+    double mean, rstd;
+    __device__ __forceinline__ void load(const float* x, int C, double eps, int lane) {
+        double sum = 0.0;
+#pragma unroll
+        for (int i = 0; i < kVec; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            v[i] = c < C ? *reinterpret_cast<const float4*>(x + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            sum += ((double)v[i].x + (double)v[i].y) + ((double)v[i].z + (double)v[i].w);
+        }
+        mean = wave_sum(sum) / (double)C;
+        double sq = 0.0;
+#pragma unroll
+        for (int i = 0; i < kVec; ++i) {
+            if ((i * 64 + lane) * 4 < C) {
+                const double a = (double)v[i].x - mean, b = (double)v[i].y - mean, c = (double)v[i].z - mean, d = (double)v[i].w - mean;
+                sq += (a * a + b * b) + (c * c + d * d);
+            }
+        }
+        rstd = 1.0 / sqrt(wave_sum(sq) / (double)C + eps);
+    }
+};
 bool vit_dim_ok(int dim, const char* who) {
     if (dim < 64 || dim > 1024 || dim % 64) { car_set_error("%s: dim = %d must be a multiple of 64 in 64..1024", who, dim); return false; }
     return true;
