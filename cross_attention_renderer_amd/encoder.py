@@ -32,8 +32,10 @@ layers cannot be pinned against timm in this image ("parity unpinned" for them, 
 """
 from __future__ import annotations
 
+import ctypes
+import itertools
 import math
-from typing import List
+from typing import Callable, Iterable, List, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -294,6 +296,46 @@ class _Scratch(nn.Module):
                                          nn.Identity(), nn.Conv2d(32, 1, 1), nn.Identity(), nn.Identity())
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# The host plumbing of get_z's device stages, stated once: the refusals, the pack, the route switches (the cached slots and the
+# workspaces are methods of MultiViewDPTEncoder below).  A new device stage uses these and states none of it again
+# ----------------------------------------------------------------------------------------------------------------------
+def refuse_off_device(switch: str, value: str, acts: Sequence[Tensor], params: Sequence[Tensor], recorded: Optional[Iterable[Tensor]],
+                      model: str = "the encoder", call: str = "call it", inference: Optional[str] = None) -> None:
+    """What a device stage behind `switch` (now `value`) refuses instead of falling back, in this order: activations or parameters off a
+    CUDA device; a dtype other than float32 (the first activation's is the one reported); and a forward that autograd records — grad mode
+    on and any tensor of `recorded` asking for a gradient (None: the stage has a backward, or the caller saw to it).  `inference` names the
+    inference-only value where `value` may be another one (vit_route's 'device_train'); `model` and `call` are the texts' two nouns."""
+    if not all(t.is_cuda for t in (*acts, *params)):
+        raise ValueError(f"{switch} = {value!r} needs the images and {model} on a CUDA device; CPU tensors run on {switch} = 'torch'")
+    if any(t.dtype != torch.float32 for t in (*acts, *params)):
+        raise ValueError(f"{switch} = {value!r} computes in float32 (got {acts[0].dtype}); other dtypes run on {switch} = 'torch'")
+    if recorded is not None and torch.is_grad_enabled() and any(t.requires_grad for t in recorded):
+        raise ValueError(f"{switch} = {inference or value!r} is inference only (its kernels have no backward): {call} under torch.no_grad(), or "
+                         f"keep {switch} = 'torch' for a forward that autograd records")
+
+
+def pack_parameters(sources: Sequence[Tensor], dev, floats: int, issue: Callable) -> Tensor:
+    """`sources` packed into one new buffer of `floats` floats on `dev`: issue(table, src, packed) calls the stage's pack entry, given the
+    sources' detached, contiguous forms `src` and the c_void_p table of their addresses.  Called inside ``torch.cuda.device(dev)``."""
+    packed = torch.empty(floats, device=dev, dtype=torch.float32)
+    src = [p.detach().contiguous() for p in sources]
+    issue((ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), src, packed)
+    return packed
+
+
+def _route_switch(name: str, allowed: Sequence[str], text: str) -> property:
+    """A route switch: an attribute that takes the values of `allowed` and refuses any other one with `text`."""
+    def get(self) -> str:
+        return getattr(self, "_" + name)
+
+    def set_(self, value: str) -> None:
+        if value not in allowed:
+            raise ValueError(f"{name} must be {text} (got {value!r})")
+        setattr(self, "_" + name, value)
+    return property(get, set_)
+
+
 class _VitBlocksTrain(torch.autograd.Function):
     """The 12 blocks as one autograd node over (tok, the 144 block parameters): car_vit_blocks_train forward, car_vit_blocks_backward
     backward (include/car_encoder_train.h).  Once differentiable: a double backward raises.
@@ -307,17 +349,14 @@ class _VitBlocksTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, BV, T, tok, *params):
-        import ctypes
         from . import _lib
         lib, dev = _lib.api(), tok.device
         b, S, dim = tok.shape
         depth, taps = len(params) // 12, enc.VIT_TAPS
         f32 = dict(device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            packed = torch.empty(_lib.user_call(lib.car_vit_packed_train_floats, dim, depth), **f32)
-            src = [p.detach().contiguous() for p in params]
-            _lib.user_call(lib.car_vit_pack_train, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), dim, depth, _lib.ptr(packed),
-                           _lib.stream())
+            packed = pack_parameters(params, dev, _lib.user_call(lib.car_vit_packed_train_floats, dim, depth), lambda table, src, out: _lib.user_call(
+                lib.car_vit_pack_train, table, len(src), dim, depth, _lib.ptr(out), _lib.stream()))
             saved = torch.empty(_lib.user_call(lib.car_vit_saved_bytes, b, S, dim, depth) // 4, **f32)
             work = enc._vit_workspace(lib, b, S, dim, dev)
             x = tok.detach().clone(memory_format=torch.contiguous_format)     # the stage runs in place
@@ -334,7 +373,6 @@ class _VitBlocksTrain(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *dtaps):
-        import ctypes
         from . import _lib
         stale = [i for i, (p, v) in enumerate(zip(ctx.params, ctx.param_versions)) if p._version != v]
         if stale:
@@ -368,6 +406,16 @@ class MultiViewDPTEncoder(nn.Module):
     VIT_BLOCK_ROUTES = ("torch", "device", "device_train")   # vit_route's own values: the blocks also have a recorded forward and a backward
     TRUNK_DEPTHS = (3, 4, 9)       # the stages of ResNetV2Trunk, as car_trunk_pack takes them
 
+    # the device stages' caches, by attribute.  Packed parameters: None until first use, then an engine._Cached (_cached below)
+    _PACKED_SLOTS = ("_vit_packed",      # the packed blocks (source: their 144 parameter tensors)
+                     "_trunk_packed",    # the packed trunk (source: its parameter tensors in state_dict order)
+                     "_tokens_packed",   # the packed token parameters (projection, class token, position and pose embeddings)
+                     "_decoder_packed")  # the packed decoder (source: the 50 parameter tensors it evaluates)
+    # ... and workspaces: a dict of one entry, replaced when the key changes (_workspace below)
+    _WORK_SLOTS = ("_vit_work",          # (b, S, device) -> the stage's workspace on the device
+                   "_trunk_work",        # (BV, H, W, device) -> the trunk's workspace, the token assembly's workspace
+                   "_decoder_work")      # (BV, gh, gw, device) -> the decoder's workspace
+
     def __init__(self):
         super().__init__()
         self.pretrained = _Pretrained()
@@ -375,62 +423,46 @@ class MultiViewDPTEncoder(nn.Module):
         # where the transformer blocks run: "torch" (the default: the modules above) or the opt-in "device" (car_vit_blocks on the packed
         # parameters: inference only, float32 CUDA tensors only; it refuses anything else instead of falling back) or the opt-in
         # "device_train" (under no_grad the "device" route, call for call; where autograd records, car_vit_blocks_train with
-        # car_vit_blocks_backward as its backward: _VitBlocksTrain below)
+        # car_vit_blocks_backward as its backward: _VitBlocksTrain above)
         self.vit_route = "torch"
-        self._vit_packed = None    # engine._Cached of the packed blocks (source: their 144 parameter tensors), made on first use
-        self._vit_work = {}        # (b, S, device) -> the stage's workspace on the device
         # where the ResNetV2 trunk and the token assembly run: "torch" (the default) or the opt-in "device" (car_trunk_forward and
         # car_vit_tokens on the packed parameters; the same conditions and the same refusals as vit_route, and independent of it)
         self.trunk_route = "torch"
-        self._trunk_packed = None  # engine._Cached of the packed trunk (source: its parameter tensors in state_dict order)
-        self._tokens_packed = None # engine._Cached of the packed token parameters (projection, class token, position and pose embeddings)
-        self._trunk_work = {}      # (BV, H, W, device) -> (the trunk's workspace, the token assembly's workspace)
         # where the read-out, the re-assembly and the fusion run: "torch" (the default) or the opt-in "device" (car_decoder_forward on the
         # packed parameters; the same conditions and the same refusals as the other two switches, and independent of them)
         self.decoder_route = "torch"
-        self._decoder_packed = None  # engine._Cached of the packed decoder (source: the 50 parameter tensors it evaluates)
-        self._decoder_work = {}      # (BV, gh, gw, device) -> the decoder's workspace
+        for slot in self._PACKED_SLOTS:
+            setattr(self, slot, None)
+        for slot in self._WORK_SLOTS:
+            setattr(self, slot, {})
 
-    @property
-    def vit_route(self) -> str:
-        return self._vit_route
-
-    @vit_route.setter
-    def vit_route(self, value: str) -> None:
-        if value not in self.VIT_BLOCK_ROUTES:
-            raise ValueError(f"vit_route must be 'torch', 'device' or 'device_train' (got {value!r})")
-        self._vit_route = value
-
-    @property
-    def trunk_route(self) -> str:
-        return self._trunk_route
-
-    @trunk_route.setter
-    def trunk_route(self, value: str) -> None:
-        if value not in self.VIT_ROUTES:
-            raise ValueError(f"trunk_route must be 'torch' or 'device' (got {value!r})")
-        self._trunk_route = value
-
-    @property
-    def decoder_route(self) -> str:
-        return self._decoder_route
-
-    @decoder_route.setter
-    def decoder_route(self, value: str) -> None:
-        if value not in self.VIT_ROUTES:
-            raise ValueError(f"decoder_route must be 'torch' or 'device' (got {value!r})")
-        self._decoder_route = value
+    vit_route = _route_switch("vit_route", VIT_BLOCK_ROUTES, "'torch', 'device' or 'device_train'")
+    trunk_route = _route_switch("trunk_route", VIT_ROUTES, "'torch' or 'device'")
+    decoder_route = _route_switch("decoder_route", VIT_ROUTES, "'torch' or 'device'")
 
     def drop_device_caches(self) -> None:
         """Forgets the packed blocks, the packed trunk and token parameters, the packed decoder and the workspaces: the next device-route forward packs the
         parameters as they are then.  The cache's key sees an in-place update through the tensors' _version, which torch's fused optimizers
         do not advance (CrossAttentionRenderer.train calls this on leaving train() mode, as it parks the engine's caches)."""
-        for cached in (self._vit_packed, self._trunk_packed, self._tokens_packed, self._decoder_packed):
-            if cached is not None:
-                cached.drop()
-        self._vit_work = {}
-        self._trunk_work = {}
-        self._decoder_work = {}
+        for slot in self._PACKED_SLOTS:
+            if getattr(self, slot) is not None:
+                getattr(self, slot).drop()
+        for slot in self._WORK_SLOTS:
+            setattr(self, slot, {})
+
+    def _cached(self, slot: str, sources: List[Tensor], extra: tuple, build: Callable):
+        """The value held in the packed slot `slot` for these sources and plain values (engine._Cached's key rule), built where it is not."""
+        from .engine import _Cached
+        if getattr(self, slot) is None:
+            setattr(self, slot, _Cached())
+        return getattr(self, slot).get(sources, extra, build)
+
+    def _workspace(self, slot: str, key: tuple, dev, nbytes: Callable) -> tuple:
+        """The float32 workspaces held in the workspace slot `slot` under `key`, one per byte count of nbytes() — which is asked, and the
+        one entry replaced, only when the key is new."""
+        if key not in getattr(self, slot):
+            setattr(self, slot, {key: tuple(torch.empty(n // 4, device=dev, dtype=torch.float32) for n in nbytes())})
+        return getattr(self, slot)[key]
 
     def _trunk_parameters(self) -> List[Tensor]:
         """The trunk's parameters in car_trunk_pack's order: state_dict order of ResNetV2Trunk."""
@@ -444,45 +476,25 @@ class MultiViewDPTEncoder(nn.Module):
     def _front_on_device(self, x: Tensor, rel_pose16: Tensor, gh: int, gw: int):
         """The trunk and the token assembly through car_trunk_forward and car_vit_tokens: x [BV, 3, H, W] ->
         (layer_1 [BV, 256, H/4, W/4], layer_2 [BV, 512, H/8, W/8] — NCHW views of the channel-last buffers — and tok [BV, 1 + gh gw, 768])."""
-        import ctypes
         from . import _lib
-        from .engine import _Cached
         trunk, toks = self._trunk_parameters(), self._token_parameters()
-        params = trunk + toks
-        if not x.is_cuda or not rel_pose16.is_cuda or not all(p.is_cuda for p in params):
-            raise ValueError("trunk_route = 'device' needs the images and the encoder on a CUDA device; CPU tensors run on trunk_route = 'torch'")
-        if x.dtype != torch.float32 or rel_pose16.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
-            raise ValueError(f"trunk_route = 'device' computes in float32 (got {x.dtype}); other dtypes run on trunk_route = 'torch'")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise ValueError("trunk_route = 'device' is inference only (its kernels have no backward): call it under torch.no_grad(), or "
-                             "keep trunk_route = 'torch' for a forward that autograd records")
-        lib, dev = _lib.api(), x.device
+        refuse_off_device("trunk_route", "device", (x, rel_pose16), trunk + toks, itertools.chain((x,), self.parameters()))
+        lib, dev, call = _lib.api(), x.device, _lib.user_call
         BV, _, H, W = x.shape
         depths = (ctypes.c_int * 3)(*self.TRUNK_DEPTHS)
         grid = int(math.sqrt(toks[3].shape[1] - 1))
-        if self._trunk_packed is None:
-            self._trunk_packed, self._tokens_packed = _Cached(), _Cached()
 
-        def build_trunk():
-            packed = torch.empty(_lib.user_call(lib.car_trunk_packed_floats, depths), device=dev, dtype=torch.float32)
-            src = [p.detach().contiguous() for p in trunk]
-            _lib.user_call(lib.car_trunk_pack, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), depths, _lib.ptr(packed), _lib.stream())
-            return packed
-
-        def build_tokens():
-            packed = torch.empty(_lib.user_call(lib.car_vit_tokens_packed_floats, gh, gw), device=dev, dtype=torch.float32)
-            pw, pb, cls, pos, sw, sb = [p.detach().contiguous() for p in toks]
-            _lib.user_call(lib.car_vit_tokens_pack, _lib.ptr(pw), _lib.ptr(pb), _lib.ptr(cls), _lib.ptr(pos), grid, _lib.ptr(sw), _lib.ptr(sb), gh, gw,
-                           _lib.ptr(packed), _lib.stream())
-            return packed
+        def pack_tokens(table, src, out):                                      # the one pack entry that takes its arrays one by one
+            pw, pb, cls, pos, sw, sb = map(_lib.ptr, src)
+            call(lib.car_vit_tokens_pack, pw, pb, cls, pos, grid, sw, sb, gh, gw, _lib.ptr(out), _lib.stream())
         with torch.cuda.device(dev):
-            packed = self._trunk_packed.get(trunk, (str(dev), self.TRUNK_DEPTHS), build_trunk)
-            tpacked = self._tokens_packed.get(toks, (str(dev), gh, gw), build_tokens)
-            key = (BV, H, W, str(dev))
-            if key not in self._trunk_work:
-                self._trunk_work = {key: (torch.empty(_lib.user_call(lib.car_trunk_workspace_bytes, BV, H, W, depths) // 4, device=dev, dtype=torch.float32),
-                                          torch.empty(_lib.user_call(lib.car_vit_tokens_workspace_bytes, BV, gh, gw) // 4, device=dev, dtype=torch.float32))}
-            work, twork = self._trunk_work[key]
+            packed = self._cached("_trunk_packed", trunk, (str(dev), self.TRUNK_DEPTHS), lambda: pack_parameters(
+                trunk, dev, call(lib.car_trunk_packed_floats, depths),
+                lambda table, src, out: call(lib.car_trunk_pack, table, len(src), depths, _lib.ptr(out), _lib.stream())))
+            tpacked = self._cached("_tokens_packed", toks, (str(dev), gh, gw), lambda: pack_parameters(
+                toks, dev, call(lib.car_vit_tokens_packed_floats, gh, gw), pack_tokens))
+            work, twork = self._workspace("_trunk_work", (BV, H, W, str(dev)), dev, lambda: (
+                call(lib.car_trunk_workspace_bytes, BV, H, W, depths), call(lib.car_vit_tokens_workspace_bytes, BV, gh, gw)))
             up = lambda v, k: -(-v // k)
             h4, w4, h8, w8, h16, w16 = up(H, 4), up(W, 4), up(H, 8), up(W, 8), up(H, 16), up(W, 16)
             if (h16, w16) != (gh, gw):
@@ -492,10 +504,10 @@ class MultiViewDPTEncoder(nn.Module):
             feat = torch.empty(BV, h16 * w16, 1024, device=dev, dtype=torch.float32)
             tok = torch.empty(BV, 1 + gh * gw, 768, device=dev, dtype=torch.float32)
             xc, pose = x.contiguous(), rel_pose16.contiguous()
-            _lib.user_call(lib.car_trunk_forward, _lib.ptr(xc), BV, H, W, _lib.ptr(packed), depths, _lib.ptr(layer_1), _lib.ptr(layer_2), _lib.ptr(feat),
-                           _lib.ptr(work), work.numel() * 4, _lib.stream())
-            _lib.user_call(lib.car_vit_tokens, _lib.ptr(feat), BV, gh, gw, _lib.ptr(pose), _lib.ptr(tpacked), _lib.ptr(tok), _lib.ptr(twork),
-                           twork.numel() * 4, _lib.stream())
+            call(lib.car_trunk_forward, _lib.ptr(xc), BV, H, W, _lib.ptr(packed), depths, _lib.ptr(layer_1), _lib.ptr(layer_2), _lib.ptr(feat),
+                 _lib.ptr(work), work.numel() * 4, _lib.stream())
+            call(lib.car_vit_tokens, _lib.ptr(feat), BV, gh, gw, _lib.ptr(pose), _lib.ptr(tpacked), _lib.ptr(tok), _lib.ptr(twork),
+                 twork.numel() * 4, _lib.stream())
         return layer_1.permute(0, 3, 1, 2), layer_2.permute(0, 3, 1, 2), tok      # NCHW views: torch's convolutions take channels_last
 
     def _vit_parameters(self) -> List[Tensor]:
@@ -504,24 +516,14 @@ class MultiViewDPTEncoder(nn.Module):
                  "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
         return [blk.get_parameter(n) for blk in self.pretrained.model.blocks for n in names]
 
-    def _refuse_off_device(self, tok: Tensor, params: List[Tensor]) -> None:
-        """What both device routes of the blocks refuse instead of falling back: CPU tensors, other dtypes."""
-        if not tok.is_cuda or not all(p.is_cuda for p in params):
-            raise ValueError(f"vit_route = {self.vit_route!r} needs the images and the encoder on a CUDA device; CPU tensors run on vit_route = 'torch'")
-        if tok.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
-            raise ValueError(f"vit_route = {self.vit_route!r} computes in float32 (got {tok.dtype}); other dtypes run on vit_route = 'torch'")
-
     def _vit_workspace(self, lib, b: int, S: int, dim: int, dev) -> Tensor:
-        key = (b, S, str(dev))
-        if key not in self._vit_work:
-            self._vit_work = {key: torch.empty(lib.car_vit_workspace_bytes(b, S, dim) // 4, device=dev, dtype=torch.float32)}
-        return self._vit_work[key]
+        return self._workspace("_vit_work", (b, S, str(dev)), dev, lambda: (lib.car_vit_workspace_bytes(b, S, dim),))[0]
 
     def _blocks_recorded_on_device(self, tok: Tensor, BV: int, T: int) -> dict:
         """The transformer stage where autograd records (vit_route = "device_train"): car_vit_blocks_train, with car_vit_blocks_backward
         as its backward.  tok [b, V T, dim] -> {tap: [BV, T, dim]}, each carrying the gradient back to tok and to the 144 block parameters."""
         params = self._vit_parameters()
-        self._refuse_off_device(tok, params)
+        refuse_off_device("vit_route", self.vit_route, (tok,), params, None)    # this route has the backward
         outs = _VitBlocksTrain.apply(self, BV, T, tok, *params)
         return dict(zip(self.VIT_TAPS, outs))
 
@@ -532,33 +534,21 @@ class MultiViewDPTEncoder(nn.Module):
     def _blocks_inference(self, tok: Tensor, x: Tensor, BV: int, T: int, recorded_elsewhere: bool) -> dict:
         """_blocks_on_device's body.  recorded_elsewhere (vit_route = "device_train" only): grad mode may be on, but neither tok nor a block
         parameter asks for a gradient, so nothing would flow through the blocks — the inference call is the whole of it."""
-        import ctypes
         from . import _lib
-        from .engine import _Cached
         params = self._vit_parameters()
-        self._refuse_off_device(tok, params)
-        if not recorded_elsewhere and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise ValueError("vit_route = 'device' is inference only (its kernels have no backward): call it under torch.no_grad(), or "
-                             "keep vit_route = 'torch' for a forward that autograd records")
-        lib, dev = _lib.api(), tok.device
+        refuse_off_device("vit_route", self.vit_route, (tok,), params, None if recorded_elsewhere else itertools.chain((x,), self.parameters()),
+                          inference="device")
+        lib, dev, call = _lib.api(), tok.device, _lib.user_call
         b, S, dim = tok.shape
         depth = len(params) // 12
-        if self._vit_packed is None:
-            self._vit_packed = _Cached()
-
-        def build():
-            packed = torch.empty(_lib.user_call(lib.car_vit_packed_floats, dim, depth), device=dev, dtype=torch.float32)
-            src = [p.detach().contiguous() for p in params]
-            _lib.user_call(lib.car_vit_pack, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), dim, depth, _lib.ptr(packed),
-                           _lib.stream())
-            return packed
         with torch.cuda.device(dev):
-            packed = self._vit_packed.get(params, (str(dev), dim, depth), build)
+            packed = self._cached("_vit_packed", params, (str(dev), dim, depth), lambda: pack_parameters(
+                params, dev, call(lib.car_vit_packed_floats, dim, depth),
+                lambda table, src, out: call(lib.car_vit_pack, table, len(src), dim, depth, _lib.ptr(out), _lib.stream())))
             work = self._vit_workspace(lib, b, S, dim, dev)
             outs = [torch.empty(BV, T, dim, device=dev, dtype=torch.float32) for _ in self.VIT_TAPS]
-            _lib.user_call(lib.car_vit_blocks, _lib.ptr(tok), b, S, dim, _lib.ptr(packed), depth, (ctypes.c_int * len(outs))(*self.VIT_TAPS),
-                           len(outs), (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _lib.ptr(work), work.numel() * 4,
-                           _lib.stream())
+            call(lib.car_vit_blocks, _lib.ptr(tok), b, S, dim, _lib.ptr(packed), depth, (ctypes.c_int * len(outs))(*self.VIT_TAPS),
+                 len(outs), (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs]), _lib.ptr(work), work.numel() * 4, _lib.stream())
         return dict(zip(self.VIT_TAPS, outs))
 
     def _decoder_parameters(self) -> List[Tensor]:
@@ -576,34 +566,16 @@ class MultiViewDPTEncoder(nn.Module):
     def _back_on_device(self, tap3: Tensor, tap4: Tensor, layer_1: Tensor, layer_2: Tensor, x: Tensor, gh: int, gw: int) -> List[Tensor]:
         """The read-out, the re-assembly and the fusion through car_decoder_forward: the two tapped states [BV, 1 + gh gw, 768] and the trunk's
         first two stage ends (NCHW) -> [path_2 [BV, 256, 4gh, 4gw], path_1 [BV, 256, 8gh, 8gw]], NCHW views of the channel-last buffers."""
-        import ctypes
         from . import _lib
-        from .engine import _Cached
         params = self._decoder_parameters()
-        acts = (tap3, tap4, layer_1, layer_2)
-        if not all(t.is_cuda for t in acts) or not all(p.is_cuda for p in params):
-            raise ValueError("decoder_route = 'device' needs the images and the encoder on a CUDA device; CPU tensors run on decoder_route = 'torch'")
-        if any(t.dtype != torch.float32 for t in acts) or any(p.dtype != torch.float32 for p in params):
-            raise ValueError(f"decoder_route = 'device' computes in float32 (got {tap3.dtype}); other dtypes run on decoder_route = 'torch'")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise ValueError("decoder_route = 'device' is inference only (its kernels have no backward): call it under torch.no_grad(), or "
-                             "keep decoder_route = 'torch' for a forward that autograd records")
-        lib, dev = _lib.api(), tap3.device
+        refuse_off_device("decoder_route", "device", (tap3, tap4, layer_1, layer_2), params, itertools.chain((x,), self.parameters()))
+        lib, dev, call = _lib.api(), tap3.device, _lib.user_call
         BV = tap3.shape[0]
-        if self._decoder_packed is None:
-            self._decoder_packed = _Cached()
-
-        def build():
-            packed = torch.empty(_lib.user_call(lib.car_decoder_packed_floats), device=dev, dtype=torch.float32)
-            src = [p.detach().contiguous() for p in params]
-            _lib.user_call(lib.car_decoder_pack, (ctypes.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), _lib.ptr(packed), _lib.stream())
-            return packed
         with torch.cuda.device(dev):
-            packed = self._decoder_packed.get(params, (str(dev),), build)
-            key = (BV, gh, gw, str(dev))
-            if key not in self._decoder_work:
-                self._decoder_work = {key: torch.empty(_lib.user_call(lib.car_decoder_workspace_bytes, BV, gh, gw) // 4, device=dev, dtype=torch.float32)}
-            work = self._decoder_work[key]
+            packed = self._cached("_decoder_packed", params, (str(dev),), lambda: pack_parameters(
+                params, dev, call(lib.car_decoder_packed_floats),
+                lambda table, src, out: call(lib.car_decoder_pack, table, len(src), _lib.ptr(out), _lib.stream())))
+            work, = self._workspace("_decoder_work", (BV, gh, gw, str(dev)), dev, lambda: (call(lib.car_decoder_workspace_bytes, BV, gh, gw),))
             if tuple(layer_1.shape[-2:]) != (4 * gh, 4 * gw) or tuple(layer_2.shape[-2:]) != (2 * gh, 2 * gw):
                 raise ValueError(f"decoder_route = 'device': stage ends of {tuple(layer_1.shape[-2:])} and {tuple(layer_2.shape[-2:])} are not 4 and 2 times "
                                  f"the {gh}x{gw} token grid")
@@ -611,8 +583,8 @@ class MultiViewDPTEncoder(nn.Module):
             t3, t4 = tap3.contiguous(), tap4.contiguous()
             path_2 = torch.empty(BV, 4 * gh, 4 * gw, 256, device=dev, dtype=torch.float32)
             path_1 = torch.empty(BV, 8 * gh, 8 * gw, 256, device=dev, dtype=torch.float32)
-            _lib.user_call(lib.car_decoder_forward, _lib.ptr(t3), _lib.ptr(t4), _lib.ptr(l1), _lib.ptr(l2), BV, gh, gw, _lib.ptr(packed), _lib.ptr(path_2),
-                           _lib.ptr(path_1), _lib.ptr(work), work.numel() * 4, _lib.stream())
+            call(lib.car_decoder_forward, _lib.ptr(t3), _lib.ptr(t4), _lib.ptr(l1), _lib.ptr(l2), BV, gh, gw, _lib.ptr(packed), _lib.ptr(path_2),
+                 _lib.ptr(path_1), _lib.ptr(work), work.numel() * 4, _lib.stream())
         return [path_2.permute(0, 3, 1, 2), path_1.permute(0, 3, 1, 2)]          # NCHW views: the engine takes channels_last without a copy
 
     def forward(self, x: Tensor, rel_pose16: Tensor, nviews: int) -> List[Tensor]:

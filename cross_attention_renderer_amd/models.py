@@ -11,11 +11,14 @@ parameter storage, ``get_z`` (image encoder + ``conv_map``, once per stereo pair
 """
 from __future__ import annotations
 
+import itertools
 from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from .encoder import MultiViewDPTEncoder, refuse_off_device
 
 Tensor = torch.Tensor
 
@@ -92,7 +95,6 @@ class CrossAttentionRenderer(nn.Module):
         if encoder is not None:
             self.encoder = encoder
         elif with_encoder and model == "midas_vit":
-            from .encoder import MultiViewDPTEncoder
             self.encoder = MultiViewDPTEncoder()
         else:
             self.encoder = EncoderNotBuilt()
@@ -248,13 +250,7 @@ class CrossAttentionRenderer(nn.Module):
 
     def _refuse_off_device(self, t: Tensor, params) -> None:
         """encoder_route = "device_full" makes the refusals of the encoder's own switches for get_z's two lines around the encoder."""
-        if not t.is_cuda or not all(p.is_cuda for p in params):
-            raise ValueError("encoder_route = 'device_full' needs the images and the model on a CUDA device; CPU tensors run on encoder_route = 'torch'")
-        if t.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
-            raise ValueError(f"encoder_route = 'device_full' computes in float32 (got {t.dtype}); other dtypes run on encoder_route = 'torch'")
-        if torch.is_grad_enabled() and (t.requires_grad or any(p.requires_grad for p in params)):
-            raise ValueError("encoder_route = 'device_full' is inference only (its kernels have no backward): call get_z under torch.no_grad(), or "
-                             "keep encoder_route = 'torch' for a forward that autograd records")
+        refuse_off_device("encoder_route", "device_full", (t,), params, itertools.chain((t,), params), model="the model", call="call get_z")
 
     def _normalize_on_device(self, rgb_cl: Tensor) -> Tensor:
         """get_z's normalisation through car_normalize_rgb: [BV, H, W, 3] in [-1, 1] -> [BV, 3, H, W]."""
